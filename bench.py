@@ -46,6 +46,13 @@ One JSON line on stdout (rank 0).  Extra objects:
                  with a kernel launch per evaluation instead of the context's persistent kernel.
   cpu_baseline   the CPU oracle (a single-threaded C port of the reference's Julia code path; the
                  Julia reference itself cannot run here) timed on this host on the same workload.
+
+`--dump-outputs DIR` writes what the timed call computed, once its timing has ended, as DIR/<name>.npy
+(float64; `_rank<k>` before `.npy` when there are several ranks): `energy` the running total energy of
+every replica after the last timed step, `run_counts` the call's counts (RUN_COUNTS), and the state of a
+fixed, seeded sample of replicas -- `sample_replica` (global indices), `sample_com`, `sample_coords`,
+`sample_sumqexp` (S(k), real and imaginary parts).  The inputs depend on the arguments only (seeded
+chains, fixed configuration), so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -68,6 +75,10 @@ FP64_PEAK_TFLOPS = 78.6   # fp64 vector peak (datasheet)
 N_K = 337
 N_CUS = 256
 N_SIMDS = 4 * N_CUS
+RUN_COUNTS = ("moves", "trans_attempt", "trans_accept", "rot_attempt", "rot_accept", "overlaps")
+DUMP_SAMPLE = 16             # replicas whose whole state --dump-outputs writes
+DUMP_SEED = 20261015
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def algorithmic_bytes_per_move(n_mol, box, r_cut=RCUT, n_k=N_K):
@@ -221,10 +232,49 @@ def shape_for(R, args):
                 zero_copy=zero_copy, prewarm=prewarm)
 
 
-def measure_moves(R, a, args, local_rank, g0, barrier, shape, n_parts=None, persistent=None):
+def dump_sample(R, n=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Sorted local indices of the replicas whose state --dump-outputs writes: all of them up to n,
+    else n drawn without replacement by a fixed seed."""
+    if R <= n:
+        return np.arange(R)
+    return np.sort(np.random.default_rng(seed).choice(R, n, replace=False))
+
+
+def timed_outputs(b, energies, st, g0):
+    """What a caller of the timed call holds after its last step: the energies it returned, its
+    counts, and the device state of the sampled replicas (mmc_batch_get_replica)."""
+    idx = dump_sample(b.R)
+    com, coords, sk = zip(*(b.get_replica(int(r)) for r in idx))
+    return {"energy": energies,
+            "run_counts": np.array([st[k] for k in RUN_COUNTS], dtype=np.float64),
+            "sample_replica": g0 + idx,
+            "sample_com": np.stack(com), "sample_coords": np.stack(coords),
+            "sample_sumqexp": np.stack(sk).view(np.float64).reshape(len(idx), -1, 2)}
+
+
+def write_outputs(dst, arrays, suffix=""):
+    """dst/<name><suffix>.npy for every array (float32 kept, anything else as float64), refused
+    above DUMP_LIMIT_BYTES in all.  Returns the file names."""
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        out[k] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes is more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(dst, exist_ok=True)
+    names = []
+    for k, v in out.items():
+        names.append(f"{k}{suffix}.npy")
+        np.save(os.path.join(dst, names[-1]), v)
+    return names
+
+
+def measure_moves(R, a, args, local_rank, g0, barrier, shape, n_parts=None, persistent=None, dump=None):
     """One timed run of the native driver on a fresh batch of R replicas.  Returns the figures of
     this rank; the caller reduces over ranks.  `persistent`: the move server for small batches
-    (None = the --persistent flag; the library's default takes it up to one replica per compute unit)."""
+    (None = the --persistent flag; the library's default takes it up to one replica per compute unit).
+    `dump`: (directory, file-name suffix) for the timed call's outputs (write_outputs)."""
     from metropolismontecarlo_amd import sharding, structs
     from metropolismontecarlo_amd.device import Batch
     box = a["box"]
@@ -265,6 +315,7 @@ def measure_moves(R, a, args, local_rank, g0, barrier, shape, n_parts=None, pers
                          energies, **kw)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = write_outputs(dump[0], timed_outputs(b, energies, st, g0), dump[1]) if dump else None
     # consistency: running totals vs a full recompute (Poly/main.jl:232-235), outside the timing
     tot2 = b.potential_ewald(as_array=True)
     drift = float(np.max(np.abs(energies - tot2["energy"]) / np.abs(energies)))
@@ -272,7 +323,8 @@ def measure_moves(R, a, args, local_rank, g0, barrier, shape, n_parts=None, pers
     streams = args.streams if args.streams > 0 else (min(shape["groups"], 2) if args.device_moves else shape["groups"])
     return dict(st=st, elapsed=elapsed, t_full=t_full, drift=drift, energy_sum=float(energies.sum()),
                 launches_per_step=st["launches"] / max(shape["steps"], 1),
-                server=st["server_steps"] > 0, streams=streams)  # (st["device_decisions"]: who decided)
+                server=st["server_steps"] > 0, streams=streams,  # (st["device_decisions"]: who decided)
+                dumped=dumped)
 
 
 def launch_mode_roofline(R, a, args, local_rank, g0, barrier, shape, n_mol, box, parts_used):
@@ -607,7 +659,7 @@ def call_surface(a, n_moves=2000, n_warm=300):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="default 600 (3000 below 4096 replicas)")
@@ -644,7 +696,18 @@ def main():
     ap.add_argument("--event-every", type=int, default=8,
                     help="bracket every Nth launch of a group with HIP events (an event pair costs "
                          "~10 us of stream time, so timing every launch slows what it measures)")
-    args = ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call computed as DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -709,7 +772,8 @@ def main():
     # only, not on the number of GPUs
     g0 = sharding.shard(R, rank)[0]
     shape = shape_for(R, args)
-    res = measure_moves(R, a, args, local_rank, g0, barrier, shape)
+    dump = (args.dump_outputs, f"_rank{rank}" if world > 1 else "") if args.dump_outputs else None
+    res = measure_moves(R, a, args, local_rank, g0, barrier, shape, dump=dump)
     st = res["st"]
 
     # C1: the only collective -- max of the time, sums of the observables (RCCL all-reduce)
@@ -764,6 +828,8 @@ def main():
             "ns_per_full_energy_eval": 1e9 * t_full_max / R,
             "full_energy_evals_per_s": R * world / t_full_max,
         }
+        if res["dumped"]:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": res["dumped"]}
         # M2: a full evaluation is fp64-VALU work, 3.5e7 flop by the survey's
         # counting against 111 KB of compulsory bytes -> fraction of the fp64 vector peak
         flops_full = algorithmic_flops_full_eval(n_mol, box)

@@ -30,26 +30,29 @@ def pytest_configure(config):
         # beside the other tests and the test only collects their output.
         out = tempfile.mkdtemp(prefix="mmc_dist_")
         env = dict(os.environ, MMC_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-        common = ["--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary", "--threads", "1"]
-        script = (
-            f"cd {ROOT} && "
-            f"{sys.executable} -m torch.distributed.run --nnodes=1 --nproc-per-node 2 "
-            f"--master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --replicas 64 "
-            f"{' '.join(common)} > {out}/two.json 2> {out}/two.err; echo $? > {out}/two.rc; "
-            f"{sys.executable} bench.py --gpus 1 --replicas 128 {' '.join(common)} "
-            f"> {out}/one.json 2> {out}/one.err; echo $? > {out}/one.rc; "
+        common = "--steps 20 --warmup 5 --no-cpu --no-secondary --threads 1"
+        two_ranks = (f"-m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 "
+                     f"--master-port")
+        runs = [
+            ("two", f"{two_ranks} 29541 bench.py --gpus 2 --replicas 64 {common}"),
+            ("one", f"bench.py --gpus 1 --replicas 128 {common}"),
             # BASELINE configs[2]'s share of a GPU (32 chains) under two ranks: the move server
-            f"{sys.executable} -m torch.distributed.run --nnodes=1 --nproc-per-node 2 "
-            f"--master-addr 127.0.0.1 --master-port 29543 bench.py --gpus 2 --replicas 32 "
-            f"--steps 200 --warmup 20 --no-cpu --no-secondary --threads 2 "
-            f"> {out}/two32.json 2> {out}/two32.err; echo $? > {out}/two32.rc; "
+            ("two32", f"{two_ranks} 29543 bench.py --gpus 2 --replicas 32 "
+                      f"--steps 200 --warmup 20 --no-cpu --no-secondary --threads 2"),
             # the headline's own mode under two ranks: the move kernel decides, eight steps per launch
-            f"{sys.executable} -m torch.distributed.run --nnodes=1 --nproc-per-node 2 "
-            f"--master-addr 127.0.0.1 --master-port 29545 bench.py --gpus 2 --replicas 10240 "
-            f"--steps 24 --warmup 8 --no-cpu --no-secondary --threads 2 "
-            f"> {out}/two_dev.json 2> {out}/two_dev.err; echo $? > {out}/two_dev.rc; "
-            f"{sys.executable} bench.py --gpus 1 --replicas 20480 --steps 24 --warmup 8 --no-cpu "
-            f"--no-secondary --threads 2 > {out}/one_dev.json 2> {out}/one_dev.err; echo $? > {out}/one_dev.rc")
+            ("two_dev", f"{two_ranks} 29545 bench.py --gpus 2 --replicas 10240 --steps 24 --warmup 8 "
+                        f"--no-cpu --no-secondary --threads 2 --dump-outputs {out}/two_dev_out"),
+            ("one_dev", f"bench.py --gpus 1 --replicas 20480 --steps 24 --warmup 8 --no-cpu "
+                        f"--no-secondary --threads 2 --dump-outputs {out}/one_dev_out"),
+            # the same command again: --dump-outputs must write the same outputs
+            ("one_dev_again", f"bench.py --gpus 1 --replicas 20480 --steps 24 --warmup 8 --no-cpu "
+                              f"--no-secondary --threads 2 --dump-outputs {out}/one_dev_again_out"),
+        ]
+        # each child under a time limit of its own; after one fails nothing more starts on the GPU
+        # (the runs that did not start leave no .rc file, and their tests fail on that)
+        script = f"cd {ROOT} && " + " && ".join(
+            f"{{ timeout -k 10 300 {sys.executable} {cmd} > {out}/{name}.json 2> {out}/{name}.err; "
+            f"rc=$?; echo $rc > {out}/{name}.rc; [ $rc -eq 0 ]; }}" for name, cmd in runs)
         proc = subprocess.Popen(["bash", "-c", script], env=env)
         config._mmc_dist = (proc, out)
 

@@ -15,11 +15,17 @@ Outputs:
                         both COM conventions (see metropolismontecarlo_amd.io.nist_system):
                         totals, per-molecule LJ_poly_dU / EwaldReal for a few molecules, and a
                         scripted list of trial moves with dU terms and S(k) checksums.
+    reference_signatures.json
+                        SHA-256 of the reference's function header at every location
+                        tests/test_julia_binding.py cites (comments and whitespace removed), so
+                        that the test checks its signatures without the reference's sources.
 The reference itself cannot be run here (Julia is not installed), so these are ORACLE values: they
 pin the oracle against regressions; the external pins are the NIST energies in test_oracle.py.
 """
+import hashlib
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -62,6 +68,29 @@ def scripted_moves(n_mol, box, com, coords, n_moves=12, seed=20261004):
             an = c + (at - c) @ Rm.T
         out.append((i, cn, an))
     return out
+
+
+def reference_header(where):
+    """The reference's function header at `where` ("file.jl:first[-last]"), from the cited line to
+    the line that closes its argument list, comments and whitespace removed."""
+    fname, lines = where.split(":")
+    lo = int(lines.split("-")[0])
+    src = open(os.path.join(REF, fname), encoding="utf-8").read().split("\n")
+    head = ""
+    for ln in src[lo - 1:lo + 12]:
+        head += re.sub(r"#[^\n]*", "", ln) + "\n"
+        if head.count("(") and head.count("(") == head.count(")"):
+            break
+    return re.sub(r"\s+", "", head)
+
+
+def signature_digests():
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_julia_binding import SIGNATURES
+    out = {w: hashlib.sha256(reference_header(w).encode("utf-8")).hexdigest() for w in sorted(SIGNATURES)}
+    with open(os.path.join(HERE, "reference_signatures.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
 
 
 def main():
@@ -114,6 +143,7 @@ def main():
                   f"recip={g['totals_ewald']['recip']:.9e} self={g['totals_ewald']['self']:.9e}")
     with open(os.path.join(HERE, "golden_oracle.json"), "w") as fh:
         json.dump(golden, fh, indent=1)
+    signature_digests()
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ import argparse
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,3 +101,56 @@ def test_a_call_whose_last_launch_is_shorter_still_gets_its_binding_block():
     assert 0 < b["frac"] <= 1.0 and b["bound"] in ("fp64_valu_issue", "hbm_access_pattern")
     assert b["hbm"]["bytes_per_move"] == pytest.approx(json.load(open(shape[-1]))["bytes_per_move"])
     assert b["access_pattern"]["floor_us"] == pytest.approx(b["access_pattern"]["frac"] * r["avg_launch_us"])
+
+
+def test_steps_and_dump_outputs_arguments():
+    a = bench.parse_args(["--gpus", "1", "--steps", "24", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 24 and a.warmup == 0 and a.dump_outputs == "out"
+    assert bench.shape_for(61440, a)["steps"] == 24 and bench.shape_for(32, a)["steps"] == 24
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_sample_is_fixed_and_seeded():
+    s = bench.dump_sample(61440)
+    assert len(s) == bench.DUMP_SAMPLE and len(set(s.tolist())) == len(s)
+    assert list(s) == sorted(s) and 0 <= s.min() and s.max() < 61440
+    assert np.array_equal(s, bench.dump_sample(61440))
+    assert np.array_equal(bench.dump_sample(5), np.arange(5))
+
+
+class _FakeBatch:
+    """get_replica of a batch whose replica r holds r everywhere"""
+    R, n_mol = 40, 3
+
+    def get_replica(self, r):
+        return (np.full((self.n_mol, 3), float(r)), np.full((3 * self.n_mol, 3), float(r)),
+                np.full(337, r + 0.5j))
+
+
+def test_timed_outputs_are_written_as_float_arrays(tmp_path):
+    st = {"moves": 800, "trans_attempt": 400, "trans_accept": 300, "rot_attempt": 400, "rot_accept": 250,
+          "overlaps": 3, "wall_ms": 1.5, "kernel_ms": 0.5}
+    energies = -np.arange(40, dtype=np.float64)
+    out = bench.timed_outputs(_FakeBatch(), energies, st, g0=1000)
+    names = bench.write_outputs(str(tmp_path / "d"), out, "_rank1")
+    assert sorted(names) == sorted(f"{k}_rank1.npy" for k in out)
+    got = {k: np.load(tmp_path / "d" / f"{k}_rank1.npy") for k in out}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["energy"], energies)
+    assert got["run_counts"].tolist() == [800, 400, 300, 400, 250, 3]
+    idx = bench.dump_sample(40)
+    assert np.array_equal(got["sample_replica"], 1000 + idx)
+    assert got["sample_com"].shape == (16, 3, 3) and got["sample_coords"].shape == (16, 9, 3)
+    assert np.array_equal(got["sample_coords"][:, 0, 0], idx)
+    assert got["sample_sumqexp"].shape == (16, 337, 2)
+    assert np.array_equal(got["sample_sumqexp"][:, 0], np.stack([idx, np.full(16, 0.5)], axis=1))
+    # float32 stays float32; anything else becomes float64; 64 MB in all is the limit
+    bench.write_outputs(str(tmp_path / "e"), {"a": np.ones(3, np.float32), "b": np.arange(3)})
+    assert np.load(tmp_path / "e" / "a.npy").dtype == np.float32
+    assert np.load(tmp_path / "e" / "b.npy").dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "f"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "f").exists()

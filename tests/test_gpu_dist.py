@@ -76,6 +76,42 @@ def test_two_ranks_in_the_headline_s_mode_run_the_same_chains_as_one(dist_rehear
     assert abs(e2 - e1) < 1e-13 * abs(e1), (e2, e1)
 
 
+def _dumped(directory, suffix=""):
+    import numpy as np
+    names = ("energy", "run_counts", "sample_replica", "sample_com", "sample_coords", "sample_sumqexp")
+    return {k: np.load(os.path.join(directory, f"{k}{suffix}.npy")) for k in names}
+
+
+def test_dumped_outputs_are_the_timed_call_s_and_repeat_from_run_to_run(dist_rehearsal):
+    """`bench.py --dump-outputs DIR`: the timed call's outputs, written after its timing.  The energies
+    are the ones the JSON line averages, the counts are the JSON line's, the same command writes the
+    same outputs again, and two ranks write the same chains as one process."""
+    import numpy as np
+    one, again, two = (load(dist_rehearsal, n) for n in ("one_dev", "one_dev_again", "two_dev"))
+    d1 = _dumped(os.path.join(dist_rehearsal, "one_dev_out"))
+    d1b = _dumped(os.path.join(dist_rehearsal, "one_dev_again_out"))
+    assert sorted(one["dumped_outputs"]["files"]) == sorted(f"{k}.npy" for k in d1)
+    for k, v in d1.items():
+        assert v.dtype == np.float64, k
+        assert np.array_equal(v, d1b[k]), k               # same arguments: the same outputs
+    R, n_mol = 20480, 750
+    assert d1["energy"].shape == (R,) and np.isfinite(d1["energy"]).all()
+    assert abs(d1["energy"].mean() - one["energy_mean_per_replica"]) < 1e-13 * abs(one["energy_mean_per_replica"])
+    moves, t_att, t_acc, r_att, r_acc, overlaps = d1["run_counts"]
+    assert moves == R * 24 == t_att + r_att and overlaps == one["overlaps"]
+    assert (t_acc + r_acc) / moves == one["acceptance"]
+    assert d1["sample_com"].shape == (16, n_mol, 3) and d1["sample_coords"].shape == (16, 3 * n_mol, 3)
+    assert d1["sample_sumqexp"].shape == (16, 337, 2)
+    idx = d1["sample_replica"].astype(np.int64)
+    assert len(set(idx.tolist())) == 16 and idx.min() >= 0 and idx.max() < R
+    # two ranks of 10240: each writes its own shard of the same 20480 chains
+    d2 = [_dumped(os.path.join(dist_rehearsal, "two_dev_out"), f"_rank{k}") for k in (0, 1)]
+    e2 = np.concatenate([d["energy"] for d in d2])
+    assert np.abs(e2 - d1["energy"]).max() <= 1e-12 * np.abs(d1["energy"]).max()
+    assert np.array_equal(d2[0]["run_counts"] + d2[1]["run_counts"], d1["run_counts"])
+    assert d2[1]["sample_replica"].min() >= 10240 and d2[0]["sample_replica"].max() < 10240
+
+
 def test_rccl_collective_behind_the_c_abi():
     """mmc_dist_*: the final reduction for hosts without torch.  A one-GPU box can form a
     communicator of ONE rank only (RCCL wants a GPU per rank): that still goes through
