@@ -2,6 +2,7 @@
 oracle (oracle.oracle.System / Ewald) and for the product (numpy arrays for device.Context)."""
 import json
 import os
+import re
 
 import numpy as np
 
@@ -87,3 +88,57 @@ def random_system(n_mol, box, seed, na_choices=(3,), n_types=2, min_sep=2.2):
     sig = (s[:, None] + s[None, :]) / 2
     return dict(com=com, first_atom=first, last_atom=last, coords=coords, atype=atype,
                 charge=charge, eps=eps, sig=sig, box=float(box))
+
+
+# ---- which replica k_move_eval_wave runs where ----------------------------------------------------
+def _wave_consts():
+    """(waves per workgroup, waves per SIMD) of k_move_eval_wave, read from its source so that the
+    unit -> wave map below follows the kernel."""
+    src = open(os.path.join(HERE, "..", "metropolismontecarlo_amd", "csrc", "mmc_wave.hpp")).read()
+    assert re.search(r"#define WV_MWAVES WV_WAVES\b", src)
+    return (int(re.search(r"#define WV_WAVES (\d+)", src).group(1)),
+            int(re.search(r"#define WV_OCC (\d+)", src).group(1)))
+
+
+def wave_units(n_units, wave_wgs=0, n_cus=256):
+    """The units each wave of one k_move_eval_wave launch over n_units takes, in the order it takes
+    them: the launch has ceil(n_units / WV_MWAVES) workgroups, capped at option "wave_wgs" or at
+    4 * WV_OCC / WV_MWAVES per compute unit (mmc_batch.inc), and wave w of workgroup g loops over
+    units g * WV_MWAVES + w, + wgs * WV_MWAVES, ... (mmc_wave.hpp).  Lists in wave order."""
+    mw, occ = _wave_consts()
+    cap = wave_wgs if wave_wgs > 0 else 4 * occ // mw * n_cus
+    wgs = min(-(-n_units // mw), cap)
+    return [list(range(g * mw + w, n_units, wgs * mw)) for g in range(wgs) for w in range(mw)]
+
+
+def replicas_by_wave_position(R, n_groups, wave_wgs=0, n_cus=256, parts=1):
+    """{local replica: where its unit runs} for the replicas worth checking when a wave runs several
+    units: in every group (replicas [R g / G, R (g + 1) / G), mmc_engine.inc) the first, second,
+    middle and last unit of wave 0 (which runs the most), the last unit of a wave that runs one unit
+    fewer, and the group's first and last replica."""
+    out = {}
+    for g in range(n_groups):
+        r0, r1 = R * g // n_groups, R * (g + 1) // n_groups
+        waves = wave_units((r1 - r0) * parts, wave_wgs, n_cus)
+        w0 = waves[0]
+        pos = [(w0[k], 0, k) for k in sorted({0, 1, len(w0) // 2, len(w0) - 1}) if k < len(w0)]
+        short = [wv for wv, w in enumerate(waves) if len(w) == len(w0) - 1 and w]
+        if short:
+            pos.append((waves[short[0]][-1], short[0], len(waves[short[0]]) - 1))
+        for u in (0, (r1 - r0) * parts - 1):
+            wv = next(k for k, w in enumerate(waves) if u in w)
+            pos.append((u, wv, waves[wv].index(u)))
+        for u, wv, k in pos:
+            out.setdefault(r0 + u // parts, f"group {g}, wave {wv}, unit {k + 1} of {len(waves[wv])}")
+    return dict(sorted(out.items()))
+
+
+def device_cu_count(device=0):
+    """Compute units of a device, asked of the HIP runtime the library itself is linked against
+    (hipDeviceGetAttribute, looked up through the library's handle)."""
+    import ctypes as C
+    from metropolismontecarlo_amd import _lib
+    get = C.CDLL(_lib.LIB_PATH).hipDeviceGetAttribute
+    n = C.c_int(0)
+    assert get(C.byref(n), 63, int(device)) == 0   # 63: hipDeviceAttributeMultiprocessorCount
+    return n.value

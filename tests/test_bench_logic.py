@@ -11,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import common  # noqa: E402
 
 
 def fake(streams, launches=40, elapsed=0.0102, span_us=350.0, timed=8):
@@ -154,3 +155,18 @@ def test_timed_outputs_are_written_as_float_arrays(tmp_path):
     with pytest.raises(ValueError):
         bench.write_outputs(str(tmp_path / "f"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
     assert not (tmp_path / "f").exists()
+
+
+def test_wave_map_of_the_headline_shape():
+    """The map the oracle tests choose their replicas from: 61440 chains in two groups on 256 compute
+    units are six units per wave; small batches under option "wave_wgs" run several, unevenly."""
+    w = common.wave_units(30720)
+    assert len(w) == 5120 and {len(x) for x in w} == {6} and w[1][:2] == [1, 5121]
+    assert sorted(u for x in w for u in x) == list(range(30720))
+    assert [len(x) for x in common.wave_units(12, 2)] == [2] * 4 + [1] * 4
+    assert [len(x) for x in common.wave_units(13, 1)] == [4, 3, 3, 3]
+    assert [len(x) for x in common.wave_units(12)] == [1] * 12              # a wave per unit
+    pos = common.replicas_by_wave_position(25, 2, wave_wgs=1)
+    assert list(pos) == [0, 4, 8, 11, 12, 16, 20, 21, 24]
+    assert pos[24] == "group 1, wave 0, unit 4 of 4" and pos[21] == "group 1, wave 1, unit 3 of 3"
+    assert list(common.replicas_by_wave_position(24, 2)) == [0, 11, 12, 23]

@@ -59,6 +59,20 @@ def test_batch_eval_chain(k, variant, parts, kernel, orc):
     diverge; every step's dU terms, overlap flags and the final device state (coordinates and
     S(k)) must match three independent oracle chains.  Proposals that touch the same molecule
     twice in a row and the 'previous move accepted' substitution are both exercised."""
+    _batch_eval_chain(k, variant, parts, kernel, orc)
+
+
+@pytest.mark.parametrize("k,variant,parts", [(4, "unwrapped", 9), (3, "reference", 16)])
+def test_batch_eval_chain_several_units_per_wave(k, variant, parts, orc):
+    """test_batch_eval_chain for the wave kernel with one workgroup per launch (option "wave_wgs"):
+    the parts of a replica, and then the next replica's, run one after another on the same four
+    waves (the SUBST = true instantiation), 7 and 6 units per wave at 9 parts, 12 at 16."""
+    waves = common.wave_units(3 * parts, wave_wgs=1)
+    assert len(waves) == 4 and len(waves[0]) >= 6
+    _batch_eval_chain(k, variant, parts, 2, orc, wave_wgs=1)
+
+
+def _batch_eval_chain(k, variant, parts, kernel, orc, wave_wgs=0):
     a = common.nist_arrays(k, variant)
     g = common.golden(k, variant)
     moves = list(g["moves"])
@@ -75,6 +89,8 @@ def test_batch_eval_chain(k, variant, parts, kernel, orc):
             b.set_parts(parts)
         b.set_option("kernel", kernel)   # 2: wave per move (default), 1: workgroup per move, 0: generic
         b.set_option("zero_copy_moves", k % 2)
+        if wave_wgs:
+            b.set_option("wave_wgs", wave_wgs)
         e0 = b.recip_long()
         ew = orc.Ewald(5.6 / a["box"], 5, 27, a["box"])
         assert rel(e0[0], orc.recip_long(ew, a["coords"], a["charge"], a["box"])) < TOL
@@ -668,25 +684,74 @@ def _rigid_proposal(seed, replica, step, com, atoms, box, dr_max, dphi_max):
     return 1, com.copy(), com + (atoms - com) @ Rm.T, u_met
 
 
-@pytest.mark.parametrize("kernel,R,parts,on_device", [(2, 24, 1, 0), (2, 24, 1, 1), (1, 2, 0, 0), (4, 1, 16, 0)])
-def test_driver_device_moves_stepped_by_the_oracle(kernel, R, parts, on_device, orc):
+T_BENCH, DR_BENCH, DPHI_BENCH = 298.15, 0.316555789, 0.05   # bench.py's TEMPERATURE, DR_MAX, DPHI_MAX
+
+
+def oracle_replay(orc, a, replica, calls, T=T_BENCH, dr=DR_BENCH, dphi=DPHI_BENCH):
+    """The chain of global replica index `replica` with device-side proposals, stepped by the oracle
+    through the calls [(n_steps, seed), ...] one batch makes in a row: the Philox counter continues
+    from the steps of the calls before (the batch's steps_done), the molecule sweep restarts at step 0
+    of every call (include/mmc_hip.h, Ewald/main.jl:490).  Every step: the proposal rebuilt from the
+    exported draws, dU from orc.trial_move, Metropolis (auxillary.jl:106-114) with math.exp and the
+    step's own uniform.  Returns the final com / coords / S(k), the sum of the accepted dU, the
+    accepted / overlap / rotation counts and every step's (dU, flags) -- flags as option
+    "trace_steps" writes them: bit 0 accepted, bit 1 overlap, bit 2 rotation."""
+    import math
+    s = common.oracle_system(a)
+    box, n_mol = a["box"], a["com"].shape[0]
+    ew = orc.Ewald(5.6 / box, 5, 27, box)
+    orc.recip_long(ew, s.coords, s.charge, box)
+    e_acc, n_acc, n_ovl, n_rot, trace, rng_off = 0.0, 0, 0, 0, [], 0
+    for n_steps, seed in calls:
+        for step in range(n_steps):
+            i = step % n_mol
+            kind, c_new, a_new, u = _rigid_proposal(seed, replica, rng_off + step, s.com[i].copy(),
+                                                    s.coords[3 * i:3 * i + 3].copy(), box, dr, dphi)
+            d, ov = orc.trial_move(i + 1, s, ew, RCUT, RCUT, c_new, a_new)
+            delta = d[0] + d[1] + d[2]                                    # main.jl:593
+            x = delta / T
+            accept = (x < 0.0 or math.exp(-x) > u) and not ov             # main.jl:598
+            trace.append((delta, int(accept) | (int(ov) << 1) | (kind << 2)))
+            n_ovl += bool(ov)
+            n_rot += kind
+            if accept:
+                e_acc += delta
+                n_acc += 1
+                s.com[i] = c_new
+                s.coords[3 * i:3 * i + 3] = a_new
+                ew.sumQExpOld = ew.sumQExpNew.copy()
+            else:
+                ew.sumQExpNew = ew.sumQExpOld.copy()
+        rng_off += n_steps
+    return dict(com=s.com, coords=s.coords, S=ew.sumQExpOld, e_acc=e_acc, n_acc=n_acc, n_ovl=n_ovl,
+                n_rot=n_rot, trace=trace)
+
+
+@pytest.mark.parametrize("kernel,R,parts,on_device,wave_wgs", [
+    pytest.param(2, 24, 1, 0, 0, id="2-24-1-0"), pytest.param(2, 24, 1, 1, 0, id="2-24-1-1"),
+    pytest.param(1, 2, 0, 0, 0, id="1-2-0-0"), pytest.param(4, 1, 16, 0, 0, id="4-1-16-0"),
+    pytest.param(2, 24, 1, 0, 1, id="2-24-1-0-wave_wgs1"), pytest.param(2, 24, 1, 1, 1, id="2-24-1-1-wave_wgs1")])
+def test_driver_device_moves_stepped_by_the_oracle(kernel, R, parts, on_device, wave_wgs, orc):
     """mmc_batch_run with device-side proposals at 750 molecules, every step checked: the oracle
     steps the same chains -- proposal rebuilt from the exported Philox draws, dU from
     orc.trial_move, Metropolis (auxillary.jl:106-114) with the step's own uniform -- and the
     driver's recorded dU and decision of EVERY step (option "trace_steps"), accepted or
     rejected, must agree: a wrong dU on a rejected move cannot hide in the final state.
-    on_device = 1: the decisions are the move kernel's own (option "accept_on_device")."""
-    import math
+    on_device = 1: the decisions are the move kernel's own (option "accept_on_device").
+    wave_wgs = 1: one workgroup per launch, so each wave runs three replicas one after another."""
     a = common.nist_arrays(4, "unwrapped")
-    n_mol, box = a["com"].shape[0], a["box"]
     n_steps, seed, T, dr, dphi = 90, 424242, 298.15, 0.316555789, 0.05
     check = (0, R - 1) if R > 1 else (0,)
+    if wave_wgs:
+        check = common.replicas_by_wave_position(R, 2, wave_wgs)
     with make_batch(a, R) as b:
         b.set_option("kernel", kernel)
         b.set_option("device_moves", 1)
         b.set_option("persistent", 0 if kernel != 4 else 1)   # launch per step; the latency server
         b.set_option("accept_on_device", on_device)
         b.set_option("trace_steps", n_steps)
+        if wave_wgs:
+            b.set_option("wave_wgs", wave_wgs)
         e0 = b.potential_ewald(as_array=True)["energy"].copy()
         e1, st = b.run(n_steps, T, dr, dphi, seed=seed, energies=e0, n_groups=min(R, 2),
                        n_parts=parts, n_threads=2, replica0=5)
@@ -695,84 +760,141 @@ def test_driver_device_moves_stepped_by_the_oracle(kernel, R, parts, on_device, 
         final = {r: b.get_replica(r) for r in check}
     n_rej = n_rot = 0
     for r in check:
-        s = common.oracle_system(a)
-        ew = orc.Ewald(5.6 / box, 5, 27, box)
-        orc.recip_long(ew, s.coords, s.charge, box)
-        running = 0.0
-        for step in range(n_steps):
-            i = step % n_mol                                              # main.jl:490
-            kind, c_new, a_new, u = _rigid_proposal(seed, 5 + r, step, s.com[i].copy(),
-                                                    s.coords[3 * i:3 * i + 3].copy(), box, dr, dphi)
-            d, ov = orc.trial_move(i + 1, s, ew, RCUT, RCUT, c_new, a_new)
-            delta = d[0] + d[1] + d[2]                                    # main.jl:593
-            x = delta / T
-            accept = (x < 0.0 or math.exp(-x) > u) and not ov             # main.jl:598
-            assert abs(d_gpu[r, step] - delta) < TOL * (abs(delta) + 1e4), (r, step, kind)
-            assert f_gpu[r, step] == (int(accept) | (int(ov) << 1) | (kind << 2)), (r, step)
-            n_rej += not accept
-            n_rot += kind
-            if accept:
-                running += delta
-                s.com[i] = c_new
-                s.coords[3 * i:3 * i + 3] = a_new
-                ew.sumQExpOld = ew.sumQExpNew.copy()
-            else:
-                ew.sumQExpNew = ew.sumQExpOld.copy()
+        o = oracle_replay(orc, a, 5 + r, [(n_steps, seed)], T, dr, dphi)
+        for step, (delta, flags) in enumerate(o["trace"]):
+            assert abs(d_gpu[r, step] - delta) < TOL * (abs(delta) + 1e4), (r, step, flags >> 2)
+            assert f_gpu[r, step] == flags, (r, step)
+        n_rej += n_steps - o["n_acc"]
+        n_rot += o["n_rot"]
         com, coords, S = final[r]
-        assert np.abs(com - s.com).max() < 2e-13 and np.abs(coords - s.coords).max() < 2e-13
-        assert np.abs(S - ew.sumQExpOld).max() < 1e-11 * np.abs(ew.sumQExpOld).max()
-        assert abs((e1[r] - e0[r]) - running) < TOL * 1e5
+        assert np.abs(com - o["com"]).max() < 2e-13 and np.abs(coords - o["coords"]).max() < 2e-13
+        assert np.abs(S - o["S"]).max() < 1e-11 * np.abs(o["S"]).max()
+        assert abs((e1[r] - e0[r]) - o["e_acc"]) < TOL * 1e5
     assert n_rej > 5 and n_rot > 10          # rejected moves and rotations were among the checked
 
 
-@pytest.mark.parametrize("per_launch,n_steps", [(8, 90), (16, 41)])
-def test_several_steps_per_launch_stepped_by_the_oracle(per_launch, n_steps, orc):
+def _check_against_the_oracle(orc, a, calls, final, e0, e1, where, replica0):
+    """The final state of the replicas in `final` ({local r: get_replica}) against oracle_replay of
+    the same calls; `where` says where each replica's unit ran."""
+    for r, (com, coords, S) in final.items():
+        o = oracle_replay(orc, a, replica0 + r, calls)
+        at = (r, where[r])
+        assert np.abs(com - o["com"]).max() < 2e-13 and np.abs(coords - o["coords"]).max() < 2e-13, at
+        assert np.abs(S - o["S"]).max() < 1e-11 * np.abs(o["S"]).max(), at
+        assert abs((e1[r] - e0[r]) - o["e_acc"]) < TOL * 1e5, at
+        assert 0 < o["n_acc"] < sum(n for n, _ in calls), at
+
+
+@pytest.mark.parametrize("per_launch,n_steps,R,wave_wgs,variant,image", [
+    pytest.param(8, 90, 24, 0, "unwrapped", -1, id="8-90"),
+    pytest.param(16, 41, 24, 0, "unwrapped", -1, id="16-41"),
+    # several units per wave: 3 each (wave_wgs 1), 2 and 1 (wave_wgs 2), 6 each (R 48, as at the
+    # headline), 4 and 3 (R 25: groups of 12 and 13)
+    pytest.param(8, 90, 24, 1, "unwrapped", -1, id="8-90-R24-wave_wgs1"),
+    pytest.param(8, 90, 24, 2, "unwrapped", -1, id="8-90-R24-wave_wgs2"),
+    pytest.param(16, 41, 24, 1, "unwrapped", -1, id="16-41-R24-wave_wgs1"),
+    pytest.param(16, 41, 24, 2, "unwrapped", -1, id="16-41-R24-wave_wgs2"),
+    pytest.param(8, 90, 48, 1, "unwrapped", -1, id="8-90-R48-wave_wgs1"),
+    pytest.param(8, 90, 25, 1, "unwrapped", -1, id="8-90-R25-wave_wgs1"),
+    # the instantiation without the molecule's minimum image (IMG = false, MULTI = true): the
+    # reference's own COMs (r_mol_max 28 A: the condition fails), and the option turned off
+    pytest.param(8, 90, 24, 1, "reference", -1, id="8-90-R24-wave_wgs1-reference"),
+    pytest.param(8, 90, 24, 1, "unwrapped", 0, id="8-90-R24-wave_wgs1-image_by_molecule0"),
+])
+def test_several_steps_per_launch_stepped_by_the_oracle(per_launch, n_steps, R, wave_wgs, variant, image, orc):
     """The headline's mode against the ORACLE: the move kernel decides and one launch takes a replica
     through several steps; no record of single steps comes back, so the oracle steps the same chains
     on its own -- proposals rebuilt from the Philox draws, dU from orc.trial_move, Metropolis
     (auxillary.jl:106-114) with math.exp and the step's uniform -- and the batch must end where the
-    oracle does: accept counts, the sum of the accepted dU, coordinates, S(k)."""
-    import math
-    a = common.nist_arrays(4, "unwrapped")
-    n_mol, box = a["com"].shape[0], a["box"]
-    R, seed, T, dr, dphi = 24, 777, 298.15, 0.316555789, 0.05
-    check = (0, 11, R - 1)
+    oracle does: accept counts, the sum of the accepted dU, coordinates, S(k).  With option
+    "wave_wgs" a wave runs several replicas in turn, as at the headline's size; the replicas checked
+    are chosen from the unit -> wave map (first, middle and last unit of a wave, a wave that runs one
+    unit fewer)."""
+    a = common.nist_arrays(4, variant)
+    seed = 777
+    check = common.replicas_by_wave_position(R, 2, wave_wgs) if wave_wgs else {0: "", 11: "", R - 1: ""}
     with make_batch(a, R) as b:
         b.set_option("kernel", 2)
         b.set_option("device_moves", 1)
         b.set_option("persistent", 0)
         b.set_option("accept_on_device", 1)
         b.set_option("steps_per_launch", per_launch)
+        b.set_option("image_by_molecule", image)
+        if wave_wgs:
+            b.set_option("wave_wgs", wave_wgs)
         e0 = b.potential_ewald(as_array=True)["energy"].copy()
-        e1, st = b.run(n_steps, T, dr, dphi, seed=seed, energies=e0, n_groups=2, n_parts=1, n_threads=2,
-                       replica0=3)
+        e1, st = b.run(n_steps, T_BENCH, DR_BENCH, DPHI_BENCH, seed=seed, energies=e0, n_groups=2,
+                       n_parts=1, n_threads=2, replica0=3)
         assert st["device_decisions"] == R * n_steps and st["launches"] == 2 * -(-n_steps // per_launch)
         final = {r: b.get_replica(r) for r in check}
-    for r in check:
-        s = common.oracle_system(a)
-        ew = orc.Ewald(5.6 / box, 5, 27, box)
-        orc.recip_long(ew, s.coords, s.charge, box)
-        running, n_acc = 0.0, 0
-        for step in range(n_steps):
-            i = step % n_mol
-            kind, c_new, a_new, u = _rigid_proposal(seed, 3 + r, step, s.com[i].copy(),
-                                                    s.coords[3 * i:3 * i + 3].copy(), box, dr, dphi)
-            d, ov = orc.trial_move(i + 1, s, ew, RCUT, RCUT, c_new, a_new)
-            delta = d[0] + d[1] + d[2]
-            x = delta / T
-            if (x < 0.0 or math.exp(-x) > u) and not ov:
-                running += delta
-                n_acc += 1
-                s.com[i] = c_new
-                s.coords[3 * i:3 * i + 3] = a_new
-                ew.sumQExpOld = ew.sumQExpNew.copy()
-            else:
-                ew.sumQExpNew = ew.sumQExpOld.copy()
-        com, coords, S = final[r]
-        assert np.abs(com - s.com).max() < 2e-13 and np.abs(coords - s.coords).max() < 2e-13, r
-        assert np.abs(S - ew.sumQExpOld).max() < 1e-11 * np.abs(ew.sumQExpOld).max(), r
-        assert abs((e1[r] - e0[r]) - running) < TOL * 1e5, r
-        assert 0 < n_acc < n_steps
+    _check_against_the_oracle(orc, a, [(n_steps, seed)], final, e0, e1, check, 3)
+
+
+def test_several_steps_per_launch_chains_continue_across_calls(orc):
+    """The bench makes three calls on one batch (prewarm, warm-up, timed), each with its own seed: the
+    Philox counter continues from the steps already run and the molecule sweep restarts.  Three calls
+    of 42, 8 and 29 steps at eight steps per launch -- no call ends on a launch boundary, every call's
+    last launch is short -- with three replicas per wave, against the oracle replaying the same
+    three calls."""
+    a = common.nist_arrays(4, "unwrapped")
+    R, per_launch = 24, 8
+    calls = [(42, 9001), (8, 77), (29, 123456789)]
+    check = common.replicas_by_wave_position(R, 2, wave_wgs=1)
+    with make_batch(a, R) as b:
+        b.set_option("kernel", 2)
+        b.set_option("device_moves", 1)
+        b.set_option("persistent", 0)
+        b.set_option("accept_on_device", 1)
+        b.set_option("steps_per_launch", per_launch)
+        b.set_option("wave_wgs", 1)
+        e0 = b.potential_ewald(as_array=True)["energy"].copy()
+        e = e0
+        for n, seed in calls:
+            e, st = b.run(n, T_BENCH, DR_BENCH, DPHI_BENCH, seed=seed, energies=e, n_groups=2, n_parts=1,
+                          n_threads=2, replica0=3)
+            assert st["device_decisions"] == R * n and st["launches"] == 2 * -(-n // per_launch), (n, st)
+            assert st["moves"] == R * n
+        final = {r: b.get_replica(r) for r in check}
+    _check_against_the_oracle(orc, a, calls, final, e0, e, check, 3)
+
+
+def test_headline_shape_stepped_by_the_oracle(orc):
+    """bench.py's flagship call in-process: 61440 chains of NIST configuration 4 in two groups, with
+    the options measure_moves sets and the shape shape_for picks at that size -- kernel 3, device
+    proposals, the accept decision left to the library (the move kernel takes it), the library's
+    own launch cap, so several units per wave -- for 90 steps (twelve launches per group at eight
+    steps each, the last one short).  Every replica's running total against a recompute: a record
+    read torn or from the wrong unit anywhere in the launch fails here; replicas at the edges of the
+    unit -> wave map against the oracle."""
+    import types
+    import bench
+    a = common.nist_arrays(4, "unwrapped")
+    R, n_steps, seed = 61440, 90, bench.SEED
+    # (two host threads, as the rehearsal in tests/conftest.py runs the bench; the bench itself takes
+    # what the host's cores near the GPU allow)
+    args = types.SimpleNamespace(groups=0, threads=2, steps=n_steps, warmup=0, zero_copy_moves=-1)
+    shape = bench.shape_for(R, args)
+    G = shape["groups"]
+    n_cus = common.device_cu_count()
+    per_wave = max(len(w) for g in range(G) for w in common.wave_units(R * (g + 1) // G - R * g // G, 0, n_cus))
+    assert per_wave >= 6, (n_cus, per_wave)   # the shape the headline times, not a smaller one
+    check = common.replicas_by_wave_position(R, G, 0, n_cus)
+    with make_batch(a, R) as b:
+        b.set_option("kernel", 3)
+        b.set_option("device_moves", 1)
+        b.set_option("accept_on_device", -1)
+        b.set_option("zero_copy_moves", shape["zero_copy"])
+        e0 = b.potential_ewald(as_array=True)["energy"].copy()
+        e1, st = b.run(n_steps, bench.TEMPERATURE, bench.DR_MAX, bench.DPHI_MAX, seed, energies=e0,
+                       n_groups=G, n_parts=0, time_kernels=8, n_threads=shape["threads"], n_streams=2)
+        assert st["device_decisions"] == R * n_steps and st["launches"] == G * -(-n_steps // 8), st
+        assert st["trans_attempt"] + st["rot_attempt"] == st["moves"] == R * n_steps
+        assert st["server_steps"] == 0
+        final = {r: b.get_replica(r) for r in check}
+        t1 = b.potential_ewald(as_array=True)["energy"]
+    worst = int(np.argmax(np.abs(e1 - t1) / np.abs(t1)))
+    assert abs(e1[worst] - t1[worst]) < 1e-11 * abs(t1[worst]), (worst, e1[worst], t1[worst])
+    _check_against_the_oracle(orc, a, [(n_steps, seed)], final, e0, e1, check, 0)
 
 
 @pytest.mark.parametrize("cfg,parts", [(4, 1), (4, 3), (1, 1)])

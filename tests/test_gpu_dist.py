@@ -112,6 +112,39 @@ def test_dumped_outputs_are_the_timed_call_s_and_repeat_from_run_to_run(dist_reh
     assert d2[1]["sample_replica"].min() >= 10240 and d2[0]["sample_replica"].max() < 10240
 
 
+def test_dumped_bench_outputs_against_the_oracle(dist_rehearsal):
+    """The state the headline's code path leaves behind, against the oracle: the sampled replicas
+    of `bench.py --replicas 20480 ... --dump-outputs` (two units per wave) replayed through the three
+    calls the bench made on its batch -- prewarm, warm-up, timed, each with its own seed, the
+    Philox counter continuing from call to call.  Step counts and seeds are the bench's own."""
+    import types
+    import numpy as np
+    import bench
+    import common
+    from metropolismontecarlo_amd import sharding
+    from oracle import oracle as orc
+    from test_gpu_batch import TOL, make_batch, oracle_replay
+    one = load(dist_rehearsal, "one_dev")
+    d = _dumped(os.path.join(dist_rehearsal, "one_dev_out"))
+    R = one["config"]["replicas_total"]
+    shape = bench.shape_for(R, types.SimpleNamespace(groups=0, threads=2, steps=one["steps"],
+                                                     warmup=one["warmup"], zero_copy_moves=-1))
+    assert one["config"]["prewarm_steps"] == shape["prewarm"] > 0
+    calls = [(shape["prewarm"], sharding.run_seed(phase=2)), (shape["warmup"], sharding.run_seed(phase=0)),
+             (shape["steps"], sharding.run_seed(phase=1))]
+    a = common.nist_arrays(4, "unwrapped")        # the bench's system
+    with make_batch(a, 1) as b:                   # the initial total every chain starts from
+        e0 = b.potential_ewald(as_array=True)["energy"][0]
+    for k, r in enumerate(d["sample_replica"].astype(np.int64)):
+        o = oracle_replay(orc, a, int(r), calls, bench.TEMPERATURE, bench.DR_MAX, bench.DPHI_MAX)
+        S = d["sample_sumqexp"][k, :, 0] + 1j * d["sample_sumqexp"][k, :, 1]
+        assert np.abs(d["sample_com"][k] - o["com"]).max() < 2e-13, r
+        assert np.abs(d["sample_coords"][k] - o["coords"]).max() < 2e-13, r
+        assert np.abs(S - o["S"]).max() < 1e-11 * np.abs(o["S"]).max(), r
+        assert abs((d["energy"][r] - e0) - o["e_acc"]) < TOL * 1e5, r
+        assert 0 < o["n_acc"] < sum(n for n, _ in calls), r
+
+
 def test_rccl_collective_behind_the_c_abi():
     """mmc_dist_*: the final reduction for hosts without torch.  A one-GPU box can form a
     communicator of ONE rank only (RCCL wants a GPU per rank): that still goes through
