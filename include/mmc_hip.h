@@ -499,6 +499,48 @@ typedef struct {
 int32_t mmc_batch_run_npt(mmc_batch *b, const mmc_run_params *p, const mmc_npt_params *q,
                           double *energy, mmc_run_stats *stats, mmc_npt_stats *npt_stats);
 
+/* ---- Per-replica boxes: independent NPT replicas in one batch ----------------------------------
+ * mmc_batch_set_boxes switches a batch to per-replica mode: replica r lives in box boxes[r] with
+ * kappa_r = alpha / boxes[r] (Ewald/main.jl:290-291), its own cfac row (PrepareEwaldVariables,
+ * ewalds.jl:45-103, over the shared k-vector list) and its own erfc(kappa_r r)/r table.  The
+ * coordinates are whatever mmc_batch_set_replica put there (the call does not rescale them); call
+ * mmc_batch_recip_long afterwards, as after creation.  Every box must be at least 2 r_cut
+ * (MMC_ERR_ARG).  The erfc table must cover the smallest box a volume move admits, L = 2 r_cut:
+ * kappa = alpha / (2 r_cut) <= MMC_QQ_KAPPA_MAX and kappa * sqrt(r_cut^2 + 100) <= MMC_QQ_XMAX,
+ * with identical 3-atom molecules; otherwise MMC_ERR_UNSUPPORTED and no state changes (SPC/E, 750
+ * molecules, r_cut 10, alpha 5.6: 3.96 <= 4).  The call may be repeated; the mode is never left.
+ * In per-replica mode:
+ *   - mmc_batch_recip_long, mmc_batch_potential_ewald and mmc_batch_run use each replica's box.
+ *     Trial moves are drawn on the device (option "device_moves" is set and cannot be cleared)
+ *     and evaluated by kernel 1 (one workgroup per move); the host decides.  A replica in which
+ *     an atom pair overlaps gets total energy +inf and n_overlap = 1 from potential_ewald.
+ *   - these return MMC_ERR_UNSUPPORTED and compute nothing: mmc_batch_eval, mmc_batch_settle,
+ *     mmc_batch_rdf, mmc_batch_qq_table, mmc_batch_run_chains, mmc_batch_run_npt,
+ *     mmc_batch_volume_change, mmc_batch_volume_trial / _accept / _reject,
+ *     mmc_batch_set_orientations, and mmc_batch_set_option for "kernel" 0, 2 or 4 (the wave and
+ *     latency kernels), "persistent" = 1 (the move server) and "device_moves" = 0.
+ * mmc_batch_get_boxes: every replica's box (the shared box when the mode is off). */
+int32_t mmc_batch_set_boxes(mmc_batch *b, const double *boxes, double alpha);
+int32_t mmc_batch_get_boxes(mmc_batch *b, double *boxes);
+/* One batched volume trial (volumeChange.jl:59-111): new_boxes[r] == 0 leaves replica r where it
+ * is.  Every replica's state is copied aside on the device; each replica that moves is rescaled
+ * about the centres of mass (:62-80) and gets its cfac row and table for alpha / L_new; tot[r] is
+ * the total energy of every replica at its (new) box.  Follow with mmc_batch_volume_settle:
+ * accept[r] != 0 keeps a moved replica's new state at no cost; every other replica (rejected, or
+ * not moved) gets back coordinates, S(k), tables and box bit for bit, in one launch. */
+int32_t mmc_batch_volume_trial_replicas(mmc_batch *b, const double *new_boxes, mmc_totals *tot);
+int32_t mmc_batch_volume_settle(mmc_batch *b, const int32_t *accept);
+/* mmc_batch_run_npt's chain for every replica: n_sweeps x { a sweep of trial moves for all
+ * replicas, then one volume move per replica, all replicas in one batched trial }.  Replica r's
+ * two uniforms are Philox draws of its stream (seed, replica0 + r) at the step count reached, slot
+ * MMC_SLOT_VOLUME; a box below 2 r_cut is rejected outright; the host decides.  pressures: [R]
+ * K / A^3, or NULL for q->pressure everywhere.  q->alpha must be the alpha of mmc_batch_set_boxes.
+ * energies: in/out [R] running totals.  per_replica: [R]; volume_ms is the wall clock of the
+ * batched volume moves, the same for every replica. */
+int32_t mmc_batch_run_npt_replicas(mmc_batch *b, const mmc_run_params *p, const mmc_npt_params *q,
+                                   const double *pressures, double *energies, mmc_run_stats *stats,
+                                   mmc_npt_stats *per_replica);
+
 /* The driver's counter-based generator, exposed for known-answer tests and for callers that
  * want to re-derive a chain's draws: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11). */
 int32_t mmc_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

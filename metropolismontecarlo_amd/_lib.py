@@ -120,6 +120,12 @@ SIGNATURES = {
     "mmc_batch_volume_reject": [_vp],
     "mmc_batch_run_npt": [_vp, C.POINTER(RunParams), C.POINTER(NptParams), _dp, C.POINTER(RunStats),
                           C.POINTER(NptStats)],
+    "mmc_batch_set_boxes": [_vp, _dp, _d],
+    "mmc_batch_get_boxes": [_vp, _dp],
+    "mmc_batch_volume_trial_replicas": [_vp, _dp, C.POINTER(Totals)],
+    "mmc_batch_volume_settle": [_vp, _i32p],
+    "mmc_batch_run_npt_replicas": [_vp, C.POINTER(RunParams), C.POINTER(NptParams), _dp, _dp,
+                                   C.POINTER(RunStats), C.POINTER(NptStats)],
     "mmc_volume_trial": [_vp, _d, _d, _d, _d, C.POINTER(Totals)],
     "mmc_volume_accept": [_vp],
     "mmc_volume_reject": [_vp],

@@ -79,6 +79,7 @@ struct mmc_batch {
     bool vol_outstanding = false; // mmc_batch_volume_trial without its accept / reject yet
     bool vol_saved_fast_ok = false;
     int vol_saved_kernel = 0;
+    std::vector<int32_t> pb_moved; // per-replica boxes: the replicas the outstanding volume trial moved
     int64_t trace_steps = 0;   // test hook: the driver records dU and the decision of the first N steps
     std::vector<double> trace_delta;   // [R][trace_steps] of the last run
     std::vector<uint8_t> trace_flags;  // bit 0 accepted, bit 1 overlap, bit 2 rotation
@@ -247,6 +248,11 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
     MMC_REQUIRE((b) != nullptr, MMC_ERR_ARG, "batch is NULL");                                   \
     MMC_HIP(hipSetDevice((b)->sys.device))
 
+// entry points that compute against the one shared box (include/mmc_hip.h, "Per-replica boxes")
+#define BATCH_ONE_BOX(b, what)                                                                   \
+    MMC_REQUIRE(!(b)->sys.pb.on, MMC_ERR_UNSUPPORTED,                                            \
+                "%s: the batch has per-replica boxes (mmc_batch_set_boxes)", what)
+
 extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t value)
 {
     BATCH_CHECK(b);
@@ -257,6 +263,8 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
                     MMC_MAX_PARTS);
         b->n_parts = (int)value;
     } else if (!strcmp(key, "kernel")) {
+        MMC_REQUIRE(!b->sys.pb.on || value == 1 || value == 3, MMC_ERR_UNSUPPORTED,
+                    "per-replica boxes run kernel 1 only");
         MMC_REQUIRE(value >= 0 && value <= 4, MMC_ERR_ARG,
                     "kernel must be 0 (generic), 1 (workgroup per move), 2 (wave per move), "
                     "3 (1 or 2 by launch size) or 4 (latency form)");
@@ -275,6 +283,8 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         b->server_wgs = (int)value;
     } else if (!strcmp(key, "persistent")) {
         MMC_REQUIRE(value >= -1 && value <= 1, MMC_ERR_ARG, "persistent must be -1, 0 or 1");
+        MMC_REQUIRE(!b->sys.pb.on || value != 1, MMC_ERR_UNSUPPORTED,
+                    "per-replica boxes: the move server has one box");
         b->persistent = (int)value;
     } else if (!strcmp(key, "server_seq_offset")) {
         MMC_REQUIRE(value >= 0, MMC_ERR_ARG, "server_seq_offset must be >= 0");
@@ -290,6 +300,8 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
     } else if (!strcmp(key, "zero_copy_moves")) {
         b->zero_copy_moves = value ? 1 : 0;
     } else if (!strcmp(key, "device_moves")) {
+        MMC_REQUIRE(!b->sys.pb.on || value, MMC_ERR_UNSUPPORTED,
+                    "per-replica boxes: the trial moves are drawn on the device");
         b->device_moves = value ? 1 : 0;
     } else if (!strcmp(key, "steps_per_launch")) {
         MMC_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16, MMC_ERR_ARG,
@@ -430,6 +442,8 @@ static inline const MoveRec *batch_ring_slot(const mmc_batch *b, int64_t step)
 // Which move kernel a launch of nr replicas x P parts runs (option "kernel"; 3 = by size).
 static int batch_kernel_for(const mmc_batch *b, int64_t nr, int P)
 {
+    if (b->sys.pb.on) // per-replica boxes: the workgroup-per-move kernel is the one with a box per replica
+        return 1;
     return b->kernel != 3 ? b->kernel : (nr * P >= (int64_t)16 * b->n_cus ? 2 : 1);
 }
 
@@ -479,8 +493,12 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
             ga.quat_mode = b->quat_mode;
             memcpy(ga.db, b->db, sizeof(ga.db));
             const int64_t n = nr * dg->n_gen;
-            k_propose<<<(unsigned)((n + 63) / 64), 64, 0, stream>>>(s.bv, s.rec, b->d_ring, ga,
-                                                                    (int)r0, (int)nr, has_prev ? 1 : 0);
+            if (s.pb.on)
+                k_propose<<<(unsigned)((n + 63) / 64), 64, 0, stream>>>(s.bv, s.rec, b->d_ring, ga, (int)r0,
+                                                                        (int)nr, has_prev ? 1 : 0, s.pb_view());
+            else
+                k_propose<<<(unsigned)((n + 63) / 64), 64, 0, stream>>>(s.bv, s.rec, b->d_ring, ga,
+                                                                        (int)r0, (int)nr, has_prev ? 1 : 0);
         }
         cur = batch_ring_slot(b, dg->step);
         prev = has_prev ? batch_ring_slot(b, dg->step + MMC_GEN_RING - 1) : nullptr;
@@ -539,7 +557,11 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
         }
 #undef MMC_WAVE_LAUNCH
 #undef MMC_WAVE_LAUNCH3
-    } else if (kernel == 1)
+    } else if (kernel == 1 && s.pb.on)
+        k_move_eval_fast<<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, nullptr, s.kpack, s.fc, cur, prev,
+                                                         b->d_parts, P, pp, (int)r0, flagv, stamp,
+                                                         s.pb_view());
+    else if (kernel == 1)
         k_move_eval_fast<<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
                                                          prev, b->d_parts, P, pp, (int)r0, flagv,
                                                          stamp);
@@ -688,6 +710,7 @@ static int32_t batch_settle_range(mmc_batch *b, hipStream_t stream, int64_t r0, 
 extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_result *results)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_eval");
     BATCH_USABLE(b);
     BATCH_NO_VOLUME_TRIAL(b);
     MMC_REQUIRE(moves && results, MMC_ERR_ARG, "NULL argument");
@@ -749,6 +772,7 @@ extern "C" int32_t mmc_batch_set_orientations(mmc_batch *b, const double *quat, 
                                               int32_t mode)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_set_orientations");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_REQUIRE(mode >= 0 && mode <= 2, MMC_ERR_ARG, "mode must be 0 (off), 1 (faithful) or 2");
     DeviceSystem &s = b->sys;
@@ -817,6 +841,7 @@ extern "C" int32_t mmc_batch_settle(mmc_batch *b, const int32_t *accept)
 {
     BATCH_CHECK(b);
     MMC_REQUIRE(accept, MMC_ERR_ARG, "NULL argument");
+    BATCH_ONE_BOX(b, "mmc_batch_settle");
     if (!b->has_prev)
         return MMC_OK;
     DeviceSystem &s = b->sys;
@@ -836,6 +861,7 @@ extern "C" int32_t mmc_batch_settle(mmc_batch *b, const int32_t *accept)
 extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double new_kappa)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_volume_change");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_REQUIRE(!b->vol_outstanding, MMC_ERR_STATE,
                 "volume move not settled: call mmc_batch_volume_accept or mmc_batch_volume_reject first");
@@ -868,6 +894,7 @@ extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double 
 extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double new_kappa, mmc_totals *tot)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_volume_trial");
     BATCH_USABLE(b);
     MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
@@ -904,6 +931,7 @@ extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double n
 extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_volume_accept");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");
     b->vol_outstanding = false;
     b->sys.snap.valid = false;
@@ -913,6 +941,7 @@ extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 extern "C" int32_t mmc_batch_volume_reject(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_volume_reject");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");
     MMC_TRY(b->sys.snapshot_restore());
     MMC_TRY(b->sys.sync()); // the next run uses the driver's own streams
@@ -926,6 +955,7 @@ extern "C" int32_t mmc_batch_volume_reject(mmc_batch *b)
 extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, double *out)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_qq_table");
     MMC_REQUIRE(u && out && n >= 0, MMC_ERR_ARG, "bad argument");
     MMC_REQUIRE(b->sys.qq_tab, MMC_ERR_STATE, "no table built");
     if (n == 0)
@@ -957,6 +987,7 @@ extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, 
 extern "C" int32_t mmc_batch_rdf(mmc_batch *b, int32_t site, int32_t numbins, uint64_t *hist)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_rdf");
     MMC_REQUIRE(hist, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_REQUIRE(numbins >= 1 && numbins <= 8192, MMC_ERR_ARG, "numbins outside 1..8192");

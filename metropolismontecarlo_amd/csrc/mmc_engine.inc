@@ -1054,7 +1054,9 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     } else if (d.P > MMC_MAX_PARTS) {
         d.P = MMC_MAX_PARTS;
     }
-    if (b->persistent != 0) { // small batches: the persistent move server
+    MMC_REQUIRE(!s.pb.on || d.devgen, MMC_ERR_UNSUPPORTED,
+                "per-replica boxes: the trial moves are drawn on the device (device_moves = 1)");
+    if (b->persistent != 0 && !s.pb.on) { // small batches: the persistent move server (one box)
         d.server = batch_server_applies(b) && (b->persistent == 1 || R <= MMC_SERVER_AUTO_MAX);
         MMC_REQUIRE(d.server || b->persistent != 1, MMC_ERR_UNSUPPORTED,
                     "the persistent move server needs device_moves = 1, the table kernel, no "
@@ -1314,6 +1316,8 @@ extern "C" int32_t mmc_batch_run_chains(mmc_batch *b, const mmc_run_params *p, m
 {
     MMC_REQUIRE(chains, MMC_ERR_ARG, "NULL argument");
     if (b)
+        BATCH_ONE_BOX(b, "mmc_batch_run_chains");
+    if (b)
         for (int64_t r = 0; r < b->sys.R; r++)
             MMC_REQUIRE(chains[r].dr_max >= 0 && chains[r].dphi_max >= 0
                             && (!adjust || (chains[r].trans_set_value > 0 && chains[r].rot_set_value > 0)),
@@ -1328,6 +1332,7 @@ extern "C" int32_t mmc_batch_run_npt(mmc_batch *b, const mmc_run_params *p, cons
                                      double *energy, mmc_run_stats *stats, mmc_npt_stats *ns)
 {
     BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_run_npt (per-replica boxes: mmc_batch_run_npt_replicas)");
     MMC_REQUIRE(p && q && energy && stats && ns, MMC_ERR_ARG, "NULL argument");
     MMC_REQUIRE(b->sys.R == 1, MMC_ERR_UNSUPPORTED,
                 "a batch has one box: an NPT chain needs a batch of ONE replica");

@@ -41,6 +41,10 @@
 #define MMC_QQ_NINT 160   // 10 octaves [2^-2, 2^8) x 16 sub-intervals
 #define MMC_QQ_NROW (MMC_QQ_NINT + 1) // ... after a row of zeros: where a masked-out evaluation lands
 #define MMC_QQ_TABLE_DOUBLES (MMC_QQ_NROW * MMC_QQ_NCOEF)
+__device__ __forceinline__ const double *pb_tab(const double *, int r, const PerBoxView &pb)
+{
+    return pb.tab + (int64_t)r * MMC_QQ_TABLE_DOUBLES;
+}
 #define MMC_QQ_UMIN 0.25
 #define MMC_QQ_UMAX 256.0    // the host selects this kernel only if r_cut^2 + 100 <= UMAX,
 #define MMC_QQ_XMAX 4.0      // kappa * sqrt(r_cut^2 + 100) <= XMAX (degree 9 is enough there)
@@ -199,10 +203,31 @@ __device__ __noinline__ double qq_pair_cold(double u, double kappa)
 
 // Build the table: one thread per piece.  Chebyshev interpolation at 11 nodes of the exact
 // (ocml) function, converted to the monomial basis in t for Horner evaluation.
-__global__ void k_build_qq_table(double kappa, double *tab)
+// Per-replica tables (a batch with per-replica boxes): grid (rows, R), replica r's table for
+// kappa[r] at tab + r * MMC_QQ_TABLE_DOUBLES, only where mask[r] != 0 (mask NULL: every replica).
+struct PerBoxTable {
+    const double *kappa; // [R]
+    const int32_t *mask; // [R] or NULL
+};
+__device__ __forceinline__ bool pb_table_replica(double &, double *&) { return true; }
+__device__ __forceinline__ bool pb_table_replica(double &kappa, double *&tab, const PerBoxTable &pb)
+{
+    const int r = blockIdx.y;
+    kappa = pb.kappa[r];
+    tab += (int64_t)r * MMC_QQ_TABLE_DOUBLES;
+    return !pb.mask || pb.mask[r];
+}
+
+// PerBox: empty = the one table of the batch, PerBoxTable = one per replica (mmc_batch_set_boxes).
+// (A pack, not a flag: the one-box kernel keeps its argument block, and the offset of the hidden
+// arguments behind it, exactly as they were.)
+template <typename... PerBox>
+__global__ void k_build_qq_table(double kappa, double *tab, PerBox... pb)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= MMC_QQ_NROW)
+        return;
+    if (!pb_table_replica(kappa, tab, pb...))
         return;
     if (idx == MMC_QQ_NINT) { // row 0: zeros (qq_table_eval_masked)
         for (int j = 0; j < MMC_QQ_NCOEF; j++)
@@ -332,17 +357,20 @@ struct FastShared {
     int32_t gflag;
 };
 
-// grid (n_parts, replicas of the group); same part semantics as k_move_eval.
+// grid (n_parts, replicas of the group); same part semantics as k_move_eval.  PerBox: empty =
+// the batch's one box; PerBoxView = replica r takes its box, kappa, cfac row and table from it
+// (pb_* in mmc_kernels.hpp).
+template <typename... PerBox>
 __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     BatchView bv, double *rec, const double *qq_tab, const int32_t *kpack, FastConsts fc,
     const MoveRec *cur, const MoveRec *prev, PartOut *out, int n_parts, PairParams pp, int r_base,
-    const uint8_t *flagv, unsigned stamp)
+    const uint8_t *flagv, unsigned stamp, PerBox... pb)
 {
     __shared__ __align__(16) FastShared sm;
 
     const int r = r_base + blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const int n_mol = bv.n_mol;
-    const double box = bv.box;
+    const double box = pb_box(bv, r, pb...);
     const double *comx = bv.comx + r * bv.mol_stride, *comy = bv.comy + r * bv.mol_stride,
                  *comz = bv.comz + r * bv.mol_stride;
     double *myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
@@ -371,7 +399,7 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     }
     if (do_pairs)
         for (int k = tid; k < MMC_QQ_TABLE_DOUBLES; k += MMC_BLOCK)
-            sm.qtab[k] = qq_tab[k];
+            sm.qtab[k] = pb_tab(qq_tab, r, pb...)[k];
     // first centres of mass of this wave's share of the COM scan
     const int len0 = min(MMC_FLIST_CAP, j_end - j_begin);
     const int seg0 = ((len0 + MMC_WAVES * 64 - 1) / (MMC_WAVES * 64)) * 64;
@@ -391,8 +419,8 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     int kp0 = 0, kp1 = 0;
     double cf0 = 0.0, cf1 = 0.0;
     if (do_recip) {
-        if (tid < bv.nkvecs) { kp0 = kpack[tid]; cf0 = bv.cfac[tid]; }
-        if (tid + MMC_BLOCK < bv.nkvecs) { kp1 = kpack[tid + MMC_BLOCK]; cf1 = bv.cfac[tid + MMC_BLOCK]; }
+        if (tid < bv.nkvecs) { kp0 = kpack[tid]; cf0 = pb_cfac(bv, r, pb...)[tid]; }
+        if (tid + MMC_BLOCK < bv.nkvecs) { kp1 = kpack[tid + MMC_BLOCK]; cf1 = pb_cfac(bv, r, pb...)[tid + MMC_BLOCK]; }
     }
     __syncthreads();
 
@@ -418,7 +446,7 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
         } else {
             const int d = tid - 9;
             (d == 0 ? bv.comx : d == 1 ? bv.comy : bv.comz)[r * bv.mol_stride + pend] = v;
-            comq_store(bv, r, pend, d, v);
+            pb_comq_store(bv, r, pend, d, v, pb...);
         }
     }
     if (part == 0 && commit && tid >= 12 && tid < 16)
@@ -561,8 +589,8 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
                 double e1 = qq_table_eval_clamped(sm.qtab, u[1]);
                 // like charges closer than 0.5 A: the series (practically never taken)
                 if (__any((in0 && u[0] < MMC_QQ_UMIN) || (in1 && u[1] < MMC_QQ_UMIN))) {
-                    if (u[0] < MMC_QQ_UMIN) e0 = qq_pair(sm.qtab, u[0], pp.kappa);
-                    if (u[1] < MMC_QQ_UMIN) e1 = qq_pair(sm.qtab, u[1], pp.kappa);
+                    if (u[0] < MMC_QQ_UMIN) e0 = qq_pair(sm.qtab, u[0], pb_kappa(pp.kappa, r, pb...));
+                    if (u[1] < MMC_QQ_UMIN) e1 = qq_pair(sm.qtab, u[1], pb_kappa(pp.kappa, r, pb...));
                 }
                 a_q0 += in0 ? qq * e0 : 0.0;
                 a_q1 += in1 ? qq * e1 : 0.0;

@@ -8,4 +8,5 @@
 #include "mmc_ctx.inc"
 #include "mmc_batch.inc"
 #include "mmc_engine.inc"
+#include "mmc_perbox.inc"
 #include "mmc_dist.inc"

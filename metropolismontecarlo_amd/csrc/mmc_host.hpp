@@ -135,6 +135,28 @@ struct DeviceSystem {
     } snap;
     int32_t snapshot_take();
     int32_t snapshot_restore();
+    // Per-replica boxes (mmc_batch_set_boxes, mmc_perbox.inc): when `on`, replica r lives in box
+    // box[r] with kappa[r] = alpha / box[r], its own cfac row and erfc table, and box / bv.box /
+    // bv.kappa / bv.cfac / qq_tab above are not used by anything that computes.
+    struct {
+        bool on = false;
+        double alpha = 0.0;
+        std::vector<double> box, kappa;  // host copies of d_box / d_kappa
+        double *d_box = nullptr;         // [R]
+        double *d_kappa = nullptr;       // [R]
+        double *d_f = nullptr;           // [R] rescale factors of a volume trial (0: stays)
+        double *d_new_box = nullptr;     // [R]
+        double *cfac = nullptr;          // [R][MMC_NK_STRIDE]
+        double *tab = nullptr;           // [R][MMC_QQ_TABLE_DOUBLES]
+        int32_t *d_mask = nullptr;       // [R] replicas a masked kernel touches
+        uint32_t *snap = nullptr;        // the volume trial's copy of every replica (lazily)
+        SnapSegsR to_snap{}, from_snap{};
+        std::vector<double> snap_box, snap_kappa;
+    } pb;
+    PerBoxView pb_view() const { return PerBoxView{ pb.d_box, pb.d_kappa, pb.cfac, pb.tab }; }
+    int32_t pb_upload_scalars();                        // pb.box / pb.kappa -> the device
+    int32_t pb_build_tables(const int32_t *d_mask);     // cfac rows and tables (d_mask NULL: all)
+    int32_t pb_snapshot(const int32_t *d_mask, bool take);
 };
 
 PairParams mmc_pair_params(double lj_rcut, double qq_rcut, double diameter, double ovr,

@@ -90,6 +90,38 @@ __device__ __forceinline__ void comq_store(const BatchView &b, int r, int j, int
     comq_store(b, r, j, d, v, 1.0 / b.box);
 }
 
+// Per-replica boxes (mmc_batch_set_boxes): L_r, kappa_r = alpha / L_r, the cfac row and the
+// erfc(kappa_r r)/r table of every replica, indexed by r.  The k-vector list (kxyz, kpack) does
+// not depend on the box and stays shared.  Kernels that run in this mode take a trailing template
+// pack `PerBox... pb`: empty for the batch's one box (the argument block is unchanged), one
+// PerBoxView otherwise; the pb_* overloads below pick the shared or the replica's value.
+struct PerBoxView {
+    const double *box;   // [R]
+    const double *kappa; // [R]
+    const double *cfac;  // [R][MMC_NK_STRIDE]
+    const double *tab;   // [R][MMC_QQ_TABLE_DOUBLES]
+};
+__device__ __forceinline__ double pb_box(const BatchView &b, int) { return b.box; }
+__device__ __forceinline__ double pb_box(const BatchView &, int r, const PerBoxView &pb) { return pb.box[r]; }
+__device__ __forceinline__ double pb_kappa(double kappa, int) { return kappa; }
+__device__ __forceinline__ double pb_kappa(double, int r, const PerBoxView &pb) { return pb.kappa[r]; }
+__device__ __forceinline__ const double *pb_cfac(const BatchView &b, int) { return b.cfac; }
+__device__ __forceinline__ const double *pb_cfac(const BatchView &, int r, const PerBoxView &pb)
+{
+    return pb.cfac + (int64_t)r * MMC_NK_STRIDE;
+}
+__device__ __forceinline__ const double *pb_tab(const double *tab, int) { return tab; }
+__device__ __forceinline__ const double *pb_tab(const double *, int r, const PerBoxView &pb);
+__device__ __forceinline__ void pb_comq_store(const BatchView &b, int r, int j, int d, double v)
+{
+    comq_store(b, r, j, d, v);
+}
+__device__ __forceinline__ void pb_comq_store(const BatchView &b, int r, int j, int d, double v,
+                                              const PerBoxView &pb)
+{
+    comq_store(b, r, j, d, v, 1.0 / pb.box[r]);
+}
+
 __device__ __forceinline__ SysView sys_view(const BatchView &b, int r)
 {
     SysView s;
@@ -261,6 +293,23 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_recip_energy(BatchView bv, int wh
     for (int k = threadIdx.x; k < bv.nkvecs; k += MMC_BLOCK) {
         const double re = S[2 * k], im = S[2 * k + 1];
         v[0] += bv.cfac[k] * (re * re - (-im) * im);
+    }
+    block_sum<1>(v, red, tot);
+    if (threadIdx.x == 0)
+        out[r] = tot[0];
+}
+
+// k_recip_energy with every replica's own cfac row ([R][MMC_NK_STRIDE])
+__global__ __launch_bounds__(MMC_BLOCK) void k_recip_energy_pb(BatchView bv, int which, double *out,
+                                                               const double *cfac_r)
+{
+    __shared__ double red[MMC_WAVES];
+    const int r = blockIdx.x;
+    const double *S = s_buf(bv, r, which), *cfac = cfac_r + (int64_t)r * MMC_NK_STRIDE;
+    double v[1] = { 0.0 }, tot[1];
+    for (int k = threadIdx.x; k < bv.nkvecs; k += MMC_BLOCK) {
+        const double re = S[2 * k], im = S[2 * k + 1];
+        v[0] += cfac[k] * (re * re - (-im) * im);
     }
     block_sum<1>(v, red, tot);
     if (threadIdx.x == 0)
@@ -696,6 +745,29 @@ __global__ void k_copy_segments(SnapSegs g)
     for (int q = 0; q < g.count; q++)
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.n[q]; i += stride)
             g.dst[q][i] = g.src[q][i];
+}
+
+// k_copy_segments per replica: segment q of replica r is n[q] 32-bit words at base + r * stride[q];
+// only replicas with mask[r] != 0 are copied (a volume move's snapshot of the replicas that move,
+// and the restoration of the ones that are rejected).  grid (blocks, R).
+struct SnapSegsR {
+    uint32_t *dst[MMC_SNAP_SEGS];
+    const uint32_t *src[MMC_SNAP_SEGS];
+    int64_t dst_stride[MMC_SNAP_SEGS], src_stride[MMC_SNAP_SEGS], n[MMC_SNAP_SEGS];
+    int count;
+};
+__global__ void k_copy_replicas(SnapSegsR g, const int32_t *mask)
+{
+    const int r = blockIdx.y;
+    if (!mask[r])
+        return;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int q = 0; q < g.count; q++) {
+        uint32_t *d = g.dst[q] + r * g.dst_stride[q];
+        const uint32_t *s = g.src[q] + r * g.src_stride[q];
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.n[q]; i += stride)
+            d[i] = s[i];
+    }
 }
 
 // AoS (Julia Vector{SVector{3,Float64}}) -> SoA for one replica; n elements.

@@ -226,8 +226,11 @@ struct GenArgs {
 // molecule and is substituted here like the move kernel does.  The flag byte (accept of the
 // previous step, S buffer) is therefore NOT part of these records: the move kernel takes it from
 // its `flagv` argument.
+// PerBox: empty = the batch's one box; PerBoxView = replica r wraps its translations with its
+// own box (mmc_kernels.hpp, pb_box).
+template <typename... PerBox>
 __global__ void k_propose(BatchView bv, const double *rec, MoveRec *ring, GenArgs ga, int r_base,
-                          int nr, int has_prev)
+                          int nr, int has_prev, PerBox... pb)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nr * ga.n_gen)
@@ -279,7 +282,7 @@ __global__ void k_propose(BatchView bv, const double *rec, MoveRec *ring, GenArg
         m.flags = u0.a < 0.5 ? 0 : 256; // (bit 8: the kind of the move, for a kernel that keeps the counts)
         if (u0.a < 0.5) { // translation: random_translate_vector + PBC, ei = quat[i] (:519-528)
             const double zeta[3] = { u0.b - 0.5, u1.a - 0.5, u1.b - 0.5 };
-            for (int k = 0; k < 3; k++) m.com_new[k] = pbc_wrap(com[k] + zeta[k] * sz.x, bv.box);
+            for (int k = 0; k < 3; k++) m.com_new[k] = pbc_wrap(com[k] + zeta[k] * sz.x, pb_box(bv, r, pb...));
             for (int q = 0; q < 4; q++) q_new[q] = q_old[q];
         } else {          // rotation: random_rotate_quaternion (:529-536)
             double e[3], norm;
@@ -303,7 +306,7 @@ __global__ void k_propose(BatchView bv, const double *rec, MoveRec *ring, GenArg
         mmc_space_fixed(m.com_new, A, ga.db, m.atoms_new);
         for (int q = 0; q < 4; q++) m.q_new[q] = q_new[q];
     } else {
-        const MoveXform x = propose_xform(ck, rs, bv.box, sz.x, sz.y, com);
+        const MoveXform x = propose_xform(ck, rs, pb_box(bv, r, pb...), sz.x, sz.y, com);
         m.flags = x.kind << 8;
         for (int q = 0; q < 3; q++) m.com_new[q] = x.com_new[q];
         for (int a = 0; a < 3; a++)

@@ -517,7 +517,7 @@ int32_t DeviceSystem::mol_energy(int i_base, int n_sel, bool lj, bool qq, int st
 
 int32_t DeviceSystem::recip_long_all(double *energies_host)
 {
-    if (R == 1 && uploaded && ewald_ready && nk == 5) { // one system: one launch, no copy
+    if (R == 1 && uploaded && ewald_ready && nk == 5 && !pb.on) { // one system: one launch, no copy
         PotOneOut o;
         MMC_TRY(potential_one(0.0, 0.0, false, true, &o));
         energies_host[0] = o.recip_e;
@@ -615,7 +615,8 @@ int32_t DeviceSystem::recip_long_enqueue(double *energies_host)
     // (the kernel has 8 bytes of static LDS besides; what the device grants is asked of the
     // device, and a refusal falls through to the column kernels below)
     const size_t lds_bytes = sizeof(double) * 7 * (size_t)n_atoms;
-    if (66 * R >= 16384 && (int64_t)lds_bytes + 64 <= lds_per_block && !recip_lds_refused
+    // (per-replica boxes: always the phase path below, its two box-dependent kernels per box)
+    if (!pb.on && 66 * R >= 16384 && (int64_t)lds_bytes + 64 <= lds_per_block && !recip_lds_refused
         && !getenv("MMC_NO_RECIP_LDS")) {
         if (!recip_lds_ready) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_recip_long_lds),
@@ -629,7 +630,7 @@ int32_t DeviceSystem::recip_long_enqueue(double *energies_host)
             }
         }
     }
-    if (66 * R >= 16384 && (int64_t)lds_bytes + 64 <= lds_per_block && recip_lds_ready
+    if (!pb.on && 66 * R >= 16384 && (int64_t)lds_bytes + 64 <= lds_per_block && recip_lds_ready
         && !getenv("MMC_NO_RECIP_LDS")) {
         k_recip_long_lds<<<(unsigned)R, RL_WAVES * 64, lds_bytes, stream>>>(bv, recip_order);
         k_recip_energy<<<(unsigned)R, MMC_BLOCK, 0, stream>>>(bv, 1, d_e);
@@ -641,9 +642,15 @@ int32_t DeviceSystem::recip_long_enqueue(double *energies_host)
     const size_t ph_bytes = sizeof(double) * 6 * (size_t)n_atoms * (size_t)R;
     if (!d_phase && ph_bytes <= ((size_t)8 << 30))
         MMC_TRY(dmalloc((void **)&d_phase, ph_bytes));
+    MMC_REQUIRE(d_phase || !pb.on, MMC_ERR_UNSUPPORTED,
+                "per-replica boxes: %lld replicas of %lld atoms are too many for the phase array",
+                (long long)R, (long long)n_atoms);
     if (d_phase) {
         dim3 ga((unsigned)((n_atoms + 255) / 256), (unsigned)R);
-        k_atom_phases<<<ga, 256, 0, stream>>>(bv, d_phase);
+        if (pb.on)
+            k_atom_phases_pb<<<ga, 256, 0, stream>>>(bv, d_phase, pb.d_box);
+        else
+            k_atom_phases<<<ga, 256, 0, stream>>>(bv, d_phase);
         // few replicas: split the atoms over up to 16 chunks so that the chip is busy
         int n_chunks = 1;
         if (66 * R < 1024) {
@@ -668,7 +675,10 @@ int32_t DeviceSystem::recip_long_enqueue(double *energies_host)
     } else {
         k_recip_long<<<grid, MMC_BLOCK, 0, stream>>>(bv);
     }
-    k_recip_energy<<<(unsigned)R, MMC_BLOCK, 0, stream>>>(bv, 1, d_e);
+    if (pb.on)
+        k_recip_energy_pb<<<(unsigned)R, MMC_BLOCK, 0, stream>>>(bv, 1, d_e, pb.cfac);
+    else
+        k_recip_energy<<<(unsigned)R, MMC_BLOCK, 0, stream>>>(bv, 1, d_e);
     MMC_HIP(hipGetLastError());
     MMC_HIP(hipMemcpyAsync(energies_host, d_e, sizeof(double) * R, hipMemcpyDeviceToHost,
                            stream));
@@ -723,7 +733,7 @@ int32_t DeviceSystem::pair_totals_enqueue(double lj_rcut, double qq_rcut,
     const PairParams pp = mmc_pair_params(lj_rcut, qq_rcut, 0.0, 0.5, bv.kappa, false);
     ht.resize(R);
     TotalsRaw *d_t = (TotalsRaw *)d_scr;
-    *fast = fast_table_ok(qq_rcut);
+    *fast = pb.on || fast_table_ok(qq_rcut); // (mmc_batch_set_boxes checked the table's domain)
     if (!*fast)
         return MMC_OK;
     // k_total_wave: a wave per pair of molecules (u, n_mol - 1 - u), see mmc_wave.hpp
@@ -739,7 +749,26 @@ int32_t DeviceSystem::pair_totals_enqueue(double lj_rcut, double qq_rcut,
     // replicas, the working set outgrows the 4 MB L2s and the hit rate drops to 46 %: measured,
     // 5.2 MB of fabric traffic per evaluation instead of ~1.)
     const int64_t wgs = (n_units + WV_WAVES - 1) / WV_WAVES;
-    if (image_by_molecule(std::max(pp.lj_gate_sq, pp.qq_gate_sq)) && pairs_inside_slack(pp.qq_gate_sq, pp.qq_slack_sq)
+    if (pb.on) {
+        // per-replica boxes: k_total_wave once per replica, on a view in which replica r is
+        // replica 0 with its own box, kappa and table (the prefilter codes first: the commit
+        // kernels of the move driver write them as fractions of bv.box)
+        dim3 gq((unsigned)((n_mol + 255) / 256), (unsigned)R);
+        k_comq_pb<<<gq, 256, 0, stream>>>(bv, pb.d_box);
+        const int64_t wgs1 = (units + WV_WAVES - 1) / WV_WAVES;
+        for (int64_t r = 0; r < R; r++) {
+            BatchView v = bv;
+            v.comx += r * bv.mol_stride; v.comy += r * bv.mol_stride; v.comz += r * bv.mol_stride;
+            v.ax += r * bv.atom_stride; v.ay += r * bv.atom_stride; v.az += r * bv.atom_stride;
+            v.comq += r * 3 * bv.cq_stride;
+            v.box = pb.box[r];
+            v.kappa = pb.kappa[r];
+            const PairParams ppr = mmc_pair_params(lj_rcut, qq_rcut, 0.0, 0.5, pb.kappa[r], false);
+            k_total_wave<false><<<(unsigned)wgs1, WV_WAVES * 64, 0, stream>>>(
+                v, rec + r * n_mol * MMC_RSTRIDE, pb.tab + r * MMC_QQ_TABLE_DOUBLES, fc, ppr,
+                d_tparts + r * units, units, units, paired);
+        }
+    } else if (image_by_molecule(std::max(pp.lj_gate_sq, pp.qq_gate_sq)) && pairs_inside_slack(pp.qq_gate_sq, pp.qq_slack_sq)
         && pairs_inside_slack(pp.lj_gate_sq, pp.lj_slack_sq))
         k_total_wave<true><<<(unsigned)wgs, WV_WAVES * 64, 0, stream>>>(bv, rec, qq_tab, fc, pp, d_tparts,
                                                                         units, (int)n_units, paired);
@@ -762,6 +791,10 @@ int32_t DeviceSystem::pair_totals_finish(double lj_rcut, double qq_rcut,
     for (int64_t r = 0; fast && r < R; r++)
         if (ht[r].n_ovl)
             need_generic = true; // overlap sentinel
+    if (pb.on) { // (the per-molecule kernels know one box: totals_ewald reports the overlap)
+        MMC_REQUIRE(fast, MMC_ERR_UNSUPPORTED, "per-replica boxes need the erfc table's fast path");
+        return MMC_OK;
+    }
     if (need_generic) {
         const PairParams pp = mmc_pair_params(lj_rcut, qq_rcut, 0.0, 0.5, bv.kappa, false);
         TotalsRaw *d_t = (TotalsRaw *)d_scr;
@@ -858,6 +891,77 @@ int32_t DeviceSystem::snapshot_restore()
     return MMC_OK;
 }
 
+// ---- per-replica boxes (mmc_perbox.inc) ----------------------------------------------------------
+int32_t DeviceSystem::pb_upload_scalars()
+{
+    MMC_HIP(hipMemcpyAsync(pb.d_box, pb.box.data(), sizeof(double) * R, hipMemcpyHostToDevice, stream));
+    MMC_HIP(hipMemcpyAsync(pb.d_kappa, pb.kappa.data(), sizeof(double) * R, hipMemcpyHostToDevice, stream));
+    return sync(); // (pageable host arrays)
+}
+
+// cfac rows (PrepareEwaldVariables, ewalds.jl:45-103, over the shared k list) and erfc tables of
+// the replicas in d_mask (NULL: all) for their current box and kappa
+int32_t DeviceSystem::pb_build_tables(const int32_t *d_mask)
+{
+    dim3 gc((unsigned)((nkvecs + 63) / 64), (unsigned)R);
+    k_cfac_pb<<<gc, 64, 0, stream>>>(bv.kxyz, (int)nkvecs, pb.d_kappa, pb.d_box, pb.cfac, d_mask,
+                                     half_k ? 1 : 0);
+    dim3 gt((unsigned)((MMC_QQ_NROW + 63) / 64), (unsigned)R);
+    k_build_qq_table<<<gt, 64, 0, stream>>>(0.0, pb.tab, PerBoxTable{ pb.d_kappa, d_mask });
+    MMC_HIP(hipGetLastError());
+    return MMC_OK;
+}
+
+// take: copy the replicas in d_mask aside; else: copy them back.  Everything a volume trial
+// rewrites: coordinates in their three layouts, the fixed-point centres of mass, both S(k)
+// buffers, the cfac row and the table (box and kappa are the caller's, on the host).
+int32_t DeviceSystem::pb_snapshot(const int32_t *d_mask, bool take)
+{
+    if (!pb.snap) {
+        struct Seg { void *p; int64_t per; };
+        const int nsb = R == 1 ? 4 : 2;
+        const Seg segs[] = {
+            { bv.comx, (int64_t)sizeof(double) * bv.mol_stride },
+            { bv.comy, (int64_t)sizeof(double) * bv.mol_stride },
+            { bv.comz, (int64_t)sizeof(double) * bv.mol_stride },
+            { bv.ax, (int64_t)sizeof(double) * bv.atom_stride },
+            { bv.ay, (int64_t)sizeof(double) * bv.atom_stride },
+            { bv.az, (int64_t)sizeof(double) * bv.atom_stride },
+            { rec, (int64_t)sizeof(double) * MMC_RSTRIDE * n_mol },
+            { bv.comq, (int64_t)sizeof(uint16_t) * 3 * bv.cq_stride },
+            { bv.S, (int64_t)sizeof(double) * 2 * nsb * MMC_NK_STRIDE },
+            { pb.cfac, (int64_t)sizeof(double) * MMC_NK_STRIDE },
+            { pb.tab, (int64_t)sizeof(double) * MMC_QQ_TABLE_DOUBLES },
+        };
+        int64_t total = 0;
+        for (const Seg &g : segs)
+            total += (g.per + 15) / 16 * 16 * R;
+        MMC_TRY(dmalloc((void **)&pb.snap, (size_t)total));
+        int64_t off = 0;
+        int c = 0;
+        for (const Seg &g : segs) {
+            const int64_t per = (g.per + 15) / 16 * 16; // (every per-replica size is a multiple of 4 bytes)
+            uint32_t *d = pb.snap + off / 4;
+            pb.to_snap.dst[c] = d;
+            pb.to_snap.src[c] = reinterpret_cast<const uint32_t *>(g.p);
+            pb.to_snap.dst_stride[c] = per / 4;
+            pb.to_snap.src_stride[c] = g.per / 4;
+            pb.from_snap.dst[c] = reinterpret_cast<uint32_t *>(g.p);
+            pb.from_snap.src[c] = d;
+            pb.from_snap.dst_stride[c] = g.per / 4;
+            pb.from_snap.src_stride[c] = per / 4;
+            pb.to_snap.n[c] = pb.from_snap.n[c] = g.per / 4;
+            off += per * R;
+            c++;
+        }
+        pb.to_snap.count = pb.from_snap.count = c;
+    }
+    dim3 grid(64, (unsigned)R);
+    k_copy_replicas<<<grid, 256, 0, stream>>>(take ? pb.to_snap : pb.from_snap, d_mask);
+    MMC_HIP(hipGetLastError());
+    return MMC_OK;
+}
+
 // potential(..., "ewald") for every replica (energy.jl:946-1032)
 int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *tot)
 {
@@ -870,7 +974,7 @@ int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *t
     std::vector<TotalsRaw> ht;
     std::vector<double> erec(R);
     bool fast = false;
-    if (R == 1 && nk == 5 && !getenv("MMC_NO_POT_ONE")) { // one system: one launch (mmc_potential.hpp)
+    if (R == 1 && nk == 5 && !pb.on && !getenv("MMC_NO_POT_ONE")) { // one system: one launch (mmc_potential.hpp)
         fast = fast_table_ok(qq_rcut);
         PotOneOut o;
         MMC_TRY(potential_one(lj_rcut, qq_rcut, fast, true, &o));
@@ -884,8 +988,9 @@ int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *t
     }
     MMC_TRY(pair_totals_finish(lj_rcut, qq_rcut, ht, fast));
     const double factor = bv.factor;
-    const double self = -bv.kappa * sq2 / sqrt(3.141592653589793) * factor; // ewalds.jl:832
     for (int64_t r = 0; r < R; r++) {
+        const double kappa = pb.on ? pb.kappa[r] : bv.kappa;
+        const double self = -kappa * sq2 / sqrt(3.141592653589793) * factor; // ewalds.jl:832
         mmc_totals t;
         memset(&t, 0, sizeof(t));
         t.energy = ht[r].lj_e / 2; // energy.jl:978-980
@@ -901,6 +1006,8 @@ int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *t
         t.energy += self; t.coulomb += self; t.virial += self / 3.0; // :1017-1021
         t.self = self;
         t.n_overlap = ht[r].n_ovl;
+        if (pb.on && ht[r].n_ovl) // (per-replica boxes: no per-molecule fallback, see mmc_hip.h)
+            t.energy = INFINITY;
         tot[r] = t;
     }
     return MMC_OK;

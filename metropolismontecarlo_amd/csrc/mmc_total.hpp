@@ -236,6 +236,91 @@ __global__ void k_rescale(BatchView bv, double *rec, double f)
     }
 }
 
+// k_rescale for a batch with per-replica boxes: replica r scales by f[r] = L_new / L_old and its
+// fixed-point centres of mass become fractions of new_box[r]; f[r] == 0: replica r stays.
+// grid (ceil(n_mol/256), R).
+__global__ void k_rescale_pb(BatchView bv, double *rec, const double *f, const double *new_box)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (j >= bv.n_mol || f[r] == 0.0)
+        return;
+    const double fr = f[r];
+    const int64_t m = r * bv.mol_stride + j;
+    double *c[3] = { bv.comx + m, bv.comy + m, bv.comz + m };
+    double d[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double old = *c[k], nw = old * fr;
+        d[k] = nw - old;
+        *c[k] = nw;
+    }
+    const int fa = bv.first0[j], na = bv.cnt[j];
+    for (int a = 0; a < na; a++) {
+        const int64_t o = r * bv.atom_stride + fa + a;
+        bv.ax[o] += d[0]; bv.ay[o] += d[1]; bv.az[o] += d[2];
+    }
+    if (rec) {
+        const double inv_box = 1.0 / new_box[r];
+        double *o = rec + ((int64_t)r * bv.n_mol + j) * MMC_RSTRIDE;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const int64_t s = r * bv.atom_stride + fa + a;
+            o[3 * a] = bv.ax[s]; o[3 * a + 1] = bv.ay[s]; o[3 * a + 2] = bv.az[s];
+        }
+        o[9] = *c[0]; o[10] = *c[1]; o[11] = *c[2];
+        comq_store(bv, r, j, 0, o[9], inv_box); comq_store(bv, r, j, 1, o[10], inv_box);
+        comq_store(bv, r, j, 2, o[11], inv_box);
+    }
+}
+
+// The fixed-point centres of mass of every replica from its coordinates and its own box (the
+// commit kernels of the move driver write them as fractions of bv.box).  grid (ceil(n_mol/256), R).
+__global__ void k_comq_pb(BatchView bv, const double *box_r)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (j >= bv.n_mol)
+        return;
+    const double inv_box = 1.0 / box_r[r];
+    const int64_t m = r * bv.mol_stride + j;
+    comq_store(bv, r, j, 0, bv.comx[m], inv_box);
+    comq_store(bv, r, j, 1, bv.comy[m], inv_box);
+    comq_store(bv, r, j, 2, bv.comz[m], inv_box);
+}
+
+// cfac of k_kvec_setup (ewalds.jl:52,79-83) for every replica's own kappa and box, over the shared
+// k-vector list; only where mask[r] != 0 (mask NULL: every replica).  grid (ceil(nkvecs/64), R).
+__global__ void k_cfac_pb(const int32_t *kxyz, int nkvecs, const double *kappa, const double *box_r,
+                          double *cfac, const int32_t *mask, int half)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (k >= nkvecs || (mask && !mask[r]))
+        return;
+    const double box = box_r[r], kap = kappa[r];
+    const double b = 1.0 / 4.0 / kap / kap / box / box; // :52
+    const double twopi = MMC_TWOPI, twopi_sq = twopi * twopi;
+    const int kx = kxyz[3 * k], ky = kxyz[3 * k + 1], kz = kxyz[3 * k + 2];
+    const double kr_sq = twopi_sq * (double)(kx * kx + ky * ky + kz * kz); // :79
+    double cf = twopi * exp(-b * kr_sq) / kr_sq / box;                    // :80
+    if (kx > 0 || half)
+        cf = cf * 2.0;                                                    // :81-83
+    cfac[(int64_t)r * MMC_NK_STRIDE + k] = cf;
+}
+
+// k_atom_phases with every replica's own box
+__global__ void k_atom_phases_pb(BatchView bv, double *ph, const double *box_r)
+{
+    const int l = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (l >= bv.n_atoms)
+        return;
+    const double L = box_r[r];
+    const int64_t a = r * bv.atom_stride + l;
+    double *o = ph + ((int64_t)r * bv.n_atoms + l) * 6;
+    double sn, cs;
+    sincos_moderate(MMC_TWOPI * bv.ax[a] / L, sn, cs); o[0] = cs; o[1] = sn;
+    sincos_moderate(MMC_TWOPI * bv.ay[a] / L, sn, cs); o[2] = cs; o[3] = sn;
+    sincos_moderate(MMC_TWOPI * bv.az[a] / L, sn, cs); o[4] = cs; o[5] = sn;
+}
+
 // cos/sin of 2 pi c / L for the three coordinates of every atom (ewalds.jl:564-569), once.
 // ph[r][l][0..5] = cos x, sin x, cos y, sin y, cos z, sin z
 __global__ void k_atom_phases(BatchView bv, double *ph)

@@ -403,6 +403,58 @@ class Batch:
         check(self._L.mmc_batch_run_npt(self._h, C.byref(p), C.byref(q), _d(e), C.byref(st), C.byref(ns)))
         return float(e[0]), st.asdict(), ns.asdict()
 
+    def set_boxes(self, boxes, alpha=5.6):
+        """mmc_batch_set_boxes: per-replica mode, replica r in box boxes[r] with kappa = alpha /
+        boxes[r].  The coordinates are not rescaled; call recip_long() afterwards."""
+        bx = _f64(boxes).ravel()
+        if bx.shape[0] != self.R:
+            raise ValueError(f"one box per replica: {self.R} expected, {bx.shape[0]} given")
+        check(self._L.mmc_batch_set_boxes(self._h, _d(bx), float(alpha)))
+
+    def get_boxes(self):
+        out = np.empty(self.R)
+        check(self._L.mmc_batch_get_boxes(self._h, _d(out)))
+        return out
+
+    def volume_trial_replicas(self, new_boxes):
+        """mmc_batch_volume_trial_replicas: new_boxes[r] == 0 leaves replica r in place.  Returns
+        the totals of every replica at its trial box (numpy record array, _lib.TOTALS_DTYPE).
+        Follow with volume_settle()."""
+        nb = _f64(new_boxes).ravel()
+        if nb.shape[0] != self.R:
+            raise ValueError(f"one box per replica: {self.R} expected, {nb.shape[0]} given")
+        out = np.zeros(self.R, dtype=TOTALS_DTYPE)
+        check(self._L.mmc_batch_volume_trial_replicas(self._h, _d(nb),
+                                                      out.ctypes.data_as(C.POINTER(Totals))))
+        return out
+
+    def volume_settle(self, accept):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(accept), (self.R,)), dtype=np.int32)
+        check(self._L.mmc_batch_volume_settle(self._h, a.ctypes.data_as(_i32p)))
+
+    def run_npt_replicas(self, n_sweeps, temperature, pressure, vmax, dr_max, dphi_max, seed,
+                         energies, moves_per_sweep=0, alpha=5.6, n_parts=0, n_threads=1,
+                         pressures=None, replica0=0):
+        """mmc_batch_run_npt_replicas: mmc_batch_run_npt's chain for every replica of a batch with
+        per-replica boxes; `pressures` (R values) overrides `pressure` per replica.  Returns
+        (energies, run stats, [per-replica npt stats])."""
+        from ._lib import NptParams, NptStats
+        p = RunParams(float(temperature), float(dr_max), float(dphi_max), int(seed), 0, 1,
+                      int(n_parts), 0, int(n_threads), 0, 0, int(replica0))
+        q = NptParams(float(pressure), float(vmax), float(alpha), int(n_sweeps), int(moves_per_sweep))
+        e = _f64(energies).ravel().copy()
+        if e.shape[0] != self.R:
+            raise ValueError(f"one energy per replica: {self.R} expected, {e.shape[0]} given")
+        pr = None
+        if pressures is not None:
+            pr = _f64(pressures).ravel()
+            if pr.shape[0] != self.R:
+                raise ValueError(f"one pressure per replica: {self.R} expected, {pr.shape[0]} given")
+        st, ns = RunStats(), (NptStats * self.R)()
+        check(self._L.mmc_batch_run_npt_replicas(self._h, C.byref(p), C.byref(q),
+                                                 None if pr is None else _d(pr), _d(e), C.byref(st), ns))
+        return e, st.asdict(), [x.asdict() for x in ns]
+
     def qq_table(self, r2):
         r2 = _f64(r2).ravel()
         out = np.empty_like(r2)

@@ -473,6 +473,62 @@ function run_npt!(b::Batch, params::MMCRunParams, npt::MMCNptParams, energy::Vec
     return st[], ns[]
 end
 
+"""
+    set_boxes!(b, boxes; alpha = 5.6);  boxes = get_boxes(b)
+
+Per-replica boxes (independent NPT replicas in one batch): replica r lives in `boxes[r]` with
+kappa = alpha / boxes[r] (main.jl:290-291).  The coordinates are not rescaled; call
+`recip_long(b)` afterwards.
+"""
+function set_boxes!(b::Batch, boxes::Vector{Float64}; alpha::Float64 = 5.6)
+    length(boxes) == b.n_replicas || error("one box per replica")
+    check(ccall((:mmc_batch_set_boxes, libmmc), Int32, (Ptr{Cvoid}, Ptr{Float64}, Float64),
+                b.h, boxes, alpha))
+end
+function get_boxes(b::Batch)
+    boxes = Vector{Float64}(undef, b.n_replicas)
+    check(ccall((:mmc_batch_get_boxes, libmmc), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h, boxes))
+    return boxes
+end
+
+"""
+    tot = volume_trial_replicas!(b, new_boxes); ...; volume_settle!(b, accept)
+
+One batched volume trial of a batch with per-replica boxes (`new_boxes[r] == 0`: replica r stays),
+then the decisions: a rejected or unmoved replica gets its state back bit for bit.
+"""
+function volume_trial_replicas!(b::Batch, new_boxes::Vector{Float64})
+    length(new_boxes) == b.n_replicas || error("one box per replica")
+    tot = Vector{MMCTotals}(undef, b.n_replicas)
+    check(ccall((:mmc_batch_volume_trial_replicas, libmmc), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{MMCTotals}), b.h, new_boxes, tot))
+    return tot
+end
+function volume_settle!(b::Batch, accept::Vector{Int32})
+    length(accept) == b.n_replicas || error("one decision per replica")
+    check(ccall((:mmc_batch_volume_settle, libmmc), Int32, (Ptr{Cvoid}, Ptr{Int32}), b.h, accept))
+end
+
+"""
+    (run_stats, npt_stats) = run_npt_replicas!(b, params, npt, energies; pressures = nothing)
+
+`run_npt!`'s chain for every replica of a batch with per-replica boxes; `pressures` (one per
+replica) overrides `npt.pressure`.  `npt_stats` has one `MMCNptStats` per replica.
+"""
+function run_npt_replicas!(b::Batch, params::MMCRunParams, npt::MMCNptParams, energies::Vector{Float64};
+                           pressures::Union{Nothing,Vector{Float64}} = nothing)
+    length(energies) == b.n_replicas || error("one energy per replica")
+    p = Ref(params); q = Ref(npt); st = Ref{MMCRunStats}()
+    ns = Vector{MMCNptStats}(undef, b.n_replicas)
+    pr = pressures === nothing ? Ptr{Float64}(C_NULL) : pointer(pressures)
+    GC.@preserve pressures begin
+        check(ccall((:mmc_batch_run_npt_replicas, libmmc), Int32,
+                    (Ptr{Cvoid}, Ptr{MMCRunParams}, Ptr{MMCNptParams}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{MMCRunStats}, Ptr{MMCNptStats}), b.h, p, q, pr, energies, st, ns))
+    end
+    return st[], ns
+end
+
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
 """
     id = dist_unique_id()                       # rank 0; send the 128 bytes to the other ranks

@@ -1,0 +1,41 @@
+"""CPU tests of the per-replica-box entry points (mmc_batch_set_boxes and the batched NPT move):
+declared, exported, bound, and loud on a bad handle without touching a device."""
+import ctypes as C
+
+import pytest
+
+from metropolismontecarlo_amd import _lib
+
+NEW = ("mmc_batch_set_boxes", "mmc_batch_get_boxes", "mmc_batch_volume_trial_replicas",
+       "mmc_batch_volume_settle", "mmc_batch_run_npt_replicas")
+
+
+def test_per_box_symbols_are_declared_exported_and_bound():
+    from test_abi import header_functions
+    names = header_functions()
+    L = C.CDLL(_lib.LIB_PATH)
+    for n in NEW:
+        assert n in names, n
+        assert hasattr(L, n), n
+        assert n in _lib.SIGNATURES, n
+        assert getattr(_lib.lib(), n).argtypes is not None, n
+
+
+def test_per_box_entry_points_fail_loudly_on_a_null_batch():
+    L = _lib.lib()
+    d = (C.c_double * 4)(30.0, 30.0, 30.0, 30.0)
+    acc = (C.c_int32 * 4)()
+    tot = (_lib.Totals * 4)()
+    p, q, st = _lib.RunParams(), _lib.NptParams(), _lib.RunStats()
+    ns = (_lib.NptStats * 4)()
+    calls = [lambda: L.mmc_batch_set_boxes(None, d, 5.6),
+             lambda: L.mmc_batch_get_boxes(None, d),
+             lambda: L.mmc_batch_volume_trial_replicas(None, d, tot),
+             lambda: L.mmc_batch_volume_settle(None, acc),
+             lambda: L.mmc_batch_run_npt_replicas(None, C.byref(p), C.byref(q), None, d,
+                                                  C.byref(st), ns)]
+    for call in calls:
+        status = call()
+        assert status != 0
+        with pytest.raises(_lib.MMCError, match="MMC_ERR_ARG"):
+            _lib.check(status)
