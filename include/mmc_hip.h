@@ -379,6 +379,11 @@ int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t value);
 /* The fast kernel's approximation of erfc(kappa r)/r (ewalds.jl:367) evaluated at n values of
  * r^2 in (0, 256): lets a test bound its error against an exact evaluation. */
 int32_t mmc_batch_qq_table(mmc_batch *b, const double *r2, int64_t n, double *out);
+/* mmc_batch_qq_table for replica `replica` of a batch with per-replica boxes: its own table and
+ * kappa = alpha / boxes[replica] (mmc_batch_set_boxes).  On a one-box batch: the shared table.  An
+ * out-of-range replica returns MMC_ERR_ARG, like the arguments mmc_batch_qq_table refuses. */
+int32_t mmc_batch_qq_table_replica(mmc_batch *b, int64_t replica, const double *r2, int64_t n,
+                                   double *out);
 /* Radial-distribution histogram over every replica of the batch: the intent of Ewald/gr.jl
  * `makeRDF` with each replica as one frame.  One site per molecule -- site >= 0: that atom slot
  * (0 = the oxygens of water), site < 0: the centre of mass (gr.jl's cm mode); all pairs i < j,

@@ -165,6 +165,7 @@ SIGNATURES = {
     "mmc_batch_set_parts": [_vp, _i32],
     "mmc_batch_set_option": [_vp, C.c_char_p, _i64],
     "mmc_batch_qq_table": [_vp, _dp, _i64, _dp],
+    "mmc_batch_qq_table_replica": [_vp, _i64, _dp, _i64, _dp],
     "mmc_batch_settle": [_vp, _i32p],
     "mmc_batch_get_trace": [_vp, _dp, C.POINTER(C.c_uint8)],
     "mmc_batch_set_orientations": [_vp, _dp, _dp, _i32],

@@ -952,12 +952,12 @@ extern "C" int32_t mmc_batch_volume_reject(mmc_batch *b)
     return MMC_OK;
 }
 
-extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, double *out)
+// qq_pair of table `tab` at kappa for n values of r^2 (mmc_batch_qq_table and _replica)
+static int32_t eval_qq_table(mmc_batch *b, const double *tab, double kappa, const double *u, int64_t n,
+                             double *out)
 {
-    BATCH_CHECK(b);
-    BATCH_ONE_BOX(b, "mmc_batch_qq_table");
     MMC_REQUIRE(u && out && n >= 0, MMC_ERR_ARG, "bad argument");
-    MMC_REQUIRE(b->sys.qq_tab, MMC_ERR_STATE, "no table built");
+    MMC_REQUIRE(tab, MMC_ERR_STATE, "no table built");
     if (n == 0)
         return MMC_OK;
     for (int64_t i = 0; i < n; i++)
@@ -970,8 +970,8 @@ extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, 
     MMC_HIP(hipMalloc((void **)&d_u, sizeof(double) * 2 * n));
     hipError_t e = hipMemcpyAsync(d_u, u, sizeof(double) * n, hipMemcpyHostToDevice, s.stream);
     if (e == hipSuccess) {
-        k_eval_qq_table<<<(unsigned)((n + 255) / 256), 256, 0, s.stream>>>(
-            s.qq_tab, s.bv.kappa, d_u, d_u + n, (int)n);
+        k_eval_qq_table<<<(unsigned)((n + 255) / 256), 256, 0, s.stream>>>(tab, kappa, d_u, d_u + n,
+                                                                           (int)n);
         e = hipGetLastError();
     }
     if (e == hipSuccess)
@@ -982,6 +982,25 @@ extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, 
     MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "qq_table evaluation failed: %s",
                 hipGetErrorString(e));
     return MMC_OK;
+}
+
+extern "C" int32_t mmc_batch_qq_table(mmc_batch *b, const double *u, int64_t n, double *out)
+{
+    BATCH_CHECK(b);
+    BATCH_ONE_BOX(b, "mmc_batch_qq_table");
+    return eval_qq_table(b, b->sys.qq_tab, b->sys.bv.kappa, u, n, out);
+}
+
+extern "C" int32_t mmc_batch_qq_table_replica(mmc_batch *b, int64_t replica, const double *u, int64_t n,
+                                              double *out)
+{
+    BATCH_CHECK(b);
+    const DeviceSystem &s = b->sys;
+    MMC_REQUIRE(replica >= 0 && replica < s.R, MMC_ERR_ARG, "replica %lld out of range [0, %lld)",
+                (long long)replica, (long long)s.R);
+    if (!s.pb.on)
+        return eval_qq_table(b, s.qq_tab, s.bv.kappa, u, n, out);
+    return eval_qq_table(b, s.pb.tab + replica * MMC_QQ_TABLE_DOUBLES, s.pb.kappa[replica], u, n, out);
 }
 
 extern "C" int32_t mmc_batch_rdf(mmc_batch *b, int32_t site, int32_t numbins, uint64_t *hist)

@@ -1006,8 +1006,10 @@ int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *t
         t.energy += self; t.coulomb += self; t.virial += self / 3.0; // :1017-1021
         t.self = self;
         t.n_overlap = ht[r].n_ovl;
-        if (pb.on && ht[r].n_ovl) // (per-replica boxes: no per-molecule fallback, see mmc_hip.h)
+        if (pb.on && ht[r].n_ovl) { // (per-replica boxes: no per-molecule fallback, see mmc_hip.h)
             t.energy = INFINITY;
+            t.n_overlap = 1;        // (a flag: the pair kernels do not count molecules)
+        }
         tot[r] = t;
     }
     return MMC_OK;

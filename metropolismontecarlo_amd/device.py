@@ -455,10 +455,16 @@ class Batch:
                                                  None if pr is None else _d(pr), _d(e), C.byref(st), ns))
         return e, st.asdict(), [x.asdict() for x in ns]
 
-    def qq_table(self, r2):
+    def qq_table(self, r2, replica=None):
+        """The fast kernel's erfc(kappa r)/r at r^2: mmc_batch_qq_table, or with `replica`
+        mmc_batch_qq_table_replica (that replica's own table and kappa under per-replica boxes)."""
         r2 = _f64(r2).ravel()
         out = np.empty_like(r2)
-        check(self._L.mmc_batch_qq_table(self._h, _d(r2), r2.shape[0], _d(out)))
+        if replica is None:
+            check(self._L.mmc_batch_qq_table(self._h, _d(r2), r2.shape[0], _d(out)))
+        else:
+            check(self._L.mmc_batch_qq_table_replica(self._h, int(replica), _d(r2), r2.shape[0],
+                                                     _d(out)))
         return out
 
     def run(self, n_steps, temperature, dr_max, dphi_max, seed, energies=None, n_groups=2,

@@ -136,11 +136,15 @@ def chain_states():
     return nist4_boxes(CHAIN["factors"])
 
 
-def oracle_npt_chain(orc, a, replica, pressure, vmax, seed, n_sweeps, per_sweep, rc=RCUT):
+def oracle_npt_chain(orc, a, replica, pressure, vmax, seed, n_sweeps, per_sweep, rc=RCUT,
+                     lj_rc=None, log=None):
     """mmc_batch_run_npt's rule for one chain, on the oracle: proposals rebuilt from the Philox
     draws of (seed, replica), dU from orc.trial_move, the volume move's uniforms from slot
     MMC_SLOT_VOLUME, its energy from orc.potential_ewald on coordinates rescaled on the host
-    (volumeChange.jl:59-147).  Returns (box, com, coords, energy, trial accepts, volume accepts)."""
+    (volumeChange.jl:59-147).  rc is the Coulomb cutoff, lj_rc the LJ one (default rc).  `log`, a
+    list, gets each sweep's volume move: "refused" (box below 2 r_cut), "accepted" or "rejected".
+    Returns (box, com, coords, energy, trial accepts, volume accepts)."""
+    lj_rc = rc if lj_rc is None else lj_rc
     from test_gpu_batch import _rigid_proposal
     from test_gpu_moves import philox_pair
     n_mol = a["com"].shape[0]
@@ -148,14 +152,14 @@ def oracle_npt_chain(orc, a, replica, pressure, vmax, seed, n_sweeps, per_sweep,
     s = common.oracle_system(cur)
     box = a["box"]
     ew = orc.Ewald(ALPHA / box, 5, 27, box)
-    energy = orc.potential_ewald(s, ew, rc, rc)["energy"]
+    energy = orc.potential_ewald(s, ew, lj_rc, rc)["energy"]
     step, n_acc, n_acc_vol = 0, 0, 0
     for sweep in range(n_sweeps):
         for k in range(per_sweep):
             i = k % n_mol                                   # every run restarts its sweep (main.jl:490)
             kind, c_new, a_new, u = _rigid_proposal(seed, replica, step, s.com[i].copy(),
                                                     s.coords[3 * i:3 * i + 3].copy(), box, DR, DPHI)
-            d, ov = orc.trial_move(i + 1, s, ew, rc, rc, c_new, a_new)
+            d, ov = orc.trial_move(i + 1, s, ew, lj_rc, rc, c_new, a_new)
             delta = d[0] + d[1] + d[2]
             x = delta / T
             if (x < 0.0 or math.exp(-x) > u) and not ov:
@@ -171,17 +175,23 @@ def oracle_npt_chain(orc, a, replica, pressure, vmax, seed, n_sweeps, per_sweep,
         vol_old = box ** 3
         vol_new = vol_old + (ua - 0.5) * vmax                   # volumeChange.jl:59
         L_new = vol_new ** (1.0 / 3.0)
-        if rc > L_new / 2:
+        if max(rc, lj_rc) > L_new / 2:
+            if log is not None:
+                log.append("refused")
             continue
         a2 = host_rescale(dict(cur, com=s.com.copy(), coords=s.coords.copy(), box=box), L_new)
         s2 = common.oracle_system(a2)
         ew2 = orc.Ewald(ALPHA / L_new, 5, 27, L_new)
-        e_new = orc.potential_ewald(s2, ew2, rc, rc)["energy"]
+        e_new = orc.potential_ewald(s2, ew2, lj_rc, rc)["energy"]
         arg = -(1.0 / T) * (pressure * (vol_new - vol_old) - n_mol * math.log(vol_new / vol_old) * T
                             + (e_new - energy))                 # :129-130
         if ub < math.exp(min(arg, 700.0)):                      # :132
             s, ew, box, energy, cur = s2, ew2, L_new, e_new, a2
             n_acc_vol += 1
+            if log is not None:
+                log.append("accepted")
+        elif log is not None:
+            log.append("rejected")
     return box, s.com, s.coords, energy, n_acc, n_acc_vol
 
 

@@ -7,7 +7,7 @@ import pytest
 from metropolismontecarlo_amd import _lib
 
 NEW = ("mmc_batch_set_boxes", "mmc_batch_get_boxes", "mmc_batch_volume_trial_replicas",
-       "mmc_batch_volume_settle", "mmc_batch_run_npt_replicas")
+       "mmc_batch_volume_settle", "mmc_batch_run_npt_replicas", "mmc_batch_qq_table_replica")
 
 
 def test_per_box_symbols_are_declared_exported_and_bound():
@@ -33,7 +33,8 @@ def test_per_box_entry_points_fail_loudly_on_a_null_batch():
              lambda: L.mmc_batch_volume_trial_replicas(None, d, tot),
              lambda: L.mmc_batch_volume_settle(None, acc),
              lambda: L.mmc_batch_run_npt_replicas(None, C.byref(p), C.byref(q), None, d,
-                                                  C.byref(st), ns)]
+                                                  C.byref(st), ns),
+             lambda: L.mmc_batch_qq_table_replica(None, 0, d, 1, d)]
     for call in calls:
         status = call()
         assert status != 0
