@@ -403,7 +403,12 @@ int32_t mmc_batch_rdf(mmc_batch *b, int32_t site, int32_t numbins, uint64_t *his
  * norm is off by more than 1e-6 returns MMC_ERR_ASSERT (the reference prints and exit()s,
  * quaternions.jl:20-25).  An accepted move commits its quaternion (`totProps.quat[i] = ei`,
  * main.jl:619).  The coordinates given at creation are the caller's: the reference builds them
- * from the same quaternions (MakeAtomArrays, Ewald/setup.jl:447-537). */
+ * from the same quaternions (MakeAtomArrays, Ewald/setup.jl:447-537).  Modes 1 and 2 raise the
+ * batch's bound on a site's distance from its centre of mass (which picks the kernels that take an
+ * atom pair's minimum image from its molecules') to what any orientation can reach: max_a |db[a]|
+ * in mode 2; max_a (|db[a]| + sqrt(2) |db[a].y|) in mode 1, whose element (2,3) adds up to
+ * sqrt(2) |db[a].y| along z; both times (1 + 1e-5) for the 1e-6 norm tolerance.  The bound is
+ * never lowered, mode 0 included. */
 int32_t mmc_batch_set_orientations(mmc_batch *b, const double *quat, const double *db,
                                    int32_t mode);
 int32_t mmc_batch_get_orientations(mmc_batch *b, int64_t r, double *quat);

@@ -29,8 +29,9 @@ struct mmc_batch {
                              // 128 VGPRs let be resident; more would queue behind the first)
     int n_cus = 256;
     bool fast_ok = false;    // the system qualifies for kernel 1
-    bool rigid_only = true;  // every move committed so far was a rigid one made on the device
-                             // (k_propose): DeviceSystem::r_mol_max still bounds every molecule
+    bool rigid_only = true;  // every move committed so far was made on the device (k_propose):
+                             // DeviceSystem::r_mol_max still bounds every molecule (a rigid move
+                             // keeps the bound; mmc_batch_set_orientations raises it for its modes)
     int image_by_molecule = -1; // option: -1 where it is valid, 0 never (the per-pair minimum image)
     int zero_copy_moves = 0; // 1: kernels read the proposals from pinned host memory
     MoveRec *h_moves[2] = { nullptr, nullptr };  // pinned + mapped host staging
@@ -798,6 +799,20 @@ extern "C" int32_t mmc_batch_set_orientations(mmc_batch *b, const double *quat, 
         MMC_HIP(hipGetLastError());
     }
     MMC_TRY(s.sync());
+    // DeviceSystem::r_mol_max must bound every site's distance from its COM in every state the
+    // chains can reach, not only in the uploaded one (image_by_molecule trusts it).
+    // mmc_space_fixed puts site a at COM + A^T db_a.  With n = |q|^2 <= 1 + 1e-6, the
+    // Allen-Tildesley A is n times a rotation.  The faithful A differs from it in a[1][2] only, by
+    // E = 2 q4 (q2 - q3), |E| <= sqrt(2) n, and a[1][2] multiplies db_a,y into z.  Hence
+    // |A^T db_a| <= n |db_a| (mode 2) and n (|db_a| + sqrt(2) |db_a,y|) (mode 1).  The 1e-5
+    // covers n and the norm's drift over a chain of unnormalised quaternion products.
+    double reach = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double *v = db + 3 * a;
+        const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        reach = std::max(reach, mode == 1 ? len + std::sqrt(2.0) * std::fabs(v[1]) : len);
+    }
+    s.r_mol_max = std::max(s.r_mol_max, reach * (1.0 + 1e-5));
     memcpy(b->db, db, sizeof(b->db));
     b->quat_mode = mode;
     s.bv.quat = b->d_quat;

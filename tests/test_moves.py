@@ -122,3 +122,44 @@ def test_adjust_controller():
 
 def test_pressure():
     assert moves.Pressure(Properties(virial=30.0), 0.5, 2.0, 10.0) == pytest.approx(4.0)
+
+
+def _site_reach(db, faithful):
+    """The bound mmc_batch_set_orientations puts on a site's distance from its centre of mass, before
+    its 1e-5 margin: max_a |db_a| (Allen-Tildesley), max_a (|db_a| + sqrt(2) |db_a,y|) (faithful)."""
+    db = np.asarray(db, dtype=float)
+    n = np.linalg.norm(db, axis=1)
+    return (n + np.sqrt(2.0) * np.abs(db[:, 1])).max() if faithful else n.max()
+
+
+def test_orientation_bound_covers_every_quaternion():
+    """space_fixed_atoms puts site a at COM + A^T db_a.  The faithful A (quirk Q12) adds
+    E = 2 q4 (q2 - q3) in element (2,3), which moves db_a,y into z, so a site can reach beyond
+    |db_a|.  The bound must hold for sampled quaternions, for adversarial ones (|E| -> sqrt(2),
+    q = (0, 1/2, -1/2, 1/sqrt(2)) and its neighbours) and at the 1e-6 norm tolerance, and the
+    faithful bound must be needed: some orientation exceeds max |db_a|."""
+    rng = np.random.default_rng(11)
+    bodies = [np.array([[-0.035, 0.0142, -0.0525], [0.964, 0.0022, -0.0105], [-0.409, -0.2268, 0.8435]]),
+              triatomic_db().T] + [rng.normal(size=(3, 3)) for _ in range(6)]
+    s2 = 1.0 / np.sqrt(2.0)
+    adversarial = [np.array([0.0, 0.5, -0.5, s2]), np.array([0.0, -0.5, 0.5, s2]),
+                   np.array([0.0, 0.5, -0.5, -s2])]
+    for k in range(200):
+        q = adversarial[k % 3] + rng.normal(size=4) * 0.05
+        adversarial.append(q / np.linalg.norm(q))
+    qs = [q / np.linalg.norm(q) for q in rng.normal(size=(1000, 4))] + adversarial
+    e = [2 * q[3] * (q[1] - q[2]) for q in qs]
+    assert max(abs(x) for x in e) == pytest.approx(np.sqrt(2.0), abs=1e-12)
+    for db in bodies:
+        for faithful in (True, False):
+            bound = _site_reach(db, faithful) * (1.0 + 1e-5)
+            worst = 0.0
+            for q in qs:
+                for scale in (1.0, np.sqrt(1.0 + 0.999e-6), np.sqrt(1.0 - 0.999e-6)):   # the norm tolerance
+                    at = moves.space_fixed_atoms(np.zeros(3), q * scale, db, faithful)
+                    worst = max(worst, np.linalg.norm(at, axis=1).max())
+            assert worst <= bound, (faithful, worst, bound)
+            if faithful and np.abs(db[:, 1]).max() > 0.1:
+                assert worst > np.linalg.norm(db, axis=1).max() * 1.05, worst   # the deformation is real
+            if not faithful:
+                assert worst > 0.999 * bound
