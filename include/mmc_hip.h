@@ -595,6 +595,53 @@ int32_t mmc_batch_run_chains(mmc_batch *b, const mmc_run_params *p, mmc_chain *c
 int32_t mmc_chain_block_line(const mmc_chain *chain, int64_t block, int64_t n_mol, double box,
                              double ideal_term, char *buf, int64_t len);
 
+/* ---- Widom test-particle insertion: the excess chemical potential of every replica ------------
+ * The reference has no insertion code (its README names free energies and adsorption as goals);
+ * the insertion energy is DEFINED through its own total energy, potential(..., "ewald")
+ * (Ewald/energy.jl:946-1032): dU is what that total changes by when the test molecule is appended
+ * as molecule N + 1 of the replica's current configuration,
+ *   dU = d_lj + d_real + d_recip
+ *   d_lj    = LJ_poly_dU(N+1)                       energy.jl:209-290 (COM gate, eps > 0.001)
+ *   d_real  = EwaldShort(N+1)                       ewalds.jl:892-910 -> EwaldReal :293-376
+ *             (slack r_cut^2 + 100; 0 when an atom pair overlaps, :359-360)
+ *   d_recip = factor sum_k cfac_k (2 Re(conj(S_k) s_k) + |s_k|^2)  RecipLong(N+1) - RecipLong(N), :538-604
+ *           - factor kappa / sqrt(pi) sum_a q_a^2   EwaldSelf(N+1) - EwaldSelf(N), :829-833
+ * S_k: the replica's committed structure factor over the batch's half-space k list (doubled
+ * weights) -- built by mmc_batch_recip_long (call it once after creation, as before the first
+ * trial move) and kept by the moves since; s_k: the test molecule's own, by the reference's phase
+ * recurrence.  Up to summation
+ * order this is potential(N+1) - potential(N).
+ *   - The test molecule is rigid with the atom types and charges of molecule 1; its atoms sit at
+ *     COM + R offsets[a] (offsets [3][3], A, from the COM).
+ *   - Overlap: an atom pair with r^2 < 0.5 and opposite charges (ewalds.jl:359).  An overlap, and
+ *     a dU that is NaN or +-inf (an atom exactly on another: the LJ term is Inf - Inf), has weight
+ *     0 and counts in n_overlap; ovl_out[i] bit 0 = overlap, bit 1 = non-finite dU.
+ *   - Random insertions: Philox4x32-10, key = seed, counter = (draw0 + j, slot, replica index in
+ *     the batch), slots MMC_SLOT_WIDOM + 0, 1, 2 (six uniforms u0..u5): COM = (u0, u1, u2) L, in
+ *     [0, L) (boundaries.jl:16-26); orientation Shoemake's uniform unit quaternion of (u3, u4, u5),
+ *     q = (w, x, y, z) = (sqrt(u3) cos 2 pi u5, sqrt(1-u3) sin 2 pi u4, sqrt(1-u3) cos 2 pi u4,
+ *     sqrt(u3) sin 2 pi u5), as its rotation matrix.
+ *   - boltz_sum[r] += exp(-dU / T) (T in K, like the energies) over the call's insertions, added in
+ *     insertion order: the result is bit-identical whatever the grid or option "wave_wgs";
+ *     n_overlap[r] += the insertions of weight 0.  Call once per sweep to accumulate.
+ *   - mol_out: [R][n_insert][12] atoms (9) then COM (3) of each insertion; du_out: [R][n_insert][3]
+ *     (d_lj, d_real, d_recip); ovl_out: [R][n_insert].  Each may be NULL.
+ *   - Read-only: coordinates, S(k), the chains' flags, step counters and random streams are not
+ *     touched; a chain run with these calls interleaved is bit-identical to one without.
+ * Preconditions as mmc_batch_potential_ewald: no proposals outstanding (MMC_ERR_STATE), no volume
+ * trial in flight (MMC_ERR_STATE).  MMC_ERR_UNSUPPORTED, nothing computed: per-replica boxes
+ * (mmc_batch_set_boxes), or a system the table kernels do not take (not identical 3-atom molecules,
+ * or a cutoff / kappa outside the erfc table).  MMC_ERR_ARG: n_insert < 1, a NULL required array,
+ * temperature <= 0 or not finite, non-finite offsets or molecules.
+ * mmc_batch_widom_at evaluates the caller's molecules mol_in [R][n_insert][12] (same layout as
+ * mol_out) with the same kernel. */
+#define MMC_SLOT_WIDOM 0x50000000u /* Philox slots of an insertion: +0, +1, +2 */
+int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t draw0,
+                        const double *offsets, double temperature, double *boltz_sum,
+                        int64_t *n_overlap, double *mol_out, double *du_out, uint8_t *ovl_out);
+int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in, double temperature,
+                           double *boltz_sum, int64_t *n_overlap, double *du_out, uint8_t *ovl_out);
+
 /* ---- the one collective of a sharded run: RCCL over xGMI ---------------------
  * Replicas shard over GPUs with no data-path collective; what is reduced, once per block, is a
  * handful of observables (sums of energies and acceptance counters, the maximum of the elapsed

@@ -177,6 +177,9 @@ SIGNATURES = {
     "mmc_study_f32_total": [_vp, C.c_double, C.c_double, C.c_int32, _dp],
     "mmc_study_f32_move": [_vp, _i64, _dp, _dp, C.c_double, C.c_double, C.c_int32, _dp, _i32p],
     "mmc_philox4x32": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "mmc_batch_widom": [_vp, _i64, C.c_uint64, _i64, _dp, _d, _dp, _i64p, _dp, _dp,
+                        C.POINTER(C.c_uint8)],
+    "mmc_batch_widom_at": [_vp, _i64, _dp, _d, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
     "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, C.c_int32, C.POINTER(RunStats)],
     "mmc_chain_block_line": [_vp, _i64, _i64, _d, _d, C.c_char_p, _i64],
     "mmc_dist_unique_id": [C.c_char_p],                      # uint8_t[128]

@@ -88,6 +88,10 @@ struct mmc_batch {
     uint8_t *bar_flags = nullptr; // [R] device memory the host threads write through the BAR
                                   // (mmc_bar_alloc): no copy kernel between a step's launches
     double2 *h_steps = nullptr, *hd_steps = nullptr, *d_steps = nullptr;
+    void *widom_buf = nullptr;  // device scratch of mmc_batch_widom (mmc_widom.inc), grown on demand
+    size_t widom_bytes = 0;
+    void *widom_host = nullptr; // ... and its pinned staging of the per-replica sums
+    size_t widom_host_bytes = 0;
 
     const MoveRec *dev_moves(int which) const
     {
@@ -235,6 +239,10 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         (void)hipFree(b->bar_flags);
     if (b->h_timeout)
         (void)hipHostFree(b->h_timeout);
+    if (b->widom_buf)
+        (void)hipFree(b->widom_buf);
+    if (b->widom_host)
+        (void)hipHostFree(b->widom_host);
     b->sys.release();
     delete b;
     return MMC_OK;

@@ -9,4 +9,5 @@
 #include "mmc_batch.inc"
 #include "mmc_engine.inc"
 #include "mmc_perbox.inc"
+#include "mmc_widom.inc"
 #include "mmc_dist.inc"

@@ -28,6 +28,17 @@ def _d(a):
     return a.ctypes.data_as(_dp)
 
 
+def _u8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def philox4x32(ctr, key):
+    """The library's Philox4x32-10 (mmc_philox4x32): four 32-bit words of counter, two of key."""
+    c, k, o = (C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), (C.c_uint32 * 4)()
+    check(_lib.lib().mmc_philox4x32(c, k, o))
+    return list(o)
+
+
 def _i(a):
     return a.ctypes.data_as(_i64p)
 
@@ -299,6 +310,12 @@ class Batch:
         self._h = h
         self.R, self.n_mol = int(n_replicas), com.shape[0]
         self.factor = float(factor)
+        self.box, self.kappa = float(box), float(kappa)
+        self.charge3 = charge[:3].copy()
+        # molecule 1 of the configuration the batch was created from, minimum-imaged about its
+        # COM (vector1D, ewalds.jl:30-38): the default test molecule of widom()
+        d = coords[:3] - com[0]
+        self.widom_offsets = d - self.box * np.round(d / self.box)
         self.nkvecs = 337
 
     def close(self):
@@ -478,6 +495,48 @@ class Batch:
         e = np.zeros(self.R) if energies is None else _f64(energies).copy()
         check(self._L.mmc_batch_run(self._h, C.byref(p), _d(e), C.byref(st)))
         return e, st.asdict()
+
+    def widom(self, n_insert, temperature, seed, draw0=0, offsets=None, boltz_sum=None,
+              n_overlap=None, outputs=False):
+        """mmc_batch_widom: n_insert random insertions of the test molecule into every replica.
+        offsets (3, 3) A from the COM, None = molecule 1 of the creating configuration
+        (self.widom_offsets).  boltz_sum / n_overlap (R,) accumulate (new zero arrays when None).
+        Returns (boltz_sum, n_overlap), and with outputs=True also mol (R, M, 12), du (R, M, 3)
+        and ovl (R, M)."""
+        off = _f64(self.widom_offsets if offsets is None else offsets).reshape(3, 3)
+        bs, no = self._widom_sums(boltz_sum, n_overlap)
+        M = int(n_insert)
+        mol = np.zeros((self.R, M, 12)) if outputs else None
+        du = np.zeros((self.R, M, 3)) if outputs else None
+        ov = np.zeros((self.R, M), dtype=np.uint8) if outputs else None
+        check(self._L.mmc_batch_widom(self._h, M, int(seed) & (2 ** 64 - 1), int(draw0), _d(off),
+                                      float(temperature), _d(bs), _i(no),
+                                      _d(mol) if outputs else None, _d(du) if outputs else None,
+                                      _u8(ov) if outputs else None))
+        return (bs, no, mol, du, ov) if outputs else (bs, no)
+
+    def widom_at(self, mol, temperature, boltz_sum=None, n_overlap=None):
+        """mmc_batch_widom_at: the caller's test molecules mol (R, M, 12) = atoms (9), COM (3).
+        Returns (boltz_sum, n_overlap, du (R, M, 3), ovl (R, M))."""
+        mol = _f64(mol)
+        if mol.ndim != 3 or mol.shape[0] != self.R or mol.shape[2] != 12:
+            raise ValueError("mol must be (R, n_insert, 12)")
+        M = mol.shape[1]
+        bs, no = self._widom_sums(boltz_sum, n_overlap)
+        du = np.zeros((self.R, M, 3))
+        ov = np.zeros((self.R, M), dtype=np.uint8)
+        check(self._L.mmc_batch_widom_at(self._h, M, _d(mol), float(temperature), _d(bs), _i(no),
+                                         _d(du), _u8(ov)))
+        return bs, no, du, ov
+
+    def _widom_sums(self, boltz_sum, n_overlap):
+        bs = np.zeros(self.R) if boltz_sum is None else boltz_sum
+        no = np.zeros(self.R, dtype=np.int64) if n_overlap is None else n_overlap
+        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (self.R,)
+                and bs.flags.c_contiguous and isinstance(no, np.ndarray) and no.dtype == np.int64
+                and no.shape == (self.R,) and no.flags.c_contiguous):
+            raise ValueError("boltz_sum: float64 (R,), n_overlap: int64 (R,), contiguous (updated in place)")
+        return bs, no
 
     def get_trace(self, n_steps):
         """(dU[R, n], flags[R, n]) of the first n steps of the last run (option "trace_steps" = n):

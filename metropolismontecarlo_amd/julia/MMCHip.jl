@@ -529,6 +529,39 @@ function run_npt_replicas!(b::Batch, params::MMCRunParams, npt::MMCNptParams, en
     return st[], ns
 end
 
+# ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom / mmc_batch_widom_at) ------
+"""
+    widom!(b, n_insert, seed, draw0, offsets, temperature, boltz_sum, n_overlap)
+    widom_at!(b, mol_in, n_insert, temperature, boltz_sum, n_overlap)
+
+`n_insert` insertions of a rigid copy of molecule 1 (atoms at COM + R offsets[a], `offsets` 9
+Float64, A) into every replica; `boltz_sum[r] += sum exp(-dU / T)` in insertion order and
+`n_overlap[r] +=` the insertions of weight 0.  dU is the change of potential(..., "ewald")
+(energy.jl:946-1032) when the molecule is appended as molecule N + 1; the reference has no
+insertion code.  `widom_at!` evaluates the caller's molecules, `mol_in` = R * n_insert * 12 Float64
+(atoms, then COM).  Read-only for the chains.  mu_ex = -T log(boltz_sum / n) in K.
+"""
+function widom!(b::Batch, n_insert::Integer, seed::Integer, draw0::Integer, offsets::Vector{Float64},
+                temperature::Float64, boltz_sum::Vector{Float64}, n_overlap::Vector{Int64})
+    length(offsets) == 9 || error("offsets: 3 atoms x 3 components")
+    length(boltz_sum) == b.n_replicas && length(n_overlap) == b.n_replicas || error("one sum per replica")
+    check(ccall((:mmc_batch_widom, libmmc), Int32,
+                (Ptr{Cvoid}, Int64, UInt64, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Int64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, n_insert, UInt64(seed), draw0, offsets, temperature, boltz_sum, n_overlap,
+                C_NULL, C_NULL, C_NULL))
+    return boltz_sum, n_overlap
+end
+function widom_at!(b::Batch, mol_in::Vector{Float64}, n_insert::Integer, temperature::Float64,
+                   boltz_sum::Vector{Float64}, n_overlap::Vector{Int64})
+    length(mol_in) == 12 * n_insert * b.n_replicas || error("mol_in: R x n_insert x 12")
+    length(boltz_sum) == b.n_replicas && length(n_overlap) == b.n_replicas || error("one sum per replica")
+    check(ccall((:mmc_batch_widom_at, libmmc), Int32,
+                (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, n_insert, mol_in, temperature, boltz_sum, n_overlap, C_NULL, C_NULL))
+    return boltz_sum, n_overlap
+end
+
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
 """
     id = dist_unique_id()                       # rank 0; send the 128 bytes to the other ranks

@@ -15,3 +15,73 @@ def normalize_rdf(hist, npart, side, nstep):
     i = np.arange(1, numbins + 1)
     rrr = (i - 0.5) * dr
     return rrr, hist[1:] / norm / (rrr * rrr + dr * dr / 12.0)
+
+
+# ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
+MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2
+
+
+def widom_mu_ex(boltz_sum, n_total, temperature):
+    """mu_ex = -T ln(sum w / n) in K (energies / k_B), w = exp(-dU / T) of n insertions; the
+    reference-definition value (its total energy omits the intramolecular Ewald term, see
+    ewald_intra_energy)."""
+    return -float(temperature) * np.log(np.asarray(boltz_sum, dtype=float) / float(n_total))
+
+
+def ewald_intra_energy(offsets, charge, kappa, factor):
+    """factor sum_{a<b} q_a q_b erf(kappa r_ab) / r_ab of one rigid molecule: the intramolecular
+    reciprocal-space term the reference's potential() omits.  An inserted
+    molecule brings it along, so the physical mu_ex is the reference-definition mu_ex minus it."""
+    import math
+    off = np.asarray(offsets, dtype=float).reshape(-1, 3)
+    q = np.asarray(charge, dtype=float).ravel()
+    e = 0.0
+    for a in range(off.shape[0]):
+        for b in range(a + 1, off.shape[0]):
+            r = float(np.sqrt(((off[a] - off[b]) ** 2).sum()))
+            e += q[a] * q[b] * math.erf(kappa * r) / r
+    return factor * e
+
+
+def philox_uniforms(philox, seed, ctr, slot, replica):
+    """mmc_draw (csrc/mmc_propose.hpp): the two uniforms of Philox4x32-10 with key = seed and
+    counter = (ctr lo, ctr hi, slot, replica); `philox(ctr4, key2) -> 4 words` is the library's
+    mmc_philox4x32 (or any equal implementation)."""
+    ctr = int(ctr) & (2 ** 64 - 1)
+    v = philox([ctr & 0xffffffff, ctr >> 32, int(slot) & 0xffffffff, int(replica) & 0xffffffff],
+               [int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff])
+    a = ((int(v[0]) << 32) | int(v[1])) >> 11
+    b = ((int(v[2]) << 32) | int(v[3])) >> 11
+    return a * 2.0 ** -53, b * 2.0 ** -53
+
+
+def shoemake_rotation(u1, u2, u3):
+    """Rotation matrix of Shoemake's uniform unit quaternion (w, x, y, z) =
+    (sqrt(u1) cos 2 pi u3, sqrt(1-u1) sin 2 pi u2, sqrt(1-u1) cos 2 pi u2, sqrt(u1) sin 2 pi u3),
+    in k_widom_wave's arithmetic."""
+    s1, s2 = np.sqrt(1.0 - u1), np.sqrt(u1)
+    a, b = 2.0 * np.pi * u2, 2.0 * np.pi * u3
+    w, x, y, z = s2 * np.cos(b), s1 * np.sin(a), s1 * np.cos(a), s2 * np.sin(b)
+    return np.array([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                     [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                     [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]])
+
+
+def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
+    """Host mirror of mmc_batch_widom's generator: [n_insert][12] (atoms 0..8, COM 9..11) of the
+    insertions of one replica.  Draw j uses counter draw0 + j; slots MMC_SLOT_WIDOM + 0, 1, 2 give
+    u0..u5: COM = (u0, u1, u2) L, rotation shoemake_rotation(u3, u4, u5), atom a = COM + R off_a."""
+    off = np.asarray(offsets, dtype=float).reshape(3, 3)
+    out = np.empty((int(n_insert), 12))
+    for j in range(int(n_insert)):
+        c = int(draw0) + j
+        u0, u1 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM, replica)
+        u2, u3 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 1, replica)
+        u4, u5 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 2, replica)
+        com = np.array([u0 * box, u1 * box, u2 * box])
+        R = shoemake_rotation(u3, u4, u5)
+        for a in range(3):
+            for d in range(3):
+                out[j, 3 * a + d] = com[d] + ((R[d, 0] * off[a, 0] + R[d, 1] * off[a, 1]) + R[d, 2] * off[a, 2])
+        out[j, 9:] = com
+    return out

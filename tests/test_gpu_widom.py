@@ -1,0 +1,328 @@
+"""Widom test-particle insertion (mmc_batch_widom / mmc_batch_widom_at) against the oracle.
+
+The reference has no insertion code; dU is defined through its total energy (include/mmc_hip.h):
+the change of potential(..., "ewald") when the test molecule is appended as molecule N + 1.  The
+oracle is asked exactly that, term by term, on an oracle.System of N + 1 molecules:
+  d_lj    == orc.lj_poly_du(N+1)
+  d_real  == orc.ewald_short(N+1)                   (0 when it reports an overlap)
+  d_recip == factor (recip_long(N+1) - recip_long(N)) + orc.ewald_self(the test molecule's charges)
+The last term is EwaldSelf(N+1) - EwaldSelf(N) without the cancellation of two 1.4e7 K numbers
+(that difference is checked separately, to its own rounding).  Tolerance: 1e-9 K absolute plus
+1e-13 of the term (the erfc table's error, tests/test_gpu_table.py).
+
+Launch shape: k_widom_wave runs WV_WAVES = 4 waves per workgroup on at most "wave_wgs" workgroups
+(default 4 per compute unit).  R = 8 replicas x M = 32 insertions = 256 units: with wave_wgs = 1 one
+workgroup's four waves take 64 insertions each, with 2 each wave takes 32, by default (64
+workgroups) every wave takes one."""
+import math
+
+import numpy as np
+import pytest
+
+import common
+from metropolismontecarlo_amd import observables as obs
+from metropolismontecarlo_amd import structs
+
+pytestmark = pytest.mark.gpu
+
+RCUT = 10.0
+T = 298.15
+
+
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import oracle
+    return oracle
+
+
+def make_batch(a, R, rcut=RCUT):
+    """A batch with S(k) built (mmc_batch_recip_long, as before the first trial move)."""
+    from metropolismontecarlo_amd.device import Batch
+    b = Batch(R, a["com"], a["coords"], a["atype"], a["charge"], a["eps"], a["sig"], a["box"],
+              5.6 / a["box"], structs.factor, rcut, rcut)
+    b.recip_long()
+    return b
+
+
+def oracle_terms(orc, a, com, coords, mol):
+    """(d_lj, d_real, d_recip, overlap, d_self_exact) of one test molecule mol[12] appended to the
+    configuration (com, coords) of the system `a` (topology, tables, box)."""
+    n = com.shape[0]
+    L = float(a["box"])
+    q3 = np.asarray(a["charge"][:3], dtype=float)
+    com1 = np.vstack([com, mol[9:12]])
+    coords1 = np.vstack([coords, mol[:9].reshape(3, 3)])
+    first = np.arange(1, 3 * (n + 1), 3, dtype=np.int64)
+    at1 = np.concatenate([a["atype"][:3 * n], a["atype"][:3]])
+    q1 = np.concatenate([np.asarray(a["charge"][:3 * n], dtype=float), q3])
+    s1 = orc.System(com1, first, first + 2, coords1, at1, q1, a["eps"], a["sig"], L)
+    ew = orc.Ewald(5.6 / L, 5, 27, L, factor=structs.factor)
+    lj, _ = orc.lj_poly_du(n + 1, s1, RCUT)
+    real, _, ov = orc.ewald_short(n + 1, s1, ew, RCUT)
+    rl1 = orc.recip_long(ew, coords1, q1, L)
+    rl0 = orc.recip_long(ew, coords, q1[:3 * n], L)
+    recip = ew.factor * (rl1 - rl0) + orc.ewald_self(ew, q3)
+    return lj, real, recip, ov, (ew, q1)
+
+
+def close(x, ref):
+    return abs(x - ref) <= 1e-9 + 1e-13 * abs(ref)
+
+
+def check_against_oracle(orc, a, b, r, mols, du, ovl):
+    com, coords, _ = b.get_replica(r)
+    bad = []
+    for j in range(mols.shape[0]):
+        lj, real, recip, ov, _ = oracle_terms(orc, a, com, coords, mols[j])
+        if bool(ovl[j] & 1) != ov:
+            bad.append((j, "overlap", int(ovl[j]), ov))
+        for name, x, ref in (("lj", du[j, 0], lj), ("real", du[j, 1], real), ("recip", du[j, 2], recip)):
+            if not close(x, ref):
+                bad.append((j, name, x, ref))
+    assert not bad, f"replica {r}: {bad[:6]}"
+
+
+def host_sums(du, ovl, boltz0, novl0):
+    """The in-order reduction the library promises, on the host."""
+    bs, no = np.array(boltz0, dtype=float), np.array(novl0, dtype=np.int64)
+    for r in range(du.shape[0]):
+        acc = bs[r]
+        for j in range(du.shape[1]):
+            d = (du[r, j, 0] + du[r, j, 1]) + du[r, j, 2]
+            if ovl[r, j] != 0:
+                no[r] += 1
+            else:
+                acc += math.exp(-d / T)
+        bs[r] = acc
+    return bs, no
+
+
+@pytest.fixture(scope="module")
+def cfg4():
+    return common.nist_arrays(4, "unwrapped")
+
+
+@pytest.fixture(scope="module")
+def diversified(cfg4):
+    """NIST config 4, 8 replicas, each taken 300 device-proposed steps along its own chain."""
+    b = make_batch(cfg4, 8)
+    b.set_option("device_moves", 1)
+    b.run(300, T, 0.3, 0.2, seed=4242)
+    yield b
+    b.close()
+
+
+def test_random_insertions_against_the_oracle(orc, cfg4, diversified):
+    b = diversified
+    bs, no, mol, du, ovl = b.widom(32, T, seed=77, draw0=5, outputs=True)
+    assert np.all(np.isfinite(du)) and np.all(ovl != 2)
+    for r in range(b.R):
+        check_against_oracle(orc, cfg4, b, r, mol[r], du[r], ovl[r])
+    # EwaldSelf(N+1) - EwaldSelf(N) by the oracle's own subtraction, to its rounding
+    _, _, _, _, (ew, q1) = oracle_terms(orc, cfg4, *b.get_replica(0)[:2], mol[0, 0])
+    d_self = orc.ewald_self(ew, q1) - orc.ewald_self(ew, q1[:-3])
+    assert abs(d_self - orc.ewald_self(ew, q1[-3:])) < 1e-8
+    # the reciprocal term restated in numpy on the batch's own S(k) (the reference's 337 entries)
+    L = float(cfg4["box"])
+    q3 = np.asarray(cfg4["charge"][:3], dtype=float)
+    for r in (0, 5):
+        _, _, S = b.get_replica(r)
+        for j in (0, 7, 31):
+            x = mol[r, j, :9].reshape(3, 3)
+            s = (q3[None, :] * np.exp(2j * np.pi * (ew.kxyz @ x.T) / L)).sum(1)
+            ref = ew.factor * (ew.cfac * (2 * (np.conj(S) * s).real + (s * np.conj(s)).real)).sum() \
+                + orc.ewald_self(ew, q3)
+            assert abs(du[r, j, 2] - ref) <= 1e-12 * abs(ref), (r, j, du[r, j, 2], ref)
+
+
+def test_generator_matches_the_host_mirror(diversified):
+    from metropolismontecarlo_amd.device import philox4x32
+    b = diversified
+    seed, draw0, M = 0x1234_5678_9abc_def0, 1 << 33, 16
+    _, _, mol, _, _ = b.widom(M, T, seed=seed, draw0=draw0, outputs=True)
+    off = b.widom_offsets
+    for r in (0, 3, 7):
+        ref = obs.widom_molecules(philox4x32, seed, draw0, M, r, b.box, off)
+        assert np.abs(mol[r] - ref).max() <= 1e-12, r
+        com = mol[r, :, 9:]
+        assert np.all((com >= 0) & (com < b.box))
+        at = mol[r, :, :9].reshape(M, 3, 3)
+        for a1, a2 in ((0, 1), (0, 2), (1, 2)):
+            d = np.linalg.norm(at[:, a1] - at[:, a2], axis=1)
+            assert np.abs(d - np.linalg.norm(off[a1] - off[a2])).max() <= 1e-12
+        # the COM of the offsets is the molecule's COM: every atom at its offset's distance from it
+        for a in range(3):
+            d = np.linalg.norm(at[:, a] - com, axis=1)
+            assert np.abs(d - np.linalg.norm(off[a])).max() <= 1e-12
+
+
+def test_reductions_and_launch_shape(diversified):
+    b = diversified
+    rng = np.random.default_rng(3)
+    b0 = rng.random(b.R) * 1e-3
+    n0 = rng.integers(0, 5, size=b.R).astype(np.int64)
+    runs = []
+    for wgs in (0, 1, 2, 0):
+        b.set_option("wave_wgs", wgs)
+        bs, no, mol, du, ovl = b.widom(32, T, seed=91, draw0=0, boltz_sum=b0.copy(),
+                                       n_overlap=n0.copy(), outputs=True)
+        runs.append((bs, no, mol, du, ovl))
+    b.set_option("wave_wgs", 0)
+    bs, no, _, du, ovl = runs[0]
+    hb, hn = host_sums(du, ovl, b0, n0)
+    assert np.array_equal(no, hn)
+    assert np.all(np.abs(bs - hb) <= 1e-14 * np.abs(hb)), (bs, hb)
+    assert np.all(bs > b0)
+    for other in runs[1:]:
+        for x, y in zip(runs[0], other):
+            assert x.tobytes() == y.tobytes()
+
+
+def test_the_call_is_read_only(cfg4):
+    R = 4
+    twins = [make_batch(cfg4, R), make_batch(cfg4, R)]
+    chains = []
+    for b in twins:
+        b.set_option("device_moves", 1)
+        e = b.potential_ewald(as_array=True)["energy"]
+        chains.append(b.new_chains(e))
+    b = twins[0]
+    before = [b.get_replica(r) for r in range(R)]
+    pe = b.potential_ewald(as_array=True)
+    b.widom(16, T, seed=5)
+    after = [b.get_replica(r) for r in range(R)]
+    for x, y in zip(before, after):
+        for u, v in zip(x, y):
+            assert u.tobytes() == v.tobytes()
+    assert pe.tobytes() == b.potential_ewald(as_array=True).tobytes()
+    acc = (np.zeros(R), np.zeros(R, dtype=np.int64))
+    for blk in range(4):
+        for b, c in zip(twins, chains):
+            b.run_chains(c, 200, T, seed=808)
+        twins[0].widom(8, T, seed=9, draw0=8 * blk, boltz_sum=acc[0], n_overlap=acc[1])
+    assert chains[0].tobytes() == chains[1].tobytes()
+    for r in range(R):
+        for u, v in zip(twins[0].get_replica(r), twins[1].get_replica(r)):
+            assert u.tobytes() == v.tobytes()
+    assert np.all(acc[0] > 0)
+    for b in twins:
+        b.close()
+
+
+def _upright(off, com):
+    """The test molecule unrotated at `com`: atoms (9) then COM (3)."""
+    return np.concatenate([(np.asarray(com) + off).ravel(), com])
+
+
+def test_edges_through_widom_at(orc, cfg4):
+    a = cfg4
+    b = make_batch(a, 1)
+    L = float(a["box"])
+    com, coords, _ = b.get_replica(0)
+    off = b.widom_offsets
+    mols = []
+    # COMs at the gate (r_cut = 10) +- 1e-12 relative from a foreign COM, across the faces and corners
+    for j in (0, 17, 400):
+        for d in (np.array([1.0, 0, 0]), np.array([0, -1.0, 0]), np.array([0, 0, 1.0]),
+                  np.array([1.0, 1.0, 1.0]) / math.sqrt(3.0), np.array([-1.0, 1.0, -1.0]) / math.sqrt(3.0)):
+            for f in (1 - 1e-12, 1 + 1e-12):
+                c = (com[j] + RCUT * f * d) % L
+                mols.append(_upright(off, c))
+    # a COM exactly on a face and one at a corner
+    mols.append(_upright(off, np.array([0.0, 7.0, 12.0])))
+    mols.append(_upright(off, np.array([L, L, 0.0])))
+    n_gate = len(mols)
+    # an H at r^2 = 0.25 from a foreign O: opposite charges inside 0.5 -> overlap (ewalds.jl:359)
+    o = coords[3 * 100]
+    h = o + np.array([0.5, 0.0, 0.0])
+    mols.append(_upright(off, h - off[1]))
+    # an O exactly on a foreign O (the same molecule twice): LJ gives Inf - Inf
+    mols.append(np.concatenate([coords[3 * 200:3 * 200 + 3].ravel(), com[200]]))
+    mols = np.array(mols)[None]
+    bs, no, du, ovl = b.widom_at(mols, T)
+    M = mols.shape[1]
+    check_against_oracle(orc, a, b, 0, mols[0, :n_gate + 1], du[0, :n_gate + 1], ovl[0, :n_gate + 1])
+    assert ovl[0, n_gate] == 1 and du[0, n_gate, 1] == 0.0
+    assert ovl[0, n_gate + 1] == 2 and not np.isfinite(du[0, n_gate + 1].sum())
+    lj, real, _, ov, _ = oracle_terms(orc, a, com, coords, mols[0, -1])
+    assert not ov and not math.isfinite(lj + real)
+    assert np.isfinite(bs[0]) and no[0] == int(np.count_nonzero(ovl[0]))
+    hb, hn = host_sums(du[:, :n_gate], ovl[:, :n_gate], [0.0], [0])
+    assert abs(bs[0] - hb[0]) <= 1e-14 * hb[0] and no[0] == hn[0] + 2
+    assert M == n_gate + 2
+    b.close()
+
+
+def test_reference_com_fixture_takes_the_per_pair_image(orc):
+    """Broken molecules (nist_arrays(4, "reference")): r_mol is unbounded, the per-pair minimum
+    image (vector1D) runs instead of the per-molecule one."""
+    a = common.nist_arrays(4, "reference")
+    b = make_batch(a, 2)
+    bs, no, mol, du, ovl = b.widom(24, T, seed=31, outputs=True)
+    for r in range(2):
+        check_against_oracle(orc, a, b, r, mol[r], du[r], ovl[r])
+    b.close()
+
+
+def test_at_size_10000_molecules(orc):
+    from test_gpu_npt import water_lattice
+    a = water_lattice(10000, "spce")
+    b = make_batch(a, 1)
+    bs, no, mol, du, ovl = b.widom(64, T, seed=2024, outputs=True)
+    check_against_oracle(orc, a, b, 0, mol[0], du[0], ovl[0])
+    b.close()
+
+
+def test_rejections_leave_outputs_untouched(cfg4):
+    from metropolismontecarlo_amd import _lib
+    a = cfg4
+    R = 2
+
+    def sentinels():
+        return np.full(R, 7.5), np.full(R, 3, dtype=np.int64)
+
+    def expect(status, fn):
+        bs, no = sentinels()
+        with pytest.raises(_lib.MMCError) as ei:
+            fn(bs, no)
+        assert ei.value.status == status
+        assert np.all(bs == 7.5) and np.all(no == 3)
+
+    # per-replica boxes
+    b = make_batch(a, R)
+    b.set_boxes([a["box"], a["box"] * 1.01], 5.6)
+    expect(_lib.MMC_ERR_UNSUPPORTED, lambda bs, no: b.widom(4, T, 1, boltz_sum=bs, n_overlap=no))
+    expect(_lib.MMC_ERR_UNSUPPORTED,
+           lambda bs, no: b.widom_at(np.zeros((R, 1, 12)) + 5.0, T, boltz_sum=bs, n_overlap=no))
+    b.close()
+    # a cutoff the erfc table does not cover (r_cut^2 + 100 > 256): no fast path
+    b = make_batch(a, R, rcut=14.0)
+    expect(_lib.MMC_ERR_UNSUPPORTED, lambda bs, no: b.widom(4, T, 1, boltz_sum=bs, n_overlap=no))
+    b.close()
+    # proposals outstanding
+    b = make_batch(a, R)
+    com, coords = np.asarray(a["com"]), np.asarray(a["coords"])
+    b.eval(np.full(R, 3), np.tile(com[2], (R, 1)), np.tile(coords[6:9], (R, 1, 1)))
+    expect(_lib.MMC_ERR_STATE, lambda bs, no: b.widom(4, T, 1, boltz_sum=bs, n_overlap=no))
+    b.settle(np.zeros(R, dtype=np.int32))
+    # bad arguments
+    expect(_lib.MMC_ERR_ARG, lambda bs, no: b.widom(0, T, 1, boltz_sum=bs, n_overlap=no))
+    expect(_lib.MMC_ERR_ARG, lambda bs, no: b.widom(4, 0.0, 1, boltz_sum=bs, n_overlap=no))
+    expect(_lib.MMC_ERR_ARG, lambda bs, no: b.widom(4, -5.0, 1, boltz_sum=bs, n_overlap=no))
+    expect(_lib.MMC_ERR_ARG, lambda bs, no: b.widom(4, float("nan"), 1, boltz_sum=bs, n_overlap=no))
+    expect(_lib.MMC_ERR_ARG, lambda bs, no: b.widom(4, T, 1, offsets=np.full((3, 3), np.inf),
+                                                    boltz_sum=bs, n_overlap=no))
+    L = _lib.lib()
+    bs, no = sentinels()
+    off = np.ascontiguousarray(b.widom_offsets)
+    dp = lambda x: x.ctypes.data_as(_lib._dp)  # noqa: E731
+    ip = lambda x: x.ctypes.data_as(_lib._i64p)  # noqa: E731
+    assert L.mmc_batch_widom(b._h, 4, 1, 0, None, T, dp(bs), ip(no), None, None, None) == _lib.MMC_ERR_ARG
+    assert L.mmc_batch_widom(b._h, 4, 1, 0, dp(off), T, None, ip(no), None, None, None) == _lib.MMC_ERR_ARG
+    assert L.mmc_batch_widom(b._h, 4, 1, 0, dp(off), T, dp(bs), None, None, None, None) == _lib.MMC_ERR_ARG
+    assert L.mmc_batch_widom_at(b._h, 1, None, T, dp(bs), ip(no), None, None) == _lib.MMC_ERR_ARG
+    assert np.all(bs == 7.5) and np.all(no == 3)
+    # ... and after all that the call works
+    bs, no = b.widom(4, T, 1)
+    assert np.all(bs > 0)
+    b.close()
