@@ -100,18 +100,21 @@ def _wave_consts():
             int(re.search(r"#define WV_OCC (\d+)", src).group(1)))
 
 
-def wave_units(n_units, wave_wgs=0, n_cus=256):
+def wave_units(n_units, wave_wgs=0, n_cus=256, occ=None):
     """The units each wave of one k_move_eval_wave launch over n_units takes, in the order it takes
     them: the launch has ceil(n_units / WV_MWAVES) workgroups, capped at option "wave_wgs" or at
     4 * WV_OCC / WV_MWAVES per compute unit (mmc_batch.inc), and wave w of workgroup g loops over
-    units g * WV_MWAVES + w, + wgs * WV_MWAVES, ... (mmc_wave.hpp).  Lists in wave order."""
-    mw, occ = _wave_consts()
+    units g * WV_MWAVES + w, + wgs * WV_MWAVES, ... (mmc_wave.hpp).  Lists in wave order.
+    `occ`: the waves per SIMD of the cap when not WV_OCC (k_widom_wave: widom_occ(), whose unit is
+    insertion j of replica r, u = r M + j, mmc_widom.inc)."""
+    mw, wv_occ = _wave_consts()
+    occ = wv_occ if occ is None else occ
     cap = wave_wgs if wave_wgs > 0 else 4 * occ // mw * n_cus
     wgs = min(-(-n_units // mw), cap)
     return [list(range(g * mw + w, n_units, wgs * mw)) for g in range(wgs) for w in range(mw)]
 
 
-def replicas_by_wave_position(R, n_groups, wave_wgs=0, n_cus=256, parts=1):
+def replicas_by_wave_position(R, n_groups, wave_wgs=0, n_cus=256, parts=1, occ=None):
     """{local replica: where its unit runs} for the replicas worth checking when a wave runs several
     units: in every group (replicas [R g / G, R (g + 1) / G), mmc_engine.inc) the first, second,
     middle and last unit of wave 0 (which runs the most), the last unit of a wave that runs one unit
@@ -119,7 +122,7 @@ def replicas_by_wave_position(R, n_groups, wave_wgs=0, n_cus=256, parts=1):
     out = {}
     for g in range(n_groups):
         r0, r1 = R * g // n_groups, R * (g + 1) // n_groups
-        waves = wave_units((r1 - r0) * parts, wave_wgs, n_cus)
+        waves = wave_units((r1 - r0) * parts, wave_wgs, n_cus, occ)
         w0 = waves[0]
         pos = [(w0[k], 0, k) for k in sorted({0, 1, len(w0) // 2, len(w0) - 1}) if k < len(w0)]
         short = [wv for wv, w in enumerate(waves) if len(w) == len(w0) - 1 and w]
@@ -142,3 +145,142 @@ def device_cu_count(device=0):
     n = C.c_int(0)
     assert get(C.byref(n), 63, int(device)) == 0   # 63: hipDeviceAttributeMultiprocessorCount
     return n.value
+
+
+def _wave_list_consts():
+    """(WV_LIST, WV_PF) of mmc_wave.hpp: the neighbour-list slots of a wave and the 64-molecule
+    blocks of one trip of the COM scan (mmc_wave_unit.inc)."""
+    src = open(os.path.join(HERE, "..", "metropolismontecarlo_amd", "csrc", "mmc_wave.hpp")).read()
+    return (int(re.search(r"#define WV_LIST (\d+)", src).group(1)),
+            int(re.search(r"#define WV_PF (\d+)", src).group(1)))
+
+
+def widom_occ():
+    """WIDOM_OCC of mmc_widom.hpp: the waves per SIMD k_widom_wave's launch is capped at."""
+    src = open(os.path.join(HERE, "..", "metropolismontecarlo_amd", "csrc", "mmc_widom.hpp")).read()
+    return int(re.search(r"#define WIDOM_OCC (\d+)", src).group(1))
+
+
+def image_shift(d, box):
+    """What the minimum image (vector1D, Ewald/boundaries.jl) adds to a coordinate difference d."""
+    return np.where(d >= 0.5 * box, -box, np.where(d <= -0.5 * box, box, 0.0))
+
+
+def scan_flushes(com, centres, gate, box, j_begin=0, j_end=None, exclude=None):
+    """Whether the COM scan of mmc_wave_unit.inc certainly empties its neighbour list mid-scan and
+    has neighbours left for a later process() call: the unit's centres (one for an insertion, old
+    and new COM for a move) scan molecules [j_begin, j_end) in trips of 64 WV_PF; after a trip the
+    list is processed and emptied when it holds more than WV_LIST - 64 WV_PF entries.  Counted here
+    is the exact gate (a COM within `gate` of a centre, minimum image, by a relative margin of 1e-9
+    so that rounding cannot add one) -- a lower bound on the 16-bit prefilter's count.  True when,
+    at some trip boundary B, more than that many gated molecules lie before B and at least one
+    after it: then some boundary <= B flushes (the count since the last flush cannot stay below
+    the threshold), and a later process() call adds to the sums.  `exclude`: a molecule left out
+    of both counts (a move's own molecule, which process() drops)."""
+    n_list, n_pf = _wave_list_consts()
+    com = np.asarray(com, dtype=float)
+    j_end = com.shape[0] if j_end is None else j_end
+    gated = np.zeros(com.shape[0], dtype=bool)
+    for c in np.atleast_2d(centres):
+        d = com - np.asarray(c, dtype=float)
+        d = d + image_shift(d, box)
+        gated |= (d * d).sum(1) < gate * gate * (1 - 1e-9)
+    if exclude is not None:
+        gated[exclude] = False
+    gated[:j_begin] = False
+    gated[j_end:] = False
+    before = np.cumsum(gated)
+    total = int(before[-1]) if before.size else 0
+    for b in range(j_begin + 64 * n_pf, j_end, 64 * n_pf):
+        if before[b - 1] > n_list - 64 * n_pf and total - before[b - 1] > 0:
+            return True
+    return False
+
+
+def image_differs(mol, com, coords, box, gate, slack_sq):
+    """Molecules j whose COM is within `gate` of the test molecule mol[12] (atoms, COM) while an
+    atom pair of (test, j) takes another minimum image than the molecules' COMs and lies inside
+    the slack r^2 < slack_sq in one of the two images: the pairs whose terms the per-molecule image
+    of the kernels' IMG variants (mmc_wave_unit.inc; the slack is tested in both) would change."""
+    at = np.asarray(mol[:9], dtype=float).reshape(3, 3)
+    dc = np.asarray(com) - np.asarray(mol[9:12])
+    sc = image_shift(dc, box)
+    near = np.nonzero(((dc + sc) ** 2).sum(1) < gate * gate)[0]
+    out = []
+    for j in near:
+        da = coords[3 * j:3 * j + 3][None, :, :] - at[:, None, :]
+        sa = image_shift(da, box)
+        per_pair, per_mol = ((da + sa) ** 2).sum(2), ((da + sc[j]) ** 2).sum(2)
+        differs = (sa != sc[j]).any(2) & (np.minimum(per_pair, per_mol) < slack_sq)
+        if differs.any():
+            out.append(int(j))
+    return out
+
+
+# ---- Widom insertion against the oracle --------------------------------------------------------
+def widom_oracle_terms(orc, a, com, coords, mol, box, lj_rcut, qq_rcut, alpha=5.6):
+    """(d_lj, d_real, d_recip, overlap, (ewald, charges)) of one test molecule mol[12] appended as
+    molecule N + 1 to the configuration (com, coords) of the system `a` (topology and tables) in
+    the box `box`, kappa = alpha / box.  The reference has no insertion code; dU is defined as the
+    change of its potential(..., "ewald") (include/mmc_hip.h):
+      d_lj    == orc.lj_poly_du(N+1)
+      d_real  == orc.ewald_short(N+1)                   (0 when it reports an overlap)
+      d_recip == factor (recip_long(N+1) - recip_long(N)) + orc.ewald_self(the test molecule)
+    RecipLong is recomputed from the coordinates, so a wrong S buffer of the device shows."""
+    from metropolismontecarlo_amd import structs
+    n = com.shape[0]
+    L = float(box)
+    q3 = np.asarray(a["charge"][:3], dtype=float)
+    com1 = np.vstack([com, mol[9:12]])
+    coords1 = np.vstack([coords, np.asarray(mol[:9]).reshape(3, 3)])
+    first = np.arange(1, 3 * (n + 1), 3, dtype=np.int64)
+    at1 = np.concatenate([np.asarray(a["atype"])[:3 * n], np.asarray(a["atype"])[:3]])
+    q1 = np.concatenate([np.asarray(a["charge"][:3 * n], dtype=float), q3])
+    s1 = orc.System(com1, first, first + 2, coords1, at1, q1, a["eps"], a["sig"], L)
+    ew = orc.Ewald(alpha / L, 5, 27, L, factor=structs.factor)
+    lj, _ = orc.lj_poly_du(n + 1, s1, lj_rcut)
+    real, _, ov = orc.ewald_short(n + 1, s1, ew, qq_rcut)
+    rl1 = orc.recip_long(ew, coords1, q1, L)
+    rl0 = orc.recip_long(ew, coords, q1[:3 * n], L)
+    recip = ew.factor * (rl1 - rl0) + orc.ewald_self(ew, q3)
+    return lj, real, recip, ov, (ew, q1)
+
+
+def widom_close(x, ref):
+    """1e-9 K absolute plus 1e-13 of the term (the erfc table's error, tests/test_gpu_table.py)."""
+    return abs(x - ref) <= 1e-9 + 1e-13 * abs(ref)
+
+
+def check_widom(orc, a, b, r, mols, du, ovl, lj_rcut, qq_rcut, alpha=5.6, what=""):
+    """Every term and the overlap flag of replica r's insertions mols [M][12] against the oracle, on
+    the replica's own coordinates (get_replica) in its own box (get_boxes)."""
+    com, coords, _ = b.get_replica(r)
+    box = float(b.get_boxes()[r])
+    bad = []
+    for j in range(mols.shape[0]):
+        lj, real, recip, ov, _ = widom_oracle_terms(orc, a, com, coords, mols[j], box, lj_rcut, qq_rcut,
+                                                    alpha)
+        if bool(ovl[j] & 1) != ov:
+            bad.append((j, "overlap", int(ovl[j]), ov))
+        for name, x, ref in (("lj", du[j, 0], lj), ("real", du[j, 1], real), ("recip", du[j, 2], recip)):
+            if not widom_close(x, ref):
+                bad.append((j, name, x, ref))
+    assert not bad, f"{what} replica {r}: {bad[:6]}"
+
+
+def widom_host_sums(du, ovl, boltz0, novl0, temperature):
+    """The in-order reduction the library promises, on the host: boltz[r] += exp(-dU / T) of every
+    unflagged insertion in insertion order, n_overlap[r] += the flagged ones.  The weight's argument
+    is -dU * (1 / T) as k_widom_reduce forms it: with weights of 1e20 and more (|dU| / T ~ 50), the
+    rounding of dividing instead moves a weight by 1e-14 of itself.  (Vectorised over the replicas,
+    sequential over the insertions: each replica's additions are those of a plain loop.)"""
+    bs = np.array(boltz0, dtype=float).copy()
+    no = np.array(novl0, dtype=np.int64).copy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = (du[:, :, 0] + du[:, :, 1]) + du[:, :, 2]
+        w = np.exp(-d * (1.0 / temperature))
+    flagged = ovl != 0
+    for j in range(du.shape[1]):
+        bs = np.where(flagged[:, j], bs, bs + w[:, j])
+    no += flagged.sum(1)
+    return bs, no

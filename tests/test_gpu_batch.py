@@ -923,9 +923,9 @@ def test_minimum_image_by_molecule_is_bit_identical(cfg, parts):
     assert 0 < out[0][3] < 24 * n_steps
 
 
-def _dense_water(n_mol, seed=5):
+def _dense_water(n_mol, seed=5, rho=0.033101144):
     from metropolismontecarlo_amd import io as mio
-    box, com, coords = mio.cubic_lattice_water(n_mol, 0.033101144, "spce", seed=seed)
+    box, com, coords = mio.cubic_lattice_water(n_mol, rho, "spce", seed=seed)
     a4 = common.nist_arrays(4, "unwrapped")
     first = 3 * np.arange(n_mol, dtype=np.int64) + 1
     return dict(com=com, coords=coords, first_atom=first, last_atom=first + 2,
@@ -949,17 +949,23 @@ def test_table_kernels_are_refused_beyond_16_bit_molecule_indices():
         b.set_option("kernel", 0)
 
 
-@pytest.mark.parametrize("kernel,parts", [(2, 1), (1, 1), (2, 3), (1, 2)])
-def test_long_neighbour_lists_and_many_molecules(kernel, parts, orc):
-    """1700 molecules with a 12.4 A cutoff: ~265 neighbours inside the gate, i.e. more than one
-    neighbour tile (150) and more than one molecule chunk (768) for the workgroup-per-move kernel,
-    and a neighbour list that overflows its 256 slots mid-scan for the wave-per-move kernel.
+@pytest.mark.parametrize("kernel,parts,n_mol,rho", [
+    pytest.param(k, p, n, rho, id=f"{k}-{p}" + ("" if n == 1700 else "-compressed"))
+    for n, rho in ((1700, 0.033101144), (2000, 0.06)) for k, p in ((2, 1), (1, 1), (2, 3), (1, 2))])
+def test_long_neighbour_lists_and_many_molecules(kernel, parts, n_mol, rho, orc):
+    """1700 molecules at liquid density with a 12.4 A cutoff: ~250 neighbours inside the gate, i.e.
+    more than one neighbour tile (150) and more than one molecule chunk (768) for the
+    workgroup-per-move kernel.  Its wave-per-move scan does not certainly empty its list of 640
+    slots mid-scan (more than WV_LIST - 64 WV_PF = 256 gated molecules after some trip of
+    64 WV_PF, common.scan_flushes, with more after): the exact gate never reaches that count.
+    2000 molecules compressed to 0.06 / A^3 (32.2 A, 430-520 in the gate) do: every move's scan
+    over all molecules (one part) flushes and goes on, so its sums add across process() calls.
     A chain of moves against the oracle and against the generic kernel, then a native-driver run
     whose running total must match a recompute."""
     from metropolismontecarlo_amd import structs
     from metropolismontecarlo_amd.device import Batch
-    a = _dense_water(1700)
-    n_mol, rcut = 1700, 12.4
+    a = _dense_water(n_mol, rho=rho)
+    rcut = 12.4
     s_o = common.oracle_system(a)
     ew = orc.Ewald(5.6 / a["box"], 5, 27, a["box"])
     orc.recip_long(ew, s_o.coords, s_o.charge, s_o.box)
@@ -977,11 +983,14 @@ def test_long_neighbour_lists_and_many_molecules(kernel, parts, orc):
         b.recip_long()
         bg.recip_long()
         acc_prev = None
+        flushes = []
         for step in range(6):
-            i = int(rng.integers(1, n_mol + 1)) if step != 3 else 1700   # the last molecule too
+            i = int(rng.integers(1, n_mol + 1)) if step != 3 else n_mol   # the last molecule too
             d = (rng.random(3) - 0.5) * 0.5
             c_new = s_o.com[i - 1] + d
             a_new = s_o.coords[3 * (i - 1):3 * i] + d
+            flushes.append(common.scan_flushes(s_o.com, [s_o.com[i - 1], c_new], rcut, a["box"],
+                                               exclude=i - 1))
             out, ov = b.eval(np.full(2, i), np.tile(c_new, (2, 1)), np.tile(a_new, (2, 1, 1)),
                              accept_prev=acc_prev)
             outg, ovg = bg.eval(np.full(2, i), np.tile(c_new, (2, 1)), np.tile(a_new, (2, 1, 1)),
@@ -1000,6 +1009,7 @@ def test_long_neighbour_lists_and_many_molecules(kernel, parts, orc):
             else:
                 ew.sumQExpNew[:] = ew.sumQExpOld
             acc_prev = np.full(2, accept)
+        assert all(flushes) if n_mol == 2000 else not any(flushes), flushes
         b.settle(acc_prev)
         bg.settle(acc_prev)
         for dev in (0, 1):

@@ -47,54 +47,16 @@ def make_batch(a, R, rcut=RCUT):
 def oracle_terms(orc, a, com, coords, mol):
     """(d_lj, d_real, d_recip, overlap, d_self_exact) of one test molecule mol[12] appended to the
     configuration (com, coords) of the system `a` (topology, tables, box)."""
-    n = com.shape[0]
-    L = float(a["box"])
-    q3 = np.asarray(a["charge"][:3], dtype=float)
-    com1 = np.vstack([com, mol[9:12]])
-    coords1 = np.vstack([coords, mol[:9].reshape(3, 3)])
-    first = np.arange(1, 3 * (n + 1), 3, dtype=np.int64)
-    at1 = np.concatenate([a["atype"][:3 * n], a["atype"][:3]])
-    q1 = np.concatenate([np.asarray(a["charge"][:3 * n], dtype=float), q3])
-    s1 = orc.System(com1, first, first + 2, coords1, at1, q1, a["eps"], a["sig"], L)
-    ew = orc.Ewald(5.6 / L, 5, 27, L, factor=structs.factor)
-    lj, _ = orc.lj_poly_du(n + 1, s1, RCUT)
-    real, _, ov = orc.ewald_short(n + 1, s1, ew, RCUT)
-    rl1 = orc.recip_long(ew, coords1, q1, L)
-    rl0 = orc.recip_long(ew, coords, q1[:3 * n], L)
-    recip = ew.factor * (rl1 - rl0) + orc.ewald_self(ew, q3)
-    return lj, real, recip, ov, (ew, q1)
-
-
-def close(x, ref):
-    return abs(x - ref) <= 1e-9 + 1e-13 * abs(ref)
+    return common.widom_oracle_terms(orc, a, com, coords, mol, a["box"], RCUT, RCUT)
 
 
 def check_against_oracle(orc, a, b, r, mols, du, ovl):
-    com, coords, _ = b.get_replica(r)
-    bad = []
-    for j in range(mols.shape[0]):
-        lj, real, recip, ov, _ = oracle_terms(orc, a, com, coords, mols[j])
-        if bool(ovl[j] & 1) != ov:
-            bad.append((j, "overlap", int(ovl[j]), ov))
-        for name, x, ref in (("lj", du[j, 0], lj), ("real", du[j, 1], real), ("recip", du[j, 2], recip)):
-            if not close(x, ref):
-                bad.append((j, name, x, ref))
-    assert not bad, f"replica {r}: {bad[:6]}"
+    common.check_widom(orc, a, b, r, mols, du, ovl, RCUT, RCUT)
 
 
 def host_sums(du, ovl, boltz0, novl0):
     """The in-order reduction the library promises, on the host."""
-    bs, no = np.array(boltz0, dtype=float), np.array(novl0, dtype=np.int64)
-    for r in range(du.shape[0]):
-        acc = bs[r]
-        for j in range(du.shape[1]):
-            d = (du[r, j, 0] + du[r, j, 1]) + du[r, j, 2]
-            if ovl[r, j] != 0:
-                no[r] += 1
-            else:
-                acc += math.exp(-d / T)
-        bs[r] = acc
-    return bs, no
+    return common.widom_host_sums(du, ovl, boltz0, novl0, T)
 
 
 @pytest.fixture(scope="module")

@@ -89,3 +89,51 @@ def test_ewald_intra_energy_by_hand():
     # two unit charges 2 A apart
     assert abs(obs.ewald_intra_energy([[0, 0, 0], [0, 0, 2.0]], [1.0, -1.0], 0.5, 1.0)
                - (-math.erf(1.0) / 2.0)) < 1e-15
+
+
+def test_scan_flush_helper_on_a_hand_built_line():
+    """common.scan_flushes, which the GPU tests use to show that a scan of mmc_wave_unit.inc empties
+    its neighbour list mid-scan, on molecules laid out by hand: gated ones 0.01 A apart around the
+    centre, the others 40 A away, in a 1000 A box."""
+    import common
+    n_list, n_pf = common._wave_list_consts()
+    trip, thr = 64 * n_pf, n_list - 64 * n_pf
+    assert (trip, thr) == (384, 256)
+    box, gate, centre = 1000.0, 10.0, np.array([5.0, 500.0, 500.0])
+
+    def line(gated):
+        com = np.tile(centre + np.array([0.0, 40.0, 0.0]), (len(gated), 1))
+        for j, g in enumerate(gated):
+            if g:
+                com[j] = centre + np.array([0.01 * (j % 500) - 2.5, 0.0, 0.0])
+        return com
+
+    def case(n_before, after_at, n=900, j_begin=0, exclude=None):
+        g = np.zeros(n, dtype=bool)
+        g[j_begin:j_begin + n_before] = True
+        if after_at is not None:
+            g[after_at] = True
+        return common.scan_flushes(line(g), [centre], gate, box, j_begin=j_begin, exclude=exclude)
+
+    assert case(257, 384)                 # 257 before the first trip boundary, one at it
+    assert case(257, 899)
+    assert not case(256, 384)             # not more than the threshold
+    assert not case(300, None)            # nothing left after the boundary
+    assert not case(257, 384, exclude=3)  # the unit's own molecule does not count
+    assert not case(257, 383, n=384)      # no boundary inside [0, n): the scan ends in one trip
+    # boundaries follow j_begin: [100, 484) is the first trip
+    assert case(257, 484, j_begin=100)
+    assert not case(257, 483, j_begin=100)
+    # two centres (a move's old and new COM) gate their union; the minimum image counts
+    g = np.zeros(900, dtype=bool)
+    g[:200] = True
+    g[400] = True
+    com = line(g)
+    com[200:260] = centre + np.array([-12.0, 0.0, 0.0])         # gated by the second centre only
+    assert not common.scan_flushes(com, [centre], gate, box)
+    assert common.scan_flushes(com, [centre, centre + np.array([-8.0, 0.0, 0.0])], gate, box)
+    com[200:260] = centre + np.array([-12.0 + box, 0.0, 0.0])    # the same through the boundary
+    assert common.scan_flushes(com, [centre, centre + np.array([-8.0, 0.0, 0.0])], gate, box)
+    # the exact gate, by a margin: a COM on the gate does not count
+    com[:200] = centre + np.array([0.0, gate, 0.0])
+    assert not common.scan_flushes(com, [centre, centre + np.array([-8.0, 0.0, 0.0])], gate, box)
