@@ -159,22 +159,29 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_mol_energy(BatchView bv, int i_ba
     __shared__ double red[3 * MMC_WAVES];
     const int r = blockIdx.y, i0 = i_base + blockIdx.x;
     const SysView s = sys_view(bv, r);
-    const int na = min(s.cnt[i0], MMC_MAX_ATOMS);
-    if (threadIdx.x < na) {
-        const int a = s.first0[i0] + threadIdx.x;
-        ch.at[0][threadIdx.x][0] = s.ax[a];
-        ch.at[0][threadIdx.x][1] = s.ay[a];
-        ch.at[0][threadIdx.x][2] = s.az[a];
-        ch.q[threadIdx.x] = s.charge[a];
-        ch.type[threadIdx.x] = s.atype[a];
-    }
-    if (threadIdx.x == 0) {
-        ch.i0 = i0; ch.na = na;
-        ch.com[0][0] = s.comx[i0]; ch.com[0][1] = s.comy[i0]; ch.com[0][2] = s.comz[i0];
-    }
-    __syncthreads();
+    // The totals call this for every molecule of any size: the chosen molecule's atoms go through
+    // the LDS staging area MMC_MAX_ATOMS at a time, each tile a full scan of the neighbours, the
+    // sums and the overlap flag carried across tiles (one tile, and the same sums, up to 16 atoms)
+    const int n_at = s.cnt[i0], f0 = s.first0[i0];
     PairAcc acc[1] = { { 0.0, 0.0, 0.0, 0 } };
-    pair_scan<1, LJ, QQ, STYLE, false>(s, &ch, nullptr, 0, s.n_mol, pp, list, wcnt, acc);
+    for (int t0 = 0; t0 < n_at; t0 += MMC_MAX_ATOMS) {
+        const int na = min(n_at - t0, MMC_MAX_ATOMS);
+        if (threadIdx.x < na) {
+            const int a = f0 + t0 + threadIdx.x;
+            ch.at[0][threadIdx.x][0] = s.ax[a];
+            ch.at[0][threadIdx.x][1] = s.ay[a];
+            ch.at[0][threadIdx.x][2] = s.az[a];
+            ch.q[threadIdx.x] = s.charge[a];
+            ch.type[threadIdx.x] = s.atype[a];
+        }
+        if (threadIdx.x == 0) {
+            ch.i0 = i0; ch.na = na;
+            ch.com[0][0] = s.comx[i0]; ch.com[0][1] = s.comy[i0]; ch.com[0][2] = s.comz[i0];
+        }
+        __syncthreads();
+        // (pair_scan ends with a barrier: no thread still reads ch when the next tile is staged)
+        pair_scan<1, LJ, QQ, STYLE, false>(s, &ch, nullptr, 0, s.n_mol, pp, list, wcnt, acc);
+    }
     double v[3] = { acc[0].lj_pot, acc[0].lj_vir, acc[0].qq_pot }, tot[3];
     const int ovl = __syncthreads_or(acc[0].ovl);
     block_sum<3>(v, red, tot);

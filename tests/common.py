@@ -90,6 +90,78 @@ def random_system(n_mol, box, seed, na_choices=(3,), n_types=2, min_sep=2.2):
                 charge=charge, eps=eps, sig=sig, box=float(box))
 
 
+TIP3P_Q = (-0.834, 0.417, 0.417)   # the SOL charges of tests/golden/decks/topol.top
+MIX_ORDERS = ("interleaved", "blocks", "minority1")
+
+
+def spce_tip3p_mixture(k, order):
+    """NIST SPC/E configuration k with some of its molecules made TIP3P waters: a 3-site mixture
+    of four atom types (SPC/E O, H = 1, 2; TIP3P O, H = 3, 4), two charge sets and two geometries
+    (TIP3P's O-H bonds shortened to 0.9572 A about the oxygen, the centre of mass recomputed with
+    the water masses).  `order`: "interleaved" (every other molecule from molecule 2), "blocks"
+    (the second half) or "minority1" (molecule 1, the homogeneity template, and every fifth: the
+    minority species).  Returns the arrays of the system and the 0/1 species of every molecule."""
+    from metropolismontecarlo_amd import structs
+    a = mio.load_nist_fixture(k, "unwrapped")
+    n = a["com"].shape[0]
+    tip = np.zeros(n, dtype=bool)
+    if order == "interleaved":
+        tip[1::2] = True
+    elif order == "blocks":
+        tip[n // 2:] = True
+    elif order == "minority1":
+        tip[::5] = True
+    else:
+        raise ValueError(order)
+    coords = a["coords"].copy().reshape(n, 3, 3)
+    com = a["com"].copy()
+    m = np.array([15.9994, 1.008, 1.008])
+    for j in np.nonzero(tip)[0]:
+        o = coords[j, 0]
+        coords[j, 1:] = o + (coords[j, 1:] - o) * 0.9572
+        com[j] = (coords[j] * m[:, None]).sum(0) / m.sum()
+    atype = np.tile([1, 2, 2], n).reshape(n, 3)
+    atype[tip] += 2
+    charge = np.tile([mio.SPCE_Q_O, mio.SPCE_Q_H, mio.SPCE_Q_H], n).reshape(n, 3)
+    charge[tip] = TIP3P_Q
+    tab = structs.Tables([mio.SPCE_EPS_O, 0.0, 0.6364 / structs.R, 0.0],
+                         [mio.SPCE_SIGMA_O, 0.0, 3.15061, 0.0])
+    return dict(a, com=com, coords=coords.reshape(-1, 3), atype=atype.ravel().astype(np.int64),
+                charge=charge.ravel(), eps=tab.eps_ij, sig=tab.sig_ij), tip.astype(int)
+
+
+def mea_tip3p_box(n_water=250, mea_at=(0, 37, 130, 201), rho=0.016, seed=5):
+    """The reference's mixture deck (tests/golden/decks: topol.top, mea.pdb, tip3p.pdb): MEA
+    molecules (11 atoms) at positions `mea_at` of the molecule list among n_water TIP3P waters, on
+    the simple-cubic sites of InitCubicGrid at number density rho with random orientations, and
+    the full 13-type table of MakeTables.  Waters follow an MEA in the arrays.  Returns the arrays
+    of Context.upload_system (plus "mass")."""
+    top = mio.ReadTopFile(os.path.join(GOLDEN, "decks", "topol.top"), substitutions={"SOLNUMBER": 1})
+    mea = mio.system_from_decks(mio.ReadPDB(os.path.join(GOLDEN, "decks", "mea.pdb")), top)
+    wat = mio.system_from_decks(mio.ReadPDB(os.path.join(GOLDEN, "decks", "tip3p.pdb")), top)
+    n_mol = n_water + len(mea_at)
+    box, sites = mio.InitCubicGrid(n_mol, rho)
+    rng = np.random.default_rng(seed)
+    com, coords, atype, charge, mass, first, last = [], [], [], [], [], [], []
+    for j in range(n_mol):
+        m = mea if j in mea_at else wat
+        body = m["coords"] - m["com"][0]
+        q = rng.normal(size=4)
+        w, x, y, z = q / np.linalg.norm(q)
+        rot = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                        [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                        [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        first.append(1 + sum(len(c) for c in coords))
+        coords.append(sites[j] + body @ rot.T)
+        last.append(first[-1] + len(body) - 1)
+        com.append(sites[j])
+        atype.append(m["atype"]); charge.append(m["charge"]); mass.append(m["mass"])
+    return dict(com=np.array(com, dtype=float), coords=np.concatenate(coords),
+                first_atom=np.array(first, dtype=np.int64), last_atom=np.array(last, dtype=np.int64),
+                atype=np.concatenate(atype).astype(np.int64), charge=np.concatenate(charge),
+                mass=np.concatenate(mass), eps=mea["eps"], sig=mea["sig"], box=float(box))
+
+
 # ---- which replica k_move_eval_wave runs where ----------------------------------------------------
 def _wave_consts():
     """(waves per workgroup, waves per SIMD) of k_move_eval_wave, read from its source so that the

@@ -224,38 +224,177 @@ def test_batch_errors():
         make_batch(bad, 1)
 
 
-def test_non_homogeneous_system_uses_generic_kernel(orc):
-    """Different charges on different molecules: the fast kernel does not apply, the batch must
-    fall back to the generic one by itself and refuse kernel=1."""
-    from metropolismontecarlo_amd._lib import MMCError
+def _rotated(rng, com, atoms, dr, dphi):
+    """A rigid move: translation by up to dr per axis, rotation by up to dphi about the COM."""
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    t = (rng.random() - 0.5) * 2 * dphi
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    rot = np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * K @ K
+    c = com + (rng.random(3) - 0.5) * 2 * dr
+    return c, (atoms - com) @ rot.T + c
+
+
+# NIST configuration 1 made non-homogeneous in exactly one place (molecule, what differs)
+NEAR_HOMOGENEOUS = {"half2": 2,      # molecule 2's charges halved
+                    "last_h": 100,   # the last molecule's H charges (O compensates: still neutral)
+                    "hoh": 37,       # molecule 37 lists its sites H, O, H
+                    "first": 1}      # molecule 1, the template of the homogeneity test, alone differs
+
+
+def non_homogeneous(name):
+    """(arrays, 0/1 species of every molecule) of the non-homogeneous 3-site systems: the
+    near-homogeneous variants of NIST configuration 1 (NEAR_HOMOGENEOUS, species 1 = the odd
+    molecule) and the mixtures spce_tip3p_mixture(1, order)."""
+    if name not in NEAR_HOMOGENEOUS:
+        return common.spce_tip3p_mixture(1, name)
     a = common.nist_arrays(1, "unwrapped")
-    a = dict(a, charge=a["charge"].copy())
-    a["charge"][3:6] *= 0.5          # molecule 2 is different (still neutral)
-    g = common.golden(1, "unwrapped")
-    mv = g["moves"][0]
-    s = common.oracle_system(a)
-    ew = orc.Ewald(5.6 / s.box, 5, 27, s.box)
-    orc.recip_long(ew, s.coords, s.charge, s.box)
-    do, ovo = orc.trial_move(mv["mol"], s, ew, RCUT, RCUT, np.array(mv["com_new"]),
-                             np.array(mv["atoms_new"]))
-    with make_batch(a, 2) as b:
+    a = dict(a, charge=a["charge"].copy(), coords=a["coords"].copy(), atype=a["atype"].copy())
+    m = NEAR_HOMOGENEOUS[name]
+    sl = slice(3 * (m - 1), 3 * m)
+    if name == "half2":
+        a["charge"][sl] *= 0.5
+    elif name == "last_h":
+        a["charge"][sl] = [-0.82, 0.41, 0.41]
+    elif name == "hoh":
+        for key in ("charge", "coords", "atype"):
+            a[key][sl] = a[key][sl][[1, 0, 2]]
+    else:
+        a["charge"][sl] *= 0.9
+    sp = np.zeros(a["com"].shape[0], dtype=int)
+    sp[m - 1] = 1
+    return a, sp
+
+
+def check_generic_only(b):
+    """A non-homogeneous batch stays on kernel 0: the fast kernels and Widom refuse it."""
+    from metropolismontecarlo_amd._lib import MMCError
+    for k in (1, 2, 3, 4):
         with pytest.raises(MMCError, match="MMC_ERR_UNSUPPORTED"):
-            b.set_option("kernel", 1)
+            b.set_option("kernel", k)
+    b.set_option("kernel", 0)
+
+
+def test_non_homogeneous_system_uses_generic_kernel(orc):
+    """Different charges on different molecules (molecule 2's halved): the fast kernel does not
+    apply, the batch must fall back to the generic one by itself and refuse kernels 1-4.  A chain
+    of host proposals moving the odd molecule and ordinary ones in three replicas with different
+    decisions, against three oracle chains."""
+    _generic_kernel_chain("half2", orc)
+
+
+@pytest.mark.parametrize("name", [n for n in NEAR_HOMOGENEOUS if n != "half2"] + list(common.MIX_ORDERS))
+def test_near_homogeneous_and_mixed_systems_use_generic_kernel(name, orc):
+    """test_non_homogeneous_system_uses_generic_kernel on the other systems that differ from
+    homogeneous in one place (NEAR_HOMOGENEOUS) and on SPC/E + TIP3P mixtures: the moves cover
+    both species (the odd molecule and ordinary ones; SPC/E and TIP3P waters)."""
+    _generic_kernel_chain(name, orc)
+
+
+def _generic_kernel_chain(name, orc):
+    a, sp = non_homogeneous(name)
+    g = common.golden(1, "unwrapped")
+    rng = np.random.default_rng(7)
+    moves = [dict(g["moves"][0])]
+    odd = [int(j) + 1 for j in np.nonzero(sp == 1)[0]]
+    even = [int(j) + 1 for j in np.nonzero(sp == 0)[0]]
+    pick = [odd[0], even[0], odd[-1], even[-1], odd[0]] + \
+        [int(x) for x in rng.choice(odd, 4)] + [int(x) for x in rng.choice(even, 4)]
+    for i in pick:
+        c, at = _rotated(rng, a["com"][i - 1], a["coords"][3 * (i - 1):3 * i], 0.2, 0.3)
+        moves.append(dict(mol=i, com_new=c.tolist(), atoms_new=at.tolist()))
+    rules = [lambda n, ov: True, lambda n, ov: False, lambda n, ov: n % 3 != 1]
+    chains = [oracle_chain(orc, a, moves, r) for r in rules]
+    R = len(rules)
+    with make_batch(a, R) as b:
+        check_generic_only(b)
         b.recip_long()
-        d, ov = b.eval(mv["mol"], np.tile(mv["com_new"], (2, 1)),
-                       np.tile(np.array(mv["atoms_new"]).ravel(), (2, 1)))
-        assert ov[0] == ovo and np.abs(d[0] - do).max() < TOL * (np.abs(do).max() + 1e4)
+        acc_prev = np.zeros(R, dtype=bool)
+        for n, mv in enumerate(moves):
+            d, ov = b.eval(mv["mol"], np.tile(mv["com_new"], (R, 1)),
+                           np.tile(np.array(mv["atoms_new"]).ravel(), (R, 1)), acc_prev)
+            for r in range(R):
+                do, ovo, acco = chains[r][0][n]
+                assert ov[r] == ovo, (n, r)
+                assert np.abs(d[r] - do).max() < TOL * (np.abs(do).max() + 1e4), (n, r, d[r], do)
+                acc_prev[r] = acco
+        b.settle(acc_prev)
+        tot = b.potential_ewald()
+        for r in range(R):
+            com, coords, S = b.get_replica(r)
+            _, s, ewr = chains[r]
+            assert np.array_equal(com, s.com) and np.array_equal(coords, s.coords), r
+            assert np.abs(S - ewr.sumQExpOld).max() < 1e-11 * np.abs(ewr.sumQExpOld).max(), r
+            to = orc.potential_ewald(s, orc.Ewald(5.6 / s.box, 5, 27, s.box), RCUT, RCUT)
+            for key in ("energy", "virial", "lj", "real", "recip", "self"):
+                assert rel(tot[r][key], to[key]) < TOL, (r, key)
+    # both species moved, with accepted and rejected moves of each in the third chain
+    acc3 = [c[2] for c in chains[2][0]]
+    for group in (odd, even):
+        steps = [n for n, mv in enumerate(moves) if mv["mol"] in group]
+        assert any(acc3[n] for n in steps) and not all(acc3[n] for n in steps), name
+
+
+@pytest.mark.parametrize("order", common.MIX_ORDERS)
+def test_mixture_batch_totals_of_different_replicas(order, orc):
+    """Batched potential_ewald and recip_long of a mixture whose replicas hold different
+    configurations (set_replica), each against the oracle; Widom and per-replica boxes refuse a
+    non-homogeneous batch."""
+    from metropolismontecarlo_amd._lib import MMCError
+    a, sp = common.spce_tip3p_mixture(1, order)
+    R, n_mol = 4, a["com"].shape[0]
+    rng = np.random.default_rng(3)
+    states = []
+    for r in range(R):
+        com, coords = a["com"].copy(), a["coords"].copy()
+        for i in rng.choice(n_mol, 10 * r, replace=False):
+            com[i], coords[3 * i:3 * i + 3] = _rotated(rng, com[i], coords[3 * i:3 * i + 3], 0.3, 0.5)
+        states.append((com, coords))
+    with make_batch(a, R) as b:
+        check_generic_only(b)
+        b.potential_ewald()
+        with pytest.raises(MMCError, match="MMC_ERR_UNSUPPORTED"):
+            b.widom(4, 298.15, 1)
+        with pytest.raises(MMCError, match="MMC_ERR_UNSUPPORTED"):
+            b.set_boxes(np.full(R, a["box"]))
+        for r, (com, coords) in enumerate(states):
+            b.set_replica(r, com, coords)
+        rl = b.recip_long()
+        tot = b.potential_ewald()
+        energies = set()
+        for r, (com, coords) in enumerate(states):
+            s = common.oracle_system(dict(a, com=com, coords=coords))
+            ew = orc.Ewald(5.6 / s.box, 5, 27, s.box)
+            assert rel(rl[r], orc.recip_long(ew, s.coords, s.charge, s.box)) < TOL, r
+            to = orc.potential_ewald(s, ew, RCUT, RCUT)
+            for key in ("energy", "virial", "lj", "real", "recip", "self"):
+                assert rel(tot[r][key], to[key]) < TOL, (r, key, tot[r][key], to[key])
+            assert tot[r]["n_overlap"] == to["n_overlap"]
+            energies.add(round(to["energy"], 3))
+        assert len(energies) == R
 
 
 @pytest.mark.parametrize("R,groups,parts,threads,kernel",
                          [(1, 1, 0, 1, 2), (5, 2, 0, 1, 2), (16, 3, 1, 3, 2), (8, 2, 4, 2, 0),
                           (12, 4, 0, 2, 1), (9, 2, 3, 2, 2)])
 def test_engine_running_total_vs_recompute(R, groups, parts, threads, kernel, orc):
+    _engine_running_total(R, groups, parts, threads, kernel, "nist1", orc)
+
+
+@pytest.mark.parametrize("R,groups,parts,threads,system",
+                         [(6, 2, 0, 2, "interleaved"), (5, 2, 3, 2, "minority1")])
+def test_engine_running_total_vs_recompute_mixture(R, groups, parts, threads, system, orc):
+    """test_engine_running_total_vs_recompute on SPC/E + TIP3P mixtures (kernel 0)."""
+    _engine_running_total(R, groups, parts, threads, 0, system, orc)
+
+
+def _engine_running_total(R, groups, parts, threads, kernel, system, orc):
     """The reference's only integration invariant (Poly/main.jl:232-235): the running total
     energy (initial + accepted deltas) equals a full recompute -- here after hundreds of native
     driver steps, which also proves that commits reached the device coordinates and that the
-    incrementally updated S(k) still matches a fresh RecipLong."""
-    a = common.nist_arrays(1, "unwrapped")
+    incrementally updated S(k) still matches a fresh RecipLong.  Also on SPC/E + TIP3P mixtures
+    (common.spce_tip3p_mixture), which run the generic kernel."""
+    a = common.nist_arrays(1, "unwrapped") if system == "nist1" else common.spce_tip3p_mixture(1, system)[0]
     n_steps = 260  # > 2 sweeps of 100 molecules: every molecule is proposed several times
     with make_batch(a, R) as b:
         b.set_option("kernel", kernel)

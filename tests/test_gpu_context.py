@@ -199,27 +199,63 @@ def test_overlap_sentinel(orc):
         assert rel(t["real"], to["real"]) < TOL and rel(t["energy"], to["energy"]) < TOL
 
 
-@pytest.mark.parametrize("seed,na", [(1, (3,)), (2, (1, 2, 3, 5)), (3, (11,)), (4, (1,))])
+@pytest.mark.parametrize("seed,na", [(1, (3,)), (2, (1, 2, 3, 5)), (3, (11,)), (4, (1,)), (5, (16,)),
+                                     (6, (3, 17)), (7, (24,)), (8, (1, 5, 16, 17))])
 def test_ragged_random_systems(seed, na, orc):
     """Molecules of different sizes (firstAtom/lastAtom ranges), several atom types, zero-eps
-    pairs, n_mol not a multiple of the workgroup size."""
+    pairs, n_mol not a multiple of the workgroup size.  Sizes straddle MMC_MAX_ATOMS = 16: the
+    totals count every atom of every molecule (k_mol_energy stages a chosen molecule 16 atoms at a
+    time), the per-molecule calls take molecules of at most 16 atoms -- next to bigger ones -- and
+    refuse bigger ones."""
+    from metropolismontecarlo_amd._lib import MMCError
     a = common.random_system(237, 24.0, seed, na_choices=na, n_types=3)
     s = common.oracle_system(a)
     kappa = 5.6 / s.box
+    ew = orc.Ewald(kappa, 5, 27, s.box)
+    cnt = a["last_atom"] - a["first_atom"] + 1
+    small = [i for i in range(1, s.n_mol + 1) if cnt[i - 1] <= 16]
+    big = [i for i in range(1, s.n_mol + 1) if cnt[i - 1] > 16]
+    assert bool(big) == (max(na) > 16) and bool(small) == (min(na) <= 16)
+    # overlaps stay rare: most molecules have an EwaldReal to compare
+    real_all = [orc.ewald_real(i, s, kappa, 9.5)[0] for i in range(1, s.n_mol + 1)]
+    assert sum(e != 0.0 for e in real_all) > 0.9 * s.n_mol
+    sel = sorted(set(i for i in (1, 2, 100, 236, 237) if cnt[i - 1] <= 16) | set(small[:3] + small[-2:]))
     with common.device_context(a) as ctx:
-        for i in (1, 2, 100, 236, 237):
+        for i in sel:
             p, v = ctx.lj_poly_du(i, 9.0)
             po, vo = orc.lj_poly_du(i, s, 9.0)
             assert rel(p, po, 1e-3) < TOL and rel(v, vo, abs(po) + 1e-3) < TOL
             e, ov = ctx.ewald_real(i, 9.5)
             eo, ovo = orc.ewald_real(i, s, kappa, 9.5)
             assert ov == ovo and rel(e, eo, 1e-3) < TOL
+            e1, ov1 = ctx.ewald_real(i, 9.5, ovr=1.0)
+            e1o, ov1o = orc.ewald_real(i, s, kappa, 9.5, ovr=1.0)
+            assert ov1 == ov1o and rel(e1, e1o, 1.0) < TOL, (i, e1, e1o)
+            es, vs, ovs = ctx.ewald_short(i, 9.5)
+            eso, vso, ovso = orc.ewald_short(i, s, ew, 9.5)
+            assert ovs == ovso and rel(es, eso, 1.0) < TOL and rel(vs, vso, 1.0) < TOL, (i, es, eso)
+            eb, ovb = ctx.coulomb_real(i, RCUT)
+            ebo, ovbo = orc.coulomb_real(i, s, RCUT)
+            assert ovb == ovbo and rel(eb, ebo, 1.0) < TOL, (i, eb, ebo)
+        for i in big[:2] + big[-1:]:
+            for call in (lambda: ctx.lj_poly_du(i, 9.0), lambda: ctx.ewald_real(i, 9.5),
+                         lambda: ctx.ewald_short(i, 9.5), lambda: ctx.coulomb_real(i, RCUT),
+                         lambda: ctx.set_molecule(i, a["com"][i - 1],
+                                                  a["coords"][a["first_atom"][i - 1] - 1:a["last_atom"][i - 1]])):
+                with pytest.raises(MMCError, match="MMC_ERR_UNSUPPORTED"):
+                    call()
+        assert rel(ctx.recip_long(), orc.recip_long(ew, s.coords, s.charge, s.box)) < TOL
+        assert rel(ctx.ewald_self(), orc.ewald_self(ew, s.charge)) < 1e-13
         t = ctx.potential_ewald(9.0, 9.5)
-        ew = orc.Ewald(kappa, 5, 27, s.box)
         to = orc.potential_ewald(s, ew, 9.0, 9.5)
         for key in ("energy", "virial", "lj", "real", "recip", "self"):
-            assert rel(t[key], to[key], 1e-3) < TOL, key
+            assert rel(t[key], to[key], 1e-3) < TOL, (key, t[key], to[key])
         assert t["n_overlap"] == to["n_overlap"]
+        w = ctx.potential_wolf(9.0, 9.5)
+        wo = orc.potential_wolf(s, ew, 9.0, 9.5, literal_prefactor=False)
+        for key in ("energy", "virial", "lj", "real", "self"):
+            assert rel(w[key], wo[key], 1.0) < TOL, (key, w[key], wo[key])
+        assert w["n_overlap"] == wo["n_overlap"]
 
 
 def test_tiny_systems(orc):

@@ -24,7 +24,7 @@ def host_rescale(a, L_new):
     f = L_new / a["box"]
     com = a["com"] * f
     d = com - a["com"]
-    coords = a["coords"] + np.repeat(d, 3, axis=0)
+    coords = a["coords"] + np.repeat(d, a["last_atom"] - a["first_atom"] + 1, axis=0)
     return dict(a, com=com, coords=coords, box=float(L_new))
 
 
@@ -43,14 +43,22 @@ def water_lattice(n_mol, geometry="spce", rho=0.033101144):
                 sig=tab.sig_ij, box=box)
 
 
+def ragged_system():
+    """237 molecules of 3 and 17 atoms (tests/common.random_system): every total goes through the
+    per-molecule kernels, and molecules of 17 atoms through k_mol_energy's second atom tile."""
+    return common.random_system(237, 24.0, 6, na_choices=(3, 17), n_types=3)
+
+
 @pytest.mark.parametrize("k,variant,dL", [(1, "unwrapped", 0.5), (4, "unwrapped", -0.3),
-                                          (4, "reference", 0.2)])
+                                          (4, "reference", 0.2), (0, "ragged", 0.4)])
 def test_volume_change_context(k, variant, dL, orc):
-    a = common.nist_arrays(k, variant)
+    a = ragged_system() if variant == "ragged" else common.nist_arrays(k, variant)
     L_new = a["box"] + dL
     a2 = host_rescale(a, L_new)
     s2 = common.oracle_system(a2)
     to = orc.potential_ewald(s2, orc.Ewald(5.6 / L_new, 5, 27, L_new), RCUT, RCUT)
+    # a molecule of 3 atoms for the per-move calls (the ragged system's molecule 3 has 17)
+    i = 3 if variant != "ragged" else 1 + int(np.argmax(a["last_atom"] - a["first_atom"] == 2))
     with common.device_context(a) as ctx:
         ctx.potential_ewald(RCUT, RCUT)
         ctx.volume_change(L_new, 5.6 / L_new)
@@ -63,12 +71,49 @@ def test_volume_change_context(k, variant, dL, orc):
         for key in ("energy", "virial", "lj", "real", "recip", "self"):
             assert rel(t[key], to[key]) < TOL, key
         # per-move calls keep working in the new box
-        p, v = ctx.lj_poly_du(3, RCUT)
-        po, vo = orc.lj_poly_du(3, s2, RCUT)
+        p, v = ctx.lj_poly_du(i, RCUT)
+        po, vo = orc.lj_poly_du(i, s2, RCUT)
         assert rel(p, po) < TOL
-        e, ov = ctx.ewald_real(3, RCUT)
-        eo, ovo = orc.ewald_real(3, s2, 5.6 / L_new, RCUT)
+        e, ov = ctx.ewald_real(i, RCUT)
+        eo, ovo = orc.ewald_real(i, s2, 5.6 / L_new, RCUT)
         assert ov == ovo and rel(e, eo) < TOL
+
+
+def test_volume_trial_ragged_accept_and_reject(orc):
+    """mmc_volume_trial on the ragged system (3- and 17-atom molecules): the trial's totals are
+    the oracle's at the rescaled coordinates; a rejected trial gives back coordinates and S(k)
+    bit for bit and the totals of the old box, an accepted one leaves the rescaled system."""
+    a = ragged_system()
+    L0, L1 = a["box"], a["box"] + 0.7
+    a1 = host_rescale(a, L1)
+    to0 = orc.potential_ewald(common.oracle_system(a), orc.Ewald(5.6 / L0, 5, 27, L0), RCUT, RCUT)
+    to1 = orc.potential_ewald(common.oracle_system(a1), orc.Ewald(5.6 / L1, 5, 27, L1), RCUT, RCUT)
+    keys = ("energy", "virial", "lj", "real", "recip", "self")
+    with common.device_context(a) as ctx:
+        t0 = ctx.potential_ewald(RCUT, RCUT)
+        for key in keys:
+            assert rel(t0[key], to0[key]) < TOL, key
+        com0, coords0 = ctx.download_system()
+        S0 = ctx.get_sumqexp()[0].copy()
+        t = ctx.volume_trial(L1, 5.6 / L1, RCUT, RCUT)
+        for key in keys:
+            assert rel(t[key], to1[key]) < TOL, ("reject", key, t[key], to1[key])
+        ctx.volume_reject()
+        com, coords = ctx.download_system()
+        assert np.array_equal(com, com0) and np.array_equal(coords, coords0)
+        assert np.array_equal(ctx.get_sumqexp()[0], S0)
+        tr = ctx.potential_ewald(RCUT, RCUT)
+        assert all(tr[key] == t0[key] for key in keys)
+        t = ctx.volume_trial(L1, 5.6 / L1, RCUT, RCUT)
+        for key in keys:
+            assert rel(t[key], to1[key]) < TOL, ("accept", key, t[key], to1[key])
+        ctx.volume_accept()
+        com, coords = ctx.download_system()
+        assert np.array_equal(com, a1["com"]) and np.array_equal(coords, a1["coords"])
+        t1 = ctx.potential_ewald(RCUT, RCUT)
+        for key in keys:
+            assert rel(t1[key], to1[key]) < TOL, key
+        assert t0["n_overlap"] == t1["n_overlap"] == to1["n_overlap"] == 0
 
 
 def test_volume_change_batch_then_moves(orc):
@@ -354,16 +399,26 @@ def test_batch_volume_move_at_10000_molecules_reject_restores_accept_matches_the
 
 
 def test_npt_chain_on_the_batch_stepped_by_the_oracle(orc):
+    _npt_chain_stepped_by_the_oracle("nist2", orc)
+
+
+def test_npt_chain_of_a_mixture_stepped_by_the_oracle(orc):
+    """The same chain on an SPC/E + TIP3P mixture: every volume move takes the generic totals."""
+    _npt_chain_stepped_by_the_oracle("blocks", orc)
+
+
+def _npt_chain_stepped_by_the_oracle(system, orc):
     """mmc_batch_run_npt on NIST configuration 2 (200 molecules, r_cut 9 A): sweeps of trial moves
     interleaved with volume moves, the whole chain replayed by the oracle -- every proposal rebuilt
     from the Philox draws, dU from orc.trial_move, the volume move's two uniforms from slot
     MMC_SLOT_VOLUME, its energy from orc.potential_ewald on coordinates rescaled on the host
     (volumeChange.jl:59-147) -- must end in the same box, the same coordinates, the same accept
-    counts and the same running energy."""
+    counts and the same running energy.  "blocks": the same on an SPC/E + TIP3P mixture
+    (common.spce_tip3p_mixture), whose every volume move takes the generic totals."""
     import math
     from test_gpu_batch import _rigid_proposal
     from test_gpu_moves import philox_pair
-    a = common.nist_arrays(2, "unwrapped")
+    a = common.nist_arrays(2, "unwrapped") if system == "nist2" else common.spce_tip3p_mixture(2, system)[0]
     n_mol, rc = a["com"].shape[0], 9.0
     T, dr, dphi, seed, rep0 = 298.15, 0.316555789, 0.05, 31337, 2
     P, n_sweeps, per_sweep = 0.03, 6, 45

@@ -506,3 +506,32 @@ def test_tiny_system_totals(n_mol, orc):
             for key in ("energy", "lj", "real", "recip", "self"):
                 assert rel(tot[r][key], want[r][key], 1e-3) < TOL, (n_mol, r, key)
             assert tot[r]["n_overlap"] == want[r]["n_overlap"]
+
+
+# ---- SPC/E + TIP3P mixtures: the generic kernel --------------------------------------------------
+M_RCUT, M_T, M_DR, M_DPHI = 10.0, 298.15, 0.3, 0.3
+M_STEPS = 2 * 100 + 5                      # two sweeps of NIST configuration 1 and the start of a third
+
+
+@pytest.mark.parametrize("parts", [1, 3])
+@pytest.mark.parametrize("order", common.MIX_ORDERS)
+def test_mixture_stepped_by_the_oracle(order, parts, orc):
+    """A 3-site mixture (common.spce_tip3p_mixture: four atom types, two charge sets, two
+    geometries) is not homogeneous, so mmc_batch_run takes kernel 0: moves drawn on the device,
+    decided on the host, eight replicas in two groups, 1 and 3 parts per replica.  Every step's dU
+    and flags of the replicas at both ends of both groups against the replay, then their final
+    state and totals; both species have accepted and rejected moves in every checked chain."""
+    a, sp = common.spce_tip3p_mixture(1, order)
+    n_mol = a["com"].shape[0]
+    R, seed, check = 8, 2718, (0, 3, 4, 7)
+    opts = dict(persistent=0, accept_on_device=0)
+    e0, e1, traces, final, tot, st = run_batch(a, R, M_RCUT, opts, [(M_STEPS, seed, 0, M_T, M_DR, M_DPHI)],
+                                               check, trace=M_STEPS, n_parts=parts)
+    assert st["device_decisions"] == 0
+    for r in check:
+        o = replay(orc, a, r, ((M_STEPS, seed, 0),), M_T, M_DR, M_DPHI, M_RCUT)
+        _check_trace(o, *traces[0], r, (order, parts))
+        _check_final(orc, a, o, final, r, e0, e1, tot, M_RCUT, (order, parts))
+        for species in (0, 1):
+            acc = [o["trace"][k][1] & 1 for k in range(M_STEPS) if sp[k % n_mol] == species]
+            assert any(acc) and not all(acc), (order, r, species)
