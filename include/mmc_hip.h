@@ -341,7 +341,16 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *                      counts the launches.  1.43e8 against 1.31e8 moves/s (61440 chains of 750
  *                      molecules, one run of bench.py).  Launches this long (1.7 ms) want groups whose size is a multiple
  *                      of 5 * 4 * (compute units) replicas -- 5120 on MI355X: every wavefront the
- *                      kernel keeps resident then takes the same number of replicas.
+ *                      kernel keeps resident then takes the same number of replicas.  In such a
+ *                      launch a wave takes its first replica by its index, every further one from
+ *                      a queue (one ticket per replica and launch): the waves of a launch do not
+ *                      finish together, and the quick ones take more replicas.
+ *   "whole_call"       where launches take several steps (above): 1 = a call of n steps takes
+ *                      ONE launch per group of min(n, 32, molecules - 1) steps, and a longer call
+ *                      launches of that many; 0 (default) = launches of "steps_per_launch".  Same
+ *                      chains bit for bit; the running energies differ by the order of a sum.  For
+ *                      comparison: at the bench's 20-step call one launch per group ran 4 % slower
+ *                      than launches of eight (the last launch's tail is one 20-step unit long).
  *   "image_by_molecule" -1 (default) = the wave kernel takes the minimum image of an atom pair with
  *                      the image of its molecule's centre of mass where that is the reference's
  *                      vector1D bit for bit: moves made on the device (rigid), and

@@ -15,6 +15,7 @@
 #define MMC_SERVER_AUTO_MAX 256
 #define MMC_GEN_MAX 16                 // steps whose proposals one k_propose launch generates
 #define MMC_GEN_RING (MMC_GEN_MAX + 2) // + the previous step's record (pending commit) + slack
+#define MMC_QUEUE_STRIDE 32            // a 128-byte line per group's ticket counter (mmc_batch::d_queue)
 
 struct mmc_batch {
     DeviceSystem sys;
@@ -47,7 +48,8 @@ struct mmc_batch {
     bool mirror_valid = false;       // built on first use; stale after device-side proposals
     // device-side move generation (mmc_propose.hpp): per-replica flag byte and step sizes
     int device_moves = 0;
-    MoveRec *d_ring = nullptr; // [MMC_GEN_RING][R] device-generated move records, by step % ring
+    MoveRec *d_ring = nullptr; // [ring_slots][R] device-generated move records, by step % ring_slots
+    int ring_slots = MMC_GEN_RING; // (more where a launch takes more than MMC_GEN_MAX steps: batch_ensure_ring)
     double *d_quat = nullptr;  // [R][n_mol][4] orientations (only with mmc_batch_set_orientations)
     unsigned stamp = 0;        // last launch stamp handed out (PartOut::ovl[1])
     int64_t steps_done = 0;    // steps the native driver has run on this batch: the random streams
@@ -68,9 +70,14 @@ struct mmc_batch {
     void *pool = nullptr;              // the native driver's worker threads (WorkerPool, mmc_engine.inc), kept
     void (*pool_destroy)(void *) = nullptr; // between calls; joined by mmc_batch_destroy through this
     int steps_per_launch = 0;          // option "steps_per_launch": 0 = by size, 1, 2, 4, 8, 16
+    int whole_call = 0;                // option "whole_call": 1 = where the kernel decides, a call of up
+                                       // to MMC_STEPS_PER_LAUNCH_MAX steps in ONE launch per group (0: launches of steps_per_launch)
     int accept_on_device = -1;         // option "accept_on_device": -1 by host threads per launch, 0 host, 1 kernel          // option "accept_on_device": 0 keeps the decision on the host
     DecideConsts *d_decide = nullptr;  // what the kernel's own accept decision needs (Driver, device-side decisions)
     DecideConsts decide_host{};        // ... as last uploaded
+    unsigned *d_queue = nullptr;       // unit tickets of the kernel's multi-step launches: group g's at [MMC_QUEUE_STRIDE g]
+    unsigned queue_base[MMC_MAX_GROUPS] = {}; // ... tickets taken so far (a launch takes one per unit)
+    bool queue_reset = false;          // a run failed: tickets and counts may disagree
     int server_stall_ms = 0;   // test hook: the host delays the control words of step 2 by this much
     int64_t server_seq_offset = 0; // test hook: sequence numbers of the control words start here
     bool needs_reload = false; // a run failed half-way: coordinates, S buffers and the caller's
@@ -316,6 +323,9 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         MMC_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16, MMC_ERR_ARG,
                     "steps_per_launch must be 0 (by size), 1, 2, 4, 8 or 16");
         b->steps_per_launch = (int)value;
+    } else if (!strcmp(key, "whole_call")) {
+        MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "whole_call must be 0 (launches of steps_per_launch) or 1 (one per call)");
+        b->whole_call = (int)value;
     } else if (!strcmp(key, "accept_on_device")) {
         MMC_REQUIRE(value >= -1 && value <= 1, MMC_ERR_ARG, "accept_on_device must be -1 (by size), 0 (host) or 1 (kernel)");
         b->accept_on_device = (int)value;
@@ -432,16 +442,27 @@ struct DevGen { // device-side proposals for this launch (mmc_propose.hpp)
     bool upload_steps; // h_steps of the range changed since the last launch
 };
 
-static int32_t batch_ensure_ring(mmc_batch *b)
+// The ring holds at least `slots` steps' records (between calls only: what it held is settled).
+static int32_t batch_ensure_ring(mmc_batch *b, int slots = MMC_GEN_RING)
 {
-    if (!b->d_ring)
-        MMC_TRY(b->sys.dmalloc((void **)&b->d_ring, sizeof(MoveRec) * MMC_GEN_RING * b->sys.R));
+    if (b->d_ring && b->ring_slots >= slots)
+        return MMC_OK;
+    if (b->d_ring) { // a larger one: the records of a call never outlive it
+        MMC_HIP(hipDeviceSynchronize());
+        std::vector<void *> &a = b->sys.allocs;
+        a.erase(std::remove(a.begin(), a.end(), (void *)b->d_ring), a.end());
+        MMC_HIP(hipFree(b->d_ring));
+        b->d_ring = nullptr;
+    }
+    slots = std::max(slots, (int)MMC_GEN_RING);
+    MMC_TRY(b->sys.dmalloc((void **)&b->d_ring, sizeof(MoveRec) * (size_t)slots * b->sys.R));
+    b->ring_slots = slots;
     return MMC_OK;
 }
 
 static inline const MoveRec *batch_ring_slot(const mmc_batch *b, int64_t step)
 {
-    return b->d_ring + (step % MMC_GEN_RING) * b->sys.R;
+    return b->d_ring + (step % b->ring_slots) * b->sys.R;
 }
 
 // Enqueue one step for replicas [r0, r0 + nr): proposals h_moves[buf] -> device (or generated
@@ -463,6 +484,8 @@ struct DevDecide {
     PartOut *parts;         // [R] where this launch's result records go (two slots alternate)
     bool fetch_flags;       // no BAR: bring the flag bytes the host wrote before the call's first launch
     int n_sub;              // steps of the chain this launch takes (> 1: one record for all of them)
+    unsigned *queue;        // n_sub > 1: the group's unit tickets (k_move_eval_wave, wave_ticket), or null
+    unsigned queue_base;    // ... tickets taken before this launch
 };
 
 static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr, int P,
@@ -498,7 +521,7 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
             GenArgs ga;
             ga.steps = stp; ga.seed = dg->seed; ga.replica0 = dg->replica0;
             ga.rng_off = dg->rng_off; ga.step0 = dg->step; ga.n_gen = dg->n_gen;
-            ga.ring = MMC_GEN_RING; ga.ring_stride = s.R; ga.flag0 = flagv;
+            ga.ring = b->ring_slots; ga.ring_stride = s.R; ga.flag0 = flagv;
             ga.quat_mode = b->quat_mode;
             memcpy(ga.db, b->db, sizeof(ga.db));
             const int64_t n = nr * dg->n_gen;
@@ -510,7 +533,7 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
                                                                         (int)r0, (int)nr, has_prev ? 1 : 0);
         }
         cur = batch_ring_slot(b, dg->step);
-        prev = has_prev ? batch_ring_slot(b, dg->step + MMC_GEN_RING - 1) : nullptr;
+        prev = has_prev ? batch_ring_slot(b, dg->step + b->ring_slots - 1) : nullptr;
     } else {
         b->rigid_only = false; // the caller's proposals: nothing is known about their shape
         s.r_mol_max = INFINITY;
@@ -556,7 +579,8 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     k_move_eval_wave<SUBST, IMG, MULTI><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>(            \
         s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,     \
         (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,      \
-        dd ? dd->n_sub : 1, (int)(dg ? dg->step % MMC_GEN_RING : 0))
+        dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,      \
+        dd ? dd->queue_base : 0u)
         if (P == 1 && dd && dd->n_sub > 1) {
             if (img) MMC_WAVE_LAUNCH3(false, true, true); else MMC_WAVE_LAUNCH3(false, false, true);
         } else if (P == 1) {

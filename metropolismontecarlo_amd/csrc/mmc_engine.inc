@@ -170,6 +170,7 @@ struct Driver {
     bool devgen = false;         // proposals generated on the device (mmc_propose.hpp)
     bool devacc = false;         // ... and the accept decision made by the move kernel itself (thread_main_devacc)
     int K = 1;                   // ... which then takes every replica through K steps per launch (DecideConsts)
+    int gen_max = MMC_GEN_MAX;   // steps one k_propose launch draws (a whole call's: K, run_impl)
     bool server = false;         // the persistent move server does the launches' work
     int server_waves = 0;        // ... with this many parts (waves of a replica's workgroup)
     int server_lat_wgs = 0;      // > 0: the latency server, this many workgroups per replica
@@ -343,10 +344,11 @@ struct Driver {
             }
             const int64_t n_sub = slot >= 0 ? std::min<int64_t>(K, p->n_steps - step_done) : 1;
             if (n_sub > 1) { // one record for the launch's steps [step_done, step_done + n_sub)
-                unsigned long long bits;
+                unsigned long long bits, kbits;
                 memcpy(&bits, &parts[0].lj_pot[1], 8);
-                const unsigned acc_mask = (unsigned)bits & 0xffffu, ovl_mask = (unsigned)(bits >> 16) & 0xffffu,
-                               kind_mask = (unsigned)(bits >> 32) & 0xffffu;
+                memcpy(&kbits, &parts[0].lj_vir[0], 8);
+                const unsigned acc_mask = (unsigned)bits, ovl_mask = (unsigned)(bits >> 32),
+                               kind_mask = (unsigned)kbits; // (the record's words: DecideConsts)
                 energies[r] += parts[0].lj_pot[0]; // the accepted steps' dU, added up in step order by the kernel
                 for (int64_t k = 0; k < n_sub; k++) {
                     const int kd = (kind_mask >> k) & 1; // (what k_propose drew: mmc_move_kind of that step)
@@ -524,7 +526,7 @@ struct Driver {
             dg.upload_steps = step == 0 || (adjust && i0 == 0);
             if (step >= g.gen_end) { // generate the next run of records (see k_propose)
                 int64_t k = n_mol - 1 < 1 ? 1 : n_mol - 1;
-                if (k > MMC_GEN_MAX) k = MMC_GEN_MAX;
+                if (k > gen_max) k = gen_max;
                 if (k > p->n_steps - step) k = p->n_steps - step;
                 if (adjust && k > n_mol - i0) k = n_mol - i0; // step sizes change between sweeps
                 dg.n_gen = (int)k;
@@ -544,7 +546,11 @@ struct Driver {
             const int slot = (int)((step / K) & 1);
             g.stamp_of[slot] = g.stamp;
             g.timed_of[slot] = g.timed;
-            DevDecide dd{ b->d_decide, rng_off + step, b->d_parts + (size_t)slot * b->sys.R, step == 0, (int)n_sub };
+            const size_t gi = (size_t)(&g - groups.data());
+            DevDecide dd{ b->d_decide, rng_off + step, b->d_parts + (size_t)slot * b->sys.R, step == 0, (int)n_sub,
+                          n_sub > 1 ? b->d_queue + MMC_QUEUE_STRIDE * gi : nullptr, b->queue_base[gi] };
+            if (n_sub > 1)
+                b->queue_base[gi] += (unsigned)(g.nr * P); // (what the launch takes: wave_ticket)
             MMC_TRY(batch_launch(b, g.launched_on, g.r0, g.nr, P, g.buf, step > 0, pp,
                                  g.timed ? g.evs[slot][0] : nullptr, &dg, g.stamp, &dd));
             if (g.timed)
@@ -1149,16 +1155,33 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
             d.K = atoi(e);
         if (d.K != 1 && d.K != 2 && d.K != 4 && d.K != 8 && d.K != 16)
             d.K = 1;
+        // A whole call in ONE launch per group (option "whole_call" = 1): K = the call's steps, as
+        // many as a record carries and a burst of proposals may draw (n_mol - 1; the ring grows to
+        // hold them).  Not taken by default: at the bench's 20-step call it ran 1.34 x 10^8 moves/s
+        // against 1.40 for launches of eight, both with the queue of units (profiles/README.md,
+        // "The 20-step call") -- one launch's tail is a whole 20-step unit long, and nothing covers it.
+        if (b->whole_call == 1) {
+            d.K = (int)std::min<int64_t>(std::min<int64_t>(p->n_steps, MMC_STEPS_PER_LAUNCH_MAX), s.n_mol - 1);
+            d.gen_max = std::max(d.K, (int)MMC_GEN_MAX);
+        }
     }
     if (d.devacc) {
-        MMC_TRY(batch_ensure_ring(b));
+        MMC_TRY(batch_ensure_ring(b, d.gen_max + 2));
         DecideConsts dc{};
         dc.temperature = p->temperature; dc.factor = s.bv.factor;
         dc.seed = p->seed; dc.replica0 = (uint32_t)p->replica0;
         dc.flags = b->d_flags;
-        dc.ring = b->d_ring; dc.ring_slots = MMC_GEN_RING; dc.ring_stride = s.R;
+        dc.ring = b->d_ring; dc.ring_slots = b->ring_slots; dc.ring_stride = s.R;
         if (!b->d_decide)
             MMC_TRY(s.dmalloc((void **)&b->d_decide, sizeof(DecideConsts)));
+        if (!b->d_queue || b->queue_reset) { // (zero tickets taken: every group's count starts again)
+            if (!b->d_queue)
+                MMC_TRY(s.dmalloc((void **)&b->d_queue, sizeof(unsigned) * MMC_QUEUE_STRIDE * MMC_MAX_GROUPS));
+            MMC_HIP(hipMemset(b->d_queue, 0, sizeof(unsigned) * MMC_QUEUE_STRIDE * MMC_MAX_GROUPS));
+            MMC_HIP(hipDeviceSynchronize()); // (the driver's streams do not wait for the null stream)
+            memset(b->queue_base, 0, sizeof(b->queue_base));
+            b->queue_reset = false;
+        }
         if (memcmp(&dc, &b->decide_host, sizeof(dc)) != 0) { // (the same from call to call of a run)
             MMC_HIP(hipMemcpy(b->d_decide, &dc, sizeof(dc), hipMemcpyHostToDevice));
             b->decide_host = dc;
@@ -1299,6 +1322,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         b->steps_done += p->n_steps;
     else { // accepted moves, S-buffer parity and the caller's energies may disagree now
         b->needs_reload = true;
+        b->queue_reset = true;
         b->reloaded.assign(R, 0);
     }
     return status;

@@ -516,10 +516,10 @@ struct DecideConsts {
 // wrote and read in one step is in the caches for the next): the launch sends ONE record per
 // replica, a PartOut whose words are
 //   [0] the sum of dU over the accepted steps, added up in step order
-//   [1] bit k: step k accepted; bit 16 + k: step k saw an overlap; bit 32 + k: step k was a rotation
-//       (an integer in a double's bits)
-//   [2..6] 0;  word 7 as ever (stamp, checksum; bit 31: the LAST step's decision)
-#define MMC_STEPS_PER_LAUNCH_MAX 16
+//   [1] bit k: step k accepted; bit 32 + k: step k saw an overlap (an integer in a double's bits)
+//   [2] bit k: step k was a rotation
+//   [3..6] 0;  word 7 as ever (stamp, checksum; bit 31: the LAST step's decision)
+#define MMC_STEPS_PER_LAUNCH_MAX 32
 
 // grid (n_parts, R).  n_parts == 1: the workgroup scans all molecules and then does the
 // reciprocal part.  n_parts > 1: parts 0..n_parts-2 split the molecule range, the last part does

@@ -215,6 +215,18 @@ __device__ __forceinline__ int wave_decide(const double *outw, bool ov_old, bool
     return acc;
 }
 
+// The next unit of a wave that has finished one: the queue's next ticket t (one global atomic of one
+// lane; the count of a launch's tickets starts at `base`) is unit n_waves + t -- units below n_waves
+// are the waves' first ones.  A launch takes exactly n_units tickets: one per unit beyond the first
+// round, plus the one each working wave takes and finds past the end.
+__device__ __forceinline__ int wave_ticket(unsigned *queue, unsigned base, int n_waves, int lane)
+{
+    unsigned t = 0;
+    if (lane == 0)
+        t = atomicAdd(queue, 1u);
+    return n_waves + (int)(__builtin_amdgcn_readfirstlane(t) - base);
+}
+
 // grid: any number of workgroups of WV_WAVES waves; wave w of workgroup g handles units
 // g * WV_WAVES + w, + gridDim.x * WV_WAVES, ...  Unit u = (replica r_base + u / n_parts,
 // part u % n_parts); part semantics as k_move_eval (the last part of n_parts > 1 does the
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
     const int32_t *__restrict__ kpack, FastConsts fc, const MoveRec *__restrict__ cur,
     const MoveRec *__restrict__ prev, PartOut *out, int n_parts, PairParams pp, int r_base,
     int n_units, const uint8_t *flagv, unsigned stamp, const DecideConsts *__restrict__ dc, long long dec_step,
-    int n_sub_arg, int slot0)
+    int n_sub_arg, int slot0, unsigned *queue, unsigned queue_base)
 {
     const int n_sub = MULTI ? n_sub_arg : 1;
     __shared__ __align__(16) WaveSharedT<WV_MWAVES> sm;
@@ -258,7 +270,13 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
     wv_list_t *const list = sm.list[wv];
     const double *const pvw = sm.pvw[wv];
 
-    for (int unit = blockIdx.x * WV_MWAVES + wv; unit < n_units; unit += gridDim.x * WV_MWAVES) {
+    // MULTI with a queue: a wave's first unit is its index in the grid, every further unit a ticket
+    // of the launch's queue (wave_ticket).  Every wave gets the same number of units otherwise, and
+    // the waves of a launch do not finish together: a 20-step launch's waves left over 1.7 of its
+    // 5.0 ms, the device emptying behind them (profiles/README.md, "The 20-step call").
+    for (int unit = blockIdx.x * WV_MWAVES + wv; unit < n_units;
+         unit = MULTI && queue ? wave_ticket(queue, queue_base, gridDim.x * WV_MWAVES, lane0)
+                               : unit + gridDim.x * WV_MWAVES) {
         // `lane` is made opaque once per unit: without this LLVM hoists every lane-derived address
         // and shuffle index of the body out of the persistent loop and holds them in registers
         // for the kernel's whole lifetime (180 VGPRs instead of 128).  (lane0 itself is spilled
@@ -371,7 +389,8 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
                 wave_sync();
                 if (lane < 7)
                     sm.outw[wv][lane] = lane == 0 ? e_sum
-                                 : lane == 1 ? __longlong_as_double((long long)(acc_mask | (ovl_mask << 16)) | ((long long)kind_mask << 32)) : 0.0;
+                                 : lane == 1 ? __longlong_as_double((long long)acc_mask | ((long long)ovl_mask << 32))
+                                 : lane == 2 ? __longlong_as_double((long long)kind_mask) : 0.0;
                 wave_sync();
             }
             return acc;
