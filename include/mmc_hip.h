@@ -651,6 +651,45 @@ int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t d
 int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in, double temperature,
                            double *boltz_sum, int64_t *n_overlap, double *du_out, uint8_t *ovl_out);
 
+/* ---- Structure observables: site-site pair histograms and total dipole moments ----------------
+ * mmc_batch_rdf_sites: what mmc_batch_rdf computes for one site, for all six unordered atom-slot
+ * pairs of 3-site molecules in one pass, per replica if wanted, in either box mode.  Kept from
+ * Ewald/gr.jl `makeRDF` (:68-92): the pair loop i < j with the difference site(i) - site(j), its
+ * minimum image (:75-80: strict < -side/2 -> + side, > side/2 -> - side), r = sqrt((xx xx + yy yy)
+ * + zz zz) unfused, bin = ceil(r / dr) (:87), counted when bin <= numbins (:88-90), and for
+ * r_max <= 0 its bin width dr = side / 2 / numbins (:5).  Not kept: its one site per molecule, its
+ * single frame, and its normalisation (observables.py: normalize_rdf_pairs).
+ *   - Rows, in this order: slot pairs (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).  Row (a,a) counts atom a
+ *     of molecule i against atom a of molecule j for every i < j; row (a,b), a < b, counts both
+ *     i.a - j.b and i.b - j.a.  Intermolecular pairs only.  Slots are positions in the molecule
+ *     (SPC/E: O, H, H); folding rows by atom type is the host's (observables.py: fold_by_type).
+ *   - r_max <= 0: dr = (L / 2) / numbins, one shared box only.  r_max > 0: dr = r_max / numbins;
+ *     r_max must not exceed half of the smallest box of the batch.  With per-replica boxes
+ *     (mmc_batch_set_boxes) each replica takes its own L for the image and all share dr; every box
+ *     is >= 2 r_cut, so r_max = r_cut is always valid there.
+ *   - per_replica == 0: hist[6][numbins + 1], summed over the replicas, like mmc_batch_rdf;
+ *     per_replica != 0: hist[R][6][numbins + 1].  hist is overwritten, not accumulated.  Counter 0
+ *     of a row only counts coincident sites.  The counts are exactly those of the arithmetic above
+ *     (the kernel finds the bin from thresholds on r^2 built with it), whatever the grid or option
+ *     "wave_wgs".
+ * mmc_batch_dipoles: dip[R][3], M_r = sum_i mu_i in e A, mu_i = (q_0 d_0 + q_1 d_1) + q_2 d_2 per
+ * component, unfused, d_a = the minimum image (vector1D, boundaries.jl, the replica's own box) of
+ * atom a minus the molecule's centre of mass -- a molecule whose atoms are stored a box away from
+ * its COM gives what the whole one gives.  Lane l of the replica's wave adds the molecules l,
+ * l + 64, ... in that order and the 64 lane sums are added in a fixed order: bitwise reproducible,
+ * independent of the launch.  Both box modes.
+ * Both calls are read-only: coordinates, S(k), flags, step counters and random streams are not
+ * touched; a chain with these calls between its blocks is bit-identical to one without.
+ * Preconditions as mmc_batch_potential_ewald: no proposals outstanding (MMC_ERR_STATE), no volume
+ * trial in flight (MMC_ERR_STATE).  MMC_ERR_ARG: numbins < 1 (or above 2046, what one wave's
+ * histograms may take of a workgroup's LDS), a NULL output, r_max not finite, above half of the
+ * smallest box, or <= 0 with per-replica boxes.  MMC_ERR_UNSUPPORTED: mmc_batch_rdf_sites with
+ * more than 2^21 molecules.  (A batch holds three-atom molecules only, mmc_batch_create, so slots
+ * 0..2 exist in every molecule.)  On any error the output is left untouched. */
+int32_t mmc_batch_rdf_sites(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica,
+                            uint64_t *hist);
+int32_t mmc_batch_dipoles(mmc_batch *b, double *dip /* [R][3] */);
+
 /* ---- the one collective of a sharded run: RCCL over xGMI ---------------------
  * Replicas shard over GPUs with no data-path collective; what is reduced, once per block, is a
  * handful of observables (sums of energies and acceptance counters, the maximum of the elapsed

@@ -99,6 +99,8 @@ struct mmc_batch {
     size_t widom_bytes = 0;
     void *widom_host = nullptr; // ... and its pinned staging of the per-replica sums
     size_t widom_host_bytes = 0;
+    void *struct_buf = nullptr; // device scratch of mmc_batch_rdf_sites / mmc_batch_dipoles (mmc_struct.inc), grown on demand
+    size_t struct_bytes = 0;
 
     const MoveRec *dev_moves(int which) const
     {
@@ -250,6 +252,8 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         (void)hipFree(b->widom_buf);
     if (b->widom_host)
         (void)hipHostFree(b->widom_host);
+    if (b->struct_buf)
+        (void)hipFree(b->struct_buf);
     b->sys.release();
     delete b;
     return MMC_OK;

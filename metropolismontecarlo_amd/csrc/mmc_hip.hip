@@ -10,4 +10,5 @@
 #include "mmc_engine.inc"
 #include "mmc_perbox.inc"
 #include "mmc_widom.inc"
+#include "mmc_struct.inc"
 #include "mmc_dist.inc"

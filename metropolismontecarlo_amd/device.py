@@ -579,6 +579,33 @@ class Batch:
                                     hist.ctypes.data_as(C.POINTER(C.c_uint64))))
         return hist
 
+    def rdf_sites(self, numbins, r_max=0.0, per_replica=False, out=None):
+        """mmc_batch_rdf_sites: the six site-site pair histograms (observables.SLOT_PAIRS, each
+        hist[0..numbins]) in one pass: uint64 [6, numbins + 1] summed over the replicas, or
+        [R, 6, numbins + 1] with per_replica.  r_max <= 0: bins of (L / 2) / numbins (one shared
+        box only), else of r_max / numbins.  `out` (that shape, uint64, contiguous) is overwritten
+        and returned."""
+        n1 = max(int(numbins), 0) + 1  # (a numbins the library refuses still gets an array to leave alone)
+        shape = (self.R, 6, n1) if per_replica else (6, n1)
+        if out is None:
+            out = np.zeros(shape, dtype=np.uint64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.shape == shape
+                  and out.flags.c_contiguous):
+            raise ValueError(f"out: uint64 {shape}, contiguous")
+        check(self._L.mmc_batch_rdf_sites(self._h, int(numbins), float(r_max), int(bool(per_replica)),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def dipoles(self, out=None):
+        """mmc_batch_dipoles: the total dipole moment of every replica, [R, 3] in e A."""
+        if out is None:
+            out = np.zeros((self.R, 3))
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (self.R, 3)
+                  and out.flags.c_contiguous):
+            raise ValueError(f"out: float64 ({self.R}, 3), contiguous")
+        check(self._L.mmc_batch_dipoles(self._h, _d(out)))
+        return out
+
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the
         bookkeeping Loop() keeps in total / averages / trans_moves / rot_moves / totProps."""

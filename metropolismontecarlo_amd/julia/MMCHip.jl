@@ -562,6 +562,30 @@ function widom_at!(b::Batch, mol_in::Vector{Float64}, n_insert::Integer, tempera
     return boltz_sum, n_overlap
 end
 
+# ---- structure observables (include/mmc_hip.h, mmc_batch_rdf_sites / mmc_batch_dipoles) ----------
+"""
+    rdf_sites(b, numbins; r_max = 0.0, per_replica = false)
+    dipoles(b)
+
+`rdf_sites`: the six site-site pair histograms of gr.jl's pair loop in one pass, slot pairs
+(0,0) (0,1) (0,2) (1,1) (1,2) (2,2): a `(numbins + 1, 6)` UInt64 matrix summed over the replicas
+(column k = row k of the C layout), or `(numbins + 1, 6, R)` with `per_replica`.  `r_max <= 0`: bins
+of (L / 2) / numbins (one shared box only), else of r_max / numbins.  `dipoles`: the total dipole
+moment of every replica, a `(3, R)` Float64 matrix in e A.  Both are read-only for the chains.
+"""
+function rdf_sites(b::Batch, numbins::Integer; r_max::Float64 = 0.0, per_replica::Bool = false)
+    numbins >= 1 || error("numbins must be >= 1")
+    hist = per_replica ? zeros(UInt64, numbins + 1, 6, b.n_replicas) : zeros(UInt64, numbins + 1, 6)
+    check(ccall((:mmc_batch_rdf_sites, libmmc), Int32, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{UInt64}),
+                b.h, numbins, r_max, per_replica ? 1 : 0, hist))
+    return hist
+end
+function dipoles(b::Batch)
+    dip = zeros(Float64, 3, b.n_replicas)
+    check(ccall((:mmc_batch_dipoles, libmmc), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h, dip))
+    return dip
+end
+
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
 """
     id = dist_unique_id()                       # rank 0; send the 128 bytes to the other ranks

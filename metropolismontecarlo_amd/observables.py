@@ -17,6 +17,56 @@ def normalize_rdf(hist, npart, side, nstep):
     return rrr, hist[1:] / norm / (rrr * rrr + dr * dr / 12.0)
 
 
+# ---- site-site pair histograms and dipole moments (include/mmc_hip.h, "Structure observables") ----
+SLOT_PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))  # rows of mmc_batch_rdf_sites, in order
+
+
+def fold_by_type(hist6, slot_types):
+    """Sum the rows of an mmc_batch_rdf_sites histogram ([..., 6, numbins + 1]) whose slot pairs
+    have the same unordered type pair.  slot_types: the type of each of the three slots, e.g.
+    ("O", "H", "H").  Returns ({(t1, t2): rows [..., numbins + 1]}, {(t1, t2): site pairs per
+    molecule pair}) with t1 <= t2.  A row (a, a) holds one site pair per molecule pair, a row
+    (a, b), a < b, two; SPC/E: OO = (0,0), 1; OH = (0,1) + (0,2), 4; HH = (1,1) + (1,2) + (2,2), 4."""
+    hist6 = np.asarray(hist6)
+    if hist6.shape[-2] != 6 or len(slot_types) != 3:
+        raise ValueError("hist6 must be [..., 6, numbins + 1] and slot_types three types")
+    rows, counts = {}, {}
+    for k, (a, b) in enumerate(SLOT_PAIRS):
+        key = tuple(sorted((slot_types[a], slot_types[b])))
+        rows[key] = hist6[..., k, :] + rows[key] if key in rows else hist6[..., k, :].copy()
+        counts[key] = counts.get(key, 0) + (1 if a == b else 2)
+    return rows, counts
+
+
+def normalize_rdf_pairs(row, n_site_pairs, dr, inv_volume_sum):
+    """g(r) of one (folded) row of pair counts, row[0 .. numbins]:
+    g(r_i) = row[i] / (n_site_pairs inv_volume_sum 4 pi (r_i^2 + dr^2/12) dr) at r_i = (i - 1/2) dr,
+    i = 1..numbins.  n_site_pairs: the counted site pairs per frame (for N molecules N (N - 1) / 2
+    times fold_by_type's count); inv_volume_sum: sum of 1 / V over the frames (replicas x samples),
+    which is how per-replica boxes enter.  4 pi (r_i^2 + dr^2/12) dr is gr.jl:100-103's own shell
+    volume; gr.jl normalises by N^2 / 2 pairs where N (N - 1) / 2 are counted, so for a same-slot
+    row this is normalize_rdf times N / (N - 1).  Returns (r, g)."""
+    row = np.asarray(row, dtype=float)
+    numbins = row.shape[-1] - 1
+    i = np.arange(1, numbins + 1)
+    rrr = (i - 0.5) * dr
+    shell = 4.0 * np.pi * (rrr * rrr + dr * dr / 12.0) * dr
+    return rrr, row[..., 1:] / (float(n_site_pairs) * float(inv_volume_sum) * shell)
+
+
+def dielectric_constant(M, temperature, volume, factor):
+    """Static dielectric constant from the fluctuation of the total dipole moment under the
+    conducting (tinfoil) boundary of the Ewald sum:
+    eps = 1 + 4 pi factor (<M.M> - <M>.<M>) / (3 V T).  M: [samples, 3] in e A
+    (mmc_batch_dipoles); temperature in K; factor: the e^2 / A -> K constant of the energies;
+    volume: A^3, a scalar or one value per sample (its mean is used)."""
+    M = np.asarray(M, dtype=float).reshape(-1, 3)
+    mean = M.mean(0)
+    fluct = (M * M).sum(1).mean() - float(mean @ mean)
+    V = float(np.mean(np.asarray(volume, dtype=float)))
+    return 1.0 + 4.0 * np.pi * float(factor) * fluct / (3.0 * V * float(temperature))
+
+
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
 MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2
 
