@@ -274,6 +274,39 @@ int32_t mmc_batch_get_replica(mmc_batch *b, int64_t r, double *com, double *coor
 int32_t mmc_batch_recip_long(mmc_batch *b, double *energies);
 /* potential(..., "ewald") for every replica. */
 int32_t mmc_batch_potential_ewald(mmc_batch *b, mmc_totals *tot);
+/* ---- Coulomb style: the reference's global `Wolf` (Ewald/main.jl:75) for the batch's chains ----
+ * A call of its own, not an option: options change nothing but summation order, the style changes
+ * the chain.  The default is MMC_COULOMB_EWALD, and a batch that never sets a style is what it
+ * always was.  In MMC_COULOMB_WOLF style mmc_batch_eval, _settle, _run and _run_chains take the
+ * reference's Wolf move (main.jl:491-593 with `Wolf = true`): d_lj, d_real and overlap as in Ewald
+ * style, no RecipMove (main.jl:580-590) -- d_recip = 0, d_vir = virial new - old without a
+ * d_recip/3 term, dU = d_lj + d_real for the host's decision, the kernel's own and the
+ * "trace_steps" hook.  Neither S(k) buffer of any replica is read or written
+ * (mmc_batch_get_replica's sum_old is bit for bit what it was), and the proposals are those of
+ * Ewald style: the same random streams at the same counters.  Every move kernel (options kernel 0,
+ * 1, 2, 3) has its own Wolf instantiation without phase tables, k loop or S(k) traffic; with
+ * "parts" > 1 every part is a pair part.
+ * Switching needs no proposals outstanding (MMC_ERR_STATE).  Switching from Wolf back to Ewald
+ * marks S(k) stale: until mmc_batch_recip_long (or mmc_batch_potential_ewald, which rebuilds S(k)
+ * itself) has run, mmc_batch_eval, _run, _run_chains and _widom* return MMC_ERR_STATE.
+ * Outside the Wolf style's scope, MMC_ERR_UNSUPPORTED with nothing computed and no state changed,
+ * whichever call comes first: per-replica boxes (mmc_batch_set_boxes), every volume-move entry
+ * point (mmc_batch_volume_*, mmc_batch_run_npt, mmc_batch_run_npt_replicas), mmc_batch_widom and
+ * _widom_at, option "kernel" = 4 and option "persistent" = 1 ("persistent" = -1 uses launches). */
+enum { MMC_COULOMB_EWALD = 0, MMC_COULOMB_WOLF = 1 };
+int32_t mmc_batch_set_coulomb_style(mmc_batch *b, int32_t style);
+int32_t mmc_batch_get_coulomb_style(mmc_batch *b, int32_t *style);
+/* potential() of the Wolf overload (Ewald/energy.jl:864-943) for every replica, as
+ * mmc_potential_wolf: lj = half the double-counted LJ sum, real = factor/2 x the EwaldReal sum with
+ * NO virial term (:919-920), recip = 0, self = (prefactor - prefactor2) factor with r_cut = lj_rcut
+ * (:875, :924-932; the double loop in closed form), n_overlap as mmc_batch_potential_ewald.  Same
+ * preconditions as that call, and one more: the batch's one shared box (MMC_ERR_UNSUPPORTED after
+ * mmc_batch_set_boxes).  Works in either style and does not touch S(k).
+ * The virial of a Wolf CHAIN is not this total's: Loop() adds EwaldShort's virial e/3 per accepted
+ * move (main.jl:566-568, :600-601) while this potential() adds none for the real part, so a chain's
+ * running virial (mmc_chain.virial) changes as `virial + real / 3` of this call does, and a chain
+ * that is to agree with a recompute starts from that sum. */
+int32_t mmc_batch_potential_wolf(mmc_batch *b, mmc_totals *tot);
 /* mmc_volume_change for every replica of the batch (they share one box). */
 int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double new_kappa);
 /* An NPT volume move of a ONE-replica batch without a host round trip -- the batch-side twin of

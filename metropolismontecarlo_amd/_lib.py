@@ -161,6 +161,9 @@ SIGNATURES = {
     "mmc_batch_get_replica": [_vp, _i64, _dp, _dp, _dp],
     "mmc_batch_recip_long": [_vp, _dp],
     "mmc_batch_potential_ewald": [_vp, _vp],  # mmc_totals[R]: a ctypes array or a numpy buffer
+    "mmc_batch_set_coulomb_style": [_vp, _i32],
+    "mmc_batch_get_coulomb_style": [_vp, _i32p],
+    "mmc_batch_potential_wolf": [_vp, _vp],   # mmc_totals[R], as mmc_batch_potential_ewald
     "mmc_batch_eval": [_vp, C.POINTER(Move), C.POINTER(MoveResult)],
     "mmc_batch_set_parts": [_vp, _i32],
     "mmc_batch_set_option": [_vp, C.c_char_p, _i64],

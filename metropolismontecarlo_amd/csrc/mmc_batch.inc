@@ -99,6 +99,9 @@ struct mmc_batch {
     size_t widom_bytes = 0;
     void *widom_host = nullptr; // ... and its pinned staging of the per-replica sums
     size_t widom_host_bytes = 0;
+    int coulomb_style = MMC_COULOMB_EWALD; // mmc_batch_set_coulomb_style (main.jl:75)
+    bool s_stale = false;       // the style went from Wolf back to Ewald: S(k) does not describe the
+                                // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
     void *struct_buf = nullptr; // device scratch of mmc_batch_rdf_sites / mmc_batch_dipoles (mmc_struct.inc), grown on demand
     size_t struct_bytes = 0;
 
@@ -273,6 +276,16 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
     MMC_REQUIRE(!(b)->sys.pb.on, MMC_ERR_UNSUPPORTED,                                            \
                 "%s: the batch has per-replica boxes (mmc_batch_set_boxes)", what)
 
+// scope of the Wolf style (include/mmc_hip.h, "Coulomb style"): one box, NVT, no test particles
+#define BATCH_NOT_WOLF(b, what)                                                                  \
+    MMC_REQUIRE((b)->coulomb_style != MMC_COULOMB_WOLF, MMC_ERR_UNSUPPORTED,                     \
+                "%s: not available in Wolf style (mmc_batch_set_coulomb_style)", what)
+// paths that read S(k) (Ewald style only: Wolf style never looks at it)
+#define BATCH_S_FRESH(b, what)                                                                   \
+    MMC_REQUIRE(!((b)->s_stale && (b)->coulomb_style == MMC_COULOMB_EWALD), MMC_ERR_STATE,       \
+                "%s: S(k) is stale after Wolf-style moves: call mmc_batch_recip_long (or "        \
+                "mmc_batch_potential_ewald) first", what)
+
 extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t value)
 {
     BATCH_CHECK(b);
@@ -288,6 +301,8 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         MMC_REQUIRE(value >= 0 && value <= 4, MMC_ERR_ARG,
                     "kernel must be 0 (generic), 1 (workgroup per move), 2 (wave per move), "
                     "3 (1 or 2 by launch size) or 4 (latency form)");
+        MMC_REQUIRE(value != 4 || b->coulomb_style != MMC_COULOMB_WOLF, MMC_ERR_UNSUPPORTED,
+                    "kernel 4 (the latency form) has no Wolf instantiation");
         MMC_REQUIRE(value == 0 || b->fast_ok, MMC_ERR_UNSUPPORTED,
                     "the fast kernel needs identical molecules (same types and charges per "
                     "slot), at most %d of them, kappa <= %.2f and r_cut^2 + 100 <= %.0f",
@@ -305,6 +320,8 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         MMC_REQUIRE(value >= -1 && value <= 1, MMC_ERR_ARG, "persistent must be -1, 0 or 1");
         MMC_REQUIRE(!b->sys.pb.on || value != 1, MMC_ERR_UNSUPPORTED,
                     "per-replica boxes: the move server has one box");
+        MMC_REQUIRE(value != 1 || b->coulomb_style != MMC_COULOMB_WOLF, MMC_ERR_UNSUPPORTED,
+                    "the persistent move server has no Wolf instantiation (persistent = -1 uses launches)");
         b->persistent = (int)value;
     } else if (!strcmp(key, "server_seq_offset")) {
         MMC_REQUIRE(value >= 0, MMC_ERR_ARG, "server_seq_offset must be >= 0");
@@ -394,7 +411,9 @@ extern "C" int32_t mmc_batch_recip_long(mmc_batch *b, double *energies)
     BATCH_CHECK(b);
     MMC_REQUIRE(energies, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
-    return b->sys.recip_long_all(energies);
+    MMC_TRY(b->sys.recip_long_all(energies));
+    b->s_stale = false; // both buffers of every replica hold S(k) of its coordinates
+    return MMC_OK;
 }
 
 extern "C" int32_t mmc_batch_potential_ewald(mmc_batch *b, mmc_totals *tot)
@@ -402,7 +421,81 @@ extern "C" int32_t mmc_batch_potential_ewald(mmc_batch *b, mmc_totals *tot)
     BATCH_CHECK(b);
     MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
-    return b->sys.totals_ewald(b->lj_rcut, b->qq_rcut, tot);
+    MMC_TRY(b->sys.totals_ewald(b->lj_rcut, b->qq_rcut, tot));
+    b->s_stale = false; // RecipLong inside wrote both arrays (energy.jl:1008)
+    return MMC_OK;
+}
+
+// ---- Coulomb style (main.jl:75 `Wolf`) -----------------------------------------------------------
+extern "C" int32_t mmc_batch_set_coulomb_style(mmc_batch *b, int32_t style)
+{
+    BATCH_CHECK(b);
+    MMC_REQUIRE(style == MMC_COULOMB_EWALD || style == MMC_COULOMB_WOLF, MMC_ERR_ARG,
+                "style must be MMC_COULOMB_EWALD (0) or MMC_COULOMB_WOLF (1)");
+    MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
+    BATCH_NO_VOLUME_TRIAL(b);
+    if (style == b->coulomb_style)
+        return MMC_OK;
+    if (style == MMC_COULOMB_WOLF) {
+        MMC_REQUIRE(!b->sys.pb.on, MMC_ERR_UNSUPPORTED,
+                    "Wolf style: the batch has per-replica boxes (mmc_batch_set_boxes)");
+        MMC_REQUIRE(b->kernel != 4, MMC_ERR_UNSUPPORTED,
+                    "Wolf style: kernel 4 (the latency form) has no Wolf instantiation");
+        MMC_REQUIRE(b->persistent != 1, MMC_ERR_UNSUPPORTED,
+                    "Wolf style: the persistent move server (option persistent = 1) has no Wolf "
+                    "instantiation");
+    } else {
+        b->s_stale = true; // the Wolf moves left both S(k) buffers where they were
+    }
+    b->coulomb_style = style;
+    return MMC_OK;
+}
+
+extern "C" int32_t mmc_batch_get_coulomb_style(mmc_batch *b, int32_t *style)
+{
+    MMC_REQUIRE(b && style, MMC_ERR_ARG, "NULL argument");
+    *style = b->coulomb_style;
+    return MMC_OK;
+}
+
+// potential() of the Wolf overload (energy.jl:864-943) for every replica: mmc_potential_wolf
+// (mmc_ctx.inc) on the batch's pair-total kernels.  Neither style nor S(k) matter to it.
+extern "C" int32_t mmc_batch_potential_wolf(mmc_batch *b, mmc_totals *tot)
+{
+    BATCH_CHECK(b);
+    MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
+    MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
+    BATCH_ONE_BOX(b, "mmc_batch_potential_wolf");
+    DeviceSystem &s = b->sys;
+    MMC_REQUIRE(s.uploaded && s.ewald_ready, MMC_ERR_STATE,
+                "potential needs an uploaded system and an EWALD (kappa, factor)");
+    std::vector<TotalsRaw> ht;
+    MMC_TRY(s.pair_totals(b->lj_rcut, b->qq_rcut, ht));
+    double sq, sq2;
+    MMC_TRY(s.charge_sums(&sq, &sq2));
+    const double factor = s.bv.factor, kappa = s.bv.kappa, r_cut = b->lj_rcut; // energy.jl:875
+    // :924-930: sum_i sum_j q_i q_j erfc(kappa r_cut)/r_cut == (sum q)^2 erfc/r_cut, negated
+    double prefactor = sq * sq * erfc(kappa * r_cut) / r_cut;
+    prefactor *= -1;
+    const double prefactor2 =
+        (erfc(kappa * r_cut) / 2 / r_cut + kappa / sqrt(3.141592653589793)) * sq2; // :931-932
+    for (int64_t r = 0; r < s.R; r++) {
+        mmc_totals t;
+        memset(&t, 0, sizeof(t));
+        t.energy = ht[r].lj_e / 2; // :895-897
+        t.virial = ht[r].lj_v / 2;
+        t.lj = ht[r].lj_e / 2;
+        double totReal = ht[r].qq;
+        totReal *= factor / 2; // :918
+        t.energy += totReal; t.coulomb += totReal; // no virial term here (:919-920)
+        t.real = totReal;
+        t.energy += (prefactor - prefactor2) * factor;
+        t.coulomb += (prefactor - prefactor2) * factor;
+        t.self = (prefactor - prefactor2) * factor;
+        t.n_overlap = ht[r].n_ovl;
+        tot[r] = t;
+    }
+    return MMC_OK;
 }
 
 // bring the host mirror back in step with the device after a run with device-side proposals
@@ -556,6 +649,8 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     // (4 per SIMD); below that the workgroup-per-move kernel, which spreads one move over 256
     // lanes, has the shorter critical path (measured crossover: 2048 .. 8192 moves per launch)
     const int kernel = batch_kernel_for(b, nr, P);
+    const bool wolf = b->coulomb_style == MMC_COULOMB_WOLF; // (never with kernel 4 or per-replica boxes)
+    MMC_REQUIRE(!wolf || (kernel != 4 && !s.pb.on), MMC_ERR_ASSERT, "Wolf style reached a kernel without a Wolf form");
     if (kernel == 4) {
         // latency form: P workgroups of four parts each per replica, one record per workgroup
         MMC_REQUIRE(lat_applies(4 * P, (int)s.n_mol, (int)s.nkvecs), MMC_ERR_UNSUPPORTED,
@@ -569,7 +664,8 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
         const int64_t n_units = nr * P;
         int64_t wgs = (n_units + WV_MWAVES - 1) / WV_MWAVES;
         // (what the kernel's registers and LDS let be resident: WV_OCC waves on each of 4 SIMDs)
-        const int64_t cap = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(4 * WV_OCC / WV_MWAVES) * b->n_cus;
+        const int64_t cap = b->wave_wgs > 0 ? b->wave_wgs
+                                            : (int64_t)(4 * (wolf ? WV_OCC_WOLF : WV_OCC) / WV_MWAVES) * b->n_cus;
         if (wgs > cap) wgs = cap;
         // the minimum image of an atom pair from its molecule's: rigid device-made moves only,
         // and gate + 2 r_mol < box / 2 (mmc_wave_unit.inc, WV_IMG)
@@ -580,31 +676,41 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
                          s.pairs_inside_slack(pp.lj_gate_sq, pp.lj_slack_sq);
 #define MMC_WAVE_LAUNCH(SUBST, IMG) MMC_WAVE_LAUNCH3(SUBST, IMG, false)
 #define MMC_WAVE_LAUNCH3(SUBST, IMG, MULTI)                                                      \
-    k_move_eval_wave<SUBST, IMG, MULTI><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>(            \
+    if (wolf) MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, true); else MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, false)
+#define MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, WOLF)                                                \
+    k_move_eval_wave<SUBST, IMG, MULTI, WOLF><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>(      \
         s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,     \
         (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,      \
         dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,      \
         dd ? dd->queue_base : 0u)
         if (P == 1 && dd && dd->n_sub > 1) {
-            if (img) MMC_WAVE_LAUNCH3(false, true, true); else MMC_WAVE_LAUNCH3(false, false, true);
+            if (img) { MMC_WAVE_LAUNCH3(false, true, true); } else { MMC_WAVE_LAUNCH3(false, false, true); }
         } else if (P == 1) {
-            if (img) MMC_WAVE_LAUNCH(false, true); else MMC_WAVE_LAUNCH(false, false);
+            if (img) { MMC_WAVE_LAUNCH(false, true); } else { MMC_WAVE_LAUNCH(false, false); }
         } else {
-            if (img) MMC_WAVE_LAUNCH(true, true); else MMC_WAVE_LAUNCH(true, false);
+            if (img) { MMC_WAVE_LAUNCH(true, true); } else { MMC_WAVE_LAUNCH(true, false); }
         }
 #undef MMC_WAVE_LAUNCH
 #undef MMC_WAVE_LAUNCH3
+#undef MMC_WAVE_LAUNCH4
     } else if (kernel == 1 && s.pb.on)
-        k_move_eval_fast<<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, nullptr, s.kpack, s.fc, cur, prev,
-                                                         b->d_parts, P, pp, (int)r0, flagv, stamp,
-                                                         s.pb_view());
+        k_move_eval_fast<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, nullptr, s.kpack, s.fc, cur, prev,
+                                                                b->d_parts, P, pp, (int)r0, flagv, stamp,
+                                                                s.pb_view());
+    else if (kernel == 1 && wolf)
+        k_move_eval_fast<true><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
+                                                               prev, b->d_parts, P, pp, (int)r0, flagv,
+                                                               stamp);
     else if (kernel == 1)
-        k_move_eval_fast<<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
-                                                         prev, b->d_parts, P, pp, (int)r0, flagv,
-                                                         stamp);
+        k_move_eval_fast<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
+                                                                prev, b->d_parts, P, pp, (int)r0, flagv,
+                                                                stamp);
+    else if (wolf)
+        k_move_eval<true><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
+                                                          s.rec, flagv, stamp);
     else
-        k_move_eval<<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
-                                                    s.rec, flagv, stamp);
+        k_move_eval<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
+                                                           s.rec, flagv, stamp);
     MMC_HIP(hipGetLastError());
     return MMC_OK;
 }
@@ -750,6 +856,7 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     BATCH_ONE_BOX(b, "mmc_batch_eval");
     BATCH_USABLE(b);
     BATCH_NO_VOLUME_TRIAL(b);
+    BATCH_S_FRESH(b, "mmc_batch_eval");
     MMC_REQUIRE(moves && results, MMC_ERR_ARG, "NULL argument");
     MMC_TRY(batch_refresh_mirror(b));
     DeviceSystem &s = b->sys;
@@ -763,7 +870,8 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     for (int64_t r = 0; r < R; r++) {
         const int acc = (b->has_prev && moves[r].accept_prev) ? 1 : 0;
         if (acc) {
-            b->s_cur[r] ^= 1; // main.jl:621: the buffer RecipMove wrote becomes sumQExpOld
+            if (b->coulomb_style != MMC_COULOMB_WOLF)
+                b->s_cur[r] ^= 1; // main.jl:621: the buffer RecipMove wrote becomes sumQExpOld
             batch_mirror_commit(b, r, prev[r]);
         }
         cur[r].mol = moves[r].mol;
@@ -900,7 +1008,8 @@ extern "C" int32_t mmc_batch_settle(mmc_batch *b, const int32_t *accept)
     for (int64_t r = 0; r < s.R; r++) {
         b->h_accept[r] = accept[r] ? 1 : 0;
         if (accept[r]) {
-            b->s_cur[r] ^= 1;
+            if (b->coulomb_style != MMC_COULOMB_WOLF)
+                b->s_cur[r] ^= 1;
             batch_mirror_commit(b, r, prev[r]);
         }
     }
@@ -912,6 +1021,7 @@ extern "C" int32_t mmc_batch_settle(mmc_batch *b, const int32_t *accept)
 extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double new_kappa)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_change");
     BATCH_ONE_BOX(b, "mmc_batch_volume_change");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_REQUIRE(!b->vol_outstanding, MMC_ERR_STATE,
@@ -945,6 +1055,7 @@ extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double 
 extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double new_kappa, mmc_totals *tot)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_trial");
     BATCH_ONE_BOX(b, "mmc_batch_volume_trial");
     BATCH_USABLE(b);
     MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
@@ -982,6 +1093,7 @@ extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double n
 extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_accept");
     BATCH_ONE_BOX(b, "mmc_batch_volume_accept");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");
     b->vol_outstanding = false;
@@ -992,6 +1104,7 @@ extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 extern "C" int32_t mmc_batch_volume_reject(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_reject");
     BATCH_ONE_BOX(b, "mmc_batch_volume_reject");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");
     MMC_TRY(b->sys.snapshot_restore());

@@ -1411,7 +1411,7 @@ extern "C" int32_t mmc_trial_move(mmc_ctx *ctx, int64_t i, const double *com_new
         MMC_TRY(ctx_quiesce(ctx));
         const PairParams pp = mmc_pair_params(lj_rcut, qq_rcut, 0.0, 0.5, s.bv.kappa, false);
         dim3 grid((unsigned)ctx->n_parts, 1);
-        k_move_eval<<<grid, MMC_BLOCK, 0, s.stream>>>(s.bv, ctx->d_move, nullptr, ctx->d_parts,
+        k_move_eval<false><<<grid, MMC_BLOCK, 0, s.stream>>>(s.bv, ctx->d_move, nullptr, ctx->d_parts,
                                                       ctx->n_parts, pp, 0, s.rec, nullptr, 0u);
         MMC_HIP(hipGetLastError());
         MMC_TRY(s.sync());

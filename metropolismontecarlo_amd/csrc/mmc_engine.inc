@@ -167,6 +167,8 @@ struct Driver {
     double *energies;          // mmc_batch_run
     mmc_chain *chains = nullptr; // mmc_batch_run_chains
     int adjust = 0;
+    uint8_t s_flip = 1;          // an accepted move hands the S buffers over (main.jl:621); 0 in Wolf style,
+                                 // whose moves leave both where they were
     bool devgen = false;         // proposals generated on the device (mmc_propose.hpp)
     bool devacc = false;         // ... and the accept decision made by the move kernel itself (thread_main_devacc)
     int K = 1;                   // ... which then takes every replica through K steps per launch (DecideConsts)
@@ -357,7 +359,7 @@ struct Driver {
                     else { st.rot_attempt++; st.rot_accept += acc; }
                     st.overlaps += (ovl_mask >> k) & 1;
                     if (acc && step_done + k + 1 < p->n_steps)
-                        b->s_cur[r] ^= 1; // main.jl:621 (the call's last step: settle_slice)
+                        b->s_cur[r] ^= s_flip; // main.jl:621 (the call's last step: settle_slice)
                     if (k + 1 == n_sub) {
                         acc_prev[r] = acc ? 1 : 0;
                         kind[r] = (uint8_t)kd;
@@ -368,7 +370,7 @@ struct Driver {
                 kind[r] = (uint8_t)mmc_move_kind(chain_key(r), (uint64_t)(rng_off + step_done));
                 decide(r, parts, step_done, st, part_accept_of(parts[0].ovl[1]));
                 if (acc_prev[r] && step_done + 1 < p->n_steps)
-                    b->s_cur[r] ^= 1; // main.jl:621 (the last step's: settle_slice)
+                    b->s_cur[r] ^= s_flip; // main.jl:621 (the last step's: settle_slice)
             } else
                 decide(r, parts, step_done, st);
         }
@@ -407,7 +409,7 @@ struct Driver {
         if (devgen) { // the device draws the move; the host only says what became of the last one
             for (int64_t r = lo; r < hi; r++) {
                 if (acc_prev[r])
-                    b->s_cur[r] ^= 1; // main.jl:621
+                    b->s_cur[r] ^= s_flip; // main.jl:621
                 b->h_flags[r] = (uint8_t)((acc_prev[r] ? 1 : 0) | (b->s_cur[r] << 1));
                 kind[r] = (uint8_t)mmc_move_kind(chain_key(r), (uint64_t)(rng_off + step));
             }
@@ -419,7 +421,7 @@ struct Driver {
         }
         for (int64_t r = lo; r < hi; r++) {
             if (acc_prev[r]) {
-                b->s_cur[r] ^= 1; // main.jl:621
+                b->s_cur[r] ^= s_flip; // main.jl:621
                 batch_mirror_commit(b, r, prev[r]);
             }
             MoveRec &m = cur[r];
@@ -579,7 +581,7 @@ struct Driver {
         for (int64_t r = lo; r < hi; r++) {
             b->h_accept[r] = acc_prev[r];
             if (acc_prev[r]) {
-                b->s_cur[r] ^= 1;
+                b->s_cur[r] ^= s_flip;
                 if (!devgen)
                     batch_mirror_commit(b, r, prev[r]);
             }
@@ -596,7 +598,7 @@ struct Driver {
     {
         for (int64_t r = g.r0; r < g.r0 + g.nr; r++)
             if (acc_prev[r])
-                b->s_cur[r] ^= 1;
+                b->s_cur[r] ^= s_flip;
     }
 
     void fail(int32_t st)
@@ -621,7 +623,7 @@ struct Driver {
         const bool new_steps = step == 0 || (adjust && step % b->sys.n_mol == 0);
         const int64_t k = r - v.off;
         if (step > 0 && v.acc[k])
-            v.scur[k] ^= 1; // main.jl:621
+            v.scur[k] ^= s_flip; // main.jl:621
         v.flags[k] = (uint8_t)((step > 0 && v.acc[k] ? 1 : 0) | (v.scur[k] << 1));
         v.kind[k] = (uint8_t)mmc_move_kind(chain_key(r), (uint64_t)(rng_off + step));
         std::atomic_thread_fence(std::memory_order_release); // h_steps before the word
@@ -1021,6 +1023,8 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     MMC_REQUIRE(p && (energies || chains) && stats, MMC_ERR_ARG, "NULL argument");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_REQUIRE(p->temperature > 0 && p->n_steps >= 0, MMC_ERR_ARG, "bad run parameters");
+    BATCH_S_FRESH(b, "mmc_batch_run");
+    const bool wolf = b->coulomb_style == MMC_COULOMB_WOLF;
     MMC_REQUIRE(!b->quat_mode || b->device_moves, MMC_ERR_UNSUPPORTED,
                 "orientations are set (mmc_batch_set_orientations): the quaternion move generation "
                 "runs on the device only, set option device_moves = 1");
@@ -1036,6 +1040,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     Driver d;
     d.b = b; d.p = p; d.energies = energies; d.chains = chains; d.adjust = adjust;
     d.devgen = b->device_moves != 0;
+    d.s_flip = wolf ? 0 : 1;
     d.rng_off = b->steps_done;
     d.inject_left.store(b->inject_torn);
     if (d.devgen) {
@@ -1062,7 +1067,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     }
     MMC_REQUIRE(!s.pb.on || d.devgen, MMC_ERR_UNSUPPORTED,
                 "per-replica boxes: the trial moves are drawn on the device (device_moves = 1)");
-    if (b->persistent != 0 && !s.pb.on) { // small batches: the persistent move server (one box)
+    if (b->persistent != 0 && !s.pb.on && !wolf) { // small batches: the persistent move server (one box, Ewald style)
         d.server = batch_server_applies(b) && (b->persistent == 1 || R <= MMC_SERVER_AUTO_MAX);
         MMC_REQUIRE(d.server || b->persistent != 1, MMC_ERR_UNSUPPORTED,
                     "the persistent move server needs device_moves = 1, the table kernel, no "
@@ -1356,6 +1361,7 @@ extern "C" int32_t mmc_batch_run_npt(mmc_batch *b, const mmc_run_params *p, cons
                                      double *energy, mmc_run_stats *stats, mmc_npt_stats *ns)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_run_npt");
     BATCH_ONE_BOX(b, "mmc_batch_run_npt (per-replica boxes: mmc_batch_run_npt_replicas)");
     MMC_REQUIRE(p && q && energy && stats && ns, MMC_ERR_ARG, "NULL argument");
     MMC_REQUIRE(b->sys.R == 1, MMC_ERR_UNSUPPORTED,

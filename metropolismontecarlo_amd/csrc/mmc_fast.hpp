@@ -29,6 +29,7 @@
 // Branch decisions (gates, overlap, slack) still use the reference's exact comparisons on
 // unfused arithmetic, so neighbour lists and overlap flags are bit-identical to the oracle's.
 #pragma once
+#include <type_traits>
 #include "mmc_kernels.hpp"
 
 #define MMC_TILE 150      // neighbours staged per LDS tile (14 KB; doubles as reduction scratch)
@@ -342,12 +343,13 @@ __global__ void k_pack_kvec(const int32_t *kxyz, const int32_t *n_kvecs, int32_t
         kpack[MMC_NK_STRIDE + col] = xy;
 }
 
-struct FastShared {
+struct FastNoTables {};
+template <bool PT> struct FastSharedT { // PT = false (WOLF): no phase tables
     alignas(16) double tile[MMC_TILE * MMC_REC]; // neighbour records, written as double2
     alignas(16) double mvw[MV_WORDS + 1];        // this replica's move record
     alignas(16) double pvw[MV_WORDS + 1];        // its previous move record (pending commit)
     alignas(16) double qtab[MMC_QQ_TABLE_DOUBLES];
-    cplx ptab[2][3][3][MMC_NKTAB];
+    typename std::conditional<PT, cplx[2][3][3][MMC_NKTAB], FastNoTables>::type ptab;
     double red[7 * MMC_WAVES];
     double qq9[9], ljp_eps[9], ljp_sig[9];
     int32_t list[MMC_FLIST_CAP];
@@ -356,17 +358,21 @@ struct FastShared {
     int32_t wcnt[MMC_WAVES];
     int32_t gflag;
 };
+typedef FastSharedT<true> FastShared;
 
 // grid (n_parts, replicas of the group); same part semantics as k_move_eval.  PerBox: empty =
 // the batch's one box; PerBoxView = replica r takes its box, kappa, cfac row and table from it
 // (pb_* in mmc_kernels.hpp).
-template <typename... PerBox>
+// WOLF = true (mmc_batch_set_coulomb_style; main.jl:75, :580-590): no reciprocal part -- no phase
+// tables, no k-vector constants, neither S(k) buffer touched -- and every part of n_parts > 1 is a
+// pair part.  Its own instantiation: the Ewald forms compile exactly as they did.
+template <bool WOLF, typename... PerBox>
 __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     BatchView bv, double *rec, const double *qq_tab, const int32_t *kpack, FastConsts fc,
     const MoveRec *cur, const MoveRec *prev, PartOut *out, int n_parts, PairParams pp, int r_base,
     const uint8_t *flagv, unsigned stamp, PerBox... pb)
 {
-    __shared__ __align__(16) FastShared sm;
+    __shared__ __align__(16) FastSharedT<!WOLF> sm;
 
     const int r = r_base + blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const int n_mol = bv.n_mol;
@@ -374,9 +380,9 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     const double *comx = bv.comx + r * bv.mol_stride, *comy = bv.comy + r * bv.mol_stride,
                  *comz = bv.comz + r * bv.mol_stride;
     double *myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
-    const bool do_pairs = (n_parts == 1) || (part < n_parts - 1);
-    const bool do_recip = (n_parts == 1) || (part == n_parts - 1);
-    const int np = (n_parts == 1) ? 1 : n_parts - 1;
+    const bool do_pairs = WOLF ? true : (n_parts == 1) || (part < n_parts - 1);
+    const bool do_recip = WOLF ? false : (n_parts == 1) || (part == n_parts - 1);
+    const int np = WOLF ? n_parts : (n_parts == 1) ? 1 : n_parts - 1;
     const int plen = (n_mol + np - 1) / np;
     const int j_begin = do_pairs ? min(part * plen, n_mol) : 0;
     const int j_end = do_pairs ? min(j_begin + plen, n_mol) : 0; // >= j_begin
@@ -451,6 +457,7 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     }
     if (part == 0 && commit && tid >= 12 && tid < 16)
         quat_commit(bv, r, pend, tid - 12, prev[r].q_new[tid - 12], quat_valid(prev[r].q_new));
+    if constexpr (!WOLF)
     if (do_recip && tid >= 64 && tid < 82) { // phase tables of the 3 moved atoms, old and new
         const int t = tid - 64;
         const int st = t / 9, l = (t % 9) / 3, d = t % 3;
@@ -659,6 +666,7 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
                 greg[q] = gather_piece(0, g, gent[q]);
         }
         // ---- reciprocal part for this thread's k-vectors (ewalds.jl:803-821) ----
+        if constexpr (!WOLF)
         if (do_recip) {
             __syncthreads(); // ptab
             double *Sn = s_buf(bv, r, scur ^ 1);

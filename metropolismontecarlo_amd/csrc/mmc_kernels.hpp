@@ -527,6 +527,10 @@ struct DecideConsts {
 // `rec`: the record array of homogeneous systems (kept in step by the commit) or NULL.
 // `flagv`: when not NULL the per-replica flag byte comes from here instead of the record header
 // (device-generated records are written before the accept decision of the previous step exists).
+// WOLF = true (mmc_batch_set_coulomb_style; main.jl:75, :580-590): no reciprocal part, neither S(k)
+// buffer touched, every part of n_parts > 1 a pair part.  Its own instantiation: the Ewald form
+// compiles exactly as it did.
+template <bool WOLF = false>
 __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval(BatchView bv, const MoveRec *cur,
                                                          const MoveRec *prev, PartOut *out,
                                                          int n_parts, PairParams pp, int r_base,
@@ -539,7 +543,6 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval(BatchView bv, const Mov
     __shared__ int32_t list[MMC_LIST_CAP];
     __shared__ int32_t wcnt[MMC_WAVES];
     __shared__ double red[6 * MMC_WAVES];
-    __shared__ cplx tab[2][3][3][MMC_NKTAB];
 
     const int r = r_base + blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const SysView s = sys_view(bv, r);
@@ -599,15 +602,15 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval(BatchView bv, const Mov
         quat_commit(bv, r, pend, tid - 12, prev[r].q_new[tid - 12], quat_valid(prev[r].q_new));
     __syncthreads();
 
-    const bool do_pairs = (n_parts == 1) || (part < n_parts - 1);
-    const bool do_recip = (n_parts == 1) || (part == n_parts - 1);
+    const bool do_pairs = WOLF ? true : (n_parts == 1) || (part < n_parts - 1);
+    const bool do_recip = WOLF ? false : (n_parts == 1) || (part == n_parts - 1);
     PartOut po;
     po.lj_pot[0] = po.lj_pot[1] = po.lj_vir[0] = po.lj_vir[1] = 0.0;
     po.qq_pot[0] = po.qq_pot[1] = po.recip = 0.0;
     po.ovl[0] = po.ovl[1] = 0;
 
     if (do_pairs) {
-        const int np = (n_parts == 1) ? 1 : n_parts - 1;
+        const int np = WOLF ? n_parts : (n_parts == 1) ? 1 : n_parts - 1;
         const int len = (s.n_mol + np - 1) / np;
         const int j0 = part * len, j1 = min(j0 + len, s.n_mol);
         PairAcc acc[2] = { { 0.0, 0.0, 0.0, 0 }, { 0.0, 0.0, 0.0, 0 } };
@@ -623,7 +626,9 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval(BatchView bv, const Mov
             po.ovl[0] = o0; po.ovl[1] = o1;
         }
     }
+    if constexpr (!WOLF)
     if (do_recip) {
+        __shared__ cplx tab[2][3][3][MMC_NKTAB]; // (no phase tables in the WOLF instantiation)
         if (tid < 18) {
             const int st = tid / 9, l = (tid % 9) / 3, d = tid % 3;
             phase_row(ch.at[st][l][d], s.box, tab[st][l][d]);

@@ -36,6 +36,7 @@ static int32_t pb_upload_mask(DeviceSystem &s, const std::vector<int32_t> &mask)
 extern "C" int32_t mmc_batch_set_boxes(mmc_batch *b, const double *boxes, double alpha)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_set_boxes");
     BATCH_USABLE(b);
     BATCH_NO_VOLUME_TRIAL(b);
     MMC_REQUIRE(boxes, MMC_ERR_ARG, "NULL argument");
@@ -90,6 +91,7 @@ extern "C" int32_t mmc_batch_get_boxes(mmc_batch *b, double *boxes)
 extern "C" int32_t mmc_batch_volume_trial_replicas(mmc_batch *b, const double *new_boxes, mmc_totals *tot)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_trial_replicas");
     BATCH_USABLE(b);
     BATCH_NO_VOLUME_TRIAL(b);
     MMC_REQUIRE(new_boxes && tot, MMC_ERR_ARG, "NULL argument");
@@ -145,6 +147,7 @@ extern "C" int32_t mmc_batch_volume_trial_replicas(mmc_batch *b, const double *n
 extern "C" int32_t mmc_batch_volume_settle(mmc_batch *b, const int32_t *accept)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_volume_settle");
     MMC_REQUIRE(accept, MMC_ERR_ARG, "NULL argument");
     DeviceSystem &s = b->sys;
     MMC_REQUIRE(s.pb.on, MMC_ERR_UNSUPPORTED,
@@ -173,6 +176,7 @@ extern "C" int32_t mmc_batch_run_npt_replicas(mmc_batch *b, const mmc_run_params
                                               mmc_run_stats *stats, mmc_npt_stats *per_replica)
 {
     BATCH_CHECK(b);
+    BATCH_NOT_WOLF(b, "mmc_batch_run_npt_replicas");
     MMC_REQUIRE(p && q && energies && stats && per_replica, MMC_ERR_ARG, "NULL argument");
     DeviceSystem &s = b->sys;
     MMC_REQUIRE(s.pb.on, MMC_ERR_UNSUPPORTED,

@@ -36,6 +36,9 @@
 #ifndef WV_OCC
 #define WV_OCC 5     // waves per SIMD k_move_eval_wave is compiled for: 96 VGPRs, and 31 KB of LDS per
 #endif               // workgroup of four waves (five workgroups per compute unit)
+#ifndef WV_OCC_WOLF
+#define WV_OCC_WOLF 4 // ... its WOLF instantiations: no phase tables and no k loop; 128 VGPRs, the fastest of
+#endif                // 3, 4, 5, 6 and 8 measured (profiles/wolf_bench.json, profiles/README.md "Wolf chains")
 #ifndef WV_MWAVES
 #define WV_MWAVES WV_WAVES // waves per workgroup of k_move_eval_wave (they share one copy of the erfc table)
 #endif
@@ -56,12 +59,25 @@
 // unit); the host takes these kernels for at most MMC_WAVE_MAX_MOL molecules.
 typedef uint16_t wv_list_t;
 #define MMC_WAVE_MAX_MOL 65535
-template <int NW> struct WaveSharedT {
+// sum6w(wv): the 24 doubles wave_sum6_add takes as scratch -- this wave's phase tables, which the
+// reciprocal loop is done with by then.
+template <int NW, bool PT = true> struct WaveSharedT {
     alignas(16) double qtab[MMC_QQ_TABLE_DOUBLES];
     cplx ptab[NW][2][3][3][MMC_NKTAB]; // phase tables of the 3 moved atoms, old and new
     wv_list_t list[NW][WV_LIST];
     alignas(16) double pvw[NW][12];    // pending commit of the unit's replica, record layout
     alignas(16) double outw[NW][8];    // the PartOut being assembled
+    __device__ __forceinline__ double *sum6w(int wv) { return reinterpret_cast<double *>(&ptab[wv][0][0][0][0]); }
+};
+// PT = false (the WOLF instantiations of k_move_eval_wave): no phase tables, the reduction's scratch
+// is a member of its own.
+template <int NW> struct WaveSharedT<NW, false> {
+    alignas(16) double qtab[MMC_QQ_TABLE_DOUBLES];
+    alignas(16) double sum6[NW][24];
+    wv_list_t list[NW][WV_LIST];
+    alignas(16) double pvw[NW][12];
+    alignas(16) double outw[NW][8];
+    __device__ __forceinline__ double *sum6w(int wv) { return sum6[wv]; }
 };
 typedef WaveSharedT<WV_WAVES> WaveShared;
 
@@ -193,8 +209,9 @@ __device__ __forceinline__ void phase_row_moderate(double x, double L, cplx *row
 // the unit's seven sums in LDS; lane 0 rewrites the replica's flag byte.  Returns accept (0 / 1).
 __device__ __forceinline__ int wave_decide(const double *outw, bool ov_old, bool ov_new,
                                            const DecideConsts *__restrict__ dc, long long step, int r,
-                                           int scur, int lane, double *delta_out = nullptr, bool store_flags = true)
-{
+                                           int scur, int lane, double *delta_out = nullptr, bool store_flags = true,
+                                           bool flip_s = true)
+{   // flip_s = false (Wolf style): no S buffer changes hands, the flag byte's bit 1 stays what it was
     const double delta = mmc_move_delta(outw, ov_old, ov_new, dc->factor);
     if (delta_out)
         *delta_out = delta;
@@ -211,7 +228,7 @@ __device__ __forceinline__ int wave_decide(const double *outw, bool ov_old, bool
     else met = exp(-x) > u;
     const int acc = (met && !(ov_old || ov_new)) ? 1 : 0;
     if (store_flags && lane == 0)
-        dc->flags[r] = (uint8_t)(acc | ((scur ^ acc) << 1));
+        dc->flags[r] = (uint8_t)(acc | ((scur ^ (flip_s ? acc : 0)) << 1));
     return acc;
 }
 
@@ -238,8 +255,13 @@ __device__ __forceinline__ int wave_ticket(unsigned *queue, unsigned base, int n
 // mmc_wave_unit.inc; the launch site checks the condition).
 // MULTI = true: several steps of the chain per launch (n_sub; the kernel decides) -- its own
 // instantiation, so that the one-step form compiles exactly as it did.
-template <bool SUBST, bool IMG, bool MULTI = false>
-__global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(WV_OCC, WV_OCC))) void k_move_eval_wave(
+// WOLF = true: the chain of main.jl:75 `Wolf = true` (mmc_batch_set_coulomb_style) -- no RecipMove
+// (main.jl:580-590): no phase tables, no k loop, neither S(k) buffer read or written, every part of
+// n_parts > 1 a pair part, the record's reciprocal sum 0.  Its own instantiations again, compiled for
+// WV_OCC_WOLF waves per SIMD; the Ewald forms compile exactly as they did.
+template <bool SUBST, bool IMG, bool MULTI = false, bool WOLF = false>
+__global__ __launch_bounds__(WV_MWAVES * 64)
+__attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WOLF : WV_OCC))) void k_move_eval_wave(
     BatchView bv, double *rec, const double *__restrict__ qq_tab,
     const int32_t *__restrict__ kpack, FastConsts fc, const MoveRec *__restrict__ cur,
     const MoveRec *__restrict__ prev, PartOut *out, int n_parts, PairParams pp, int r_base,
@@ -247,7 +269,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
     int n_sub_arg, int slot0, unsigned *queue, unsigned queue_base)
 {
     const int n_sub = MULTI ? n_sub_arg : 1;
-    __shared__ __align__(16) WaveSharedT<WV_MWAVES> sm;
+    __shared__ __align__(16) WaveSharedT<WV_MWAVES, !WOLF> sm;
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -258,7 +280,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
     const int n_mol = bv.n_mol, nkv = bv.nkvecs;
     const double box = bv.box;
     const BoxConsts bc = box_consts(box);
-    const int np = (n_parts == 1) ? 1 : n_parts - 1;
+    const int np = WOLF ? n_parts : (n_parts == 1) ? 1 : n_parts - 1;
     const int plen = (n_mol + np - 1) / np;
     const bool same_gate = pp.lj_gate_sq == pp.qq_gate_sq;
     // prefilter of the COM scan: 16-bit box fractions (com_quant, mmc_kernels.hpp)
@@ -291,8 +313,8 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
             part = unit - rl * n_parts;
         }
         const int r = r_base + rl;
-        const bool do_pairs = (n_parts == 1) || (part < n_parts - 1);
-        const bool do_recip = (n_parts == 1) || (part == n_parts - 1);
+        const bool do_pairs = WOLF ? true : (n_parts == 1) || (part < n_parts - 1);
+        const bool do_recip = WOLF ? false : (n_parts == 1) || (part == n_parts - 1);
         const int j_begin = do_pairs ? min(part * plen, n_mol) : 0;
         const int j_end = do_pairs ? min(j_begin + plen, n_mol) : 0;
         double *const myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
@@ -362,6 +384,8 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
                     quat_commit(bv, r, pend, lane - 13, pw, q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3 > 0.25);
             }
             wave_sync();
+            if (WOLF && !SUBST) // (the Ewald forms wait behind their phase tables: WV_AFTER_PHASE_TABLES)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* this wave's commit is in memory */
         }
 
         // (expanded where they are used: as variables they would be live across the whole unit)
@@ -373,10 +397,10 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
             if (!dc)
                 return 0;
             if (n_sub <= 1)
-                return wave_decide(sm.outw[wv], o0, o1, dc, dec_step, r, scur, lane);
+                return wave_decide(sm.outw[wv], o0, o1, dc, dec_step, r, scur, lane, nullptr, true, !WOLF);
             double delta;
             const bool last = sub + 1 == n_sub;
-            const int acc = wave_decide(sm.outw[wv], o0, o1, dc, dec_step + sub, r, scur, lane, &delta, last);
+            const int acc = wave_decide(sm.outw[wv], o0, o1, dc, dec_step + sub, r, scur, lane, &delta, last, !WOLF);
             if (acc) {
                 e_sum += delta;
                 acc_mask |= 1u << sub;
@@ -384,7 +408,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
             if (o0 || o1)
                 ovl_mask |= 1u << sub;
             kind_mask |= (unsigned)((lane_i32((int)(hdr >> 32), 0) >> 8) & 1) << sub; // (k_propose's note in the record)
-            flags_carry = acc | ((scur ^ acc) << 1);
+            flags_carry = acc | ((scur ^ (WOLF ? 0 : acc)) << 1);
             if (last) {
                 wave_sync();
                 if (lane < 7)
@@ -404,6 +428,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
 #define WV_ZERO opaque_f64(0.0)
 #define WV_SUBST SUBST
 #define WV_IMG IMG
+#define WV_WOLF WOLF
 #ifndef WV_XY_MOVE
 #define WV_XY_MOVE 1
 #endif
@@ -417,6 +442,7 @@ __global__ __launch_bounds__(WV_MWAVES * 64) __attribute__((amdgpu_waves_per_eu(
 #include "mmc_wave_unit.inc"
 #undef WV_AFTER_PHASE_TABLES
 #undef WV_IMG
+#undef WV_WOLF
 #undef WV_PASSES
 #undef WV_XY
 #undef WV_SUBST

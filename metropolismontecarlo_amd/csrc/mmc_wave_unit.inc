@@ -57,6 +57,10 @@
 #ifndef WV_KPF // iterations of the k loop whose loads are in flight ahead of the one being computed
 #define WV_KPF 2
 #endif
+#ifndef WV_WOLF // 1 (k_move_eval_wave's WOLF instantiations): no reciprocal part at all -- do_recip is
+#define WV_WOLF 0 // false and sm has no phase tables but the reduction's scratch (WaveSharedT<.., false>)
+#define WV_WOLF_DEFAULTED
+#endif
 #ifndef WV_ZERO // (a zero the includer can keep from being hoisted into a long-lived register pair)
 #define WV_ZERO 0.0
 #define WV_ZERO_DEFAULTED
@@ -70,6 +74,8 @@
         // their lines in the L2 -- 290 us per launch instead of 270: the touches double the number of
         // line requests of the gathers, and those requests, not the trip to HBM, are what the gathers
         // cost.  Holding the gathered records in registers across the k loop spills at 96 VGPRs.)
+        constexpr bool wv_wolf = WV_WOLF;
+        if constexpr (!wv_wolf) {
         if (do_recip) {
             // phase tables e^{i 2 pi k x / L}, k = -5..5, of the 3 moved atoms, old and new: 18 rows
             {
@@ -205,6 +211,7 @@
         };
         if (do_recip)
             recip_loop();
+        } // !wv_wolf
         if (!do_recip && lane == 0)
             outw[6] = WV_ZERO;
 
@@ -472,9 +479,7 @@
 #undef WV_MIN1
                 // wave reduction (fixed order: bitwise reproducible)
 #if WV_NS == 2
-                // (scratch: this wave's phase tables, which the reciprocal loop is done with)
-                wave_sum6_add(a_lj0, a_lj1, a_v0, a_v1, a_q0, a_q1, outw,
-                              reinterpret_cast<double *>(&sm.ptab[wv][0][0][0][0]), lane);
+                wave_sum6_add(a_lj0, a_lj1, a_v0, a_v1, a_q0, a_q1, outw, sm.sum6w(wv), lane);
 #else
                 const double s1 = wave_sum_rows(a_lj1), s3 = wave_sum_rows(a_v1), s5 = wave_sum_rows(a_q1);
                 if (lane == 0) {
@@ -629,6 +634,10 @@
 #ifdef WV_ZERO_DEFAULTED
 #undef WV_ZERO
 #undef WV_ZERO_DEFAULTED
+#endif
+#ifdef WV_WOLF_DEFAULTED
+#undef WV_WOLF
+#undef WV_WOLF_DEFAULTED
 #endif
 #ifdef WV_NS_DEFAULTED
 #undef WV_NS

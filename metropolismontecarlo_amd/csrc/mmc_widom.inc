@@ -51,7 +51,9 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     BATCH_NO_VOLUME_TRIAL(b);
     MMC_REQUIRE(!b->needs_reload, MMC_ERR_STATE, "%s: a run failed half-way; set every replica again", what);
+    BATCH_S_FRESH(b, what);
     BATCH_ONE_BOX(b, what);
+    BATCH_NOT_WOLF(b, what);
     MMC_REQUIRE(b->fast_ok, MMC_ERR_UNSUPPORTED,
                 "%s: needs identical 3-atom molecules and a cutoff / kappa the erfc table covers", what);
 

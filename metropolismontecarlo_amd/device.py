@@ -363,6 +363,33 @@ class Batch:
         check(self._L.mmc_batch_potential_ewald(self._h, t))
         return [x.asdict() for x in t]
 
+    COULOMB_STYLES = ("ewald", "wolf")   # MMC_COULOMB_EWALD, MMC_COULOMB_WOLF
+
+    def set_coulomb_style(self, style):
+        """"ewald" (the default) or "wolf": the reference's global `Wolf` (main.jl:75) for the moves
+        of eval / settle / run / run_chains.  Wolf moves skip RecipMove and leave S(k) alone; after
+        switching back to "ewald" call recip_long() (or potential_ewald()) before the next move."""
+        if style not in self.COULOMB_STYLES:
+            raise ValueError(f"coulomb style must be one of {self.COULOMB_STYLES}, not {style!r}")
+        check(self._L.mmc_batch_set_coulomb_style(self._h, self.COULOMB_STYLES.index(style)))
+
+    @property
+    def coulomb_style(self):
+        v = C.c_int32()
+        check(self._L.mmc_batch_get_coulomb_style(self._h, C.byref(v)))
+        return self.COULOMB_STYLES[v.value]
+
+    def potential_wolf(self, as_array=False):
+        """potential() of the Wolf overload (energy.jl:864-943) of every replica, in either style:
+        a list of dicts, or with as_array=True one numpy record array (_lib.TOTALS_DTYPE)."""
+        if as_array:
+            out = np.zeros(self.R, dtype=TOTALS_DTYPE)
+            check(self._L.mmc_batch_potential_wolf(self._h, out.ctypes.data_as(C.c_void_p)))
+            return out
+        t = (Totals * self.R)()
+        check(self._L.mmc_batch_potential_wolf(self._h, t))
+        return [x.asdict() for x in t]
+
     def eval(self, mol, com_new, atoms_new, accept_prev=None):
         """mol: (R,) 1-based; com_new: (R,3); atoms_new: (R,3,3); accept_prev: (R,) bool."""
         mol = np.broadcast_to(np.asarray(mol, dtype=np.int64), (self.R,))

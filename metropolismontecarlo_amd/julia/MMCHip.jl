@@ -363,6 +363,31 @@ function potential_ewald(b::Batch)
     return tot
 end
 
+"""
+    set_coulomb_style!(b, :ewald | :wolf)
+
+The reference's global `Wolf` (main.jl:75) for the batch's moves: `:wolf` skips RecipMove
+(main.jl:580-590) and leaves S(k) alone.  After switching back to `:ewald` call `recip_long!(b)` (or
+`potential_ewald(b)`) before the next move.
+"""
+function set_coulomb_style!(b::Batch, style::Symbol)
+    style in (:ewald, :wolf) || throw(ArgumentError("coulomb style must be :ewald or :wolf"))
+    check(ccall((:mmc_batch_set_coulomb_style, libmmc), Int32, (Ptr{Cvoid}, Int32), b.h, style == :wolf ? 1 : 0))
+end
+
+function coulomb_style(b::Batch)
+    v = Ref{Int32}(0)
+    check(ccall((:mmc_batch_get_coulomb_style, libmmc), Int32, (Ptr{Cvoid}, Ptr{Int32}), b.h, v))
+    return v[] == 1 ? :wolf : :ewald
+end
+
+"potential() of the Wolf overload of every replica (energy.jl:864-943), in either style."
+function potential_wolf(b::Batch)
+    tot = Vector{MMCTotals}(undef, b.n_replicas)
+    check(ccall((:mmc_batch_potential_wolf, libmmc), Int32, (Ptr{Cvoid}, Ptr{MMCTotals}), b.h, tot))
+    return tot
+end
+
 "RecipLong of every replica; energies WITHOUT factor (ewalds.jl:603)."
 function recip_long!(b::Batch)
     e = Vector{Float64}(undef, b.n_replicas)
