@@ -233,6 +233,13 @@ def widom_occ():
     return int(re.search(r"#define WIDOM_OCC (\d+)", src).group(1))
 
 
+def wolf_occ():
+    """WV_OCC_WOLF of mmc_wave.hpp: the waves per SIMD the launch of k_move_eval_wave's Wolf
+    instantiations is capped at (mmc_batch.inc)."""
+    src = open(os.path.join(HERE, "..", "metropolismontecarlo_amd", "csrc", "mmc_wave.hpp")).read()
+    return int(re.search(r"#define WV_OCC_WOLF (\d+)", src).group(1))
+
+
 def image_shift(d, box):
     """What the minimum image (vector1D, Ewald/boundaries.jl) adds to a coordinate difference d."""
     return np.where(d >= 0.5 * box, -box, np.where(d <= -0.5 * box, box, 0.0))

@@ -128,20 +128,23 @@ def propose(mode, seed, replica, step, com, atoms, q, db, box, dr, dphi):
     return kind, c_new, moves.space_fixed_atoms(c_new, q_new, db, mode == 1), q_new, u
 
 
-def replay(orc, a, replica, calls, T, dr, dphi, rcut, quat=None, db=None, probe=False):
+def replay(orc, a, replica, calls, T, dr, dphi, rcut, quat=None, db=None, probe=False, wolf=False):
     """The chain of global replica index `replica` through the calls [(n_steps, seed, mode), ...]
     one batch makes in a row (mode 0 rigid, 1 / 2 quaternions from `quat`, body `db`): the Philox
     counter continues across calls, the molecule sweep restarts at step 0 of every call.  Returns
     the final com / coords / S(k) / quaternions, the accepted rotations per molecule, the sum of the
     accepted dU, counts, every step's (dU, flags) -- bit 0 accepted, bit 1 overlap, bit 2 rotation
-    -- and with `probe` the steps whose old or new state has an image crossing (image_crossings)."""
+    -- and with `probe` the steps whose old or new state has an image crossing (image_crossings).
+    `wolf`: the chain of the reference's `Wolf = true` (main.jl:580-593: deltaRecip = 0), so
+    dU = d_lj + d_real and the oracle's S arrays are neither committed nor rolled back; v_acc, the
+    sum of the accepted moves' virial changes (main.jl:600-601), then leaves out d_recip / 3."""
     s = common.oracle_system(a)
     box, n_mol = a["box"], a["com"].shape[0]
     ew = orc.Ewald(5.6 / box, 5, 27, box)
     orc.recip_long(ew, s.coords, s.charge, box)
     q = None if quat is None else np.array(quat, dtype=float)
     n_qrot = np.zeros(n_mol, dtype=np.int64)
-    e_acc, n_acc, n_ovl, n_rot, trace, crossed, rng_off = 0.0, 0, 0, 0, [], [], 0
+    e_acc, v_acc, n_acc, n_ovl, n_rot, trace, crossed, rng_off = 0.0, 0.0, 0, 0, 0, [], [], 0
     for n_steps, seed, mode in calls:
         for step in range(n_steps):
             i = step % n_mol
@@ -152,7 +155,7 @@ def replay(orc, a, replica, calls, T, dr, dphi, rcut, quat=None, db=None, probe=
                           or image_crossings(i, c_new, a_new, s.com, s.coords, box, rcut)):
                 crossed.append(len(trace))
             d, ov = orc.trial_move(i + 1, s, ew, rcut, rcut, c_new, a_new)
-            delta = d[0] + d[1] + d[2]                                    # main.jl:593
+            delta = d[0] + d[1] if wolf else d[0] + d[1] + d[2]           # main.jl:593
             x = delta / T
             accept = (x < 0.0 or math.exp(-x) > u) and not ov             # main.jl:598
             trace.append((delta, int(accept) | (int(ov) << 1) | (kind << 2)))
@@ -160,27 +163,29 @@ def replay(orc, a, replica, calls, T, dr, dphi, rcut, quat=None, db=None, probe=
             n_rot += kind
             if accept:
                 e_acc += delta
+                v_acc += d[3] - d[2] / 3 if wolf else d[3]                # main.jl:600-601
                 n_acc += 1
                 s.com[i] = c_new
                 s.coords[3 * i:3 * i + 3] = a_new
                 if mode:
                     q[i] = q_new
                     n_qrot[i] += kind
-                ew.sumQExpOld = ew.sumQExpNew.copy()
-            else:
+                if not wolf:
+                    ew.sumQExpOld = ew.sumQExpNew.copy()
+            elif not wolf:
                 ew.sumQExpNew = ew.sumQExpOld.copy()
         rng_off += n_steps
-    return dict(com=s.com, coords=s.coords, S=ew.sumQExpOld, quat=q, n_qrot=n_qrot, e_acc=e_acc,
+    return dict(com=s.com, coords=s.coords, S=ew.sumQExpOld, quat=q, n_qrot=n_qrot, e_acc=e_acc, v_acc=v_acc,
                 n_acc=n_acc, n_ovl=n_ovl, n_rot=n_rot, trace=trace, crossed=crossed)
 
 
 @functools.lru_cache(maxsize=None)
-def replay_of(name, faithful, replica, calls, T, dr, dphi, rcut, probe=False):
+def replay_of(name, faithful, replica, calls, T, dr, dphi, rcut, probe=False, wolf=False):
     """replay() of a named system (the same chain is checked under several kernels)."""
     from oracle import oracle as orc
     a, quat, db = system(name, faithful)
     uses_quat = any(m for _, _, m in calls)
-    return replay(orc, a, replica, calls, T, dr, dphi, rcut, quat if uses_quat else None, db, probe)
+    return replay(orc, a, replica, calls, T, dr, dphi, rcut, quat if uses_quat else None, db, probe, wolf)
 
 
 def _check_trace(o, d_gpu, f_gpu, r, at):

@@ -3,8 +3,8 @@
 alone, the Wolf total (energy.jl:864-943), run_chains, eval / settle, the untouched default and
 the fences.
 
-replay_wolf() is test_gpu_replay_paths.replay() with two differences: dU = d_lj + d_real
-(main.jl:580-593 with Wolf: deltaRecip = 0) and no commit or rollback of the oracle's S arrays.
+replay_wolf() is test_gpu_replay_paths.replay(wolf=True): dU = d_lj + d_real (main.jl:580-593
+with Wolf: deltaRecip = 0) and no commit or rollback of the oracle's S arrays.
 Tolerances as there: TOL * (|dU| + 1e4) per step, flags exact, 2e-13 A on coordinates,
 TOL * 1e5 on a call's energy change.
 
@@ -15,14 +15,13 @@ change therefore equals the change of potential_wolf's `virial + real / 3`, not 
 alone; test_run_chains_against_the_recompute compares with that, from potential_wolf's own two
 fields, at the tolerance of 1e-9 relative to the magnitudes the difference is formed from."""
 import functools
-import math
 
 import numpy as np
 import pytest
 
 import common
 from common import rel
-from test_gpu_replay_paths import make_batch, propose, system
+from test_gpu_replay_paths import make_batch, replay, system
 
 pytestmark = pytest.mark.gpu
 
@@ -51,33 +50,9 @@ def oracle_ewald(orc, a):
 
 
 def replay_wolf(orc, a, replica, calls, T, dr, dphi, rcut):
-    """One Wolf chain on the host (rigid device-made moves): see the module docstring."""
-    s = common.oracle_system(a)
-    box, n_mol = a["box"], a["com"].shape[0]
-    ew = oracle_ewald(orc, a)
-    orc.recip_long(ew, s.coords, s.charge, box)
-    e_acc, v_acc, n_acc, n_ovl, n_rot, trace, rng_off = 0.0, 0.0, 0, 0, 0, [], 0
-    for n_steps, seed in calls:
-        for step in range(n_steps):
-            i = step % n_mol
-            kind, c_new, a_new, _, u = propose(0, seed, replica, rng_off + step, s.com[i].copy(),
-                                               s.coords[3 * i:3 * i + 3].copy(), None, None, box, dr, dphi)
-            d, ov = orc.trial_move(i + 1, s, ew, rcut, rcut, c_new, a_new)
-            delta = d[0] + d[1]                                           # main.jl:593, deltaRecip = 0
-            x = delta / T
-            accept = (x < 0.0 or math.exp(-x) > u) and not ov             # main.jl:598
-            trace.append((delta, int(accept) | (int(ov) << 1) | (kind << 2)))
-            n_ovl += bool(ov)
-            n_rot += kind
-            if accept:
-                e_acc += delta
-                v_acc += d[3] - d[2] / 3                                  # main.jl:600-601, deltaRecip = 0
-                n_acc += 1
-                s.com[i] = c_new
-                s.coords[3 * i:3 * i + 3] = a_new
-        rng_off += n_steps
-    return dict(com=s.com, coords=s.coords, e_acc=e_acc, v_acc=v_acc, n_acc=n_acc, n_ovl=n_ovl, n_rot=n_rot,
-                trace=trace)
+    """One Wolf chain on the host (rigid device-made moves) through the calls [(n_steps, seed), ...]:
+    test_gpu_replay_paths.replay(wolf=True), see the module docstring."""
+    return replay(orc, a, replica, [(n, seed, 0) for n, seed in calls], T, dr, dphi, rcut, wolf=True)
 
 
 @functools.lru_cache(maxsize=None)
