@@ -342,6 +342,9 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *   "inject_torn"      N > 0: the native driver corrupts its first N copies of result records
  *                      before checking them, as a torn PCIe write would (test hook: the check must
  *                      refuse them and read again; mmc_run_stats.torn_records counts them)
+ *   "local_stage"      0 = mmc_batch_local_order reads the O positions from device memory even where a
+ *                      replica's fit in LDS (default 1; the path of systems too large to stage,
+ *                      same results: a test hook)
  *   "zero_copy_moves"  1 = the kernel reads proposals from pinned host memory instead of an
  *                      H2D copy on the stream (lower latency for one replica, default 0)
  *   "device_moves"     1 = mmc_batch_run / mmc_batch_run_chains generate the trial moves on the
@@ -722,6 +725,46 @@ int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in,
 int32_t mmc_batch_rdf_sites(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica,
                             uint64_t *hist);
 int32_t mmc_batch_dipoles(mmc_batch *b, double *dip /* [R][3] */);
+
+/* ---- Local order: hydrogen bonds and the tetrahedral order parameter of 3-site molecules ------
+ * The first coordination shell of every molecule of every replica in one read-only pass.  Slot 0 of
+ * a molecule is the heavy atom ("O"), slots 1 and 2 are the hydrogens: the order of every water deck
+ * here.  The reference has no such analysis; the arithmetic is defined here and restated in numpy by
+ * tests/local_order_ref.py.
+ *   d(x, y) is vector1D (Ewald/boundaries.jl; csrc/mmc_device.hpp): y - x, moved by one box when
+ *   |d| >= L / 2, per component, with the replica's own box.  Every r^2 and every dot product is
+ *   (x x' + y y') + z z' in unfused fp64.
+ *   - Neighbours.  For molecule i every other molecule j has r2_ij = r^2 of d(O_i, O_j).  The four
+ *     nearest are the four smallest under the key (bit pattern of r2_ij, then j): ties go to the
+ *     lower index; rank 0 is the nearest.
+ *   - Tetrahedral order (Errington and Debenedetti).  With d_a = d(O_i, O_a) for ranks a, b:
+ *     c_ab = (d_a . d_b) / sqrt(r2_a r2_b); s = the sum of (c_ab + 1/3)^2 over (0,1) (0,2) (0,3)
+ *     (1,2) (1,3) (2,3), added in that order; q_i = 1 - 0.375 s.  A molecule with a coincident
+ *     neighbour (r2 == 0) has q_i = NaN, is counted in no bin and not in q_sum.  Its bin is
+ *     k = min(q_bins - 1, max(0, (int)floor((q_i + 3.0) (q_bins / 4.0)))) over [-3, 1].
+ *   - Hydrogen bonds (Luzar-Chandler geometry).  Donor i through its hydrogen h in {1, 2} to
+ *     acceptor j != i: r2_ij < r_hb r_hb, and with u = d(O_i, H_i,h), v = d(O_i, O_j), t = u . v:
+ *     t > 0 and t t >= cos_hb cos_hb (|u|^2 |v|^2).  No sqrt, division or trigonometry; pass
+ *     cos_hb = cos(30 deg).  donated_i counts the pairs (h, j) with i the donor, accepted_i the pairs
+ *     (j, h) with i the acceptor, total_i their sum; each of the three is clamped to 8.
+ *   - Outputs, all overwritten, each may be NULL but not all of hb_hist, q_hist and q_sum:
+ *     hb_hist [3][9] (rows donated, accepted, total; molecules over n = 0..8), [R][3][9] with
+ *     per_replica; q_hist [q_bins], [R][q_bins] with per_replica; q_sum [R][2] = (the sum of the
+ *     replica's finite q_i, their number as a double): lane l of the replica's wave adds the
+ *     molecules l, l + 64, ... in that order and the 64 lane sums are added in a fixed order --
+ *     bitwise reproducible, independent of the launch, like mmc_batch_dipoles; nbr_out [R][N][4]
+ *     0-based j by rank; q_out [R][N]; hb_out [R][N][2] donated, accepted.  The counts do not depend
+ *     on the grid or option "wave_wgs".
+ * Both box modes and either Coulomb style: the call reads coordinates only, and is read-only as
+ * mmc_batch_rdf_sites is (coordinates, S(k), flags, step counters and random streams are not
+ * touched; S(k) need not be fresh).  Preconditions as mmc_batch_rdf_sites: no proposals
+ * outstanding, no volume trial in flight, no run that failed half-way (MMC_ERR_STATE).
+ * MMC_ERR_ARG: r_hb not finite, <= 0 or above half of the smallest box; cos_hb outside (0, 1];
+ * q_bins outside 1..4096; hb_hist, q_hist and q_sum all NULL.  MMC_ERR_UNSUPPORTED: fewer than 5
+ * molecules (no four neighbours) or more than 2^21.  On any error every output is left untouched. */
+int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t q_bins,
+                              int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist,
+                              double *q_sum, int32_t *nbr_out, double *q_out, uint8_t *hb_out);
 
 /* ---- the one collective of a sharded run: RCCL over xGMI ---------------------
  * Replicas shard over GPUs with no data-path collective; what is reduced, once per block, is a

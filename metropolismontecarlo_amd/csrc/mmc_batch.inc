@@ -104,6 +104,8 @@ struct mmc_batch {
                                 // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
     void *struct_buf = nullptr; // device scratch of mmc_batch_rdf_sites / mmc_batch_dipoles (mmc_struct.inc), grown on demand
     size_t struct_bytes = 0;
+    int local_stage = 1;        // mmc_batch_local_order copies a replica's O positions to LDS where they fit
+                                // (option "local_stage" = 0: never, the path of systems too large for it)
 
     const MoveRec *dev_moves(int which) const
     {
@@ -331,6 +333,9 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         b->server_stall_ms = (int)value;
     } else if (!strcmp(key, "inject_torn")) {
         b->inject_torn = (int)value;
+    } else if (!strcmp(key, "local_stage")) {
+        MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "local_stage must be 1 (where the positions fit) or 0 (never)");
+        b->local_stage = (int)value;
     } else if (!strcmp(key, "trace_steps")) {
         MMC_REQUIRE(value >= 0 && value * b->sys.R <= (1LL << 26), MMC_ERR_ARG, "trace_steps out of range");
         b->trace_steps = value;

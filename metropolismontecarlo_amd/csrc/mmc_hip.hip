@@ -11,4 +11,5 @@
 #include "mmc_perbox.inc"
 #include "mmc_widom.inc"
 #include "mmc_struct.inc"
+#include "mmc_local.inc"
 #include "mmc_dist.inc"

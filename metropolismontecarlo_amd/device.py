@@ -633,6 +633,38 @@ class Batch:
         check(self._L.mmc_batch_dipoles(self._h, _d(out)))
         return out
 
+    def local_order(self, q_bins=400, r_hb=3.5, theta_deg=30.0, per_replica=False, details=False, out=None):
+        """mmc_batch_local_order: hydrogen bonds (O-O closer than r_hb, H-O...O angle within
+        theta_deg) and the tetrahedral order parameter q of every molecule (slot 0 = O, slots 1, 2
+        = H).  Returns a dict: hb_hist uint64 [3, 9] (rows donated, accepted, total; molecules with
+        n = 0..8), q_hist uint64 [q_bins] over [-3, 1] -- each [R, ...] with per_replica -- and
+        q_sum [R, 2] (sum of the replica's finite q, their number).  details=True adds nbr int32
+        [R, N, 4] (the four nearest, by rank), q [R, N] and hb uint8 [R, N, 2] (donated, accepted).
+        `out`: a dict of arrays under those names to overwrite instead (each of its shape and
+        dtype, contiguous)."""
+        R, N, nq = self.R, self.n_mol, max(int(q_bins), 0)
+        lead = (R,) if per_replica else ()
+        spec = {"hb_hist": (lead + (3, 9), np.uint64), "q_hist": (lead + (nq,), np.uint64),
+                "q_sum": ((R, 2), np.float64)}
+        if details:
+            spec.update(nbr=((R, N, 4), np.int32), q=((R, N), np.float64), hb=((R, N, 2), np.uint8))
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_local_order(
+            self._h, float(r_hb), float(np.cos(np.deg2rad(float(theta_deg)))), int(q_bins),
+            int(bool(per_replica)), ptr("hb_hist", C.c_uint64), ptr("q_hist", C.c_uint64),
+            ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
+        return res
+
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the
         bookkeeping Loop() keeps in total / averages / trans_moves / rot_moves / totProps."""

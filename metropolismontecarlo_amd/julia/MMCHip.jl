@@ -611,6 +611,31 @@ function dipoles(b::Batch)
     return dip
 end
 
+# ---- local order (include/mmc_hip.h, mmc_batch_local_order) ----------------------------------------
+"""
+    local_order(b; q_bins = 400, r_hb = 3.5, theta_deg = 30.0, per_replica = false)
+
+Hydrogen bonds (O-O closer than `r_hb`, H-O...O angle within `theta_deg`) and the tetrahedral order
+parameter q of every molecule (slot 1 = O, slots 2 and 3 = H) in one read-only pass.  Returns
+`(hb_hist, q_hist, q_sum)`: `hb_hist` a `(9, 3)` UInt64 matrix (columns donated, accepted, total;
+molecules with n = 0..8 bonds), `q_hist` `q_bins` counts over [-3, 1] -- `(9, 3, R)` and
+`(q_bins, R)` with `per_replica` -- and `q_sum` `(2, R)`: the sum of the replica's finite q and their
+number.
+"""
+function local_order(b::Batch; q_bins::Integer = 400, r_hb::Float64 = 3.5, theta_deg::Float64 = 30.0,
+                     per_replica::Bool = false)
+    1 <= q_bins <= 4096 || error("q_bins must be in 1..4096")
+    hb_hist = per_replica ? zeros(UInt64, 9, 3, b.n_replicas) : zeros(UInt64, 9, 3)
+    q_hist = per_replica ? zeros(UInt64, q_bins, b.n_replicas) : zeros(UInt64, q_bins)
+    q_sum = zeros(Float64, 2, b.n_replicas)
+    check(ccall((:mmc_batch_local_order, libmmc), Int32,
+                (Ptr{Cvoid}, Float64, Float64, Int32, Int32, Ptr{UInt64}, Ptr{UInt64}, Ptr{Float64},
+                 Ptr{Int32}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, r_hb, cosd(theta_deg), q_bins, per_replica ? 1 : 0, hb_hist, q_hist, q_sum,
+                C_NULL, C_NULL, C_NULL))
+    return hb_hist, q_hist, q_sum
+end
+
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
 """
     id = dist_unique_id()                       # rank 0; send the 128 bytes to the other ranks

@@ -67,6 +67,38 @@ def dielectric_constant(M, temperature, volume, factor):
     return 1.0 + 4.0 * np.pi * float(factor) * fluct / (3.0 * V * float(temperature))
 
 
+# ---- hydrogen bonds and tetrahedral order (include/mmc_hip.h, "Local order") -----------------------
+def hbonds_per_molecule(hb_hist):
+    """Mean number of donated, accepted and total hydrogen bonds per molecule from an
+    mmc_batch_local_order histogram ([..., 3, 9]: molecules with n = 0..8 bonds; 8 stands for 8 or
+    more).  Returns [..., 3]."""
+    h = np.asarray(hb_hist, dtype=float)
+    if h.shape[-2:] != (3, 9):
+        raise ValueError("hb_hist must be [..., 3, 9]")
+    return (h * np.arange(9.0)).sum(-1) / h.sum(-1)
+
+
+def tetrahedral_mean(q_sum):
+    """<q> from mmc_batch_local_order's q_sum ([..., 2]: sum of the finite q_i, their number): per
+    replica for [R, 2] (NaN for a replica with no finite q_i).  Average the replicas' values, or
+    pass q_sum.sum(0) for the mean over all molecules."""
+    s = np.asarray(q_sum, dtype=float)
+    if s.shape[-1] != 2:
+        raise ValueError("q_sum must be [..., 2]")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s[..., 0] / s[..., 1]
+
+
+def normalize_q_hist(q_hist):
+    """P(q) as a density over [-3, 1] from counts [..., q_bins]: returns (q at the bin centres,
+    density), the density integrating to 1 over the bins (bin width 4 / q_bins)."""
+    h = np.asarray(q_hist, dtype=float)
+    nb = h.shape[-1]
+    dq = 4.0 / nb
+    centres = -3.0 + (np.arange(nb) + 0.5) * dq
+    return centres, h / (h.sum(-1, keepdims=True) * dq)
+
+
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
 MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2
 
