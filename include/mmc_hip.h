@@ -766,6 +766,59 @@ int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t 
                               int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist,
                               double *q_sum, int32_t *nbr_out, double *q_out, uint8_t *hb_out);
 
+/* ---- Virtual volume moves: the pressure of every replica in one read-only pass -----------------
+ * The volume-perturbation estimator (Eppenga and Frenkel; Harismiadis, Vorholz and Panagiotopoulos)
+ *   beta P = ln < (V'/V)^N exp(-beta dU) > / dV
+ * with dU what the NPT move of this library (Ewald/volumeChange.jl:59-147) would see: the change of
+ * potential(..., "ewald") under its own rescale.  n_scale test boxes (1..8) per call, all evaluated
+ * from one load of every replica's coordinates; nothing in the batch is written.
+ *   - Test box k: L_k = scale[k] L and kappa_k = alpha / L_k with alpha = kappa L of the batch
+ *     (Ewald/main.jl:290-291, the rule of mmc_batch_run_npt).
+ *   - Test configuration: k_rescale's arithmetic (volumeChange.jl:62-80) on a copy: per COM
+ *     component new = old * f and d = new - old, every atom of the molecule atom + d, f = scale[k],
+ *     unfused fp64.
+ *   - Energy: U_k = potential(..., "ewald") (Ewald/energy.jl:946-1032) of that configuration in box
+ *     L_k -- LJ (Ewald/energy.jl:209-290) and EwaldReal (Ewald/ewalds.jl:293-376) behind the COM gate
+ *     with the minimum image of L_k and the erfc table of kappa_k, RecipLong (Ewald/ewalds.jl:538-604)
+ *     with the k-vector weights of PrepareEwaldVariables at (kappa_k, L_k) (Ewald/ewalds.jl:45-103) over
+ *     the batch's k list, EwaldSelf at kappa_k (Ewald/ewalds.jl:829-833) -- in four parts
+ *     (LJ, real, recip, self), each in mmc_batch_potential_ewald's normalisation.
+ *   - U_0: the same evaluation at f = 1 (L_0 = 1.0 L, kappa_0 = alpha / L_0), by the same kernels in
+ *     the same call.
+ *   - du_out[r][k][0..3] = (dLJ, dreal, drecip, dself), each part of U_k minus that part of U_0;
+ *     base_out[r][0..3] = the four parts of U_0; dU = ((dLJ + dreal) + drecip) + dself.  A scale of
+ *     exactly 1.0 gives four zeros and dU == 0.0 bit for bit.
+ *   - Weight: w = exp(-dU / T + N ln(scale^3)), N the number of molecules, scale^3 = (s s) s: the
+ *     acceptance test of volumeChange.jl:129-130 at P = 0.  boltz_sum[r][k] += w.
+ *   - Order of summation.  A replica's pair terms are summed per tile pair (64 x 64 molecules, tiles
+ *     I <= J in row-major order) by a fixed tree over the workgroup's 256 threads, the tile pairs then
+ *     in index order; S(k) per (kx, ky) column lane l adding atoms l, l + 64, ... and the 64 lanes by
+ *     a fixed tree; the reciprocal energy thread t adding k = t, t + 1024, ..., lanes by the same
+ *     tree, the 16 waves in index order.  Parts, differences, exp and the accumulation are the
+ *     host's, in fp64, replica by replica, k = 0 .. n_scale - 1.  None of it depends on the grid or on
+ *     option "wave_wgs": results are bitwise reproducible.
+ *   - Overlap: an atom pair with r^2 < 0.5 and opposite charges inside the COM gate (ewalds.jl:359),
+ *     as mmc_batch_potential_ewald reports it with per-replica boxes.  A replica that overlaps at
+ *     test box k, or whose dU is not finite, has weight 0 there and n_overlap[r][k] += 1; an overlap
+ *     at f = 1 does so for every k of the replica.  Where an overlap decides, the real part reported
+ *     (du_out[r][k][1], base_out[r][1]) is +inf, as that call's energy is.
+ *   - Read-only: coordinates, S(k), cfac and tables of the batch, flags, step counters and random
+ *     streams are not touched; a chain with these calls interleaved is bit-identical to one without.
+ *     S(k) need not be fresh.
+ * MMC_ERR_STATE as mmc_batch_potential_ewald: proposals outstanding, a volume trial in flight.
+ * MMC_ERR_ARG: n_scale outside 1..8; scale NULL; a scale not finite or <= 0; L_k < 2 r_cut;
+ * temperature <= 0 or not finite; all four outputs NULL.  MMC_ERR_UNSUPPORTED, nothing computed:
+ * per-replica boxes (mmc_batch_set_boxes); Wolf style; a system the table kernels refuse (not
+ * identical 3-atom molecules); (kappa_k, r_cut) outside the erfc table's domain at the smallest L_k
+ * (kappa <= 0.5 and kappa sqrt(r_cut^2 + 100) <= 4); a replica whose atoms' phases do not fit one
+ * workgroup's LDS (56 bytes per atom: about 2800 atoms).  On any error every output is untouched. */
+int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *scale /* [K] */,
+                                 double temperature,
+                                 double *boltz_sum  /* [R][K] in/out, may be NULL */,
+                                 int64_t *n_overlap /* [R][K] in/out, may be NULL */,
+                                 double *du_out     /* [R][K][4] may be NULL */,
+                                 double *base_out   /* [R][4]    may be NULL */);
+
 /* ---- the one collective of a sharded run: RCCL over xGMI ---------------------
  * Replicas shard over GPUs with no data-path collective; what is reduced, once per block, is a
  * handful of observables (sums of energies and acceptance counters, the maximum of the elapsed

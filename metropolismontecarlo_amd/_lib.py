@@ -187,6 +187,7 @@ SIGNATURES = {
     "mmc_batch_dipoles": [_vp, _dp],
     "mmc_batch_local_order": [_vp, _d, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                               _dp, _i32p, _dp, C.POINTER(C.c_uint8)],
+    "mmc_batch_volume_perturb": [_vp, C.c_int32, _dp, _d, _dp, _i64p, _dp, _dp],
     "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, C.c_int32, C.POINTER(RunStats)],
     "mmc_chain_block_line": [_vp, _i64, _i64, _d, _d, C.c_char_p, _i64],
     "mmc_dist_unique_id": [C.c_char_p],                      # uint8_t[128]

@@ -12,4 +12,5 @@
 #include "mmc_widom.inc"
 #include "mmc_struct.inc"
 #include "mmc_local.inc"
+#include "mmc_vperturb.inc"
 #include "mmc_dist.inc"

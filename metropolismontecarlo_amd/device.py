@@ -665,6 +665,34 @@ class Batch:
             ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
         return res
 
+    def volume_perturb(self, temperature, scales=None, dv=None, boltz_sum=None, n_overlap=None, details=False):
+        """mmc_batch_volume_perturb: virtual volume moves of every replica, read-only.  Test boxes
+        L_k = scales[k] L (1..8 of them), or volume changes dv (A^3) converted by
+        ((V + dv) / V) ** (1 / 3) (volumeChange.jl:60).  boltz_sum float64 (R, K) and n_overlap int64
+        (R, K) accumulate w = exp(-dU / T + N ln(scale^3)) and the weights forced to 0 (new zero
+        arrays when None).  Returns (boltz_sum, n_overlap), and with details=True also du (R, K, 4) =
+        (dLJ, dreal, drecip, dself) and base (R, 4), the parts of the energy at f = 1
+        (observables.pressure_from_volume_perturbation turns the sums into a pressure)."""
+        if (scales is None) == (dv is None):
+            raise ValueError("give either scales or dv")
+        if scales is None:
+            v = self.box ** 3
+            sc = np.array([((v + float(x)) / v) ** (1.0 / 3.0) for x in np.atleast_1d(dv)])
+        else:
+            sc = _f64(np.atleast_1d(scales)).ravel()
+        K = sc.shape[0]
+        bs = np.zeros((self.R, K)) if boltz_sum is None else boltz_sum
+        no = np.zeros((self.R, K), dtype=np.int64) if n_overlap is None else n_overlap
+        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (self.R, K)
+                and bs.flags.c_contiguous and isinstance(no, np.ndarray) and no.dtype == np.int64
+                and no.shape == (self.R, K) and no.flags.c_contiguous):
+            raise ValueError("boltz_sum: float64 (R, K), n_overlap: int64 (R, K), contiguous (updated in place)")
+        du = np.zeros((self.R, K, 4)) if details else None
+        base = np.zeros((self.R, 4)) if details else None
+        check(self._L.mmc_batch_volume_perturb(self._h, K, _d(sc), float(temperature), _d(bs), _i(no),
+                                               _d(du) if details else None, _d(base) if details else None))
+        return (bs, no, du, base) if details else (bs, no)
+
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the
         bookkeeping Loop() keeps in total / averages / trans_moves / rot_moves / totProps."""

@@ -636,6 +636,27 @@ function local_order(b::Batch; q_bins::Integer = 400, r_hb::Float64 = 3.5, theta
     return hb_hist, q_hist, q_sum
 end
 
+# ---- virtual volume moves (include/mmc_hip.h, mmc_batch_volume_perturb) ---------------------------
+"""
+    volume_perturb!(b, scales, temperature, boltz_sum, n_overlap)
+
+Virtual volume moves of every replica, read-only: for each test box `L_k = scales[k] L` (1 to 8 of
+them; `kappa_k = alpha / L_k`) the change dU of potential(..., "ewald") (energy.jl:946-1032) under
+the NPT move's own rescale (volumeChange.jl:62-80), `boltz_sum[k, r] += exp(-dU / T + N log(scale^3))`
+and `n_overlap[k, r] +=` the weights forced to 0; both are `(K, R)` matrices (column r = row r of
+the C layout).  beta P = log(mean w) / dV.
+"""
+function volume_perturb!(b::Batch, scales::Vector{Float64}, temperature::Float64,
+                         boltz_sum::Matrix{Float64}, n_overlap::Matrix{Int64})
+    K = length(scales)
+    1 <= K <= 8 || error("1 to 8 scales")
+    size(boltz_sum) == (K, b.n_replicas) && size(n_overlap) == (K, b.n_replicas) || error("sums are (K, R)")
+    check(ccall((:mmc_batch_volume_perturb, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, K, scales, temperature, boltz_sum, n_overlap, C_NULL, C_NULL))
+    return boltz_sum, n_overlap
+end
+
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
 """
     id = dist_unique_id()                       # rank 0; send the 128 bytes to the other ranks

@@ -167,3 +167,29 @@ def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
                 out[j, 3 * a + d] = com[d] + ((R[d, 0] * off[a, 0] + R[d, 1] * off[a, 1]) + R[d, 2] * off[a, 2])
         out[j, 9:] = com
     return out
+
+
+# ---- virtual volume moves (include/mmc_hip.h, mmc_batch_volume_perturb) ----------------------------
+def pressure_from_volume_perturbation(boltz_sum, n_calls, dv, temperature):
+    """P = T ln(<w>) / dv in K / A^3 from mmc_batch_volume_perturb's sums: boltz_sum [R, K] (or [K])
+    of w = (V'/V)^N exp(-dU / T) over n_calls calls, dv [K] the volume change of each test box in
+    A^3 (V' - V; none zero).  Returns a dict: "per_replica" [R, K], the estimator of each replica's
+    own mean; "pooled" [K], that of the mean over all replicas and calls (the estimator is the log
+    of a mean, so this is not the mean of the replicas' values); and for every dv > 0 whose -dv is
+    among the test boxes the two-sided average (P(+dv) + P(-dv)) / 2, whose leading error in dv
+    cancels: "two_sided_dv" [P], "two_sided_per_replica" [R, P], "two_sided_pooled" [P]."""
+    bs = np.atleast_2d(np.asarray(boltz_sum, dtype=float))
+    dv = np.atleast_1d(np.asarray(dv, dtype=float))
+    if bs.shape[1] != dv.shape[0] or np.any(dv == 0.0):
+        raise ValueError("boltz_sum must be [R, K] with one non-zero dv per column")
+    n, T = float(n_calls), float(temperature)
+    with np.errstate(divide="ignore"):
+        per = np.log(bs / n) * T / dv
+        pooled = np.log(bs.sum(0) / (n * bs.shape[0])) * T / dv
+    pairs = [(k, int(np.flatnonzero(dv == -dv[k])[0])) for k in range(dv.shape[0])
+             if dv[k] > 0 and np.any(dv == -dv[k])]
+    return {"per_replica": per, "pooled": pooled,
+            "two_sided_dv": np.array([dv[k] for k, _ in pairs]),
+            "two_sided_per_replica": np.stack([(per[:, k] + per[:, m]) / 2 for k, m in pairs], axis=1)
+            if pairs else np.zeros((bs.shape[0], 0)),
+            "two_sided_pooled": np.array([(pooled[k] + pooled[m]) / 2 for k, m in pairs])}
