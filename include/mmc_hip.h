@@ -687,6 +687,67 @@ int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t d
 int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in, double temperature,
                            double *boltz_sum, int64_t *n_overlap, double *du_out, uint8_t *ovl_out);
 
+/* ---- Deletion energies: binding-energy histograms and the deletion half of BAR ------------------
+ * The mirror image of mmc_batch_widom: the energy each EXISTING molecule is bound with.  The
+ * reference has no deletion code; the deletion energy of molecule i of a replica's committed
+ * configuration is DEFINED through its own total energy, potential(..., "ewald")
+ * (Ewald/energy.jl:946-1032), as what that total loses when the molecule is taken out,
+ *   dU = (d_lj + d_real) + d_recip
+ *   d_lj    = LJ_poly_dU(i)                         energy.jl:209-290 (COM gate, eps > 0.001)
+ *   d_real  = EwaldShort(i)                         ewalds.jl:892-910 -> EwaldReal :293-376, the
+ *             factor applied (:905); 0, and the overlap flag set, when an atom pair of opposite
+ *             charges has r^2 < 0.5 (:359-360)
+ *   d_recip = factor sum_k cfac_k (2 Re(conj(S_k) s_k) - |s_k|^2)
+ *           - factor kappa / sqrt(pi) sum_a q_a^2
+ *             == RecipLong(N) - RecipLong(N \ i) (:538-604) + EwaldSelf(N) - EwaldSelf(N \ i) (:829-833)
+ * S_k: the replica's committed structure factor over the batch's half-space k list (doubled
+ * weights), molecule i included -- built by mmc_batch_recip_long and kept by the moves since, as
+ * for mmc_batch_widom; s_k: molecule i's own, by the reference's phase recurrence.  Without
+ * overlaps this is potential(N) - potential(N \ i) up to summation order, and term by term it is
+ * what mmc_batch_widom_at returns for molecule i's coordinates inserted into the N - 1 others.  The
+ * constant intramolecular Ewald term is absent, as in mmc_batch_widom
+ * (observables.ewald_intra_energy).
+ *   - Selection: sel [n_sel] 0-based molecules, the same for every replica; duplicates are allowed
+ *     and evaluated twice.  sel == NULL: all N molecules in index order (n_sel is ignored).  Below,
+ *     n = n_sel, or N when sel is NULL.
+ *   - Flags (ovl_out [R][n]): bit 0 = overlap, bit 1 = dU is NaN or +-inf (an atom exactly on
+ *     another) -- mmc_batch_widom's bits.  A flagged molecule enters no bin, no esum and no
+ *     boltz_sum; it counts in n_flagged[r] (+=).
+ *   - Histogram of dU over [u_lo, u_hi) in n_bins bins plus two outer counters: with
+ *     s = n_bins / (u_hi - u_lo) in fp64 and k = floor((dU - u_lo) * s), unfused, dU < u_lo goes to
+ *     slot 0, dU >= u_hi or k >= n_bins to slot n_bins + 1, everything else to slot k + 1.
+ *     per_replica == 0: hist [n_bins + 2], summed over the replicas; else hist [R][n_bins + 2].
+ *     Overwritten.  64-bit integer counts, exact and independent of the launch
+ *     (observables.energy_bins is the same rule in numpy, for mmc_batch_widom's du_out).
+ *   - esum [R][4], overwritten: the sums of d_lj, d_real and d_recip over the replica's unflagged
+ *     selected molecules and their number (as a double).  boltz_sum[r] += sum exp(+dU / T), the
+ *     inverse-Widom sum (T in K, like the energies).  Order: lane l of the replica's wave adds the
+ *     selected entries l, l + 64, ... in that order, the 64 lane sums are added in a fixed order
+ *     (as mmc_batch_dipoles), and boltz_sum's is added to the caller's value last: bitwise
+ *     reproducible, whatever the grid or option "wave_wgs".
+ *   - Sum rules (sel == NULL, no flags): every pair is counted from both of its molecules, and
+ *     potential()'s totals count it once (energy.jl:978-980 and :1001 halve the sums over molecules), so
+ *     esum[r][0] == 2 lj and esum[r][1] == 2 real of mmc_batch_potential_ewald's totals of the
+ *     replica, up to summation order; esum[r][3] == N.
+ *   - du_out [R][n][3] = (d_lj, d_real, d_recip).  Each output may be NULL, but not all of them.
+ *   - Read-only: coordinates, S(k), the chains' flags, step counters and random streams are not
+ *     touched; a chain run with these calls interleaved is bit-identical to one without.
+ * MMC_ERR_STATE as mmc_batch_widom: proposals outstanding, a volume trial in flight, S(k) stale
+ * after Wolf-style moves (call mmc_batch_recip_long), a run that failed half-way.
+ * MMC_ERR_UNSUPPORTED, nothing computed: per-replica boxes (mmc_batch_set_boxes), Wolf style, a
+ * system the table kernels do not take (not identical 3-atom molecules, or a cutoff / kappa
+ * outside the erfc table), fewer than 2 molecules.  MMC_ERR_ARG: temperature <= 0 or not finite;
+ * every output NULL; hist given with n_bins outside 1..4096, u_lo >= u_hi or a bound not finite;
+ * sel given with n_sel < 1 or an index outside 0..N-1.  On any error every output is untouched. */
+int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t *sel, double temperature,
+                           int32_t n_bins, double u_lo, double u_hi, int32_t per_replica,
+                           uint64_t *hist      /* [n_bins + 2] or [R][n_bins + 2]; may be NULL */,
+                           double *esum        /* [R][4] may be NULL */,
+                           double *boltz_sum   /* [R] in/out, may be NULL */,
+                           int64_t *n_flagged  /* [R] in/out, may be NULL */,
+                           double *du_out      /* [R][n][3] may be NULL */,
+                           uint8_t *ovl_out    /* [R][n] may be NULL */);
+
 /* ---- Structure observables: site-site pair histograms and total dipole moments ----------------
  * mmc_batch_rdf_sites: what mmc_batch_rdf computes for one site, for all six unordered atom-slot
  * pairs of 3-site molecules in one pass, per replica if wanted, in either box mode.  Kept from

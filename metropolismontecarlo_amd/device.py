@@ -565,6 +565,51 @@ class Batch:
             raise ValueError("boltz_sum: float64 (R,), n_overlap: int64 (R,), contiguous (updated in place)")
         return bs, no
 
+    def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
+                 n_flagged=None, details=False):
+        """mmc_batch_deletion: the deletion (binding) energy dU_i = potential(N) - potential(N
+        without i) of the molecules `sel` (0-based indices shared by all replicas, duplicates
+        allowed; None = all N) of every replica, read-only.  bins = (n_bins, u_lo, u_hi) asks for
+        the histogram of dU (observables.energy_bins' rule), summed over the replicas or one row
+        each with per_replica.  boltz_sum float64 (R,) and n_flagged int64 (R,) accumulate
+        sum exp(+dU / T) and the flagged molecules (new zero arrays when None).  Returns a dict:
+        esum (R, 4) = sums of d_lj, d_real, d_recip and the number summed, boltz_sum, n_flagged,
+        hist uint64 (n_bins + 2,) or (R, n_bins + 2) when bins is given, and with details=True du
+        (R, n, 3) and ovl uint8 (R, n) (bit 0 overlap, bit 1 non-finite dU)."""
+        R = self.R
+        if sel is None:
+            sel_a, n = None, self.n_mol
+        else:
+            sel_a = np.ascontiguousarray(sel)
+            if sel_a.ndim != 1 or not np.issubdtype(sel_a.dtype, np.integer):
+                raise ValueError("sel: a 1-d array of integer molecule indices (0-based)")
+            if sel_a.size and (sel_a.min() < -2 ** 31 or sel_a.max() >= 2 ** 31):
+                raise ValueError("sel: an index does not fit 32 bits")
+            sel_a = np.ascontiguousarray(sel_a, dtype=np.int32)
+            n = sel_a.shape[0]
+        bs = np.zeros(R) if boltz_sum is None else boltz_sum
+        nf = np.zeros(R, dtype=np.int64) if n_flagged is None else n_flagged
+        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (R,)
+                and bs.flags.c_contiguous and isinstance(nf, np.ndarray) and nf.dtype == np.int64
+                and nf.shape == (R,) and nf.flags.c_contiguous):
+            raise ValueError("boltz_sum: float64 (R,), n_flagged: int64 (R,), contiguous (updated in place)")
+        res = {"esum": np.zeros((R, 4)), "boltz_sum": bs, "n_flagged": nf}
+        n_bins, u_lo, u_hi = 0, 0.0, 0.0
+        if bins is not None:
+            n_bins, u_lo, u_hi = int(bins[0]), float(bins[1]), float(bins[2])
+            slots = max(n_bins, 0) + 2   # (an n_bins the library refuses still gets an array to leave alone)
+            res["hist"] = np.zeros((R, slots) if per_replica else (slots,), dtype=np.uint64)
+        if details:
+            res["du"] = np.zeros((R, n, 3))
+            res["ovl"] = np.zeros((R, n), dtype=np.uint8)
+        check(self._L.mmc_batch_deletion(
+            self._h, n, None if sel_a is None else sel_a.ctypes.data_as(C.POINTER(C.c_int32)),
+            float(temperature), n_bins, u_lo, u_hi, int(bool(per_replica)),
+            res["hist"].ctypes.data_as(C.POINTER(C.c_uint64)) if bins is not None else None,
+            _d(res["esum"]), _d(bs), _i(nf), _d(res["du"]) if details else None,
+            _u8(res["ovl"]) if details else None))
+        return res
+
     def get_trace(self, n_steps):
         """(dU[R, n], flags[R, n]) of the first n steps of the last run (option "trace_steps" = n):
         flags bit 0 accepted, bit 1 overlap, bit 2 rotation."""

@@ -587,6 +587,40 @@ function widom_at!(b::Batch, mol_in::Vector{Float64}, n_insert::Integer, tempera
     return boltz_sum, n_overlap
 end
 
+# ---- deletion energies (include/mmc_hip.h, mmc_batch_deletion) -------------------------------------
+"""
+    deletion(b, temperature; sel = nothing, bins = nothing, per_replica = false,
+             boltz_sum = zeros(R), n_flagged = zeros(Int64, R))
+
+The deletion (binding) energy dU_i = potential(N) - potential(N without i) (energy.jl:946-1032) of
+the molecules `sel` (1-based indices shared by all replicas, duplicates allowed; `nothing` = all)
+of every replica, read-only for the chains; the reference has no deletion code.  `bins` =
+`(n_bins, u_lo, u_hi)` asks for the histogram of dU: `n_bins + 2` UInt64 counts (slot 1 below
+`u_lo`, the last at or above `u_hi`), or an `(n_bins + 2, R)` matrix with `per_replica`.  Returns
+`(hist, esum, boltz_sum, n_flagged)`: `esum` a `(4, R)` matrix (sums of d_lj, d_real, d_recip and the
+number summed), `boltz_sum[r] += sum exp(+dU / T)` (inverse Widom), `n_flagged[r] +=` the molecules
+with an overlap or a non-finite dU, which enter no sum and no bin.
+"""
+function deletion(b::Batch, temperature::Float64; sel::Union{Nothing,Vector{<:Integer}} = nothing,
+                  bins::Union{Nothing,Tuple{Int,Float64,Float64}} = nothing, per_replica::Bool = false,
+                  boltz_sum::Vector{Float64} = zeros(Float64, b.n_replicas),
+                  n_flagged::Vector{Int64} = zeros(Int64, b.n_replicas))
+    length(boltz_sum) == b.n_replicas && length(n_flagged) == b.n_replicas || error("one sum per replica")
+    sel0 = sel === nothing ? Int32[] : Int32[i - 1 for i in sel]
+    sel === nothing || !isempty(sel0) || error("sel must not be empty")
+    n_bins, u_lo, u_hi = bins === nothing ? (0, 0.0, 0.0) : bins
+    hist = bins === nothing ? UInt64[] :
+           per_replica ? zeros(UInt64, n_bins + 2, b.n_replicas) : zeros(UInt64, n_bins + 2)
+    esum = zeros(Float64, 4, b.n_replicas)
+    check(ccall((:mmc_batch_deletion, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int32}, Float64, Int32, Float64, Float64, Int32, Ptr{UInt64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, length(sel0), sel === nothing ? C_NULL : sel0, temperature, n_bins, u_lo, u_hi,
+                per_replica ? 1 : 0, bins === nothing ? C_NULL : hist, esum, boltz_sum, n_flagged,
+                C_NULL, C_NULL))
+    return hist, esum, boltz_sum, n_flagged
+end
+
 # ---- structure observables (include/mmc_hip.h, mmc_batch_rdf_sites / mmc_batch_dipoles) ----------
 """
     rdf_sites(b, numbins; r_max = 0.0, per_replica = false)

@@ -169,6 +169,99 @@ def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
     return out
 
 
+# ---- deletion energies, overlapping distributions and BAR (include/mmc_hip.h, mmc_batch_deletion) ----
+def energy_bins(du, n_bins, u_lo, u_hi):
+    """mmc_batch_deletion's binning rule in numpy, for histogramming mmc_batch_widom's insertion
+    energies (du_out summed to dU) on the same grid: uint64 [n_bins + 2].  With
+    s = n_bins / (u_hi - u_lo) and k = floor((dU - u_lo) * s): dU < u_lo goes to slot 0, dU >= u_hi
+    or k >= n_bins to slot n_bins + 1, everything else to slot k + 1.  NaN is counted nowhere
+    (+-inf in the outer slots)."""
+    n_bins = int(n_bins)
+    lo, hi = np.float64(u_lo), np.float64(u_hi)
+    if n_bins < 1 or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("n_bins >= 1 and finite u_lo < u_hi")
+    x = np.asarray(du, dtype=np.float64).ravel()
+    x = x[~np.isnan(x)]
+    s = np.float64(n_bins) / (hi - lo)
+    with np.errstate(invalid="ignore", over="ignore"):
+        k = np.floor((x - lo) * s)
+    k = np.clip(np.where(np.isnan(k), 0.0, k), -1.0, float(n_bins)).astype(np.int64)
+    slot = np.where(x < lo, 0, np.where((x >= hi) | (k >= n_bins), n_bins + 1, k + 1))
+    return np.bincount(slot, minlength=n_bins + 2).astype(np.uint64)
+
+
+def overlap_curves(hist_ins, hist_del, n_bins, u_lo, u_hi, temperature):
+    """The overlapping-distribution (Shing-Gubbins) check from two histograms on one grid
+    (energy_bins / mmc_batch_deletion, [n_bins + 2] each): f(u), the density of the insertion
+    energies, and g(u), that of the deletion energies, obey g(u) = f(u) exp(-(u - mu_ex) / T), so
+    ln g - ln f + u / T is the constant mu_ex / T wherever both are populated.  Each density is
+    normalised by ALL of its histogram's counts, the outer slots included (add the insertions of
+    weight 0 to slot n_bins + 1 before calling: they are insertions of infinite energy).  Returns
+    (centres [n_bins], ln f, ln g, ln g - ln f + centres / T); an empty bin gives -inf and NaN."""
+    n_bins = int(n_bins)
+    hi_, hd_ = np.asarray(hist_ins, dtype=np.float64), np.asarray(hist_del, dtype=np.float64)
+    if hi_.shape != (n_bins + 2,) or hd_.shape != (n_bins + 2,):
+        raise ValueError("both histograms must be [n_bins + 2]")
+    w = (float(u_hi) - float(u_lo)) / n_bins
+    centres = float(u_lo) + (np.arange(n_bins) + 0.5) * w
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ln_f = np.log(hi_[1:-1] / (hi_.sum() * w))
+        ln_g = np.log(hd_[1:-1] / (hd_.sum() * w))
+        const = np.where(np.isfinite(ln_f) & np.isfinite(ln_g), ln_g - ln_f + centres / float(temperature), np.nan)
+    return centres, ln_f, ln_g, const
+
+
+def bennett_mu_ex(u_ins, u_del, temperature, w_ins=None, w_del=None):
+    """mu_ex (K) and its standard error by Bennett's acceptance ratio from insertion energies
+    u_ins = U(N+1) - U(N) (mmc_batch_widom's du_out) and deletion energies u_del = U(N) - U(N-1)
+    (mmc_batch_deletion), raw samples or bin centres with weights (counts) w_ins / w_del.  Both are
+    sampled in the N-molecule system: the insertions are the forward work of N -> N+1, the
+    deletions stand for the reverse work of N+1 -> N.  Identifying the N -> N-1 pair with the
+    N+1 -> N pair is exact in the thermodynamic limit and costs O(1/N) in mu_ex at finite N (the
+    density differs by 1/N).  Flagged (overlapping) insertions belong in u_ins with a large finite
+    energy or in w_ins as counts at the top; they do not bias the estimate, dropping them does.
+    Solves, by bisection on the monotone difference of the two sides,
+      sum_ins fermi((u - mu) / T + M) = sum_del fermi(-(u - mu) / T - M),   M = ln(n_ins / n_del),
+    fermi(x) = 1 / (1 + e^x); the variance of mu / T is Bennett's (J. Comput. Phys. 22, 245, 1976,
+    in the form of Shirts et al., Phys. Rev. Lett. 91, 140601): 1 / sum_all fermi(x) fermi(-x)
+    - 1 / n_ins - 1 / n_del, x = (u - mu) / T + M over both sets, for independent samples."""
+    T = float(temperature)
+    ui, ud = np.asarray(u_ins, dtype=np.float64).ravel(), np.asarray(u_del, dtype=np.float64).ravel()
+    wi = np.ones_like(ui) if w_ins is None else np.asarray(w_ins, dtype=np.float64).ravel()
+    wd = np.ones_like(ud) if w_del is None else np.asarray(w_del, dtype=np.float64).ravel()
+    if wi.shape != ui.shape or wd.shape != ud.shape:
+        raise ValueError("weights must match their energies")
+    keep_i, keep_d = wi > 0, wd > 0
+    ui, wi, ud, wd = ui[keep_i], wi[keep_i], ud[keep_d], wd[keep_d]
+    if not (ui.size and ud.size and np.all(np.isfinite(ui)) and np.all(np.isfinite(ud)) and T > 0):
+        raise ValueError("needs finite energies on both sides and T > 0")
+    ni, nd = wi.sum(), wd.sum()
+    M = np.log(ni / nd)
+
+    def fermi(x):
+        return 0.5 * (1.0 - np.tanh(0.5 * x))   # 1 / (1 + e^x) without overflow
+
+    def diff(mu):
+        return (wi * fermi((ui - mu) / T + M)).sum() - (wd * fermi(-(ud - mu) / T - M)).sum()
+    pad = T * (50.0 + abs(M))
+    lo, hi = min(ui.min(), ud.min()) - pad, max(ui.max(), ud.max()) + pad
+    if not (diff(lo) < 0.0 < diff(hi)):
+        raise ValueError("the two sets do not bracket a solution")
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if diff(mid) < 0.0:
+            lo = mid
+        else:
+            hi = mid
+    mu = 0.5 * (lo + hi)
+    xi, xd = (ui - mu) / T + M, (ud - mu) / T + M
+    s = (wi * fermi(xi) * fermi(-xi)).sum() + (wd * fermi(xd) * fermi(-xd)).sum()
+    var = 1.0 / s - 1.0 / ni - 1.0 / nd
+    return float(mu), float(T * np.sqrt(max(var, 0.0)))
+
+
 # ---- virtual volume moves (include/mmc_hip.h, mmc_batch_volume_perturb) ----------------------------
 def pressure_from_volume_perturbation(boltz_sum, n_calls, dv, temperature):
     """P = T ln(<w>) / dv in K / A^3 from mmc_batch_volume_perturb's sums: boltz_sum [R, K] (or [K])
