@@ -420,12 +420,16 @@ class Batch:
 
     def volume_change(self, new_box, new_kappa):
         check(self._L.mmc_batch_volume_change(self._h, float(new_box), float(new_kappa)))
+        self.box, self.kappa = float(new_box), float(new_kappa)
 
     def volume_trial(self, new_box, new_kappa):
         """mmc_batch_volume_trial (a batch of ONE replica): device-side snapshot, rescale, new
-        tables, total energy at the new volume.  Follow with volume_accept() or volume_reject()."""
+        tables, total energy at the new volume.  Follow with volume_accept() or volume_reject().
+        self.box and self.kappa are the trial's until a reject puts the old ones back."""
         t = Totals()
         check(self._L.mmc_batch_volume_trial(self._h, float(new_box), float(new_kappa), C.byref(t)))
+        self._before_trial = (self.box, self.kappa)
+        self.box, self.kappa = float(new_box), float(new_kappa)
         return t.asdict()
 
     def volume_accept(self):
@@ -433,6 +437,7 @@ class Batch:
 
     def volume_reject(self):
         check(self._L.mmc_batch_volume_reject(self._h))
+        self.box, self.kappa = self._before_trial
 
     def run_npt(self, n_sweeps, temperature, pressure, vmax, dr_max, dphi_max, seed, energy,
                 moves_per_sweep=0, alpha=5.6, n_parts=0, n_threads=1, replica0=0):
@@ -444,7 +449,13 @@ class Batch:
         q = NptParams(float(pressure), float(vmax), float(alpha), int(n_sweeps), int(moves_per_sweep))
         st, ns = RunStats(), NptStats()
         e = np.array([float(energy)])
-        check(self._L.mmc_batch_run_npt(self._h, C.byref(p), C.byref(q), _d(e), C.byref(st), C.byref(ns)))
+        try:
+            check(self._L.mmc_batch_run_npt(self._h, C.byref(p), C.byref(q), _d(e), C.byref(st), C.byref(ns)))
+        finally:
+            # every accepted volume move set kappa = alpha / L_new (also before an error part-way)
+            box = float(self.get_boxes()[0])
+            if box != self.box:
+                self.box, self.kappa = box, float(alpha) / box
         return float(e[0]), st.asdict(), ns.asdict()
 
     def set_boxes(self, boxes, alpha=5.6):
