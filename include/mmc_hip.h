@@ -748,6 +748,81 @@ int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t *sel, doub
                            double *du_out      /* [R][n][3] may be NULL */,
                            uint8_t *ovl_out    /* [R][n] may be NULL */);
 
+/* ---- Forces and torques on every molecule of every replica in one read-only pass ----------------
+ * The reference has no forces beyond `fab` in LJ_poly_dU (Ewald/energy.jl:279-281).  Forces are
+ * DEFINED as minus the gradient of its own total, potential(..., "ewald") (Ewald/energy.jl:946-1032),
+ * at fixed neighbour sets: the COM gates r_ij^2 < r_cut^2 (energy.jl:254, ewalds.jl:340) and the atom
+ * slack + 100 (energy.jl:270, ewalds.jl:362) decide which pairs count and are not differentiated --
+ * exactly what a finite difference of the reference gives when atoms move and the stored COM array
+ * does not.  For atom a of molecule i and atom b of a gated molecule j, rab = vector1D(ra, rb)
+ * (boundaries.jl:8-14: b - a, minimum image) and r^2 = (x x + y y) + z z, unfused as everywhere:
+ *   Lennard-Jones (energy.jl:270-281; eps > 0.001 and r^2 < r_cut^2 + 100), s2 = sigma^2 / r^2,
+ *   s6 = s2^3, s12 = s6^2:
+ *     f_a -= 24 eps (2 s12 - s6) / r^2 * rab
+ *   Real-space Ewald (ewalds.jl:359-367; r^2 < r_cut^2 + 100):
+ *     f_a -= factor q_a q_b (erfc(kappa r) / r + 2 kappa / sqrt(pi) exp(-kappa^2 r^2)) / r^2 * rab
+ *     An atom pair of opposite charges with r^2 < 0.5 (:359-360) sets the overlap flag, as in
+ *     mmc_batch_deletion.
+ *   Reciprocal space (ewalds.jl:538-604; the batch's half-space list, doubled weights cfac_k, integer
+ *   vectors n_k = (kx, ky, kz), k = 2 pi n / L):
+ *     f_a += factor (4 pi / L) q_a sum_k cfac_k n_k Im(conj(S_k) e_{a,k})
+ *     e_{a,k} = exp(i k . r_a) by the reference's phase recurrence, S_k the replica's committed
+ *     structure factor (mmc_batch_recip_long, kept by the moves since).  Molecule i's own atoms are in
+ *     S_k: this includes its interaction with itself that the reference's energy includes; EwaldSelf
+ *     (:829-833) has no gradient.
+ * Per molecule, with d_a = vector1D(COM_i, r_a) and the stored COM the point the library's rotations
+ * turn about:
+ *   F_i    = (f_0 + f_1) + f_2
+ *   tau_i  = sum_a d_a x f_a, atoms in index order
+ *   w_lj,i = the `vir` of LJ_poly_dU(i) in its own normalisation (energy.jl:281, :289):
+ *            (24 / 3) sum_j sum_ab rij . (rab eps (2 s12 - s6) s2), rij = vector1D(COM_i, COM_j) --
+ *            the reference's fab carries s2 = sigma^2 / r^2 where a force has 1 / r^2
+ *   w_real,i = (1 / 3) sum_j rij . sum_ab factor q_a q_b (erfc(kappa r) / r + 2 kappa / sqrt(pi)
+ *            exp(-kappa^2 r^2)) / r^2 * rab: the same form with the real-space Coulomb pair force
+ *   t_i    = tau' I^-1 tau when mass [3] (per atom slot, > 0) is given, I = sum_a m_a (|d_a|^2 1 -
+ *            d_a d_a'), the inverse by cofactors; else 0
+ *   - Selection: as mmc_batch_deletion.  sel [n_sel] 0-based molecules, the same for every replica,
+ *     duplicates allowed; sel == NULL: all N in index order (n_sel is ignored).  n = n_sel, or N.
+ *   - Flags (ovl_out [R][n]): mmc_batch_widom's bits.  Bit 0 = overlap, bit 1 = some output of the
+ *     molecule is not finite (an atom exactly on another, or a singular I: collinear sites).  A
+ *     flagged molecule has zeros in every row, enters no sum and counts in n_flagged[r] (+=).
+ *   - Rows: force_out [R][n][3] = F, torque_out [R][n][3] = tau, vir_out [R][n][3] = (w_lj, w_real,
+ *     t), atom_out [R][n][3][3] = f_a.  Units: K / A, K, K (t: K^2 / (mass unit A^2)).
+ *   - Order of summation within a molecule.  Pair part: lane l of the molecule's wave takes the
+ *     gated-list entries l, l + 64, ... (molecules inside the 16-bit COM prefilter in ascending
+ *     index, flushed when the list fills) and adds, per neighbour, the atom pairs a = 0..2, b = 0..2
+ *     in that order to its sums; the 64 lane sums are added in a fixed order (as mmc_batch_dipoles).
+ *     Reciprocal part: lane l adds k = l, l + 64, ...; same fixed order over the lanes.
+ *     f_a = pair sum + (factor (4 pi / L) q_a) * reciprocal sum.
+ *   - fsum [R][9], overwritten: (number summed, sum F.F, sum tau.tau, sum t, sum F_x, sum F_y,
+ *     sum F_z, sum w_lj, sum w_real) over the replica's unflagged selected molecules, every product
+ *     (x x + y y) + z z unfused.  Lane l of the replica's wave adds the entries l, l + 64, ... in
+ *     that order and the 64 lane sums are added in a fixed order (mmc_batch_deletion's order):
+ *     bitwise reproducible, whatever the grid or option "wave_wgs".
+ *   - Sum rules (sel == NULL, no flags): sum_i F_i vanishes up to rounding (a pair's gate is the same
+ *     from both sides, and the reciprocal forces sum to n_k Im(conj(S_k) S_k) = 0).  Every pair is
+ *     counted from both of its molecules and potential()'s totals halve the sum over molecules
+ *     (energy.jl:978-980), so fsum[r][7] == 2 (virial - coulomb / 3) of mmc_batch_potential_ewald's
+ *     totals of the replica (its `virial` carries a third of every Coulomb term besides, :1001-1032),
+ *     as esum[r][0] == 2 lj for mmc_batch_deletion.
+ *   - Read-only: coordinates, S(k), the chains' flags, step counters and random streams are not
+ *     touched; a chain run with these calls interleaved is bit-identical to one without.
+ * MMC_ERR_STATE as mmc_batch_deletion: proposals outstanding, a volume trial in flight, S(k) stale
+ * after Wolf-style moves (call mmc_batch_recip_long), a run that failed half-way.
+ * MMC_ERR_UNSUPPORTED, nothing computed: per-replica boxes (mmc_batch_set_boxes), Wolf style, a
+ * system the table kernels do not take (not identical 3-atom molecules, or a cutoff / kappa outside
+ * the erfc table), fewer than 2 molecules.  MMC_ERR_ARG: every output NULL; sel given with
+ * n_sel < 1 or an index outside 0..N-1; a mass <= 0 or not finite.  On any error every output is
+ * untouched. */
+int32_t mmc_batch_forces(mmc_batch *b, int32_t n_sel, const int32_t *sel, const double *mass /* [3] or NULL */,
+                         double *force_out  /* [R][n][3]    may be NULL */,
+                         double *torque_out /* [R][n][3]    may be NULL */,
+                         double *vir_out    /* [R][n][3] = (w_lj, w_real, t)  may be NULL */,
+                         double *atom_out   /* [R][n][3][3] f_a  may be NULL */,
+                         double *fsum       /* [R][9]       may be NULL */,
+                         int64_t *n_flagged /* [R] in/out   may be NULL */,
+                         uint8_t *ovl_out   /* [R][n]       may be NULL */);
+
 /* ---- Structure observables: site-site pair histograms and total dipole moments ----------------
  * mmc_batch_rdf_sites: what mmc_batch_rdf computes for one site, for all six unordered atom-slot
  * pairs of 3-site molecules in one pass, per replica if wanted, in either box mode.  Kept from

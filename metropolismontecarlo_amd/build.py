@@ -24,7 +24,8 @@ DEPS = ["mmc_hip.hip", "mmc_wave_unit.inc", "mmc_host.hpp", "mmc_device.hpp", "m
         "mmc_ctx.inc", "mmc_batch.inc", "mmc_engine.inc", "mmc_dist.inc", "mmc_ctxsrv.hpp",
         "mmc_lat.hpp", "mmc_wave_lat.inc", "mmc_potential.hpp", "mmc_perbox.inc", "mmc_widom.hpp",
         "mmc_widom.inc", "mmc_struct.hpp", "mmc_struct.inc", "mmc_local.hpp", "mmc_local.inc",
-        "mmc_vperturb.hpp", "mmc_vperturb.inc", "mmc_deletion.hpp", "mmc_deletion.inc"]
+        "mmc_vperturb.hpp", "mmc_vperturb.inc", "mmc_deletion.hpp", "mmc_deletion.inc",
+        "mmc_forces.hpp", "mmc_forces.inc"]
 
 
 def _stale():

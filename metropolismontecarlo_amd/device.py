@@ -621,6 +621,46 @@ class Batch:
             _u8(res["ovl"]) if details else None))
         return res
 
+    def forces(self, sel=None, mass=None, details=False, n_flagged=None):
+        """mmc_batch_forces: minus the gradient of potential(..., "ewald") at fixed neighbour sets on
+        the atoms of the molecules `sel` (0-based indices shared by all replicas, duplicates allowed;
+        None = all N) of every replica, read-only.  mass (3,) per atom slot asks for t = tau' I^-1 tau
+        (else 0).  n_flagged int64 (R,) accumulates the flagged molecules (a new zero array when
+        None).  Returns a dict: fsum (R, 9) = (number summed, sum F.F, sum tau.tau, sum t, sum F_x,
+        sum F_y, sum F_z, sum w_lj, sum w_real), n_flagged, and with details=True force (R, n, 3),
+        torque (R, n, 3), vir (R, n, 3) = (w_lj, w_real, t), atom (R, n, 3, 3) and ovl uint8 (R, n)
+        (bit 0 overlap, bit 1 a non-finite output; a flagged molecule's rows are zeros)."""
+        R = self.R
+        if sel is None:
+            sel_a, n = None, self.n_mol
+        else:
+            sel_a = np.ascontiguousarray(sel)
+            if sel_a.ndim != 1 or not np.issubdtype(sel_a.dtype, np.integer):
+                raise ValueError("sel: a 1-d array of integer molecule indices (0-based)")
+            if sel_a.size and (sel_a.min() < -2 ** 31 or sel_a.max() >= 2 ** 31):
+                raise ValueError("sel: an index does not fit 32 bits")
+            sel_a = np.ascontiguousarray(sel_a, dtype=np.int32)
+            n = sel_a.shape[0]
+        mass_a = None
+        if mass is not None:
+            mass_a = np.ascontiguousarray(mass, dtype=np.float64)
+            if mass_a.shape != (3,):
+                raise ValueError("mass: three values, one per atom slot")
+        nf = np.zeros(R, dtype=np.int64) if n_flagged is None else n_flagged
+        if not (isinstance(nf, np.ndarray) and nf.dtype == np.int64 and nf.shape == (R,) and nf.flags.c_contiguous):
+            raise ValueError("n_flagged: int64 (R,), contiguous (updated in place)")
+        res = {"fsum": np.zeros((R, 9)), "n_flagged": nf}
+        if details:
+            res.update(force=np.zeros((R, n, 3)), torque=np.zeros((R, n, 3)), vir=np.zeros((R, n, 3)),
+                       atom=np.zeros((R, n, 3, 3)), ovl=np.zeros((R, n), dtype=np.uint8))
+        check(self._L.mmc_batch_forces(
+            self._h, n, None if sel_a is None else sel_a.ctypes.data_as(C.POINTER(C.c_int32)),
+            None if mass_a is None else _d(mass_a),
+            _d(res["force"]) if details else None, _d(res["torque"]) if details else None,
+            _d(res["vir"]) if details else None, _d(res["atom"]) if details else None,
+            _d(res["fsum"]), _i(nf), _u8(res["ovl"]) if details else None))
+        return res
+
     def get_trace(self, n_steps):
         """(dU[R, n], flags[R, n]) of the first n steps of the last run (option "trace_steps" = n):
         flags bit 0 accepted, bit 1 overlap, bit 2 rotation."""

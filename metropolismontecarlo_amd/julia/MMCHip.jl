@@ -621,6 +621,40 @@ function deletion(b::Batch, temperature::Float64; sel::Union{Nothing,Vector{<:In
     return hist, esum, boltz_sum, n_flagged
 end
 
+# ---- forces and torques (include/mmc_hip.h, mmc_batch_forces) --------------------------------------
+"""
+    forces(b; sel = nothing, mass = nothing, details = false, n_flagged = zeros(Int64, R))
+
+Minus the gradient of potential(..., "ewald") (energy.jl:946-1032) at fixed neighbour sets on the
+atoms of the molecules `sel` (1-based indices shared by all replicas, duplicates allowed; `nothing`
+= all) of every replica, read-only for the chains; the reference has no forces.  `mass` (3 values,
+one per atom slot) asks for t = tau' I^-1 tau.  Returns `(fsum, n_flagged)`: `fsum` a `(9, R)` matrix
+(number summed, sum F.F, sum tau.tau, sum t, sum F_x, sum F_y, sum F_z, sum w_lj, sum w_real);
+with `details` also `force`, `torque`, `vir` `(3, n, R)`, `atom` `(3, 3, n, R)` and `ovl` `(n, R)`.
+"""
+function forces(b::Batch; sel::Union{Nothing,Vector{<:Integer}} = nothing,
+                mass::Union{Nothing,Vector{Float64}} = nothing, details::Bool = false,
+                n_flagged::Vector{Int64} = zeros(Int64, b.n_replicas))
+    length(n_flagged) == b.n_replicas || error("one count per replica")
+    mass === nothing || length(mass) == 3 || error("mass: one value per atom slot")
+    sel0 = sel === nothing ? Int32[] : Int32[i - 1 for i in sel]
+    sel === nothing || !isempty(sel0) || error("sel must not be empty")
+    n = sel === nothing ? b.n_mol : length(sel0)
+    fsum = zeros(Float64, 9, b.n_replicas)
+    force = details ? zeros(Float64, 3, n, b.n_replicas) : Float64[]
+    torque = details ? zeros(Float64, 3, n, b.n_replicas) : Float64[]
+    vir = details ? zeros(Float64, 3, n, b.n_replicas) : Float64[]
+    atom = details ? zeros(Float64, 3, 3, n, b.n_replicas) : Float64[]
+    ovl = details ? zeros(UInt8, n, b.n_replicas) : UInt8[]
+    check(ccall((:mmc_batch_forces, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{UInt8}),
+                b.h, length(sel0), sel === nothing ? C_NULL : sel0, mass === nothing ? C_NULL : mass,
+                details ? force : C_NULL, details ? torque : C_NULL, details ? vir : C_NULL,
+                details ? atom : C_NULL, fsum, n_flagged, details ? ovl : C_NULL))
+    return details ? (fsum, n_flagged, force, torque, vir, atom, ovl) : (fsum, n_flagged)
+end
+
 # ---- structure observables (include/mmc_hip.h, mmc_batch_rdf_sites / mmc_batch_dipoles) ----------
 """
     rdf_sites(b, numbins; r_max = 0.0, per_replica = false)

@@ -286,3 +286,64 @@ def pressure_from_volume_perturbation(boltz_sum, n_calls, dv, temperature):
             "two_sided_per_replica": np.stack([(per[:, k] + per[:, m]) / 2 for k, m in pairs], axis=1)
             if pairs else np.zeros((bs.shape[0], 0)),
             "two_sided_pooled": np.array([(pooled[k] + pooled[m]) / 2 for k, m in pairs])}
+
+
+# ---- forces and torques (include/mmc_hip.h, mmc_batch_forces) -----------------------------------------
+# hbar^2 / (k_B amu A^2) in K, from CODATA 2018: hbar = 1.054571817e-34 J s and k_B = 1.380649e-23 J/K
+# (both exact by definition of the SI), amu = 1.66053906660e-27 kg, 1 A^2 = 1e-20 m^2.
+HBAR_J_S = 1.054571817e-34
+KB_J_PER_K = 1.380649e-23
+AMU_KG = 1.66053906660e-27
+HBAR2_OVER_KB_AMU_A2 = HBAR_J_S * HBAR_J_S / (KB_J_PER_K * AMU_KG * 1.0e-20)
+
+
+def _fsum(fsum):
+    fs = np.atleast_2d(np.asarray(fsum, dtype=np.float64))
+    if fs.ndim != 2 or fs.shape[1] != 9:
+        raise ValueError("fsum must be [R, 9] (or [9]): mmc_batch_forces' sums, or their sum over calls")
+    return fs
+
+
+def mean_square_force(fsum):
+    """<F^2>, <tau^2> and <tau' I^-1 tau> per molecule from mmc_batch_forces' fsum [R, 9] (number
+    summed, sum F.F, sum tau.tau, sum t, ...; sums over several calls may be added first).  Returns
+    a dict: "f2", "tau2", "t" [R], each replica's own mean (NaN where nothing was summed);
+    "f2_pooled", "tau2_pooled", "t_pooled", the means over all molecules of all replicas; and
+    "f2_err", "tau2_err", "t_err", the standard error of the replicas' means (NaN for one replica).
+    Units: (K/A)^2, K^2, K^2 / (mass unit A^2)."""
+    fs = _fsum(fsum)
+    n = fs[:, 0]
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name, col in (("f2", 1), ("tau2", 2), ("t", 3)):
+            per = fs[:, col] / n
+            out[name] = per
+            out[name + "_pooled"] = float(fs[:, col].sum() / n.sum())
+            ok = per[np.isfinite(per)]
+            out[name + "_err"] = float(np.std(ok, ddof=1) / np.sqrt(ok.size)) if ok.size > 1 else float("nan")
+    return out
+
+
+def quantum_correction(fsum, temperature, mass):
+    """The first-order (Wigner-Kirkwood) quantum correction to the Helmholtz free energy of a rigid
+    molecule, per molecule and in K:
+      dA = hbar^2 / (24 (k_B T)^2) (<F^2> / M + <tau' I^-1 tau>)
+    from mmc_batch_forces' fsum [R, 9] taken WITH mass (forces in K/A, mass [3] per atom slot in
+    amu, M their sum, T in K; the constant is HBAR2_OVER_KB_AMU_A2).  Returns a dict: "dA" (pooled
+    over the replicas), "translational" and "rotational" (its two parts), "per_replica" [R] and
+    "err", the standard error of the replicas' values."""
+    T = float(temperature)
+    m = np.asarray(mass, dtype=np.float64).ravel()
+    if not (np.isfinite(T) and T > 0):
+        raise ValueError("temperature must be positive and finite")
+    if m.shape != (3,) or not (np.all(np.isfinite(m)) and np.all(m > 0)):
+        raise ValueError("mass: three positive finite values (amu)")
+    ms = mean_square_force(fsum)
+    c = HBAR2_OVER_KB_AMU_A2 / (24.0 * T * T)
+    M = (m[0] + m[1]) + m[2]
+    per = c * (ms["f2"] / M + ms["t"])
+    trans, rot = c * ms["f2_pooled"] / M, c * ms["t_pooled"]
+    ok = per[np.isfinite(per)]
+    return {"dA": float(trans + rot), "translational": float(trans), "rotational": float(rot),
+            "per_replica": per,
+            "err": float(np.std(ok, ddof=1) / np.sqrt(ok.size)) if ok.size > 1 else float("nan")}
