@@ -19,13 +19,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["mmc_hip.hip"]
-DEPS = ["mmc_hip.hip", "mmc_wave_unit.inc", "mmc_host.hpp", "mmc_device.hpp", "mmc_kernels.hpp", "mmc_fast.hpp", "mmc_total.hpp", "mmc_wave.hpp",
-        "mmc_propose.hpp", "mmc_study.hpp", "mmc_system.inc",
-        "mmc_ctx.inc", "mmc_batch.inc", "mmc_engine.inc", "mmc_dist.inc", "mmc_ctxsrv.hpp",
-        "mmc_lat.hpp", "mmc_wave_lat.inc", "mmc_potential.hpp", "mmc_perbox.inc", "mmc_widom.hpp",
-        "mmc_widom.inc", "mmc_struct.hpp", "mmc_struct.inc", "mmc_local.hpp", "mmc_local.inc",
-        "mmc_vperturb.hpp", "mmc_vperturb.inc", "mmc_deletion.hpp", "mmc_deletion.inc",
-        "mmc_forces.hpp", "mmc_forces.inc"]
+# what the library is built from: every source file under csrc/ (and the public header, _stale)
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".inc")))
 
 
 def _stale():

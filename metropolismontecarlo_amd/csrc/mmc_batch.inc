@@ -95,15 +95,13 @@ struct mmc_batch {
     uint8_t *bar_flags = nullptr; // [R] device memory the host threads write through the BAR
                                   // (mmc_bar_alloc): no copy kernel between a step's launches
     double2 *h_steps = nullptr, *hd_steps = nullptr, *d_steps = nullptr;
-    void *widom_buf = nullptr;  // device scratch of mmc_batch_widom (mmc_widom.inc), grown on demand
-    size_t widom_bytes = 0;
-    void *widom_host = nullptr; // ... and its pinned staging of the per-replica sums
-    size_t widom_host_bytes = 0;
+    void *obs_buf = nullptr;    // device scratch of every observable call (obs_scratch, mmc_units.inc), grown on demand
+    size_t obs_bytes = 0;
+    void *obs_host = nullptr;   // ... and the pinned staging of a unit call's per-replica block (obs_staging)
+    size_t obs_host_bytes = 0;
     int coulomb_style = MMC_COULOMB_EWALD; // mmc_batch_set_coulomb_style (main.jl:75)
     bool s_stale = false;       // the style went from Wolf back to Ewald: S(k) does not describe the
                                 // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
-    void *struct_buf = nullptr; // device scratch of mmc_batch_rdf_sites / mmc_batch_dipoles (mmc_struct.inc), grown on demand
-    size_t struct_bytes = 0;
     int local_stage = 1;        // mmc_batch_local_order copies a replica's O positions to LDS where they fit
                                 // (option "local_stage" = 0: never, the path of systems too large for it)
 
@@ -253,12 +251,10 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         (void)hipFree(b->bar_flags);
     if (b->h_timeout)
         (void)hipHostFree(b->h_timeout);
-    if (b->widom_buf)
-        (void)hipFree(b->widom_buf);
-    if (b->widom_host)
-        (void)hipHostFree(b->widom_host);
-    if (b->struct_buf)
-        (void)hipFree(b->struct_buf);
+    if (b->obs_buf)
+        (void)hipFree(b->obs_buf);
+    if (b->obs_host)
+        (void)hipHostFree(b->obs_host);
     b->sys.release();
     delete b;
     return MMC_OK;

@@ -49,80 +49,21 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(D
     BatchView bv, const double *__restrict__ rec, const double *__restrict__ qq_tab,
     const int32_t *__restrict__ kpack, FastConsts fc, PairParams pp, DeletionArgs da, int n_units)
 {
-    __shared__ __align__(16) WaveShared sm;
-    const int tid = threadIdx.x, lane0 = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    for (int k = tid; k < MMC_QQ_TABLE_DOUBLES; k += WV_WAVES * 64)
-        sm.qtab[k] = qq_tab[k];
-    __syncthreads(); // the only workgroup barrier
-
-    const int n_mol = bv.n_mol, nkv = bv.nkvecs;
-    const double box = bv.box;
-    const BoxConsts bc = box_consts(box);
-    const bool same_gate = pp.lj_gate_sq == pp.qq_gate_sq;
-    const double inv_box = uniform_f64(1.0 / box);
-    uint32_t gate_q;
-    asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(gate_q) : "v"(com_quant_gate(fmax(pp.lj_gate_sq, pp.qq_gate_sq), box)));
-    wv_list_t *const list = sm.list[wv];
+    UNIT_PROLOGUE();
     const double *const pvw = sm.pvw[wv]; // (unused: no pending commit)
     const int n_sel = da.n;
 
-    for (int unit = blockIdx.x * WV_WAVES + wv; unit < n_units; unit += gridDim.x * WV_WAVES) {
-        int lane = lane0;
-        asm volatile("" : "+v"(lane)); // see k_move_eval_wave
+    UNIT_FOR(unit) {
+        const int lane = unit_lane(lane0);
         const int r = unit / n_sel, ent = unit - r * n_sel;
         const int i0 = __builtin_amdgcn_readfirstlane(da.sel[ent]);
         const double *const myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
 
-        // ---- molecule i0: word t of its record (atoms 0..8, COM 9..11) in lane t.  Every lane loads
-        // a word of the record's own 128-byte line (no load in a branch); words 12..15 are padding ----
-        const double raw = myrec[(int64_t)i0 * MMC_RSTRIDE + (lane & (MMC_RSTRIDE - 1))];
-        const double mw = lane < MMC_REC ? raw : 0.0;
-        // ... and in MoveRec layout, the proposal slot (mmc_wave_unit.inc reads MV_COM_NEW, MV_AT_NEW)
-        const int src = (lane >= MV_COM_NEW && lane < MV_COM_NEW + 3) ? 9 + lane - MV_COM_NEW
-                        : (lane >= MV_AT_NEW && lane < MV_AT_NEW + 9) ? lane - MV_AT_NEW : 12;
-        double w = wave_pick(mw, src);
-        if (!(src < 12))
-            w = 0.0;
+        const double mw = unit_load_record(myrec, i0, lane);
+        const double w = unit_proposal_slot(mw, lane);
 
-        // ================= reciprocal part: s_k of molecule i0 against S_k (which holds it) =================
-        {
-            { // rows of (atom t / 3, axis t % 3), t = lane < 9
-                const int t = lane < 9 ? lane : 0;
-                const double x = wave_pick(mw, t);
-                if (lane < 9)
-                    phase_row_moderate(x, box, sm.ptab[wv][1][t / 3][t % 3]);
-            }
-            wave_sync();
-            const double *So = s_buf(bv, r, da.scur[r]);
-            double a_rec = 0.0;
-            const int n_it = (nkv + 63) >> 6;
-            for (int it = 0; it < n_it; it++) {
-                // lanes past the last k-vector redo the last one with weight zero
-                const int k = lane + 64 * it;
-                const int kc = min(k, nkv - 1);
-                const int kp = kpack[kc];
-                const double cf = bv.cfac[kc];
-                const double2 so = *reinterpret_cast<const double2 *>(So + 2 * kc);
-                const int kx = kp & 15, ky = (kp >> 4) & 15, kz = (kp >> 8) & 15;
-                double sr = 0.0, si = 0.0;
-#pragma unroll
-                for (int l = 0; l < 3; l++) {
-                    const cplx tn = c_mul_fused(c_mul_fused(sm.ptab[wv][1][l][0][5 + kx], sm.ptab[wv][1][l][1][ky]),
-                                                sm.ptab[wv][1][l][2][kz]);
-                    sr = fma(fc.q[l], tn.re, sr);
-                    si = fma(fc.q[l], tn.im, si);
-                }
-                const double wgt = k < nkv ? cf : 0.0;
-                // cfac (2 Re(conj(S) s) - |s|^2) == cfac (|S|^2 - |S - s|^2)
-                a_rec = fma(wgt, fma(2.0, fma(so.x, sr, so.y * si), -fma(sr, sr, si * si)), a_rec);
-            }
-            const double s_rec = wave_sum_rows(a_rec);
-            if (lane == 0)
-                sm.pvw[wv][0] = s_rec;
-            wave_sync(); // (ptab is rewritten by this wave's next unit)
-        }
+        // reciprocal part: s_k of molecule i0 against S_k (which holds it), cfac (|S|^2 - |S - s|^2)
+        unit_recip_energy<-1>(sm, wv, bv, kpack, fc, r, da.scur[r], mw, lane, nkv, box);
 
         // ================= pair part: mmc_wave_unit.inc, one state, the molecule itself dropped =================
         const int pend = -1, scur = 0;
@@ -140,21 +81,7 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(D
 #undef WV_IMG
 #undef WV_SUBST
 #undef WV_NS
-        wave_sync();
-        if (lane == 0) { // mmc_combine_parts' arithmetic for the one state
-            const double *o = sm.outw[wv];
-            const int ov = (int)(__double_as_longlong(o[7]) >> 1) & 1;
-            const double d_lj = (0.0 + o[1]) * 4;                    // energy.jl:289
-            double d_real = ov ? 0.0 : 0.0 + o[5];                   // ewalds.jl:359-360
-            d_real *= bv.factor;                                     // ewalds.jl:905
-            const double d_rec = sm.pvw[wv][0] * bv.factor + da.self_d;
-            double *t = da.terms + (int64_t)unit * 3;
-            t[0] = d_lj;
-            t[1] = d_real;
-            t[2] = d_rec;
-            da.flags[unit] = (uint8_t)(ov ? MMC_WIDOM_OVERLAP : 0); // (k_deletion_reduce adds the non-finite bit)
-        }
-        wave_sync(); // outw and pvw are rewritten by this wave's next unit
+        unit_store_terms(sm, wv, lane, bv.factor, da.self_d, da.terms + (int64_t)unit * 3, da.flags + unit);
     }
 }
 

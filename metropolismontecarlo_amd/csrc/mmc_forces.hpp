@@ -51,74 +51,39 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(F
     BatchView bv, const double *__restrict__ rec, const double *__restrict__ qq_tab,
     const int32_t *__restrict__ kpack, FastConsts fc, PairParams pp, ForcesArgs fa, int n_units)
 {
-    __shared__ __align__(16) WaveShared sm;
-    const int tid = threadIdx.x, lane0 = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    for (int k = tid; k < MMC_QQ_TABLE_DOUBLES; k += WV_WAVES * 64)
-        sm.qtab[k] = qq_tab[k];
-    __syncthreads(); // the only workgroup barrier
-
-    const int n_mol = bv.n_mol, nkv = bv.nkvecs;
-    const double box = bv.box;
-    const BoxConsts bc = box_consts(box);
-    const bool same_gate = pp.lj_gate_sq == pp.qq_gate_sq;
-    const double inv_box = uniform_f64(1.0 / box);
-    uint32_t gate_q;
-    asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(gate_q) : "v"(com_quant_gate(fmax(pp.lj_gate_sq, pp.qq_gate_sq), box)));
-    wv_list_t *const list = sm.list[wv];
+    UNIT_PROLOGUE();
     double *const frec = sm.pvw[wv]; // the nine reciprocal sums of the unit
     const int n_sel = fa.n;
 
-    for (int unit = blockIdx.x * WV_WAVES + wv; unit < n_units; unit += gridDim.x * WV_WAVES) {
-        int lane = lane0;
-        asm volatile("" : "+v"(lane)); // see k_move_eval_wave
+    UNIT_FOR(unit) {
+        const int lane = unit_lane(lane0);
         const int r = unit / n_sel, ent = unit - r * n_sel;
         const int i0 = __builtin_amdgcn_readfirstlane(fa.sel[ent]);
         const double *const myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
 
-        // ---- molecule i0: word t of its record (atoms 0..8, COM 9..11) in lane t.  Every lane loads
-        // a word of the record's own 128-byte line (no load in a branch); words 12..15 are padding ----
-        const double raw = myrec[(int64_t)i0 * MMC_RSTRIDE + (lane & (MMC_RSTRIDE - 1))];
-        const double mw = lane < MMC_REC ? raw : 0.0;
+        const double mw = unit_load_record(myrec, i0, lane);
 
         // ================= reciprocal part: nine sums of cfac n_d Im(conj(S) e_a) =================
         {
-            { // rows of (atom t / 3, axis t % 3), t = lane < 9
-                const int t = lane < 9 ? lane : 0;
-                const double x = wave_pick(mw, t);
-                if (lane < 9)
-                    phase_row_moderate(x, box, sm.ptab[wv][1][t / 3][t % 3]);
-            }
-            wave_sync();
+            unit_phase_rows(sm, wv, mw, lane, box);
             const double *So = s_buf(bv, r, fa.scur[r]);
             double g[9];
 #pragma unroll
             for (int q = 0; q < 9; q++)
                 g[q] = 0.0;
-            const int n_it = (nkv + 63) >> 6;
-            for (int it = 0; it < n_it; it++) {
-                // lanes past the last k-vector redo the last one with weight zero
-                const int k = lane + 64 * it;
-                const int kc = min(k, nkv - 1);
-                const int kp = kpack[kc];
-                const double cf = bv.cfac[kc];
-                const double2 so = *reinterpret_cast<const double2 *>(So + 2 * kc);
-                const int kx = kp & 15, ky = (kp >> 4) & 15, kz = (kp >> 8) & 15;
-                const double wgt = k < nkv ? cf : 0.0;
+            unit_k_loop(bv, kpack, So, nkv, lane, [&](double wgt, double2 so, int kx, int ky, int kz) {
                 // the integer vector n of k = 2 pi n / L (ky and kz are stored with their offset of nk = 5)
                 const double nx = (double)kx, ny = (double)(ky - 5), nz = (double)(kz - 5);
 #pragma unroll
                 for (int l = 0; l < 3; l++) {
-                    const cplx e = c_mul_fused(c_mul_fused(sm.ptab[wv][1][l][0][5 + kx], sm.ptab[wv][1][l][1][ky]),
-                                               sm.ptab[wv][1][l][2][kz]);
+                    const cplx e = unit_phase(sm, wv, l, kx, ky, kz);
                     // Im(conj(S) e) = S.re e.im - S.im e.re
                     const double wi = wgt * fma(so.x, e.im, -(so.y * e.re));
                     g[3 * l] = fma(wi, nx, g[3 * l]);
                     g[3 * l + 1] = fma(wi, ny, g[3 * l + 1]);
                     g[3 * l + 2] = fma(wi, nz, g[3 * l + 2]);
                 }
-            }
+            });
             // (three sums at a time: the row totals of a sum pass through eight scalar registers)
 #pragma unroll
             for (int l = 0; l < 3; l++) {

@@ -9,6 +9,7 @@
 #include "mmc_batch.inc"
 #include "mmc_engine.inc"
 #include "mmc_perbox.inc"
+#include "mmc_units.inc"
 #include "mmc_widom.inc"
 #include "mmc_deletion.inc"
 #include "mmc_forces.inc"

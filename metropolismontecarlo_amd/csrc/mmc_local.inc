@@ -1,6 +1,6 @@
 // mmc_local.inc -- host side of mmc_batch_local_order (include/mmc_hip.h, "Local order"; the
 // kernels are in mmc_local.hpp).  Included by mmc_hip.hip after mmc_struct.inc, whose state checks
-// and device scratch it shares.
+// it shares, and after mmc_units.inc, whose device scratch (obs_scratch) it uses.
 #include "mmc_local.hpp"
 
 extern "C" int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t q_bins,
@@ -35,7 +35,7 @@ extern "C" int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_h
     const size_t qs_bytes = up16(q_sum ? 16 * (size_t)R : 0), qa_bytes = up16(want_q ? 8 * (size_t)(R * N) : 0);
     const size_t nb_bytes = up16(nbr_out ? 16 * (size_t)(R * N) : 0), hm_bytes = up16(hb_out ? 2 * (size_t)(R * N) : 0);
     char *d_buf = nullptr;
-    MMC_TRY(struct_scratch(b, hb_bytes + qh_bytes + qs_bytes + qa_bytes + nb_bytes + hm_bytes, &d_buf));
+    MMC_TRY(obs_scratch(b, hb_bytes + qh_bytes + qs_bytes + qa_bytes + nb_bytes + hm_bytes, &d_buf));
     char *d_hb = d_buf, *d_qh = d_hb + hb_bytes, *d_qs = d_qh + qh_bytes, *d_qa = d_qs + qs_bytes,
          *d_nb = d_qa + qa_bytes, *d_hm = d_nb + nb_bytes;
 

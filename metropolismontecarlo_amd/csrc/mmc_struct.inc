@@ -1,5 +1,6 @@
 // mmc_struct.inc -- host side of the structure observables (include/mmc_hip.h, "Structure
-// observables"; the kernels are in mmc_struct.hpp).  Included by mmc_hip.hip after mmc_widom.inc.
+// observables"; the kernels are in mmc_struct.hpp).  Included by mmc_hip.hip after mmc_units.inc,
+// whose device scratch (obs_scratch) both calls use.
 #include "mmc_struct.hpp"
 
 // gr.jl:87 on r^2, in the arithmetic of k_rdf: the bin of a squared distance
@@ -39,22 +40,6 @@ static void rdf_thresholds(double dr, int numbins, std::vector<double> &thr)
     MMC_REQUIRE(!(b)->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first"); \
     BATCH_NO_VOLUME_TRIAL(b)
 
-// device scratch of both calls, kept on the batch and grown on demand (no allocation, and no
-// device-wide synchronisation of a hipFree, per sample)
-static int32_t struct_scratch(mmc_batch *b, size_t bytes, char **out)
-{
-    if (bytes > b->struct_bytes) {
-        if (b->struct_buf)
-            MMC_HIP(hipFree(b->struct_buf));
-        b->struct_buf = nullptr;
-        b->struct_bytes = 0;
-        MMC_HIP(hipMalloc(&b->struct_buf, bytes));
-        b->struct_bytes = bytes;
-    }
-    *out = static_cast<char *>(b->struct_buf);
-    return MMC_OK;
-}
-
 // the 128-byte records where the batch keeps them in step with the coordinates (as the totals do)
 static inline bool struct_use_rec(const mmc_batch *b)
 {
@@ -92,7 +77,7 @@ extern "C" int32_t mmc_batch_rdf_sites(mmc_batch *b, int32_t numbins, double r_m
     const size_t n_out = (size_t)(per_replica ? R : 1) * 6 * (size_t)(numbins + 1);
     const size_t hist_bytes = sizeof(unsigned long long) * n_out, thr_bytes = sizeof(double) * thr.size();
     char *d_buf = nullptr;
-    MMC_TRY(struct_scratch(b, hist_bytes + thr_bytes, &d_buf));
+    MMC_TRY(obs_scratch(b, hist_bytes + thr_bytes, &d_buf));
     std::vector<uint64_t> h_out(n_out);
 
     RdfSitesArgs sa{};
@@ -147,7 +132,7 @@ extern "C" int32_t mmc_batch_dipoles(mmc_batch *b, double *dip)
     STRUCT_STATE(b);
     const size_t bytes = sizeof(double) * 3 * (size_t)R;
     char *d_buf = nullptr;
-    MMC_TRY(struct_scratch(b, bytes, &d_buf));
+    MMC_TRY(obs_scratch(b, bytes, &d_buf));
     double *d_dip = reinterpret_cast<double *>(d_buf);
     std::vector<double> h_out(3 * (size_t)R);
     hipStream_t st = s.stream;

@@ -1,6 +1,7 @@
 // mmc_vperturb.inc -- host side of mmc_batch_volume_perturb (include/mmc_hip.h, "Virtual volume
 // moves"; the kernels are in mmc_vperturb.hpp).  Included by mmc_hip.hip after mmc_local.inc; shares
-// the state checks and the device scratch of mmc_struct.inc and the domain rule of mmc_perbox.inc.
+// the state checks of mmc_struct.inc, the device scratch of mmc_units.inc (obs_scratch) and the domain
+// rule of mmc_perbox.inc.
 #include "mmc_vperturb.hpp"
 
 #define VP_PARTS_BYTES ((size_t)256 << 20) // tile-pair partials of one chunk of replicas
@@ -71,7 +72,7 @@ extern "C" int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const
                  pt_bytes = up16(sizeof(VpPart) * (size_t)chunk * n_box * n_pairs),
                  sm_bytes = up16(sizeof(VpPart) * (size_t)R * n_box), er_bytes = up16(sizeof(double) * (size_t)R * n_box);
     char *d_buf = nullptr;
-    MMC_TRY(struct_scratch(b, sc_bytes + cf_bytes + tb_bytes + pt_bytes + sm_bytes + er_bytes, &d_buf));
+    MMC_TRY(obs_scratch(b, sc_bytes + cf_bytes + tb_bytes + pt_bytes + sm_bytes + er_bytes, &d_buf));
     double *d_kappa = reinterpret_cast<double *>(d_buf), *d_box = d_kappa + VP_BOXES;
     double *d_cfac = reinterpret_cast<double *>(d_buf + sc_bytes);
     double *d_tabs = reinterpret_cast<double *>(d_buf + sc_bytes + cf_bytes);

@@ -25,14 +25,12 @@
 // the grid, on "wave_wgs" or on how many insertions a persistent wave takes.
 // Nothing the chains own is written: coordinates, S(k), flags and step counters are only read.
 #pragma once
-#include "mmc_wave.hpp"
+#include "mmc_unit.hpp"
 
 #ifndef WIDOM_OCC
 #define WIDOM_OCC 4 // waves per SIMD k_widom_wave is compiled for: 102 VGPRs, no scratch (at 5 = 96 VGPRs
 #endif              // it spilled 5 VGPRs: the test molecule's record and the insertion's bookkeeping)
 #define MMC_WIDOM_SLOT 0x50000000u // == MMC_SLOT_WIDOM (include/mmc_hip.h): slots +0, +1, +2
-#define MMC_WIDOM_OVERLAP 1        // flags of an insertion: an atom pair overlaps (ewalds.jl:359)
-#define MMC_WIDOM_NONFINITE 2      // ... dU is NaN or +-inf
 
 struct WidomArgs {
     uint64_t seed;       // Philox key
@@ -86,28 +84,12 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(W
     BatchView bv, const double *__restrict__ rec, const double *__restrict__ qq_tab,
     const int32_t *__restrict__ kpack, FastConsts fc, PairParams pp, WidomArgs wa, int n_units)
 {
-    __shared__ __align__(16) WaveShared sm;
-    const int tid = threadIdx.x, lane0 = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    for (int k = tid; k < MMC_QQ_TABLE_DOUBLES; k += WV_WAVES * 64)
-        sm.qtab[k] = qq_tab[k];
-    __syncthreads(); // the only workgroup barrier
-
-    const int n_mol = bv.n_mol, nkv = bv.nkvecs;
-    const double box = bv.box;
-    const BoxConsts bc = box_consts(box);
-    const bool same_gate = pp.lj_gate_sq == pp.qq_gate_sq;
-    const double inv_box = uniform_f64(1.0 / box);
-    uint32_t gate_q;
-    asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(gate_q) : "v"(com_quant_gate(fmax(pp.lj_gate_sq, pp.qq_gate_sq), box)));
-    wv_list_t *const list = sm.list[wv];
+    UNIT_PROLOGUE();
     const double *const pvw = sm.pvw[wv]; // (unused: no pending commit)
     const int M = wa.n_insert;
 
-    for (int unit = blockIdx.x * WV_WAVES + wv; unit < n_units; unit += gridDim.x * WV_WAVES) {
-        int lane = lane0;
-        asm volatile("" : "+v"(lane)); // see k_move_eval_wave
+    UNIT_FOR(unit) {
+        const int lane = unit_lane(lane0);
         const int r = unit / M, jins = unit - r * M;
         const double *const myrec = rec + (int64_t)r * n_mol * MMC_RSTRIDE;
 
@@ -133,49 +115,10 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(W
         }
         if (wa.mol_out && lane < MMC_REC)
             wa.mol_out[(int64_t)unit * MMC_REC + lane] = mw;
-        // ... and in MoveRec layout, the proposal slot (mmc_wave_unit.inc reads MV_COM_NEW, MV_AT_NEW)
-        const int src = (lane >= MV_COM_NEW && lane < MV_COM_NEW + 3) ? 9 + lane - MV_COM_NEW
-                        : (lane >= MV_AT_NEW && lane < MV_AT_NEW + 9) ? lane - MV_AT_NEW : 12;
-        double w = wave_pick(mw, src);
-        if (!(src < 12))
-            w = 0.0;
+        const double w = unit_proposal_slot(mw, lane);
 
-        // ================= reciprocal part: s_k of the test molecule against S_k =================
-        {
-            { // rows of (atom t / 3, axis t % 3), t = lane < 9
-                const int t = lane < 9 ? lane : 0;
-                const double x = wave_pick(mw, t);
-                if (lane < 9)
-                    phase_row_moderate(x, box, sm.ptab[wv][1][t / 3][t % 3]);
-            }
-            wave_sync();
-            const double *So = s_buf(bv, r, wa.scur[r]);
-            double a_rec = 0.0;
-            const int n_it = (nkv + 63) >> 6;
-            for (int it = 0; it < n_it; it++) {
-                const int k = lane + 64 * it;
-                const int kc = min(k, nkv - 1);
-                const int kp = kpack[kc];
-                const double cf = bv.cfac[kc];
-                const double2 so = *reinterpret_cast<const double2 *>(So + 2 * kc);
-                const int kx = kp & 15, ky = (kp >> 4) & 15, kz = (kp >> 8) & 15;
-                double sr = 0.0, si = 0.0;
-#pragma unroll
-                for (int l = 0; l < 3; l++) {
-                    const cplx tn = c_mul_fused(c_mul_fused(sm.ptab[wv][1][l][0][5 + kx], sm.ptab[wv][1][l][1][ky]),
-                                                sm.ptab[wv][1][l][2][kz]);
-                    sr = fma(fc.q[l], tn.re, sr);
-                    si = fma(fc.q[l], tn.im, si);
-                }
-                const double wgt = k < nkv ? cf : 0.0;
-                // cfac (2 Re(conj(S) s) + |s|^2) == cfac (|S + s|^2 - |S|^2)
-                a_rec = fma(wgt, fma(2.0, fma(so.x, sr, so.y * si), fma(sr, sr, si * si)), a_rec);
-            }
-            const double s_rec = wave_sum_rows(a_rec);
-            if (lane == 0)
-                sm.pvw[wv][0] = s_rec;
-            wave_sync(); // (ptab is rewritten by this wave's next unit)
-        }
+        // reciprocal part: s_k of the test molecule against S_k, cfac (|S + s|^2 - |S|^2)
+        unit_recip_energy<+1>(sm, wv, bv, kpack, fc, r, wa.scur[r], mw, lane, nkv, box);
 
         // ================= pair part: mmc_wave_unit.inc, one state =================
         const int i0 = -1, pend = -1, scur = 0;
@@ -193,21 +136,7 @@ __global__ __launch_bounds__(WV_WAVES * 64) __attribute__((amdgpu_waves_per_eu(W
 #undef WV_IMG
 #undef WV_SUBST
 #undef WV_NS
-        wave_sync();
-        if (lane == 0) { // mmc_combine_parts' arithmetic for the one state
-            const double *o = sm.outw[wv];
-            const int ov = (int)(__double_as_longlong(o[7]) >> 1) & 1;
-            const double d_lj = (0.0 + o[1]) * 4;                    // energy.jl:289
-            double d_real = ov ? 0.0 : 0.0 + o[5];                   // ewalds.jl:359-360
-            d_real *= bv.factor;                                     // ewalds.jl:905
-            const double d_rec = sm.pvw[wv][0] * bv.factor + wa.self_d;
-            double *t = wa.terms + (int64_t)unit * 4;
-            t[0] = d_lj;
-            t[1] = d_real;
-            t[2] = d_rec;
-            wa.flags[unit] = (uint8_t)(ov ? MMC_WIDOM_OVERLAP : 0); // (k_widom_reduce adds the non-finite bit)
-        }
-        wave_sync(); // outw and pvw are rewritten by this wave's next unit
+        unit_store_terms(sm, wv, lane, bv.factor, wa.self_d, wa.terms + (int64_t)unit * 4, wa.flags + unit);
     }
 }
 

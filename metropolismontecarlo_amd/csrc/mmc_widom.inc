@@ -1,6 +1,7 @@
 // mmc_widom.inc -- host side of Widom test-particle insertion (include/mmc_hip.h, "Widom
 // test-particle insertion"; the kernels are in mmc_widom.hpp).  Included by mmc_hip.hip after
-// mmc_batch.inc.
+// mmc_units.inc, which holds what the call shares with mmc_deletion.inc and mmc_forces.inc: the state
+// checks, the device scratch and pinned staging, the launch and the drain of the stream.
 #include "mmc_widom.hpp"
 
 // Largest distance of an atom from its COM over the caller's molecules [n][12] (atoms, COM), or
@@ -48,60 +49,18 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
             MMC_REQUIRE(std::isfinite(mol_in[k]), MMC_ERR_ARG, "%s: non-finite mol_in", what);
         r_test = widom_extent(mol_in, R * M, s.box);
     }
-    MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
-    BATCH_NO_VOLUME_TRIAL(b);
-    MMC_REQUIRE(!b->needs_reload, MMC_ERR_STATE, "%s: a run failed half-way; set every replica again", what);
-    BATCH_S_FRESH(b, what);
-    BATCH_ONE_BOX(b, what);
-    BATCH_NOT_WOLF(b, what);
-    MMC_REQUIRE(b->fast_ok, MMC_ERR_UNSUPPORTED,
-                "%s: needs identical 3-atom molecules and a cutoff / kappa the erfc table covers", what);
+    MMC_TRY(units_state_scope(b, what));
 
-    // ---- device scratch: terms [R M][4], flags [R M], the per-replica block (sums [R], counts [R],
-    // S-buffer bits [R] -- one copy each way through the pinned staging of the same layout),
+    // ---- device scratch: terms [R M][4], flags [R M], the per-replica block (sums [R], counts [R]),
     // offsets [9], molecules [R M][12] ----
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t n = (size_t)(R * M);
-    const size_t sums_bytes = (sizeof(double) + sizeof(long long)) * (size_t)R, blk_bytes = sums_bytes + (size_t)R;
-    const size_t o_flags = up(sizeof(double) * 4 * n), o_blk = o_flags + up(n), o_off = o_blk + up(blk_bytes),
-                 o_mol = o_off + up(sizeof(double) * 9);
     const bool need_mol = mol_in || mol_out;
-    const size_t bytes = o_mol + (need_mol ? sizeof(double) * 12 * n : 0);
-    if (bytes > b->widom_bytes) {
-        if (b->widom_buf)
-            MMC_HIP(hipFree(b->widom_buf));
-        b->widom_buf = nullptr;
-        b->widom_bytes = 0;
-        MMC_HIP(hipMalloc(&b->widom_buf, bytes));
-        b->widom_bytes = bytes;
-    }
-    if (blk_bytes > b->widom_host_bytes) {
-        if (b->widom_host)
-            MMC_HIP(hipHostFree(b->widom_host));
-        b->widom_host = nullptr;
-        b->widom_host_bytes = 0;
-        MMC_HIP(hipHostMalloc(&b->widom_host, blk_bytes, hipHostMallocDefault));
-        b->widom_host_bytes = blk_bytes;
-    }
-    char *base = static_cast<char *>(b->widom_buf);
-    double *d_terms = reinterpret_cast<double *>(base);
-    uint8_t *d_flags = reinterpret_cast<uint8_t *>(base + o_flags);
-    double *d_boltz = reinterpret_cast<double *>(base + o_blk);
-    long long *d_novl = reinterpret_cast<long long *>(base + o_blk + sizeof(double) * R);
-    uint8_t *d_scur = reinterpret_cast<uint8_t *>(base + o_blk + sums_bytes);
-    double *d_off = reinterpret_cast<double *>(base + o_off);
-    double *d_mol = need_mol ? reinterpret_cast<double *>(base + o_mol) : nullptr;
-    char *hblk = static_cast<char *>(b->widom_host);
-    memcpy(hblk, boltz_sum, sizeof(double) * R);
-    memcpy(hblk + sizeof(double) * R, n_overlap, sizeof(long long) * R);
-    memcpy(hblk + sums_bytes, b->s_cur.data(), (size_t)R);
-
-    hipStream_t st = s.stream;
-    MMC_HIP(hipMemcpyAsync(base + o_blk, hblk, blk_bytes, hipMemcpyHostToDevice, st));
-    if (offsets)
-        MMC_HIP(hipMemcpyAsync(d_off, offsets, sizeof(double) * 9, hipMemcpyHostToDevice, st));
-    if (mol_in)
-        MMC_HIP(hipMemcpyAsync(d_mol, mol_in, sizeof(double) * 12 * n, hipMemcpyHostToDevice, st));
+    UnitsCall uc(b, n, 4, 1);
+    const size_t o_off = uc.take(sizeof(double) * 9), o_mol = uc.take(need_mol ? sizeof(double) * 12 * n : 0);
+    MMC_TRY(uc.alloc());
+    double *d_off = uc.at<double>(o_off), *d_mol = need_mol ? uc.at<double>(o_mol) : nullptr;
+    memcpy(uc.h_sums(), boltz_sum, sizeof(double) * R);
+    memcpy(uc.h_counts(), n_overlap, sizeof(long long) * R);
 
     WidomArgs wa{};
     wa.seed = seed;
@@ -109,9 +68,9 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     wa.off = d_off;
     wa.mol_in = mol_in ? d_mol : nullptr;
     wa.mol_out = (!mol_in && mol_out) ? d_mol : nullptr;
-    wa.terms = d_terms;
-    wa.flags = d_flags;
-    wa.scur = d_scur;
+    wa.terms = uc.d_rows();
+    wa.flags = uc.d_flags();
+    wa.scur = uc.d_scur();
     wa.n_insert = (int32_t)M;
     {   // EwaldSelf(N+1) - EwaldSelf(N) in orc_ewald_self's arithmetic (ewalds.jl:829-833)
         double q2 = 0.0;
@@ -121,42 +80,33 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     }
 
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
-    // the minimum image of an atom pair from its molecules' (WV_IMG): k_move_eval_wave's condition,
-    // gate + r_mol + r_test < box / 2 and inside the slack of the pair tests, where the chains'
-    // molecules are known to be rigid
+    // the minimum image of an atom pair from its molecules' (WV_IMG): k_move_eval_wave's condition with
+    // the test molecule's extent in place of one r_mol_max, gate + r_mol + r_test < box / 2 and inside
+    // the slack of the pair tests, where the chains' molecules are known to be rigid.  (Not
+    // units_image_by_molecule: a different expression in fp64, and r_test is this call's own.)
     const double far = std::sqrt(std::max(pp.lj_gate_sq, pp.qq_gate_sq)) + s.r_mol_max + r_test + 1e-6;
     const bool img = b->rigid_only && b->image_by_molecule != 0 && std::isfinite(far) && far < 0.5 * s.box &&
                      far * far < pp.qq_slack_sq && far * far < pp.lj_slack_sq;
-    // persistent workgroups as k_move_eval_wave's launches (mmc_batch.inc), capped at option "wave_wgs"
-    // or at what is resident: WIDOM_OCC waves on each of the 4 SIMDs of every compute unit
-    const int64_t n_units = (int64_t)n;
-    int64_t wgs = (n_units + WV_WAVES - 1) / WV_WAVES;
-    const int64_t cap = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(4 * WIDOM_OCC / WV_WAVES) * b->n_cus;
-    if (wgs > cap) wgs = cap;
-    if (img)
-        k_widom_wave<true><<<(unsigned)wgs, WV_WAVES * 64, 0, st>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, pp, wa,
-                                                                    (int)n_units);
-    else
-        k_widom_wave<false><<<(unsigned)wgs, WV_WAVES * 64, 0, st>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, pp, wa,
-                                                                     (int)n_units);
-    MMC_HIP(hipGetLastError());
-    k_widom_reduce<<<(unsigned)R, 64, 0, st>>>(d_terms, d_flags, (int)M, 1.0 / temperature, d_boltz, d_novl);
-    MMC_HIP(hipGetLastError());
 
-    std::vector<double> h_terms(du_out ? 4 * n : 0);
-    if (du_out)
-        MMC_HIP(hipMemcpyAsync(h_terms.data(), d_terms, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, st));
-    MMC_HIP(hipMemcpyAsync(hblk, base + o_blk, sums_bytes, hipMemcpyDeviceToHost, st));
-    std::vector<uint8_t> h_flags(ovl_out ? n : 0);
-    if (ovl_out)
-        MMC_HIP(hipMemcpyAsync(h_flags.data(), d_flags, n, hipMemcpyDeviceToHost, st));
-    std::vector<double> h_mol(mol_out ? 12 * n : 0);
+    // ---- from here to finish() nothing returns ----
+    uc.upload_block();
+    if (offsets)
+        uc.to_device(d_off, offsets, sizeof(double) * 9);
+    if (mol_in)
+        uc.to_device(d_mol, mol_in, sizeof(double) * 12 * n);
+    uc.launch(img, k_widom_wave<true>, k_widom_wave<false>, WIDOM_OCC, pp, wa);
+    if (uc.e == hipSuccess)
+        k_widom_reduce<<<(unsigned)R, 64, 0, uc.st>>>(uc.d_rows(), uc.d_flags(), (int)M, 1.0 / temperature, uc.d_sums(),
+                                                     uc.d_counts());
+    uc.launched();
+    std::vector<double> h_terms, h_mol(mol_out ? 12 * n : 0);
+    std::vector<uint8_t> h_flags;
     if (mol_out)
-        MMC_HIP(hipMemcpyAsync(h_mol.data(), d_mol, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, st));
-    MMC_TRY(s.sync());
+        uc.to_host(h_mol.data(), d_mol, sizeof(double) * 12 * n);
+    MMC_TRY(uc.finish(du_out ? &h_terms : nullptr, ovl_out ? &h_flags : nullptr, what));
     // (the caller's arrays are written only once the whole call has succeeded)
-    memcpy(boltz_sum, hblk, sizeof(double) * R);
-    memcpy(n_overlap, hblk + sizeof(double) * R, sizeof(long long) * R);
+    memcpy(boltz_sum, uc.h_sums(), sizeof(double) * R);
+    memcpy(n_overlap, uc.h_counts(), sizeof(long long) * R);
     if (du_out)
         for (size_t i = 0; i < n; i++)
             for (int c = 0; c < 3; c++)

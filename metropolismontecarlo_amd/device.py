@@ -43,6 +43,29 @@ def _i(a):
     return a.ctypes.data_as(_i64p)
 
 
+def _selection(sel, n_mol):
+    """(int32 array or None, count) of a selection of molecules shared by all replicas: 0-based
+    indices, duplicates allowed; None = all n_mol."""
+    if sel is None:
+        return None, n_mol
+    sel_a = np.ascontiguousarray(sel)
+    if sel_a.ndim != 1 or not np.issubdtype(sel_a.dtype, np.integer):
+        raise ValueError("sel: a 1-d array of integer molecule indices (0-based)")
+    if sel_a.size and (sel_a.min() < -2 ** 31 or sel_a.max() >= 2 ** 31):
+        raise ValueError("sel: an index does not fit 32 bits")
+    sel_a = np.ascontiguousarray(sel_a, dtype=np.int32)
+    return sel_a, sel_a.shape[0]
+
+
+def _accumulator(a, R, dtype, name):
+    """A per-replica sum the library adds to in place: the caller's array, or a new zero one."""
+    if a is None:
+        return np.zeros(R, dtype=dtype)
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == (R,) and a.flags.c_contiguous):
+        raise ValueError(f"{name}: {np.dtype(dtype).name} (R,), contiguous (updated in place)")
+    return a
+
+
 REFERENCE_IDEAL_TERM = 4.60453   # the ideal-gas term Loop() hard-codes in its block line (main.jl:677)
 
 
@@ -542,7 +565,8 @@ class Batch:
         Returns (boltz_sum, n_overlap), and with outputs=True also mol (R, M, 12), du (R, M, 3)
         and ovl (R, M)."""
         off = _f64(self.widom_offsets if offsets is None else offsets).reshape(3, 3)
-        bs, no = self._widom_sums(boltz_sum, n_overlap)
+        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
+        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
         M = int(n_insert)
         mol = np.zeros((self.R, M, 12)) if outputs else None
         du = np.zeros((self.R, M, 3)) if outputs else None
@@ -560,21 +584,13 @@ class Batch:
         if mol.ndim != 3 or mol.shape[0] != self.R or mol.shape[2] != 12:
             raise ValueError("mol must be (R, n_insert, 12)")
         M = mol.shape[1]
-        bs, no = self._widom_sums(boltz_sum, n_overlap)
+        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
+        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
         du = np.zeros((self.R, M, 3))
         ov = np.zeros((self.R, M), dtype=np.uint8)
         check(self._L.mmc_batch_widom_at(self._h, M, _d(mol), float(temperature), _d(bs), _i(no),
                                          _d(du), _u8(ov)))
         return bs, no, du, ov
-
-    def _widom_sums(self, boltz_sum, n_overlap):
-        bs = np.zeros(self.R) if boltz_sum is None else boltz_sum
-        no = np.zeros(self.R, dtype=np.int64) if n_overlap is None else n_overlap
-        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (self.R,)
-                and bs.flags.c_contiguous and isinstance(no, np.ndarray) and no.dtype == np.int64
-                and no.shape == (self.R,) and no.flags.c_contiguous):
-            raise ValueError("boltz_sum: float64 (R,), n_overlap: int64 (R,), contiguous (updated in place)")
-        return bs, no
 
     def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
                  n_flagged=None, details=False):
@@ -588,22 +604,9 @@ class Batch:
         hist uint64 (n_bins + 2,) or (R, n_bins + 2) when bins is given, and with details=True du
         (R, n, 3) and ovl uint8 (R, n) (bit 0 overlap, bit 1 non-finite dU)."""
         R = self.R
-        if sel is None:
-            sel_a, n = None, self.n_mol
-        else:
-            sel_a = np.ascontiguousarray(sel)
-            if sel_a.ndim != 1 or not np.issubdtype(sel_a.dtype, np.integer):
-                raise ValueError("sel: a 1-d array of integer molecule indices (0-based)")
-            if sel_a.size and (sel_a.min() < -2 ** 31 or sel_a.max() >= 2 ** 31):
-                raise ValueError("sel: an index does not fit 32 bits")
-            sel_a = np.ascontiguousarray(sel_a, dtype=np.int32)
-            n = sel_a.shape[0]
-        bs = np.zeros(R) if boltz_sum is None else boltz_sum
-        nf = np.zeros(R, dtype=np.int64) if n_flagged is None else n_flagged
-        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (R,)
-                and bs.flags.c_contiguous and isinstance(nf, np.ndarray) and nf.dtype == np.int64
-                and nf.shape == (R,) and nf.flags.c_contiguous):
-            raise ValueError("boltz_sum: float64 (R,), n_flagged: int64 (R,), contiguous (updated in place)")
+        sel_a, n = _selection(sel, self.n_mol)
+        bs = _accumulator(boltz_sum, R, np.float64, "boltz_sum")
+        nf = _accumulator(n_flagged, R, np.int64, "n_flagged")
         res = {"esum": np.zeros((R, 4)), "boltz_sum": bs, "n_flagged": nf}
         n_bins, u_lo, u_hi = 0, 0.0, 0.0
         if bins is not None:
@@ -631,24 +634,13 @@ class Batch:
         torque (R, n, 3), vir (R, n, 3) = (w_lj, w_real, t), atom (R, n, 3, 3) and ovl uint8 (R, n)
         (bit 0 overlap, bit 1 a non-finite output; a flagged molecule's rows are zeros)."""
         R = self.R
-        if sel is None:
-            sel_a, n = None, self.n_mol
-        else:
-            sel_a = np.ascontiguousarray(sel)
-            if sel_a.ndim != 1 or not np.issubdtype(sel_a.dtype, np.integer):
-                raise ValueError("sel: a 1-d array of integer molecule indices (0-based)")
-            if sel_a.size and (sel_a.min() < -2 ** 31 or sel_a.max() >= 2 ** 31):
-                raise ValueError("sel: an index does not fit 32 bits")
-            sel_a = np.ascontiguousarray(sel_a, dtype=np.int32)
-            n = sel_a.shape[0]
+        sel_a, n = _selection(sel, self.n_mol)
         mass_a = None
         if mass is not None:
             mass_a = np.ascontiguousarray(mass, dtype=np.float64)
             if mass_a.shape != (3,):
                 raise ValueError("mass: three values, one per atom slot")
-        nf = np.zeros(R, dtype=np.int64) if n_flagged is None else n_flagged
-        if not (isinstance(nf, np.ndarray) and nf.dtype == np.int64 and nf.shape == (R,) and nf.flags.c_contiguous):
-            raise ValueError("n_flagged: int64 (R,), contiguous (updated in place)")
+        nf = _accumulator(n_flagged, R, np.int64, "n_flagged")
         res = {"fsum": np.zeros((R, 9)), "n_flagged": nf}
         if details:
             res.update(force=np.zeros((R, n, 3)), torque=np.zeros((R, n, 3)), vir=np.zeros((R, n, 3)),
