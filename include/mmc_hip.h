@@ -862,6 +862,50 @@ int32_t mmc_batch_rdf_sites(mmc_batch *b, int32_t numbins, double r_max, int32_t
                             uint64_t *hist);
 int32_t mmc_batch_dipoles(mmc_batch *b, double *dip /* [R][3] */);
 
+/* ---- Orientational pair correlations: h110(r), h112(r), <P2>(r) and the Kirkwood factor G_K(r) ---
+ * The orientation-resolved pair pass between mmc_batch_rdf_sites (separations only) and
+ * mmc_batch_local_order (orientation, first shell only): what the epsilon of the dipole fluctuation
+ * (mmc_batch_dipoles) is made of, distance by distance.  The reference has no such analysis; the
+ * arithmetic is defined here, in unfused fp64, and restated in numpy by tests/orient_ref.py.  Every
+ * pair i < j of molecules of every replica contributes once.
+ *   - Separation and bin: exactly row (0,0) of mmc_batch_rdf_sites.  d = site0(i) - site0(j) per
+ *     component, its image gr.jl:75-80 with the replica's own box, r^2 = (xx xx + yy yy) + zz zz,
+ *     bin = ceil(sqrt(r^2) / dr); dr and the validity of r_max as mmc_batch_rdf_sites in both box
+ *     modes.  Bins 0..numbins are in range; slot numbins + 1 takes every pair beyond r_max and,
+ *     unlike mmc_batch_rdf_sites, is returned.
+ *   - Axis u_i of molecule i: mu_i as mmc_batch_dipoles computes it, (q_0 d_0 + q_1 d_1) + q_2 d_2
+ *     with d_a = vector1D (boundaries.jl) of atom a minus the COM; n^2 = (mu_x^2 + mu_y^2) + mu_z^2,
+ *     u = mu / sqrt(n^2), and u = 0 when n^2 is 0 or not finite.
+ *   - Per pair: c = (u_i.x u_j.x + u_i.y u_j.y) + u_i.z u_j.z; p2 = 1.5 c^2 - 0.5;
+ *     hd = 3 (u_i . d)(u_j . d) / r^2 - c, and hd = 0 when r^2 = 0 (dot products as c).
+ *   - Rows: 0 the pair count; 1, 2, 3 the sums of Q(c), Q(hd), Q(p2) with Q(v) = v 2^30
+ *     (MMC_ORIENT_SCALE) rounded to the nearest integer, ties to even, as a 64-bit integer.  In slot
+ *     numbins + 1 rows 0 and 1 are filled, rows 2 and 3 are 0.  hd is evaluated with a per-pair error
+ *     below 2^-31 (a refined reciprocal of r^2): a row-2 entry may differ from the exact arithmetic
+ *     above by at most one unit per pair of its slot.
+ *   - All four rows are integer sums: the result does not depend on the grid, on option "wave_wgs",
+ *     on the flush order or on the order of atomics -- bitwise reproducible with no ordered
+ *     reduction, at the price of a 2^-30 quantum per pair.  |Q| <= 2^31: the sums cannot wrap.
+ *   - per_replica == 0: hist[4][numbins + 2] summed over the replicas; else hist[R][4][numbins + 2].
+ *     hist is overwritten, not accumulated.
+ *   - Use: G_K(R) = 1 + 2 sum_{bins <= R} row1 / (2^30 N frames), whose last element (slot
+ *     numbins + 1 included) is the whole-box <|sum_i u_i|^2> / N; h110, h112 = rows 1, 2 over the
+ *     ideal-gas pair count of the shell; <P2>(r) = row3 / (2^30 row0) (observables.py: kirkwood_gk,
+ *     orient_projections).
+ * Both box modes and either Coulomb style: the call reads coordinates and charges only, no S(k) and no
+ * erfc table, and is read-only as mmc_batch_rdf_sites is.  Preconditions as mmc_batch_rdf_sites: no
+ * proposals outstanding, no volume trial in flight (MMC_ERR_STATE).  MMC_ERR_ARG: numbins < 1 or above
+ * MMC_ORIENT_MAX_BINS, a NULL hist, r_max not finite, above half of the smallest box, or <= 0 with
+ * per-replica boxes.  MMC_ERR_UNSUPPORTED: more than 2^21 molecules.  Arguments are checked first,
+ * then the state, then the size.  On any error hist is left untouched. */
+int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica,
+                              int64_t *hist /* [4][numbins + 2] or [R][4][numbins + 2] */);
+#define MMC_ORIENT_SCALE 1073741824.0 /* 2^30: one unit of rows 1..3 */
+/* What one wave per workgroup fits in the 65536 bytes of LDS a workgroup may ask for: the bin
+ * thresholds, 8 (numbins + 2) bytes, and four 64-bit rows, 32 (numbins + 2) bytes:
+ * 40 (numbins + 2) <= 65536  ->  numbins + 2 <= 1638. */
+#define MMC_ORIENT_MAX_BINS 1636
+
 /* ---- Local order: hydrogen bonds and the tetrahedral order parameter of 3-site molecules ------
  * The first coordination shell of every molecule of every replica in one read-only pass.  Slot 0 of
  * a molecule is the heavy atom ("O"), slots 1 and 2 are the hydrogens: the order of every water deck

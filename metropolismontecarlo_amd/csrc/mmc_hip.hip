@@ -14,6 +14,7 @@
 #include "mmc_deletion.inc"
 #include "mmc_forces.inc"
 #include "mmc_struct.inc"
+#include "mmc_orient.inc"
 #include "mmc_local.inc"
 #include "mmc_vperturb.inc"
 #include "mmc_dist.inc"

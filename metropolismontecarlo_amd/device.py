@@ -721,6 +721,25 @@ class Batch:
         check(self._L.mmc_batch_dipoles(self._h, _d(out)))
         return out
 
+    def orient_corr(self, numbins, r_max=0.0, per_replica=False, out=None):
+        """mmc_batch_orient_corr: orientational pair correlations over the slot-0 separation, the
+        bins of rdf_sites' row (0,0) plus slot numbins + 1 for every pair beyond r_max: int64
+        [4, numbins + 2] summed over the replicas, or [R, 4, numbins + 2] with per_replica.  Row 0
+        the pair count, rows 1..3 the sums of u_i.u_j, 3 (u_i.rhat)(u_j.rhat) - u_i.u_j and
+        P2(u_i.u_j) in units of 2^-30 (observables.kirkwood_gk, orient_projections); u the unit
+        vector of the molecule's dipole.  `out` (that shape, int64, contiguous) is overwritten and
+        returned."""
+        n2 = max(int(numbins), 0) + 2  # (a numbins the library refuses still gets an array to leave alone)
+        shape = (self.R, 4, n2) if per_replica else (4, n2)
+        if out is None:
+            out = np.zeros(shape, dtype=np.int64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.shape == shape
+                  and out.flags.c_contiguous):
+            raise ValueError(f"out: int64 {shape}, contiguous")
+        check(self._L.mmc_batch_orient_corr(self._h, int(numbins), float(r_max), int(bool(per_replica)),
+                                            _i(out)))
+        return out
+
     def local_order(self, q_bins=400, r_hb=3.5, theta_deg=30.0, per_replica=False, details=False, out=None):
         """mmc_batch_local_order: hydrogen bonds (O-O closer than r_hb, H-O...O angle within
         theta_deg) and the tetrahedral order parameter q of every molecule (slot 0 = O, slots 1, 2

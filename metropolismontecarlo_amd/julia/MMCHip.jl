@@ -679,6 +679,25 @@ function dipoles(b::Batch)
     return dip
 end
 
+# ---- orientational pair correlations (include/mmc_hip.h, mmc_batch_orient_corr) --------------------
+"""
+    orient_corr(b, numbins; r_max = 0.0, per_replica = false)
+
+Orientational pair correlations over the slot-1 (O) separation, every pair i < j once, in the bins of
+`rdf_sites`' first column plus slot numbins + 1 for every pair beyond r_max: a `(numbins + 2, 4)`
+Int64 matrix summed over the replicas (column k = row k of the C layout), or `(numbins + 2, 4, R)`
+with `per_replica`.  Column 1 the pair count; columns 2, 3, 4 the sums of u_i.u_j,
+3 (u_i.rhat)(u_j.rhat) - u_i.u_j and P2(u_i.u_j) in units of 2^-30, u the unit vector of the
+molecule's dipole.  G_K(R) = 1 + 2 cumsum(column 2) / (2^30 N frames); read-only for the chains.
+"""
+function orient_corr(b::Batch, numbins::Integer; r_max::Float64 = 0.0, per_replica::Bool = false)
+    numbins >= 1 || error("numbins must be >= 1")
+    hist = per_replica ? zeros(Int64, numbins + 2, 4, b.n_replicas) : zeros(Int64, numbins + 2, 4)
+    check(ccall((:mmc_batch_orient_corr, libmmc), Int32, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Int64}),
+                b.h, numbins, r_max, per_replica ? 1 : 0, hist))
+    return hist
+end
+
 # ---- local order (include/mmc_hip.h, mmc_batch_local_order) ----------------------------------------
 """
     local_order(b; q_bins = 400, r_hb = 3.5, theta_deg = 30.0, per_replica = false)

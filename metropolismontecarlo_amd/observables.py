@@ -67,6 +67,46 @@ def dielectric_constant(M, temperature, volume, factor):
     return 1.0 + 4.0 * np.pi * float(factor) * fluct / (3.0 * V * float(temperature))
 
 
+# ---- orientational pair correlations (include/mmc_hip.h, "Orientational pair correlations") --------
+ORIENT_SCALE = 2.0 ** 30  # MMC_ORIENT_SCALE: one unit of rows 1..3 of mmc_batch_orient_corr
+
+
+def _orient_hist(hist):
+    h = np.asarray(hist)
+    if h.ndim < 2 or h.shape[-2] != 4 or h.shape[-1] < 3:
+        raise ValueError("hist must be [..., 4, numbins + 2] (mmc_batch_orient_corr)")
+    return h
+
+
+def kirkwood_gk(hist, n_mol, n_frames=1):
+    """The distance-dependent Kirkwood factor from an mmc_batch_orient_corr histogram
+    ([..., 4, numbins + 2]; sums over several calls may be added first):
+    G_K(R_k) = 1 + 2 cumsum(row1[0..k]) / (2^30 N frames), k = 0..numbins + 1, R_k = k dr the outer
+    edge of bin k.  n_frames: the frames summed into each histogram (calls, times the replicas for a
+    summed output).  The last element takes in slot numbins + 1, every pair beyond r_max: the
+    whole-box value <|sum_i u_i|^2> / N.  Returns [..., numbins + 2]."""
+    h = _orient_hist(hist)
+    return 1.0 + 2.0 * np.cumsum(h[..., 1, :].astype(np.float64), axis=-1) / (ORIENT_SCALE * float(n_mol) * float(n_frames))
+
+
+def orient_projections(hist, n_mol, dr, inv_volume_sum):
+    """(r, g, h110, h112, <P2>) at the centres of bins 1..numbins of an mmc_batch_orient_corr
+    histogram ([..., 4, numbins + 2]): g(r), h110(r) = g(r) <u_i.u_j>_r and
+    h112(r) = g(r) <3 (u_i.rhat)(u_j.rhat) - u_i.u_j>_r are rows 0, 1 / 2^30 and 2 / 2^30 over
+    normalize_rdf_pairs' ideal-gas pair count of the shell with N (N - 1) / 2 pairs per frame
+    (inv_volume_sum: the sum of 1 / V over the frames in the histogram); <P2>(r) = row3 / (2^30 row0),
+    NaN where the bin is empty."""
+    h = _orient_hist(hist)
+    pairs = float(n_mol) * (float(n_mol) - 1.0) / 2.0
+    rows = h[..., :-1].astype(np.float64)                       # bins 0..numbins
+    r, g = normalize_rdf_pairs(rows[..., 0, :], pairs, dr, inv_volume_sum)
+    h110 = normalize_rdf_pairs(rows[..., 1, :] / ORIENT_SCALE, pairs, dr, inv_volume_sum)[1]
+    h112 = normalize_rdf_pairs(rows[..., 2, :] / ORIENT_SCALE, pairs, dr, inv_volume_sum)[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p2 = np.where(rows[..., 0, 1:] > 0, rows[..., 3, 1:] / (ORIENT_SCALE * rows[..., 0, 1:]), np.nan)
+    return r, g, h110, h112, p2
+
+
 # ---- hydrogen bonds and tetrahedral order (include/mmc_hip.h, "Local order") -----------------------
 def hbonds_per_molecule(hb_hist):
     """Mean number of donated, accepted and total hydrogen bonds per molecule from an
