@@ -906,6 +906,56 @@ int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32
  * 40 (numbins + 2) <= 65536  ->  numbins + 2 <= 1638. */
 #define MMC_ORIENT_MAX_BINS 1636
 
+/* ---- Partial structure factors: S_ab(q) and the charge structure factor S_ZZ(q) of every replica ---
+ * The reciprocal-space counterpart of mmc_batch_rdf_sites: the products rho_a(n) rho_b(n)* of the three
+ * atom-slot densities over the box's own wave vectors, summed per shell of |n|^2, in one read-only
+ * pass.  What mmc_batch_recip_long builds for the 337 Ewald vectors, charge-weighted and only as an
+ * energy (Ewald/ewalds.jl:538-604, the powers :575-585), is built here per slot out to |n| <= 32.
+ * The arithmetic is defined here, in unfused fp64, and restated in numpy by tests/sofq_ref.py.
+ *   - Vectors and shells.  n = (nx, ny, nz) integer with 0 < s = nx^2 + ny^2 + nz^2 <= n_max^2;
+ *     q = 2 pi n / L with L the replica's own box; the shell index is s.  count[s] is the number of
+ *     all such vectors, r_3(s): 0 for empty shells and for s = 0.  The kernel visits the half space
+ *     (nx > 0, or nx = 0 and ny > 0, or nx = ny = 0 and nz > 0) and doubles each contribution:
+ *     rho(-n) = conj rho(n), so doubling is exact.
+ *   - Slot densities.  rho_a(n) = sum_i e^{i 2 pi n . r_{i,a} / L} over the molecules i, for atom
+ *     slot a = 0, 1, 2 (a batch holds three-atom molecules only).  The stored coordinates are used
+ *     with no imaging: the phase is periodic.
+ *   - Phase arithmetic: k_recip_long_lds' (csrc/mmc_total.hpp).  Per component (cos, sin) of
+ *     2 pi x / L by sincos_moderate (csrc/mmc_device.hpp); powers by repeated c_mul, p_0 = 1,
+ *     p_k = c_mul(p_{k-1}, e1) (the first product, 1 e1, is exact); negative indices by conjugation;
+ *     product order (x y) z: the term of atom (i, a) is c_mul(c_mul(ex, ey), ez).
+ *   - Summation order.  Lane l of one wave adds the molecules l, l + 64, ... in that order, the 64
+ *     lane sums go through wave_sum (csrc/mmc_device.hpp: lane l += lane l + 32, 16, 8, 4, 2, 1), and
+ *     one wave computes a given rho_a(n) alone: the bits of every rho do not depend on the launch.
+ *   - Rows, in mmc_batch_rdf_sites' order: slot pairs (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).  Per
+ *     half-space vector v_ab = rho_a.re rho_b.re + rho_a.im rho_b.im, unfused; Q(v) = v 2^24
+ *     (MMC_SOFQ_SCALE) rounded to the nearest integer, ties to even, as a 64-bit integer;
+ *     sq[r][row][s] = 2 sum over the half-space vectors n of shell s of Q(v_ab(n)).  Row (a,b), a < b,
+ *     holds the cross term once: the host doubles it when it forms |sum_a w_a rho_a|^2.  Self terms
+ *     and intramolecular terms are included: S_aa -> 1 at large q.
+ *   - All sums are integers: no order of waves, atomics or flushes can change a bit, whatever the
+ *     grid or option "wave_wgs".  N <= 2^10 and count <= 552 give |sq| < 2^54: the sums cannot wrap.
+ *   - per_replica != 0: sq[R][6][n_max^2 + 1], overwritten; sq_sum must be NULL.  per_replica == 0:
+ *     sq_sum[row][s] = sum over r = 0 .. R - 1, ascending, of (double)sq[r][row][s] 2^-24 in fp64,
+ *     added in that order; sq must be NULL.  Bitwise reproducible.  count [n_max^2 + 1] may be NULL.
+ *   - Use (observables.py): S_ab(q) = <rho_a rho_b*> / sqrt(N_a N_b) averaged over the shell's
+ *     vectors (partial_structure_factors), S_ZZ = <|sum_a q_a rho_a|^2> / N (charge_structure_factor),
+ *     1 - 1 / eps_L(q) = 4 pi beta N S_ZZ / (V q^2) (dielectric_longitudinal).
+ * Both box modes and either Coulomb style: the call reads coordinates only, and is read-only as
+ * mmc_batch_rdf_sites is.  Preconditions as mmc_batch_rdf_sites: no proposals outstanding, no volume
+ * trial in flight (MMC_ERR_STATE).  MMC_ERR_ARG, checked before the batch: n_max outside
+ * 1..MMC_SOFQ_MAX_N, the output that per_replica selects NULL, the other output given; checked with
+ * the batch: per_replica == 0 with per-replica boxes (equal s are different q there: ask per
+ * replica).  MMC_ERR_UNSUPPORTED: more than MMC_SOFQ_MAX_MOL molecules.  Arguments are checked first,
+ * then the state, then the size.  On any error every output is left untouched. */
+#define MMC_SOFQ_MAX_N   32            /* largest n_max */
+#define MMC_SOFQ_MAX_MOL 1024          /* largest N: the phases of 3 N atoms stay in one workgroup's LDS */
+#define MMC_SOFQ_SCALE   16777216.0    /* 2^24: one unit of sq */
+int32_t mmc_batch_structure_factor(mmc_batch *b, int32_t n_max, int32_t per_replica,
+                                   int32_t *count /* [n_max*n_max + 1] may be NULL */,
+                                   int64_t *sq    /* [R][6][n_max*n_max + 1], per_replica != 0; may be NULL */,
+                                   double  *sq_sum/* [6][n_max*n_max + 1],    per_replica == 0; may be NULL */);
+
 /* ---- Local order: hydrogen bonds and the tetrahedral order parameter of 3-site molecules ------
  * The first coordination shell of every molecule of every replica in one read-only pass.  Slot 0 of
  * a molecule is the heavy atom ("O"), slots 1 and 2 are the hydrogens: the order of every water deck

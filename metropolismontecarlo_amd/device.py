@@ -740,6 +740,28 @@ class Batch:
                                             _i(out)))
         return out
 
+    def structure_factor(self, n_max, per_replica=False, out=None):
+        """mmc_batch_structure_factor: the products rho_a(n) rho_b(n)* of the three atom-slot
+        densities over the box's own wave vectors q = 2 pi n / L, 0 < |n|^2 <= n_max^2, summed per
+        shell s = |n|^2.  Returns (count, sq): count int32 [n_max^2 + 1], the vectors of each shell;
+        sq int64 [R, 6, n_max^2 + 1] in units of 2^-24 with per_replica, else float64
+        [6, n_max^2 + 1] summed over the replicas; rows observables.SLOT_PAIRS, a row (a, b), a < b,
+        holding the cross term once (observables.partial_structure_factors,
+        charge_structure_factor).  `out` (sq's shape and dtype, contiguous) is overwritten and
+        returned.  With per-replica boxes only per_replica=True."""
+        S = max(int(n_max), 0) ** 2 + 1  # (an n_max the library refuses still gets arrays to leave alone)
+        shape, dt = ((self.R, 6, S), np.int64) if per_replica else ((6, S), np.float64)
+        if out is None:
+            out = np.zeros(shape, dtype=dt)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.shape == shape and out.flags.c_contiguous):
+            raise ValueError(f"out: {np.dtype(dt).name} {shape}, contiguous")
+        count = np.zeros(S, dtype=np.int32)
+        check(self._L.mmc_batch_structure_factor(self._h, int(n_max), int(bool(per_replica)),
+                                                 count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 _i(out) if per_replica else None,
+                                                 None if per_replica else _d(out)))
+        return count, out
+
     def local_order(self, q_bins=400, r_hb=3.5, theta_deg=30.0, per_replica=False, details=False, out=None):
         """mmc_batch_local_order: hydrogen bonds (O-O closer than r_hb, H-O...O angle within
         theta_deg) and the tetrahedral order parameter q of every molecule (slot 0 = O, slots 1, 2

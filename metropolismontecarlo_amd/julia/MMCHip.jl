@@ -698,6 +698,36 @@ function orient_corr(b::Batch, numbins::Integer; r_max::Float64 = 0.0, per_repli
     return hist
 end
 
+# ---- partial structure factors (include/mmc_hip.h, mmc_batch_structure_factor) --------------------
+"""
+    structure_factor(b, n_max; per_replica = false)
+
+The products rho_a(n) rho_b(n)* of the three atom-slot densities over the box's own wave vectors
+q = 2 pi n / L, 0 < |n|^2 <= n_max^2 (n_max <= 32), summed per shell s = |n|^2 (index s + 1).
+Returns `(count, sq)`: `count` the Int32 number of vectors of each shell; `sq` an
+`(n_max^2 + 1, 6, R)` Int64 array in units of 2^-24 with `per_replica`, else an `(n_max^2 + 1, 6)`
+Float64 matrix summed over the replicas (column k = row k of the C layout: slot pairs (0,0) (0,1)
+(0,2) (1,1) (1,2) (2,2), a cross term held once).  S_ab(q) = sq / (count sqrt(N_a N_b) frames);
+read-only for the chains.  With per-replica boxes only `per_replica = true`.
+"""
+function structure_factor(b::Batch, n_max::Integer; per_replica::Bool = false)
+    1 <= n_max <= 32 || error("n_max must be in 1..32")
+    S = n_max * n_max + 1
+    count = zeros(Int32, S)
+    if per_replica
+        sq = zeros(Int64, S, 6, b.n_replicas)
+        check(ccall((:mmc_batch_structure_factor, libmmc), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}),
+                    b.h, n_max, 1, count, sq, C_NULL))
+        return count, sq
+    end
+    sq_sum = zeros(Float64, S, 6)
+    check(ccall((:mmc_batch_structure_factor, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}),
+                b.h, n_max, 0, count, C_NULL, sq_sum))
+    return count, sq_sum
+end
+
 # ---- local order (include/mmc_hip.h, mmc_batch_local_order) ----------------------------------------
 """
     local_order(b; q_bins = 400, r_hb = 3.5, theta_deg = 30.0, per_replica = false)

@@ -107,6 +107,78 @@ def orient_projections(hist, n_mol, dr, inv_volume_sum):
     return r, g, h110, h112, p2
 
 
+# ---- partial structure factors (include/mmc_hip.h, "Partial structure factors") --------------------
+SOFQ_SCALE = 2.0 ** 24  # MMC_SOFQ_SCALE: one unit of mmc_batch_structure_factor's per-replica integers
+
+
+def structure_factor_shells(n_max, box):
+    """(s, count, q) of the non-empty shells of mmc_batch_structure_factor: s = |n|^2 in
+    1..n_max^2, count = the integer vectors n with |n|^2 = s (r_3(s)), q = 2 pi sqrt(s) / box."""
+    n_max = int(n_max)
+    if n_max < 1:
+        raise ValueError("n_max >= 1")
+    n = np.arange(-n_max, n_max + 1)
+    s3 = (n * n)[:, None, None] + (n * n)[None, :, None] + (n * n)[None, None, :]
+    count = np.bincount(s3[s3 <= n_max * n_max].ravel(), minlength=n_max * n_max + 1)
+    count[0] = 0
+    s = np.flatnonzero(count)
+    return s, count[s], 2.0 * np.pi * np.sqrt(s.astype(np.float64)) / float(box)
+
+
+def _sofq_rows(sq, count):
+    """float64 [..., 6, shells] in units of 1 of the non-empty shells, and their counts."""
+    sq, count = np.asarray(sq), np.asarray(count)
+    if sq.ndim < 2 or sq.shape[-2] != 6 or count.shape != (sq.shape[-1],):
+        raise ValueError("sq must be [..., 6, n_max^2 + 1] and count [n_max^2 + 1] (mmc_batch_structure_factor)")
+    rows = sq / SOFQ_SCALE if np.issubdtype(sq.dtype, np.integer) else sq.astype(np.float64)
+    keep = np.flatnonzero(count)
+    return rows[..., keep], count[keep].astype(np.float64)
+
+
+def partial_structure_factors(sq, count, n_mol, slot_types, n_frames=1):
+    """Ashcroft-Langreth partial structure factors from mmc_batch_structure_factor's output:
+    S_tu(q) = <rho_t rho_u*> / sqrt(N_t N_u), averaged over the shell's vectors, with rho_t the sum
+    of the slot densities of type t and N_t = n_mol times the slots of that type.  sq: int64
+    [..., 6, n_max^2 + 1] (per replica, units of 2^-24) or float64 (the summed output, or a sum of
+    outputs over several calls); n_frames: the frames summed into it (calls, times the replicas for
+    a summed output).  slot_types as fold_by_type, e.g. ("O", "H", "H"); keys are (t, u) with
+    t <= u.  A cross row (a, b), a < b, enters S_tt twice (rho_a rho_b* and its conjugate) and S_tu,
+    t != u, once.  Returns {(t, u): [..., shells]} over the non-empty shells, in
+    structure_factor_shells' order."""
+    if len(slot_types) != 3:
+        raise ValueError("slot_types: three types")
+    rows, cnt = _sofq_rows(sq, count)
+    n_type = {t: float(n_mol) * sum(1 for u in slot_types if u == t) for t in slot_types}
+    out = {}
+    for k, (a, b) in enumerate(SLOT_PAIRS):
+        ta, tb = slot_types[a], slot_types[b]
+        key = tuple(sorted((ta, tb)))
+        w = 2.0 if (a != b and ta == tb) else 1.0
+        term = w * rows[..., k, :] / (np.sqrt(n_type[ta] * n_type[tb]) * cnt * float(n_frames))
+        out[key] = out[key] + term if key in out else term
+    return out
+
+
+def charge_structure_factor(sq, count, charges, n_mol, n_frames=1):
+    """S_ZZ(q) = <|sum_a q_a rho_a|^2> / N per non-empty shell from mmc_batch_structure_factor's
+    output (sq and n_frames as partial_structure_factors): charges the three slot charges in e, the
+    cross rows doubled.  Returns [..., shells]."""
+    qa = np.asarray(charges, dtype=np.float64).ravel()
+    if qa.shape != (3,):
+        raise ValueError("charges: one per slot")
+    rows, cnt = _sofq_rows(sq, count)
+    w = np.array([(1.0 if a == b else 2.0) * qa[a] * qa[b] for a, b in SLOT_PAIRS])
+    return np.tensordot(rows, w, axes=([-2], [0])) / (float(n_mol) * cnt * float(n_frames))
+
+
+def dielectric_longitudinal(szz, q, n_mol, volume, temperature, factor):
+    """The longitudinal dielectric response 1 - 1 / eps_L(q) = 4 pi beta factor N S_ZZ(q) / (V q^2)
+    from charge_structure_factor's S_ZZ (e^2 per molecule) at q in 1 / A: volume in A^3, temperature
+    in K, factor the library's e^2 / A -> K constant."""
+    szz, q = np.asarray(szz, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    return 4.0 * np.pi * float(factor) * float(n_mol) * szz / (float(volume) * float(temperature) * q * q)
+
+
 # ---- hydrogen bonds and tetrahedral order (include/mmc_hip.h, "Local order") -----------------------
 def hbonds_per_molecule(hb_hist):
     """Mean number of donated, accepted and total hydrogen bonds per molecule from an
