@@ -342,9 +342,9 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *   "inject_torn"      N > 0: the native driver corrupts its first N copies of result records
  *                      before checking them, as a torn PCIe write would (test hook: the check must
  *                      refuse them and read again; mmc_run_stats.torn_records counts them)
- *   "local_stage"      0 = mmc_batch_local_order reads the O positions from device memory even where a
- *                      replica's fit in LDS (default 1; the path of systems too large to stage,
- *                      same results: a test hook)
+ *   "local_stage"      0 = mmc_batch_local_order and mmc_batch_cavity read the site positions from device
+ *                      memory even where a replica's fit in LDS (default 1; the path of systems too
+ *                      large to stage, same results: a test hook)
  *   "zero_copy_moves"  1 = the kernel reads proposals from pinned host memory instead of an
  *                      H2D copy on the stream (lower latency for one replica, default 0)
  *   "device_moves"     1 = mmc_batch_run / mmc_batch_run_chains generate the trial moves on the
@@ -995,6 +995,72 @@ int32_t mmc_batch_structure_factor(mmc_batch *b, int32_t n_max, int32_t per_repl
 int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t q_bins,
                               int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist,
                               double *q_sum, int32_t *nbr_out, double *q_out, uint8_t *hb_out);
+
+/* ---- Cavities and occupancy: p_n(R), its moments and the cavity-size distribution ---------------
+ * How many sites lie within R of a random point of the liquid, for up to eight radii at once, and
+ * how far the nearest site is: the occupancy distribution p_n(R) of scaled-particle and
+ * information theory (Hummer, Garde, Garcia, Pohorille and Pratt, PNAS 93, 8951, 1996).  p_0(R) is
+ * the probability of a cavity of exclusion radius R, and -T ln p_0(R) the excess chemical potential
+ * of a hard sphere that keeps the sites at R.  The reference has no such analysis; the arithmetic is
+ * defined here and restated in numpy by tests/cavity_ref.py.  All results are integers or plain
+ * copies: nothing is left to a tolerance.
+ *   - Sites.  site = 0, 1 or 2: that atom slot of every molecule (slot 0 is the oxygen of every water
+ *     deck here); site = -1: the stored centre of mass.  One site per molecule, N in all.
+ *   - Probe points of mmc_batch_cavity.  Probe j of replica r is (u0, u1, u2) L_r: u0, u1 the two
+ *     uniforms of Philox slot MMC_SLOT_CAVITY + 0, u2 the first uniform of slot MMC_SLOT_CAVITY + 1,
+ *     counter draw0 + j, key = seed, replica index = the index in the batch; L_r the replica's own box
+ *     with per-replica boxes.  MMC_SLOT_CAVITY == MMC_SLOT_WIDOM: this is bit for bit the COM that
+ *     mmc_batch_widom draws for the same (seed, draw0 + j, r) (observables.widom_molecules;
+ *     observables.cavity_points is the host mirror).  mmc_batch_cavity_at takes the caller's
+ *     points_in [R][n_probe][3] instead.
+ *   - Distances.  d = vector1D(point, site) (Ewald/boundaries.jl; csrc/mmc_device.hpp) per component
+ *     with the replica's own box; r^2 = (dx dx + dy dy) + dz dz in unfused fp64.  (The kernel takes
+ *     |d| through vector1D_abs: the same bits once squared.)
+ *   - Occupancy.  For radius k, n_k = the number of sites with r^2 < radii[k] radii[k] (strict; the
+ *     square formed in fp64 by the host).  occ_hist[k][min(n_k, n_cap)] += 1 per probe: [K][n_cap + 1],
+ *     [R][K][n_cap + 1] with per_replica; the last bin means "n_cap or more".
+ *     occ_mom[k] += (n_k, n_k n_k), unclamped, as 64-bit integers: [K][2] or [R][K][2].
+ *     count_out [R][n_probe][K]: the unclamped n_k.
+ *   - Nearest site.  The minimum over the sites under the key (bit pattern of r^2, then index j):
+ *     ties go to the lower index.  nn_r2_out [R][n_probe] and nn_idx_out [R][n_probe] (0-based).
+ *     Its histogram uses no square root: with dr = nn_max / nn_bins and e2[m] = (m dr)(m dr) for
+ *     m = 0 .. nn_bins, both products in fp64, the bin is the largest m with e2[m] <= r^2 of the
+ *     nearest site (numpy: searchsorted(e2, r2, side = "right") - 1).  nn_hist [nn_bins + 1], or
+ *     [R][nn_bins + 1] with per_replica; the last bin means "at or beyond nn_max".  Summed from the
+ *     top, nn_hist is p_0(R) at every edge m dr from one pass: the cavity-size distribution
+ *     (observables.cavity_size_distribution).
+ *   - Outputs.  All are overwritten, not accumulated.  Each may be NULL, but not all three of
+ *     occ_hist, occ_mom and nn_hist; without nn_hist, nn_bins and nn_max are ignored.  All sums are
+ *     integers: no order of lanes, waves, atomics or flushes can change a bit, whatever the grid or
+ *     option "wave_wgs".
+ *   - Use (observables.py): occupancy_probabilities, occupancy_moments, cavity_mu_ex,
+ *     cavity_size_distribution, and information_theory_pn, the two-moment maximum-entropy p_n.
+ * Both box modes and either Coulomb style: the call reads coordinates only -- no erfc table, no S(k)
+ * -- and is read-only exactly as mmc_batch_local_order is (coordinates, S(k), flags, step counters
+ * and random streams are not touched; S(k) need not be fresh).  Preconditions as
+ * mmc_batch_rdf_sites: no proposals outstanding, no volume trial in flight, no run that failed
+ * half-way (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: n_probe outside 1..2^20; site outside -1..2; n_radii outside
+ * 1..MMC_CAVITY_MAX_RADII; radii NULL; a radius not finite, <= 0 or not strictly above the one before;
+ * n_cap outside 1..MMC_CAVITY_MAX_CAP; with nn_hist, nn_bins outside 1..MMC_CAVITY_MAX_BINS or nn_max
+ * not finite or <= 0; occ_hist, occ_mom and nn_hist all NULL; points_in NULL.  Checked with the
+ * batch: a non-finite point; a radius above half of the smallest box; N^2 R n_probe >= 2^63 (the
+ * moment sums could wrap).  Then the state; then MMC_ERR_UNSUPPORTED: more than 2^21 molecules.  On
+ * any error every output is left untouched. */
+#define MMC_SLOT_CAVITY        MMC_SLOT_WIDOM   /* the probe points ARE Widom's COM draws */
+#define MMC_CAVITY_MAX_RADII   8
+#define MMC_CAVITY_MAX_CAP     255
+#define MMC_CAVITY_MAX_BINS    4096
+int32_t mmc_batch_cavity(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, int32_t site,
+                         int32_t n_radii, const double *radii, int32_t n_cap,
+                         int32_t nn_bins, double nn_max, int32_t per_replica,
+                         uint64_t *occ_hist, uint64_t *occ_mom, uint64_t *nn_hist,
+                         double *points_out, int32_t *count_out, double *nn_r2_out, int32_t *nn_idx_out);
+int32_t mmc_batch_cavity_at(mmc_batch *b, int64_t n_probe, const double *points_in, int32_t site,
+                            int32_t n_radii, const double *radii, int32_t n_cap,
+                            int32_t nn_bins, double nn_max, int32_t per_replica,
+                            uint64_t *occ_hist, uint64_t *occ_mom, uint64_t *nn_hist,
+                            int32_t *count_out, double *nn_r2_out, int32_t *nn_idx_out);
 
 /* ---- Virtual volume moves: the pressure of every replica in one read-only pass -----------------
  * The volume-perturbation estimator (Eppenga and Frenkel; Harismiadis, Vorholz and Panagiotopoulos)

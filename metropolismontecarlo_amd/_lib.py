@@ -192,6 +192,10 @@ SIGNATURES = {
     "mmc_batch_structure_factor": [_vp, C.c_int32, C.c_int32, _i32p, _i64p, _dp],
     "mmc_batch_local_order": [_vp, _d, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                               _dp, _i32p, _dp, C.POINTER(C.c_uint8)],
+    "mmc_batch_cavity": [_vp, _i64, C.c_uint64, _i64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,
+                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _i32p, _dp, _i32p],
+    "mmc_batch_cavity_at": [_vp, _i64, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,
+                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, _dp, _i32p],
     "mmc_batch_volume_perturb": [_vp, C.c_int32, _dp, _d, _dp, _i64p, _dp, _dp],
     "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, C.c_int32, C.POINTER(RunStats)],
     "mmc_chain_block_line": [_vp, _i64, _i64, _d, _d, C.c_char_p, _i64],

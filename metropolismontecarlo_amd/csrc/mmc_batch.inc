@@ -102,8 +102,8 @@ struct mmc_batch {
     int coulomb_style = MMC_COULOMB_EWALD; // mmc_batch_set_coulomb_style (main.jl:75)
     bool s_stale = false;       // the style went from Wolf back to Ewald: S(k) does not describe the
                                 // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
-    int local_stage = 1;        // mmc_batch_local_order copies a replica's O positions to LDS where they fit
-                                // (option "local_stage" = 0: never, the path of systems too large for it)
+    int local_stage = 1;        // mmc_batch_local_order and mmc_batch_cavity copy a replica's site positions to LDS
+                                // where they fit (option "local_stage" = 0: never, the path of systems too large for it)
 
     const MoveRec *dev_moves(int which) const
     {

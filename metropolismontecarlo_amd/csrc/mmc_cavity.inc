@@ -1,0 +1,164 @@
+// mmc_cavity.inc -- host side of mmc_batch_cavity and mmc_batch_cavity_at (include/mmc_hip.h,
+// "Cavities and occupancy"; the kernel is in mmc_cavity.hpp).  Included by mmc_hip.hip after
+// mmc_struct.inc, whose state checks it shares, and after mmc_units.inc, whose device scratch
+// (obs_scratch) it uses.
+#include "mmc_cavity.hpp"
+
+static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, const double *points_in,
+                          bool at, int32_t site, int32_t n_radii, const double *radii, int32_t n_cap,
+                          int32_t nn_bins, double nn_max, int32_t per_replica, uint64_t *occ_hist,
+                          uint64_t *occ_mom, uint64_t *nn_hist, double *points_out, int32_t *count_out,
+                          double *nn_r2_out, int32_t *nn_idx_out, const char *what)
+{
+    // what can be refused without the batch comes first
+    MMC_REQUIRE(n_probe >= 1 && n_probe <= (1 << 20), MMC_ERR_ARG, "%s: n_probe outside 1..2^20", what);
+    MMC_REQUIRE(site >= -1 && site <= 2, MMC_ERR_ARG,
+                "%s: site must be an atom slot 0..2 or -1 (the centre of mass)", what);
+    MMC_REQUIRE(n_radii >= 1 && n_radii <= MMC_CAVITY_MAX_RADII, MMC_ERR_ARG, "%s: n_radii outside 1..%d", what,
+                MMC_CAVITY_MAX_RADII);
+    MMC_REQUIRE(radii, MMC_ERR_ARG, "%s: NULL radii", what);
+    for (int k = 0; k < n_radii; k++)
+        MMC_REQUIRE(std::isfinite(radii[k]) && radii[k] > 0.0 && (k == 0 || radii[k] > radii[k - 1]), MMC_ERR_ARG,
+                    "%s: radii must be finite, > 0 and strictly ascending", what);
+    MMC_REQUIRE(n_cap >= 1 && n_cap <= MMC_CAVITY_MAX_CAP, MMC_ERR_ARG, "%s: n_cap outside 1..%d", what,
+                MMC_CAVITY_MAX_CAP);
+    if (nn_hist) {
+        MMC_REQUIRE(nn_bins >= 1 && nn_bins <= MMC_CAVITY_MAX_BINS, MMC_ERR_ARG, "%s: nn_bins outside 1..%d", what,
+                    MMC_CAVITY_MAX_BINS);
+        MMC_REQUIRE(std::isfinite(nn_max) && nn_max > 0.0, MMC_ERR_ARG, "%s: nn_max must be finite and > 0", what);
+    }
+    MMC_REQUIRE(occ_hist || occ_mom || nn_hist, MMC_ERR_ARG,
+                "%s: give at least one of occ_hist, occ_mom and nn_hist", what);
+    MMC_REQUIRE(!at || points_in, MMC_ERR_ARG, "%s: NULL points_in", what);
+    BATCH_CHECK(b);
+    DeviceSystem &s = b->sys;
+    const int64_t R = s.R, N = s.n_mol, P = n_probe;
+    if (at)
+        for (int64_t q = 0; q < 3 * R * P; q++)
+            MMC_REQUIRE(std::isfinite(points_in[q]), MMC_ERR_ARG, "%s: non-finite points_in", what);
+    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
+    MMC_REQUIRE(radii[n_radii - 1] <= min_box / 2.0, MMC_ERR_ARG,
+                "%s: radius %g exceeds half of the smallest box %g", what, radii[n_radii - 1], min_box);
+    // the moment sums: a probe adds at most N^2
+    MMC_REQUIRE((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)R * (unsigned __int128)P
+                    < ((unsigned __int128)1 << 63),
+                MMC_ERR_ARG, "%s: N^2 x replicas x n_probe reaches 2^63: the moment sums could wrap", what);
+    STRUCT_STATE(b);
+    BATCH_USABLE(b);
+    MMC_REQUIRE(N >= 1 && N <= (1 << 21), MMC_ERR_UNSUPPORTED, "%s: 1 .. 2^21 molecules", what);
+    // (a batch holds three-atom molecules only, mmc_batch_create: slots 0..2 exist in every molecule)
+
+    // device scratch: the counters first (zeroed), then what is asked for per probe
+    const int K = n_radii;
+    const int64_t n_rep = per_replica ? R : 1;
+    const size_t n_occ = occ_hist ? (size_t)K * (n_cap + 1) : 0, n_nn = nn_hist ? (size_t)nn_bins + 1 : 0;
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t oh_bytes = up16(8 * (size_t)n_rep * n_occ), om_bytes = up16(occ_mom ? 16 * (size_t)n_rep * K : 0);
+    const size_t nh_bytes = up16(8 * (size_t)n_rep * n_nn);
+    const bool want_pts = at || points_out;
+    const size_t pt_bytes = up16(want_pts ? 24 * (size_t)(R * P) : 0), ct_bytes = up16(count_out ? 4 * (size_t)(R * P) * K : 0);
+    const size_t r2_bytes = up16(nn_r2_out ? 8 * (size_t)(R * P) : 0), ix_bytes = up16(nn_idx_out ? 4 * (size_t)(R * P) : 0);
+    char *d_buf = nullptr;
+    MMC_TRY(obs_scratch(b, oh_bytes + om_bytes + nh_bytes + pt_bytes + ct_bytes + r2_bytes + ix_bytes, &d_buf));
+    char *d_oh = d_buf, *d_om = d_oh + oh_bytes, *d_nh = d_om + om_bytes, *d_pt = d_nh + nh_bytes,
+         *d_ct = d_pt + pt_bytes, *d_r2 = d_ct + ct_bytes, *d_ix = d_r2 + r2_bytes;
+
+    CavityArgs ca{};
+    ca.box_r = s.pb.on ? s.pb.d_box : nullptr;
+    ca.points_in = at ? reinterpret_cast<const double *>(d_pt) : nullptr;
+    ca.points_out = (!at && points_out) ? reinterpret_cast<double *>(d_pt) : nullptr;
+    ca.occ_hist = occ_hist ? reinterpret_cast<unsigned long long *>(d_oh) : nullptr;
+    ca.occ_mom = occ_mom ? reinterpret_cast<unsigned long long *>(d_om) : nullptr;
+    ca.nn_hist = nn_hist ? reinterpret_cast<unsigned long long *>(d_nh) : nullptr;
+    ca.count = count_out ? reinterpret_cast<int32_t *>(d_ct) : nullptr;
+    ca.nn_r2 = nn_r2_out ? reinterpret_cast<double *>(d_r2) : nullptr;
+    ca.nn_idx = nn_idx_out ? reinterpret_cast<int32_t *>(d_ix) : nullptr;
+    for (int k = 0; k < CV_MAX_RADII; k++)
+        ca.rad2[k] = k < K ? radii[k] * radii[k] : 0.0;
+    ca.rmax2 = ca.rad2[K - 1];
+    ca.dr = nn_hist ? nn_max / nn_bins : 1.0;
+    ca.seed = seed;
+    ca.draw0 = draw0;
+    ca.n_probe = (int32_t)P;
+    ca.n_radii = K;
+    ca.n_cap = n_cap;
+    ca.nn_bins = nn_hist ? nn_bins : 0;
+    ca.site = site;
+    ca.per_replica = per_replica ? 1 : 0;
+    ca.R = (int32_t)R;
+
+    // waves per workgroup: as many of CV_WAVES as keep their counters within half of the LDS; the site
+    // positions are staged when they fit in the rest
+    const size_t per_wave = 4 * (n_occ + n_nn);
+    int nw = CV_WAVES;
+    while (nw > 1 && (size_t)nw * per_wave > CV_LDS_BYTES / 2)
+        nw >>= 1;
+    const size_t lds_w = up16((size_t)nw * per_wave);
+    const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= CV_LDS_BYTES;
+    const size_t lds = lds_w + (stage ? 24 * (size_t)N : 0);
+    // persistent workgroups: four waves per SIMD of every compute unit, or option "wave_wgs"; no more
+    // than give every wave a block of 64 probes
+    const int64_t units = R * ((P + 63) / 64);
+    int64_t wgs = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(16 / nw) * b->n_cus;
+    wgs = std::max<int64_t>(1, std::min(wgs, (units + nw - 1) / nw));
+
+    hipStream_t st = s.stream;
+    hipError_t e = hipMemsetAsync(d_buf, 0, oh_bytes + om_bytes + nh_bytes, st);
+    if (e == hipSuccess && at)
+        e = hipMemcpyAsync(d_pt, points_in, 24 * (size_t)(R * P), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        const bool use_rec = struct_use_rec(b);
+        const unsigned g = (unsigned)wgs, t = (unsigned)nw * 64;
+        if (use_rec && stage)
+            k_cavity_lane<true, true><<<g, t, lds, st>>>(s.bv, s.rec, ca);
+        else if (use_rec)
+            k_cavity_lane<true, false><<<g, t, lds, st>>>(s.bv, s.rec, ca);
+        else if (stage)
+            k_cavity_lane<false, true><<<g, t, lds, st>>>(s.bv, nullptr, ca);
+        else
+            k_cavity_lane<false, false><<<g, t, lds, st>>>(s.bv, nullptr, ca);
+        e = hipGetLastError();
+    }
+    // everything goes through host copies: the caller's arrays are written only on success
+    const size_t out_bytes[7] = { 8 * (size_t)n_rep * n_occ, occ_mom ? 16 * (size_t)n_rep * K : 0, 8 * (size_t)n_rep * n_nn,
+                                  (!at && points_out) ? 24 * (size_t)(R * P) : 0, count_out ? 4 * (size_t)(R * P) * K : 0,
+                                  nn_r2_out ? 8 * (size_t)(R * P) : 0, nn_idx_out ? 4 * (size_t)(R * P) : 0 };
+    const char *d_src[7] = { d_oh, d_om, d_nh, d_pt, d_ct, d_r2, d_ix };
+    void *dst[7] = { occ_hist, occ_mom, nn_hist, points_out, count_out, nn_r2_out, nn_idx_out };
+    std::vector<char> h_out[7];
+    for (int k = 0; k < 7 && e == hipSuccess; k++) {
+        if (!out_bytes[k])
+            continue;
+        h_out[k].resize(out_bytes[k]);
+        e = hipMemcpyAsync(h_out[k].data(), d_src[k], out_bytes[k], hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    else
+        (void)hipStreamSynchronize(st); // (the host buffers of copies already queued outlive them)
+    MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    for (int k = 0; k < 7; k++)
+        if (out_bytes[k])
+            memcpy(dst[k], h_out[k].data(), out_bytes[k]);
+    return MMC_OK;
+}
+
+extern "C" int32_t mmc_batch_cavity(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, int32_t site,
+                                    int32_t n_radii, const double *radii, int32_t n_cap, int32_t nn_bins,
+                                    double nn_max, int32_t per_replica, uint64_t *occ_hist, uint64_t *occ_mom,
+                                    uint64_t *nn_hist, double *points_out, int32_t *count_out, double *nn_r2_out,
+                                    int32_t *nn_idx_out)
+{
+    return cavity_run(b, n_probe, seed, draw0, nullptr, false, site, n_radii, radii, n_cap, nn_bins, nn_max,
+                      per_replica, occ_hist, occ_mom, nn_hist, points_out, count_out, nn_r2_out, nn_idx_out,
+                      "mmc_batch_cavity");
+}
+
+extern "C" int32_t mmc_batch_cavity_at(mmc_batch *b, int64_t n_probe, const double *points_in, int32_t site,
+                                       int32_t n_radii, const double *radii, int32_t n_cap, int32_t nn_bins,
+                                       double nn_max, int32_t per_replica, uint64_t *occ_hist, uint64_t *occ_mom,
+                                       uint64_t *nn_hist, int32_t *count_out, double *nn_r2_out, int32_t *nn_idx_out)
+{
+    return cavity_run(b, n_probe, 0, 0, points_in, true, site, n_radii, radii, n_cap, nn_bins, nn_max, per_replica,
+                      occ_hist, occ_mom, nn_hist, nullptr, count_out, nn_r2_out, nn_idx_out, "mmc_batch_cavity_at");
+}

@@ -17,5 +17,6 @@
 #include "mmc_orient.inc"
 #include "mmc_sofq.inc"
 #include "mmc_local.inc"
+#include "mmc_cavity.inc"
 #include "mmc_vperturb.inc"
 #include "mmc_dist.inc"

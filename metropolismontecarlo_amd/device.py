@@ -794,6 +794,60 @@ class Batch:
             ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
         return res
 
+    def _cavity(self, points, n_probe, seed, draw0, radii, site, n_cap, nn_bins, nn_max, per_replica, details):
+        R, P = self.R, max(int(n_probe), 0)
+        rad = _f64(np.atleast_1d(radii)).ravel()
+        K, cap, nb = rad.shape[0], max(int(n_cap), 0), max(int(nn_bins), 0)
+        lead = (R,) if per_replica else ()
+        # (sizes the library refuses still get arrays to leave alone)
+        res = {"occ_hist": np.zeros(lead + (K, cap + 1), dtype=np.uint64),
+               "occ_mom": np.zeros(lead + (K, 2), dtype=np.uint64)}
+        if nb > 0:
+            res["nn_hist"] = np.zeros(lead + (nb + 1,), dtype=np.uint64)
+            if nn_max is None:
+                raise ValueError("nn_bins > 0 needs nn_max")
+        if details:
+            if points is None:
+                res["points"] = np.zeros((R, P, 3))
+            res.update(count=np.zeros((R, P, K), dtype=np.int32), nn_r2=np.zeros((R, P)),
+                       nn_idx=np.zeros((R, P), dtype=np.int32))
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        common = (int(site), K, _d(rad), int(n_cap), nb, float(nn_max) if nb > 0 else 0.0, int(bool(per_replica)),
+                  ptr("occ_hist", C.c_uint64), ptr("occ_mom", C.c_uint64), ptr("nn_hist", C.c_uint64))
+        tail = (ptr("count", C.c_int32), ptr("nn_r2", C.c_double), ptr("nn_idx", C.c_int32))
+        if points is None:
+            check(self._L.mmc_batch_cavity(self._h, int(n_probe), int(seed) & (2 ** 64 - 1), int(draw0), *common,
+                                           ptr("points", C.c_double), *tail))
+        else:
+            check(self._L.mmc_batch_cavity_at(self._h, int(n_probe), _d(points), *common, *tail))
+            if details:
+                res["points"] = points
+        return res
+
+    def cavity(self, n_probe, seed, draw0=0, radii=(3.3,), site=0, n_cap=32, nn_bins=0, nn_max=None,
+               per_replica=False, details=False):
+        """mmc_batch_cavity: n_probe random points in every replica (bit for bit the COMs widom draws
+        for the same seed and draw0), read-only.  For each radius (1..8, ascending, A) the number n
+        of sites -- atom slot `site` of every molecule, or the centres of mass with site = -1 --
+        closer than it to a point.  Returns a dict: occ_hist uint64 [K, n_cap + 1] (points with
+        n = 0 .. n_cap; the last bin stands for n_cap or more), occ_mom uint64 [K, 2] (the sums of n
+        and n^2, unclamped) and, with nn_bins > 0, nn_hist uint64 [nn_bins + 1]: the distance of the
+        nearest site in bins of nn_max / nn_bins, the last for nn_max and beyond
+        (observables.cavity_size_distribution) -- each [R, ...] with per_replica.  details=True adds
+        points [R, n_probe, 3], count int32 [R, n_probe, K], nn_r2 [R, n_probe] and nn_idx int32
+        [R, n_probe]."""
+        return self._cavity(None, n_probe, seed, draw0, radii, site, n_cap, nn_bins, nn_max, per_replica, details)
+
+    def cavity_at(self, points, radii=(3.3,), site=0, n_cap=32, nn_bins=0, nn_max=None, per_replica=False,
+                  details=False):
+        """mmc_batch_cavity_at: as cavity(), at the caller's points (R, n_probe, 3)."""
+        points = _f64(points)
+        if points.ndim != 3 or points.shape[0] != self.R or points.shape[2] != 3:
+            raise ValueError("points must be (R, n_probe, 3)")
+        return self._cavity(points, points.shape[1], 0, 0, radii, site, n_cap, nn_bins, nn_max, per_replica, details)
+
     def volume_perturb(self, temperature, scales=None, dv=None, boltz_sum=None, n_overlap=None, details=False):
         """mmc_batch_volume_perturb: virtual volume moves of every replica, read-only.  Test boxes
         L_k = scales[k] L (1..8 of them), or volume changes dv (A^3) converted by

@@ -753,6 +753,55 @@ function local_order(b::Batch; q_bins::Integer = 400, r_hb::Float64 = 3.5, theta
     return hb_hist, q_hist, q_sum
 end
 
+# ---- cavities and occupancy (include/mmc_hip.h, mmc_batch_cavity, mmc_batch_cavity_at) --------------
+"""
+    cavity(b, n_probe, seed; draw0 = 0, radii = [3.3], site = 0, n_cap = 32, nn_bins = 0, nn_max = 0.0,
+           per_replica = false)
+    cavity_at(b, points; radii = [3.3], site = 0, n_cap = 32, nn_bins = 0, nn_max = 0.0, per_replica = false)
+
+Occupancy statistics of probe spheres in one read-only pass: for each of the 1 to 8 ascending `radii`
+the number n of sites (atom slot `site` = 0, 1, 2 of every molecule, C numbering; -1 = the centres of
+mass) closer than it to each of `n_probe` random points per replica -- bit for bit the COMs `widom!`
+draws for the same `seed` and `draw0` -- or to the caller's `points` `(3, n_probe, R)`.  Returns
+`(occ_hist, occ_mom, nn_hist)`: `occ_hist` `(n_cap + 1, K)` UInt64 (points with n = 0..n_cap, the last
+row n_cap or more), `occ_mom` `(2, K)` (the sums of n and n^2) and, with `nn_bins > 0`, `nn_hist`
+`nn_bins + 1` counts of the distance to the nearest site in bins of `nn_max / nn_bins` (else
+`nothing`); each with a trailing dimension R with `per_replica`.
+"""
+function cavity(b::Batch, n_probe::Integer, seed::Integer; draw0::Integer = 0, radii::Vector{Float64} = [3.3],
+                site::Integer = 0, n_cap::Integer = 32, nn_bins::Integer = 0, nn_max::Float64 = 0.0,
+                per_replica::Bool = false)
+    occ_hist, occ_mom, nn_hist = cavity_outputs(b, radii, n_cap, nn_bins, per_replica)
+    check(ccall((:mmc_batch_cavity, libmmc), Int32,
+                (Ptr{Cvoid}, Int64, UInt64, Int64, Int32, Int32, Ptr{Float64}, Int32, Int32, Float64, Int32,
+                 Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                b.h, n_probe, seed % UInt64, draw0, site, length(radii), radii, n_cap, nn_bins, nn_max,
+                per_replica ? 1 : 0, occ_hist, occ_mom, nn_hist === nothing ? C_NULL : nn_hist,
+                C_NULL, C_NULL, C_NULL, C_NULL))
+    return occ_hist, occ_mom, nn_hist
+end
+function cavity_at(b::Batch, points::Array{Float64,3}; radii::Vector{Float64} = [3.3], site::Integer = 0,
+                   n_cap::Integer = 32, nn_bins::Integer = 0, nn_max::Float64 = 0.0, per_replica::Bool = false)
+    size(points, 1) == 3 && size(points, 3) == b.n_replicas || error("points are (3, n_probe, R)")
+    occ_hist, occ_mom, nn_hist = cavity_outputs(b, radii, n_cap, nn_bins, per_replica)
+    check(ccall((:mmc_batch_cavity_at, libmmc), Int32,
+                (Ptr{Cvoid}, Int64, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Float64, Int32,
+                 Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                b.h, size(points, 2), points, site, length(radii), radii, n_cap, nn_bins, nn_max,
+                per_replica ? 1 : 0, occ_hist, occ_mom, nn_hist === nothing ? C_NULL : nn_hist,
+                C_NULL, C_NULL, C_NULL))
+    return occ_hist, occ_mom, nn_hist
+end
+function cavity_outputs(b::Batch, radii::Vector{Float64}, n_cap::Integer, nn_bins::Integer, per_replica::Bool)
+    K = length(radii)
+    1 <= K <= 8 || error("1 to 8 radii")
+    1 <= n_cap <= 255 || error("n_cap must be in 1..255")
+    0 <= nn_bins <= 4096 || error("nn_bins must be in 0..4096")
+    tail = per_replica ? (b.n_replicas,) : ()
+    return zeros(UInt64, n_cap + 1, K, tail...), zeros(UInt64, 2, K, tail...),
+           nn_bins > 0 ? zeros(UInt64, nn_bins + 1, tail...) : nothing
+end
+
 # ---- virtual volume moves (include/mmc_hip.h, mmc_batch_volume_perturb) ---------------------------
 """
     volume_perturb!(b, scales, temperature, boltz_sum, n_overlap)

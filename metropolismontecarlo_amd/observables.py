@@ -281,6 +281,117 @@ def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
     return out
 
 
+# ---- cavities and occupancy (include/mmc_hip.h, "Cavities and occupancy") ---------------------------
+MMC_SLOT_CAVITY = MMC_SLOT_WIDOM  # the probe points are Widom's COM draws: slots +0 and +1
+
+
+def cavity_points(philox, seed, draw0, n_probe, replica, box):
+    """Host mirror of mmc_batch_cavity's generator: [n_probe][3], the probe points of one replica.
+    Probe j uses counter draw0 + j: (u0, u1) of slot MMC_SLOT_CAVITY and the first uniform of slot
+    MMC_SLOT_CAVITY + 1 give the point (u0, u1, u2) box -- widom_molecules(...)[:, 9:] bit for bit."""
+    out = np.empty((int(n_probe), 3))
+    for j in range(int(n_probe)):
+        c = int(draw0) + j
+        u0, u1 = philox_uniforms(philox, seed, c, MMC_SLOT_CAVITY, replica)
+        u2, _ = philox_uniforms(philox, seed, c, MMC_SLOT_CAVITY + 1, replica)
+        out[j] = (u0 * box, u1 * box, u2 * box)
+    return out
+
+
+def occupancy_probabilities(occ_hist, allow_overflow=False):
+    """p_n per radius from mmc_batch_cavity's occ_hist ([..., K, n_cap + 1] counts): each row divided
+    by its number of probes.  The last bin stands for "n_cap or more": unless allow_overflow, a count
+    there is refused (p_n would be wrong at n_cap; ask for a larger n_cap).  Returns [..., K, n_cap + 1]."""
+    h = np.asarray(occ_hist, dtype=np.float64)
+    if h.ndim < 2:
+        raise ValueError("occ_hist must be [..., K, n_cap + 1]")
+    if not allow_overflow and np.any(h[..., -1] != 0):
+        raise ValueError("the overflow bin (n_cap or more) is not empty: raise n_cap, or pass allow_overflow=True")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h / h.sum(-1, keepdims=True)
+
+
+def occupancy_moments(occ_mom, n_total):
+    """(<n>, <dn^2>) per radius from mmc_batch_cavity's occ_mom ([..., K, 2]: the sums of n and n^2
+    over n_total probes): the mean and the variance <n^2> - <n>^2, each [..., K]."""
+    m = np.asarray(occ_mom, dtype=np.float64)
+    if m.shape[-1] != 2:
+        raise ValueError("occ_mom must be [..., K, 2]")
+    mean = m[..., 0] / float(n_total)
+    return mean, m[..., 1] / float(n_total) - mean * mean
+
+
+def cavity_mu_ex(p0, temperature):
+    """The excess chemical potential of a hard sphere from the probability p0 of finding its exclusion
+    sphere empty: -T ln p0 in K, like widom_mu_ex (+inf where p0 is 0)."""
+    with np.errstate(divide="ignore"):
+        return -float(temperature) * np.log(np.asarray(p0, dtype=np.float64))
+
+
+def cavity_size_distribution(nn_hist, nn_max):
+    """(edges [nn_bins + 1], p0 [..., nn_bins + 1]) from mmc_batch_cavity's nn_hist ([..., nn_bins + 1]):
+    edges[m] = m (nn_max / nn_bins) and p0[m] = the fraction of probes whose nearest site is at or
+    beyond edges[m] -- the probability that a sphere of radius edges[m] about a random point is
+    empty, on the whole grid from one pass (p0[0] = 1).  Exactly occ_hist[k][0] / probes for a radius
+    that was passed as m * (nn_max / nn_bins)."""
+    h = np.asarray(nn_hist)
+    nb = h.shape[-1] - 1
+    if nb < 1:
+        raise ValueError("nn_hist must be [..., nn_bins + 1]")
+    edges = np.arange(nb + 1) * (np.float64(nn_max) / nb)
+    tail = np.cumsum(h[..., ::-1].astype(np.uint64), axis=-1)[..., ::-1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return edges, tail.astype(np.float64) / tail[..., :1].astype(np.float64)
+
+
+def information_theory_pn(mean, var, n_max, tol=1e-12, max_iter=200):
+    """The two-moment information-theory model of the occupancy distribution (Hummer et al., PNAS
+    93, 8951, 1996): the maximum-entropy p_n relative to a flat default model on n = 0 .. n_max with
+    the given mean and variance, p_n = exp(l1 n + l2 n^2) / Z.  The two multipliers come from a
+    damped Newton iteration on the convex dual ln Z - l1 <n> - l2 <n^2>, started at the continuous
+    Gaussian (l2 = -1 / (2 var), l1 = mean / var).  Returns p [n_max + 1]; p[0] is the model's cavity
+    probability.  Raises when the moments cannot be met on the grid."""
+    mean, var, n_max = float(mean), float(var), int(n_max)
+    if not (n_max >= 2 and 0.0 < mean < n_max and var > 0.0):
+        raise ValueError("needs n_max >= 2, 0 < mean < n_max and var > 0")
+    n = np.arange(n_max + 1, dtype=np.float64)
+    f = np.stack([n, n * n])
+    target = np.array([mean, var + mean * mean])
+    lam = np.array([mean / var, -0.5 / var])
+
+    def model(l):
+        a = l[0] * n + l[1] * n * n
+        a -= a.max()
+        w = np.exp(a)
+        z = w.sum()
+        return w / z, np.log(z) + (l[0] * n + l[1] * n * n).max() - l @ target
+
+    p, dual = model(lam)
+    for _ in range(int(max_iter)):
+        g = f @ p - target
+        if np.all(np.abs(g) <= tol * np.maximum(1.0, np.abs(target))):
+            return p
+        d = f - (f @ p)[:, None]
+        hess = (d * p) @ d.T
+        try:
+            step = np.linalg.solve(hess, g)
+        except np.linalg.LinAlgError:
+            break
+        t = 1.0
+        while t > 1e-10:
+            p_new, dual_new = model(lam - t * step)
+            if np.isfinite(dual_new) and dual_new <= dual:
+                break
+            t *= 0.5
+        else:
+            break
+        lam, p, dual = lam - t * step, p_new, dual_new
+    g = f @ p - target
+    if np.all(np.abs(g) <= 1e-8 * np.maximum(1.0, np.abs(target))):
+        return p
+    raise ValueError("no two-moment distribution on 0..n_max has these moments (or the solve did not converge)")
+
+
 # ---- deletion energies, overlapping distributions and BAR (include/mmc_hip.h, mmc_batch_deletion) ----
 def energy_bins(du, n_bins, u_lo, u_hi):
     """mmc_batch_deletion's binning rule in numpy, for histogramming mmc_batch_widom's insertion
