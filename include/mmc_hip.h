@@ -365,6 +365,11 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *                      there are about 8 threads per 32768-move launch).  -1 (default) = 1 where
  *                      a launch can take several steps ("steps_per_launch"), or where a host thread
  *                      would have more than 4096 records per launch to decide; else 0.
+ *                      The record of a launch of several steps ("steps_per_launch") has three words:
+ *                      the sum of dU over the accepted steps, the accepted | overlap << 32 masks
+ *                      and the kinds of the moves.  It carries NO virial: such launches compute
+ *                      none (mmc_batch_run_chains, which accumulates the virial, takes one step
+ *                      per launch).
  *   "steps_per_launch" where the move kernel decides (above) and the caller asks for energies and
  *                      counts only (mmc_batch_run; not _run_chains, not the "trace_steps" hook), ONE
  *                      launch takes every replica of a group through this many consecutive steps

@@ -519,6 +519,11 @@ struct DecideConsts {
 //   [1] bit k: step k accepted; bit 32 + k: step k saw an overlap (an integer in a double's bits)
 //   [2] bit k: step k was a rotation
 //   [3..6] 0;  word 7 as ever (stamp, checksum; bit 31: the LAST step's decision)
+// Three words -- dU, the accept | overlap masks, the kinds -- and NO virial: the host's n_sub > 1
+// branch (Driver::metropolis) reads nothing else.  So the instantiations that send this record
+// (k_move_eval_wave<.., MULTI = true>, launched with n_sub > 1 only: mmc_batch.inc) compute only
+// what mmc_move_delta reads, sums 0, 1, 4, 5 and 6: no LJ virial in the pair loops (WV_VIRIAL 0), a
+// reduction of four sums (wave_sum4_add), and checksum and word 7 only in the step that stores.
 #define MMC_STEPS_PER_LAUNCH_MAX 32
 
 // grid (n_parts, R).  n_parts == 1: the workgroup scans all molecules and then does the

@@ -144,6 +144,30 @@ __device__ __forceinline__ void wave_sum6_add(double v0, double v1, double v2, d
         out[lane] += ((r[0] + r[1]) + r[2]) + r[3];
     }
 }
+// The same for four sums, added to out[0], [1], [4], [5] by lanes 0..3 (scratch: 16 doubles): what
+// wave_sum6_add does with (v0, v1) and (v4, v5), without the pair in between -- a pair part whose
+// includer has no use for the virial (WV_VIRIAL 0 in mmc_wave_unit.inc).
+__device__ __forceinline__ void wave_sum4_add(double v0, double v1, double v4, double v5, double *out,
+                                              double *scratch, int lane)
+{
+    const bool odd = (lane & 1) != 0;
+    double p0 = (odd ? v1 : v0) + dpp_quad_swap_f64(odd ? v0 : v1);
+    double p1 = (odd ? v5 : v4) + dpp_quad_swap_f64(odd ? v4 : v5);
+    p0 += dpp_row_shr_f64<2>(p0); p1 += dpp_row_shr_f64<2>(p1);
+    p0 += dpp_row_shr_f64<4>(p0); p1 += dpp_row_shr_f64<4>(p1);
+    p0 += dpp_row_shr_f64<8>(p0); p1 += dpp_row_shr_f64<8>(p1);
+    if ((lane & 14) == 14) { // lanes 14 and 15 of each row: the row totals of (v0, v1), (v4, v5)
+        double *dst = scratch + 4 * (lane & 1) + (lane >> 4);
+        dst[0] = p0; dst[8] = p1;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 4) {
+        const double *r = scratch + 4 * lane;
+        out[lane < 2 ? lane : lane + 2] += ((r[0] + r[1]) + r[2]) + r[3];
+    }
+}
 // (The same packing for the three sums of k_total_wave measured 12 % SLOWER per evaluation, round 4:
 // that kernel is bound by vector issue with its sums in flight beside the next unit's scan.)
 // One sum, the total STORED to *out by lane 0 (scratch: 4 doubles): wave_sum_rows' bits.
@@ -253,8 +277,10 @@ __device__ __forceinline__ int wave_ticket(unsigned *queue, unsigned base, int n
 // unit, same L1) instead of substituting the pending words in every gather and scan block.
 // IMG = true: the minimum image of an atom pair from the image of its molecule (WV_IMG in
 // mmc_wave_unit.inc; the launch site checks the condition).
-// MULTI = true: several steps of the chain per launch (n_sub; the kernel decides) -- its own
-// instantiation, so that the one-step form compiles exactly as it did.
+// MULTI = true: several steps of the chain per launch (n_sub > 1; the kernel decides) -- its own
+// instantiation, so that the one-step form compiles exactly as it did.  Its launches send the record
+// of DecideConsts (mmc_kernels.hpp): dU, the masks, no virial -- so the pair part computes none
+// (WV_VIRIAL 0), and only the step that stores the record makes its checksum.
 // WOLF = true: the chain of main.jl:75 `Wolf = true` (mmc_batch_set_coulomb_style) -- no RecipMove
 // (main.jl:580-590): no phase tables, no k loop, neither S(k) buffer read or written, every part of
 // n_parts > 1 a pair part, the record's reciprocal sum 0.  Its own instantiations again, compiled for
@@ -429,6 +455,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #define WV_SUBST SUBST
 #define WV_IMG IMG
 #define WV_WOLF WOLF
+#define WV_VIRIAL (!MULTI)
 #ifndef WV_XY_MOVE
 #define WV_XY_MOVE 1
 #endif
@@ -443,6 +470,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #undef WV_AFTER_PHASE_TABLES
 #undef WV_IMG
 #undef WV_WOLF
+#undef WV_VIRIAL
 #undef WV_PASSES
 #undef WV_XY
 #undef WV_SUBST

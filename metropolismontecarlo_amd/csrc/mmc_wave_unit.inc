@@ -65,6 +65,17 @@
 #define WV_ZERO 0.0
 #define WV_ZERO_DEFAULTED
 #endif
+#ifndef WV_VIRIAL // 0 (k_move_eval_wave's MULTI instantiations, whose record has no slot for it): the LJ
+#define WV_VIRIAL 1 // virial is not computed; outw[2..3] stay the zeros the pair part starts from
+#define WV_VIRIAL_DEFAULTED
+#endif
+#ifndef WV_STORE_IF // a step whose record is not stored makes neither its checksum nor its word 7
+#define WV_STORE_IF true
+#define WV_STORE_IF_DEFAULTED
+#endif
+#if WV_NS != 2
+static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
+#endif
         double *const outw = sm.outw[wv];
         unsigned long long ovm0 = 0, ovm1 = 0; // lanes that saw an overlap, old / new state
 
@@ -274,6 +285,7 @@
                     // the box (vector1D's own choice, mmc_device.hpp): the image every atom pair
                     // of this neighbour takes in state st
                     constexpr bool wv_img = WV_IMG;
+                    constexpr bool wv_virial = WV_VIRIAL;
                     double m[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
                     auto min1 = [&](int st, int d, double a, double b) {
                         if constexpr (wv_img)
@@ -356,15 +368,20 @@
                                         const double s2 = sg * sg / u;
                                         const double s6 = s2 * s2 * s2;
                                         const double s12 = s6 * s6;
-                                        const double virab = eps * (2.0 * s12 - s6);
-                                        const double f0 = (wv_img ? px : vector1D(ax, bx, bc)) * virab * s2,
-                                                     f1 = (wv_img ? py : vector1D(ay, by, bc)) * virab * s2,
-                                                     f2 = (wv_img ? pz : vector1D(az, bz, bc)) * virab * s2;
+                                        double f0, f1, f2; // (the pair's force, for the virial only)
+                                        if constexpr (wv_virial) {
+                                            const double virab = eps * (2.0 * s12 - s6);
+                                            f0 = (wv_img ? px : vector1D(ax, bx, bc)) * virab * s2;
+                                            f1 = (wv_img ? py : vector1D(ay, by, bc)) * virab * s2;
+                                            f2 = (wv_img ? pz : vector1D(az, bz, bc)) * virab * s2;
+                                        }
                                         a_lj += eps * (s12 - s6);
-                                        // COM vector of the virial (energy.jl:248-250, :279-281)
-                                        a_v += (wv_img ? WV_MIN1(ST, 0, cc[ST][0], t[9]) : vector1D(cc[ST][0], t[9], bc)) * f0
-                                               + (wv_img ? WV_MIN1(ST, 1, cc[ST][1], t[10]) : vector1D(cc[ST][1], t[10], bc)) * f1
-                                               + (wv_img ? WV_MIN1(ST, 2, cc[ST][2], t[11]) : vector1D(cc[ST][2], t[11], bc)) * f2;
+                                        if constexpr (wv_virial) {
+                                            // COM vector of the virial (energy.jl:248-250, :279-281)
+                                            a_v += (wv_img ? WV_MIN1(ST, 0, cc[ST][0], t[9]) : vector1D(cc[ST][0], t[9], bc)) * f0
+                                                   + (wv_img ? WV_MIN1(ST, 1, cc[ST][1], t[10]) : vector1D(cc[ST][1], t[10], bc)) * f1
+                                                   + (wv_img ? WV_MIN1(ST, 2, cc[ST][2], t[11]) : vector1D(cc[ST][2], t[11], bc)) * f2;
+                                        }
                                     }
                                 }
                             };
@@ -426,30 +443,40 @@
                                 const double s2 = sg * sg / u0;
                                 const double s6 = s2 * s2 * s2;
                                 const double s12 = s6 * s6;
-                                const double virab = eps * (2.0 * s12 - s6);
-                                // (WV_IMG: the signed minimum image is what the distance was made of)
-                                const double f0 = (wv_img ? p0x : vector1D(a0x, bx, bc)) * virab * s2,
-                                             f1 = (wv_img ? p0y : vector1D(a0y, by, bc)) * virab * s2,
-                                             f2 = (wv_img ? p0z : vector1D(a0z, bz, bc)) * virab * s2;
+                                double f0, f1, f2; // (the pair's force, for the virial only)
+                                if constexpr (wv_virial) {
+                                    const double virab = eps * (2.0 * s12 - s6);
+                                    // (WV_IMG: the signed minimum image is what the distance was made of)
+                                    f0 = (wv_img ? p0x : vector1D(a0x, bx, bc)) * virab * s2;
+                                    f1 = (wv_img ? p0y : vector1D(a0y, by, bc)) * virab * s2;
+                                    f2 = (wv_img ? p0z : vector1D(a0z, bz, bc)) * virab * s2;
+                                }
                                 a_lj0 += eps * (s12 - s6);
-                                // COM vector of the virial (energy.jl:248-250, :279-281)
-                                a_v0 += (wv_img ? WV_MIN1(0, 0, cc[0][0], t[9]) : vector1D(cc[0][0], t[9], bc)) * f0
-                                        + (wv_img ? WV_MIN1(0, 1, cc[0][1], t[10]) : vector1D(cc[0][1], t[10], bc)) * f1
-                                        + (wv_img ? WV_MIN1(0, 2, cc[0][2], t[11]) : vector1D(cc[0][2], t[11], bc)) * f2;
+                                if constexpr (wv_virial) {
+                                    // COM vector of the virial (energy.jl:248-250, :279-281)
+                                    a_v0 += (wv_img ? WV_MIN1(0, 0, cc[0][0], t[9]) : vector1D(cc[0][0], t[9], bc)) * f0
+                                            + (wv_img ? WV_MIN1(0, 1, cc[0][1], t[10]) : vector1D(cc[0][1], t[10], bc)) * f1
+                                            + (wv_img ? WV_MIN1(0, 2, cc[0][2], t[11]) : vector1D(cc[0][2], t[11], bc)) * f2;
+                                }
                             }
 #endif
                             if (l1 && u1 < pp.lj_slack_sq) {
                                 const double s2 = sg * sg / u1;
                                 const double s6 = s2 * s2 * s2;
                                 const double s12 = s6 * s6;
-                                const double virab = eps * (2.0 * s12 - s6);
-                                const double f0 = (wv_img ? p1x : vector1D(a1x, bx, bc)) * virab * s2,
-                                             f1 = (wv_img ? p1y : vector1D(a1y, by, bc)) * virab * s2,
-                                             f2 = (wv_img ? p1z : vector1D(a1z, bz, bc)) * virab * s2;
+                                double f0, f1, f2; // (the pair's force, for the virial only)
+                                if constexpr (wv_virial) {
+                                    const double virab = eps * (2.0 * s12 - s6);
+                                    f0 = (wv_img ? p1x : vector1D(a1x, bx, bc)) * virab * s2;
+                                    f1 = (wv_img ? p1y : vector1D(a1y, by, bc)) * virab * s2;
+                                    f2 = (wv_img ? p1z : vector1D(a1z, bz, bc)) * virab * s2;
+                                }
                                 a_lj1 += eps * (s12 - s6);
-                                a_v1 += (wv_img ? WV_MIN1(1, 0, cc[1][0], t[9]) : vector1D(cc[1][0], t[9], bc)) * f0
-                                        + (wv_img ? WV_MIN1(1, 1, cc[1][1], t[10]) : vector1D(cc[1][1], t[10], bc)) * f1
-                                        + (wv_img ? WV_MIN1(1, 2, cc[1][2], t[11]) : vector1D(cc[1][2], t[11], bc)) * f2;
+                                if constexpr (wv_virial) {
+                                    a_v1 += (wv_img ? WV_MIN1(1, 0, cc[1][0], t[9]) : vector1D(cc[1][0], t[9], bc)) * f0
+                                            + (wv_img ? WV_MIN1(1, 1, cc[1][1], t[10]) : vector1D(cc[1][1], t[10], bc)) * f1
+                                            + (wv_img ? WV_MIN1(1, 2, cc[1][2], t[11]) : vector1D(cc[1][2], t[11], bc)) * f2;
+                                }
                             }
                         }
                     };
@@ -479,7 +506,10 @@
 #undef WV_MIN1
                 // wave reduction (fixed order: bitwise reproducible)
 #if WV_NS == 2
-                wave_sum6_add(a_lj0, a_lj1, a_v0, a_v1, a_q0, a_q1, outw, sm.sum6w(wv), lane);
+                if constexpr (WV_VIRIAL)
+                    wave_sum6_add(a_lj0, a_lj1, a_v0, a_v1, a_q0, a_q1, outw, sm.sum6w(wv), lane);
+                else
+                    wave_sum4_add(a_lj0, a_lj1, a_q0, a_q1, outw, sm.sum6w(wv), lane);
 #else
                 const double s1 = wave_sum_rows(a_lj1), s3 = wave_sum_rows(a_v1), s5 = wave_sum_rows(a_q1);
                 if (lane == 0) {
@@ -579,20 +609,18 @@
 #else
             const int accept = 0;
 #endif
-            const uint32_t csum = part_checksum_lanes(lane < 7 ? outw[lane] : 0.0, lane, stamp);
+            if (WV_STORE_IF) {
+                const uint32_t csum = part_checksum_lanes(lane < 7 ? outw[lane] : 0.0, lane, stamp);
 #ifdef WV_RECORD_OVL // (... and the overlap bits of the record it sends)
-            if (lane == 0)
-                outw[7] = pack_ovl(WV_RECORD_OVL(ovm0 != 0ULL), WV_RECORD_OVL(ovm1 != 0ULL), stamp, csum, accept);
+                if (lane == 0)
+                    outw[7] = pack_ovl(WV_RECORD_OVL(ovm0 != 0ULL), WV_RECORD_OVL(ovm1 != 0ULL), stamp, csum, accept);
 #else
-            if (lane == 0)
-                outw[7] = pack_ovl(ovm0 != 0ULL, ovm1 != 0ULL, stamp, csum, accept);
+                if (lane == 0)
+                    outw[7] = pack_ovl(ovm0 != 0ULL, ovm1 != 0ULL, stamp, csum, accept);
 #endif
+            }
         }
         wave_sync();
-#ifndef WV_STORE_IF
-#define WV_STORE_IF true
-#define WV_STORE_IF_DEFAULTED
-#endif
 #ifdef WV_STORE_WT // a persistent kernel: the host waits for this record while the kernel lives
         store_part<true>(WV_PART_DST, sm.outw[wv], lane);
 #else
@@ -607,12 +635,12 @@
 #undef WV_STORE_SYSTEM_DEFAULTED
 #endif
 #endif
+        wave_sync();
+        WV_STAMP(7); // result stored
+#endif
 #ifdef WV_STORE_IF_DEFAULTED
 #undef WV_STORE_IF
 #undef WV_STORE_IF_DEFAULTED
-#endif
-        wave_sync();
-        WV_STAMP(7); // result stored
 #endif
 #undef WV_IF2
 #ifdef WV_XY_DEFAULTED
@@ -634,6 +662,10 @@
 #ifdef WV_ZERO_DEFAULTED
 #undef WV_ZERO
 #undef WV_ZERO_DEFAULTED
+#endif
+#ifdef WV_VIRIAL_DEFAULTED
+#undef WV_VIRIAL
+#undef WV_VIRIAL_DEFAULTED
 #endif
 #ifdef WV_WOLF_DEFAULTED
 #undef WV_WOLF
