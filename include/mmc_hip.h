@@ -911,6 +911,80 @@ int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32
  * 40 (numbins + 2) <= 65536  ->  numbins + 2 <= 1638. */
 #define MMC_ORIENT_MAX_BINS 1636
 
+/* ---- Pair-energy distributions: p(u), <u_C>(r), <u_LJ>(r) and energetic hydrogen bonds -----------
+ * The energy of a PAIR of molecules, which no other call exports (mmc_batch_deletion sums over the
+ * partners, mmc_batch_rdf_sites has no energies, mmc_batch_local_order counts bonds by geometry): the
+ * distribution p(u) of dimer interaction energies, the decomposition of the potential energy by
+ * distance, and the hydrogen-bond count of the energetic criterion u < u_hb (Jorgensen: -2.25
+ * kcal/mol = -1132.2 K).  The reference has no such analysis; the arithmetic is defined here, in
+ * unfused fp64, and restated in numpy by tests/pair_energy_ref.py.  Every pair i < j of three-site
+ * molecules of every replica contributes once.  Energies are in K.
+ *   - Separation and r-bin: exactly mmc_batch_orient_corr's.  D = site0(i) - site0(j) per component,
+ *     its image gr.jl:75-80 with the replica's own box, r^2 = (xx xx + yy yy) + zz zz,
+ *     bin = ceil(sqrt(r^2) / dr) from the host-built thresholds; dr and the validity of r_max as
+ *     mmc_batch_rdf_sites in both box modes.  Bins 0..numbins are in range; slot numbins + 1 takes
+ *     every pair beyond r_max.
+ *   - Molecule image.  e_a(m) = vector1D(site 0 of m, atom a of m) (boundaries.jl) per component with
+ *     the replica's own box, so e_0 = 0 and a molecule whose atoms are stored a box apart is whole.
+ *     The atom-pair vector is x_ab = (D + e_a(i)) - e_b(j) per component, r2_ab = (x x + y y) + z z.
+ *     The cutoff is by molecule: all nine atom pairs of a pair in range count, with no atomic cutoff.
+ *   - Energies of a pair in range, a = 0, 1, 2 major and b = 0, 1, 2 minor, each sum added left to
+ *     right in that order:
+ *         u_C  = factor * (sum_ab (q_a * q_b) / sqrt(r2_ab))
+ *         u_LJ = sum_ab (4.0 * eps_ab) * (s6 * s6 - s6),  s6 = (s2 * s2) * s2,
+ *                s2 = (sig_ab * sig_ab) / r2_ab, over the atom pairs with eps_ab > 0.001 (the
+ *                reference's LJ rule, energy.jl:270; quirk Q2), 0 when there is none
+ *         u    = u_C + u_LJ
+ *     with q_a the charge of atom a of i, q_b of atom b of j, eps and sig the tables at (type of a,
+ *     type of b), factor the Coulomb constant of the batch.  The device may evaluate u_C and u_LJ of
+ *     an unflagged pair to within 2^-21 K of this arithmetic (refined reciprocal square roots for the
+ *     divisions).
+ *   - Flagged pairs.  A pair in range whose u_C or u_LJ is not finite or has magnitude >= 2^20 K
+ *     (atoms on top of each other) is counted in flagged and in row 0 and enters no other output.
+ *   - rows: 0 the pair count per slot; 1 and 2 the sums of Q(u_C) and Q(u_LJ) over the unflagged
+ *     pairs of bins 0..numbins, Q(v) = v 2^20 (MMC_PAIRE_SCALE) rounded to the nearest integer,
+ *     ties to even, as a 64-bit integer; rows 1 and 2 of slot numbins + 1 are 0: pairs beyond r_max
+ *     compute no energy.  A row-1 or row-2 entry may differ from the exact arithmetic above by at
+ *     most one unit per pair of its slot.  The sums are integers, added modulo 2^64: a slot is right
+ *     whenever its true sum is below 2^43 K in magnitude (ask per replica where a summed call could
+ *     pass that), and the result does not depend on the grid, on option "wave_wgs", on the flush
+ *     order or on the order of atomics.
+ *   - uhist: every unflagged pair in range, binned on u by mmc_batch_deletion's rule: with
+ *     s = n_ebins / (u_hi - u_lo) in fp64 and k = floor((u - u_lo) * s), unfused, u < u_lo goes to
+ *     slot 0, u >= u_hi or k >= n_ebins to slot n_ebins + 1, everything else to slot k + 1
+ *     (observables.energy_bins).
+ *   - nhb: c_m = the number of unflagged partners of molecule m in range with u < u_hb; nhb[k] = the
+ *     number of molecules with c_m = k, the last slot MMC_PAIRE_NHB - 1 = 8 taking c_m >= 8.
+ *   - per_replica == 0: rows[3][numbins + 2], uhist[n_ebins + 2], nhb[MMC_PAIRE_NHB], flagged[1],
+ *     summed over the replicas; else rows[R][3][numbins + 2], uhist[R][n_ebins + 2],
+ *     nhb[R][MMC_PAIRE_NHB], flagged[R].  All are overwritten, not accumulated.  uhist and nhb may be
+ *     NULL; without uhist n_ebins, u_lo and u_hi are ignored, without nhb u_hb is.
+ *   - Use (observables.py): pair_energy_distribution, pair_energy_profile, energetic_hbonds.
+ * Both box modes and either Coulomb style: the call reads coordinates, charges and the eps / sig
+ * tables only, no S(k) and no erfc table (the pair energy is the bare Coulomb one in both styles), and
+ * is read-only as mmc_batch_rdf_sites is.  Arguments are checked first, then the state, then the
+ * size; on any error every output is left untouched.  MMC_ERR_ARG, before the batch is looked at:
+ * NULL rows or NULL flagged; numbins outside 1..MMC_PAIRE_MAX_BINS; r_max not finite; uhist given
+ * with n_ebins outside 1..MMC_PAIRE_MAX_EBINS, u_lo >= u_hi or a bound that is not finite; nhb given
+ * with u_hb not finite; with the batch: r_max above half of the smallest box, or <= 0 with
+ * per-replica boxes.  MMC_ERR_STATE: proposals outstanding, a volume trial in flight.
+ * MMC_ERR_UNSUPPORTED: molecules that are not three-site; more than 2^21 molecules. */
+int32_t mmc_batch_pair_energy(mmc_batch *b, int32_t numbins, double r_max,
+        int32_t n_ebins, double u_lo, double u_hi, double u_hb, int32_t per_replica,
+        int64_t *rows     /* [3][numbins + 2] or [R][3][numbins + 2] */,
+        uint64_t *uhist   /* [n_ebins + 2]    or [R][n_ebins + 2];   may be NULL */,
+        uint64_t *nhb     /* [MMC_PAIRE_NHB]  or [R][MMC_PAIRE_NHB]; may be NULL */,
+        uint64_t *flagged /* [1] or [R] */);
+#define MMC_PAIRE_SCALE 1048576.0 /* 2^20: one unit of rows 1 and 2 */
+#define MMC_PAIRE_NHB 9           /* molecules with 0..7 energetic bonds, then 8 or more */
+#define MMC_PAIRE_MAX_EBINS 4096  /* largest n_ebins (mmc_batch_deletion's) */
+/* What one wave per workgroup fits in the 65536 bytes of LDS a workgroup may ask for, all counters
+ * 64-bit: the bin thresholds, 8 (numbins + 2) bytes, three rows, 24 (numbins + 2) bytes, the LJ
+ * constants of the nine atom pairs, 144 bytes, the largest energy histogram,
+ * 8 (MMC_PAIRE_MAX_EBINS + 2) bytes, and the flagged count, 8 bytes:
+ * 32 (numbins + 2) + 144 + 32784 + 8 <= 65536  ->  numbins + 2 <= 1018. */
+#define MMC_PAIRE_MAX_BINS 1016
+
 /* ---- Partial structure factors: S_ab(q) and the charge structure factor S_ZZ(q) of every replica ---
  * The reciprocal-space counterpart of mmc_batch_rdf_sites: the products rho_a(n) rho_b(n)* of the three
  * atom-slot densities over the box's own wave vectors, summed per shell of |n|^2, in one read-only

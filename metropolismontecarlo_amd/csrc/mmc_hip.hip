@@ -15,6 +15,7 @@
 #include "mmc_forces.inc"
 #include "mmc_struct.inc"
 #include "mmc_orient.inc"
+#include "mmc_pair_energy.inc"
 #include "mmc_sofq.inc"
 #include "mmc_local.inc"
 #include "mmc_cavity.inc"

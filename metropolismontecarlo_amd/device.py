@@ -4,12 +4,15 @@ reference's per-call surface) and ``Batch`` (R replicas, one launch per step).
 numpy arrays in, numpy arrays / floats out.  Index conventions are the reference's: molecule
 indices, atom ranges and atom types are 1-based.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import CHAIN_DTYPE, TOTALS_DTYPE, Move, MoveResult, RunParams, RunStats, Totals, check
+
+PairEnergy = collections.namedtuple("PairEnergy", "rows uhist nhb flagged")  # Batch.pair_energy
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -739,6 +742,45 @@ class Batch:
         check(self._L.mmc_batch_orient_corr(self._h, int(numbins), float(r_max), int(bool(per_replica)),
                                             _i(out)))
         return out
+
+    def pair_energy(self, numbins, r_max=0.0, n_ebins=0, u_lo=-4000.0, u_hi=2000.0, u_hb=None, per_replica=False,
+                    out=None):
+        """mmc_batch_pair_energy: the interaction energy u = u_C + u_LJ (K) of every pair of
+        molecules whose slot-0 separation is in range, over orient_corr's bins.  Returns
+        PairEnergy(rows, uhist, nhb, flagged), summed over the replicas or with a leading [R] axis
+        with per_replica: rows int64 [3, numbins + 2], the pair count and the sums of u_C and u_LJ
+        in units of 2^-20 K (observables.pair_energy_profile); uhist uint64 [n_ebins + 2], the
+        pairs in range binned on u over [u_lo, u_hi) by observables.energy_bins' rule, None with
+        n_ebins = 0 (observables.pair_energy_distribution); nhb uint64 [9], the molecules with
+        0..7 and 8 or more partners below u_hb, None with u_hb = None
+        (observables.energetic_hbonds); flagged uint64 [1], the pairs in range whose u_C or u_LJ
+        is not finite or beyond 2^20 K, which enter row 0 only.  `out`: a dict of arrays under
+        those names to overwrite instead (each of its shape and dtype, contiguous)."""
+        R, n2, ne = self.R, max(int(numbins), 0) + 2, int(n_ebins)
+        lead = (R,) if per_replica else ()
+        spec = {"rows": (lead + (3, n2), np.int64), "flagged": (lead if per_replica else (1,), np.uint64)}
+        if ne != 0:   # (an n_ebins the library refuses still gets an array to leave alone)
+            spec["uhist"] = (lead + (max(ne, 0) + 2,), np.uint64)
+        if u_hb is not None:
+            spec["nhb"] = (lead + (9,), np.uint64)
+        if out is not None and not (isinstance(out, dict) and set(out) <= set(spec)):
+            raise ValueError(f"out: a dict with keys among {sorted(spec)}")
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k):
+            return res[k].ctypes.data_as(C.POINTER(C.c_uint64)) if k in res else None
+        check(self._L.mmc_batch_pair_energy(
+            self._h, int(numbins), float(r_max), ne, float(u_lo), float(u_hi),
+            0.0 if u_hb is None else float(u_hb), int(bool(per_replica)), _i(res["rows"]), ptr("uhist"),
+            ptr("nhb"), ptr("flagged")))
+        return PairEnergy(res["rows"], res.get("uhist"), res.get("nhb"), res["flagged"])
 
     def structure_factor(self, n_max, per_replica=False, out=None):
         """mmc_batch_structure_factor: the products rho_a(n) rho_b(n)* of the three atom-slot

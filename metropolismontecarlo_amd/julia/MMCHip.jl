@@ -698,6 +698,39 @@ function orient_corr(b::Batch, numbins::Integer; r_max::Float64 = 0.0, per_repli
     return hist
 end
 
+# ---- pair-energy distributions (include/mmc_hip.h, mmc_batch_pair_energy) --------------------------
+"""
+    pair_energy(b, numbins; r_max = 0.0, ebins = nothing, u_hb = nothing, per_replica = false)
+
+The interaction energy u = u_C + u_LJ (K) of every pair of molecules whose slot-1 (O) separation is in
+range, every pair i < j once, over the bins of `orient_corr`.  Returns `(rows, uhist, nhb, flagged)`:
+`rows` a `(numbins + 2, 3)` Int64 matrix (column k = row k of the C layout: the pair count and the sums
+of u_C and u_LJ in units of 2^-20 K); with `ebins = (n_ebins, u_lo, u_hi)` `uhist`, `n_ebins + 2`
+UInt64 counts of the pairs in range binned on u (slot 1 below `u_lo`, the last at or above `u_hi`),
+else `nothing`; with `u_hb` `nhb`, 9 UInt64 counts of the molecules with 0..7 and 8 or more partners
+below `u_hb`, else `nothing`; `flagged`, the pairs in range whose energy is not finite or beyond
+2^20 K.  Summed over the replicas, or with a trailing replica axis with `per_replica`.  Read-only for
+the chains.
+"""
+function pair_energy(b::Batch, numbins::Integer; r_max::Float64 = 0.0,
+                     ebins::Union{Nothing,Tuple{Integer,Float64,Float64}} = nothing,
+                     u_hb::Union{Nothing,Float64} = nothing, per_replica::Bool = false)
+    numbins >= 1 || error("numbins must be >= 1")
+    n_ebins, u_lo, u_hi = ebins === nothing ? (0, 0.0, 1.0) : ebins
+    ebins === nothing || 1 <= n_ebins <= 4096 || error("n_ebins must be in 1..4096")
+    tail = per_replica ? (b.n_replicas,) : ()
+    rows = zeros(Int64, numbins + 2, 3, tail...)
+    uhist = ebins === nothing ? nothing : zeros(UInt64, n_ebins + 2, tail...)
+    nhb = u_hb === nothing ? nothing : zeros(UInt64, 9, tail...)
+    flagged = zeros(UInt64, per_replica ? b.n_replicas : 1)
+    check(ccall((:mmc_batch_pair_energy, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Float64, Int32, Float64, Float64, Float64, Int32, Ptr{Int64}, Ptr{UInt64},
+                 Ptr{UInt64}, Ptr{UInt64}),
+                b.h, numbins, r_max, n_ebins, u_lo, u_hi, u_hb === nothing ? 0.0 : u_hb, per_replica ? 1 : 0,
+                rows, uhist === nothing ? C_NULL : uhist, nhb === nothing ? C_NULL : nhb, flagged))
+    return rows, uhist, nhb, flagged
+end
+
 # ---- partial structure factors (include/mmc_hip.h, mmc_batch_structure_factor) --------------------
 """
     structure_factor(b, n_max; per_replica = false)

@@ -107,6 +107,61 @@ def orient_projections(hist, n_mol, dr, inv_volume_sum):
     return r, g, h110, h112, p2
 
 
+# ---- pair-energy distributions (include/mmc_hip.h, "Pair-energy distributions") -------------------
+PAIRE_SCALE = 2.0 ** 20  # MMC_PAIRE_SCALE: one unit of rows 1 and 2 of mmc_batch_pair_energy
+
+
+def pair_energy_distribution(uhist, n_mol, u_lo, u_hi, n_frames=1):
+    """(centres [n_ebins], p [..., n_ebins]) from mmc_batch_pair_energy's uhist ([..., n_ebins + 2]):
+    p(u), the pairs per molecule per K with pair energy in the bin, uhist[k + 1] / (N frames width);
+    its integral over u is the mean number of partners in range (the two outer slots left out).
+    n_frames: the frames summed into each histogram (calls, times the replicas for a summed
+    output)."""
+    h = np.asarray(uhist)
+    if h.ndim < 1 or h.shape[-1] < 3:
+        raise ValueError("uhist must be [..., n_ebins + 2] (mmc_batch_pair_energy)")
+    lo, hi = float(u_lo), float(u_hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("finite u_lo < u_hi")
+    n = h.shape[-1] - 2
+    w = (hi - lo) / n
+    centres = lo + (np.arange(n) + 0.5) * w
+    return centres, h[..., 1:-1].astype(np.float64) / (float(n_mol) * float(n_frames) * w)
+
+
+def pair_energy_profile(rows, n_mol, n_frames=1):
+    """(<u_C>(r), <u_LJ>(r), E(R)) from mmc_batch_pair_energy's rows ([..., 3, numbins + 2]), each
+    [..., numbins + 1] over bins 0..numbins: the mean Coulomb and Lennard-Jones energy (K) of a pair
+    of molecules in the bin, row 1 and row 2 over 2^20 row 0 (NaN where the bin is empty; a flagged
+    pair counts in row 0 only), and the cumulative pair energy per molecule
+    E(R_k) = cumsum(row1 + row2)[0..k] / (2^20 N frames), R_k = k dr the outer edge of bin k: the
+    potential energy per molecule that the pairs within R_k carry."""
+    h = np.asarray(rows)
+    if h.ndim < 2 or h.shape[-2] != 3 or h.shape[-1] < 3:
+        raise ValueError("rows must be [..., 3, numbins + 2] (mmc_batch_pair_energy)")
+    r = h[..., :-1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uc = np.where(r[..., 0, :] > 0, r[..., 1, :] / (PAIRE_SCALE * r[..., 0, :]), np.nan)
+        ulj = np.where(r[..., 0, :] > 0, r[..., 2, :] / (PAIRE_SCALE * r[..., 0, :]), np.nan)
+    cum = np.cumsum(r[..., 1, :] + r[..., 2, :], axis=-1) / (PAIRE_SCALE * float(n_mol) * float(n_frames))
+    return uc, ulj, cum
+
+
+def energetic_hbonds(nhb):
+    """(p [..., 9], mean [...]) from mmc_batch_pair_energy's nhb ([..., 9]): the fraction of
+    molecules with k = 0..7 and 8 or more partners below u_hb, and the mean number per molecule
+    (the last slot taken as 8).  NaN where no molecule was counted."""
+    h = np.asarray(nhb)
+    if h.ndim < 1 or h.shape[-1] != 9:
+        raise ValueError("nhb must be [..., 9] (mmc_batch_pair_energy)")
+    h = h.astype(np.float64)
+    tot = h.sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = h / tot[..., None]
+        mean = (h * np.arange(9)).sum(-1) / tot
+    return p, mean
+
+
 # ---- partial structure factors (include/mmc_hip.h, "Partial structure factors") --------------------
 SOFQ_SCALE = 2.0 ** 24  # MMC_SOFQ_SCALE: one unit of mmc_batch_structure_factor's per-replica integers
 
