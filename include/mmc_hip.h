@@ -692,6 +692,59 @@ int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t d
 int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in, double temperature,
                            double *boltz_sum, int64_t *n_overlap, double *du_out, uint8_t *ovl_out);
 
+/* ---- Foreign solutes: hydration free energies (Henry constants) of every replica ----------------
+ * mmc_batch_widom inserts a copy of the batch's own molecule; these calls insert a rigid solute
+ * that is NOT water -- methane, an ion, an alcohol -- as a test particle: the excess chemical
+ * potential at infinite dilution.  The insertion energy is defined exactly as mmc_batch_widom's,
+ * through the reference's potential(..., "ewald") (Ewald/energy.jl:946-1032): dU is what that
+ * total changes by when the solute is appended as molecule N + 1 with its own atom types,
+ *   d_lj    = LJ_poly_dU(N+1)        energy.jl:209-290: waters whose COM lies within lj_rcut of the
+ *             solute's reference point c (vector1D per axis, strict <); over those all S x 3 atom
+ *             pairs on the per-pair vector1D image; a pair counts when r^2 < r_cut^2 + 100 and
+ *             eps > 0.001; the sum times 4
+ *   d_real  = EwaldShort(N+1)        ewalds.jl:892-910 -> :293-376: COM gate on qq_rcut; a pair with
+ *             r^2 < 0.5 and q_a q_b < 0 is an overlap (d_real = 0, flag bit 0); else factor times
+ *             sum q_a q_b erfc(kappa r) / r over pairs with r^2 < r_cut^2 + 100 (the batch's table)
+ *   d_recip = factor sum_k cfac_k (2 Re(conj(S_k) s_k) + |s_k|^2) - factor kappa / sqrt(pi) sum_a q_a^2
+ *             s_k = sum_a q_a exp(2 pi i k . r_a / L) by the reference's phase recurrence, over the
+ *             batch's half-space k list against the replica's committed S(k); computed whether or
+ *             not the insertion overlaps.
+ * The solute: n_sites = S sites, 1 <= S <= MMC_SOLUTE_MAX_SITES;
+ *   - offsets [S][3] (A) from its reference point c.  c is the "centre of mass" of the reference's
+ *     molecule-level gates and the caller's choice (io.solute_from_decks takes the mass COM);
+ *   - charge [S];
+ *   - eps [S][3], sig [S][3] (K, A) against the three atom slots of the batch's molecule, already
+ *     mixed: the entries eps_ij[type_a, type_slot] of the reference's Tables.
+ *   - A solute whose charges are all zero has d_real = d_recip = +0.0 exactly and S(k) is not read.
+ *   - A net-charged solute is allowed.  NO neutralising-background term is added, because the
+ *     reference's total energy has none: d_recip of an ion is the bare expression above.
+ *   - The constant intramolecular Ewald term of the solute is absent, as in mmc_batch_widom
+ *     (observables.ewald_intra_energy takes any number of sites).
+ * Draws: those of mmc_batch_widom -- the same three Philox slots MMC_SLOT_WIDOM + 0, 1, 2 with
+ * counter draw0 + j: c = (u0, u1, u2) L, Shoemake's rotation Rm of (u3, u4, u5), site a at
+ * c + Rm offsets[a].  For one (seed, draw0) the reference points are bit for bit the COMs
+ * mmc_batch_widom draws and the probes of mmc_batch_cavity (observables.solute_molecules).
+ * mol_out (mmc_batch_widom_solute) / mol_in (_at): [R][n_insert][S + 1][3], the sites, then c.
+ * du_out [R][n_insert][3] (d_lj, d_real, d_recip); ovl_out [R][n_insert], bit 0 = overlap, bit 1 =
+ * non-finite dU.  boltz_sum[r] += exp(-dU / T) in insertion order and n_overlap[r] += the
+ * insertions of weight 0, exactly as mmc_batch_widom: bit-identical whatever the grid or option
+ * "wave_wgs".  mol_out, du_out and ovl_out may be NULL.  Read-only for the chains.
+ * MMC_ERR_ARG (in this order; what needs no batch is refused without one): n_sites outside
+ * 1..MMC_SOLUTE_MAX_SITES, a NULL required array, n_insert < 1, temperature <= 0 or not finite,
+ * a non-finite charge, eps, sig, offset or coordinate, eps < 0 or sig < 0, replicas x n_insert above
+ * 2^31 - 1.  MMC_ERR_STATE and MMC_ERR_UNSUPPORTED as mmc_batch_widom (proposals outstanding, S(k)
+ * stale; per-replica boxes, Wolf style, a system the table kernels do not take).  Nothing is
+ * written on a refusal. */
+#define MMC_SOLUTE_MAX_SITES 16
+int32_t mmc_batch_widom_solute(mmc_batch *b, int32_t n_sites, const double *offsets, const double *charge,
+                               const double *eps, const double *sig, int64_t n_insert, uint64_t seed,
+                               int64_t draw0, double temperature, double *boltz_sum, int64_t *n_overlap,
+                               double *mol_out, double *du_out, uint8_t *ovl_out);
+int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *charge, const double *eps,
+                                  const double *sig, int64_t n_insert, const double *mol_in,
+                                  double temperature, double *boltz_sum, int64_t *n_overlap,
+                                  double *du_out, uint8_t *ovl_out);
+
 /* ---- Deletion energies: binding-energy histograms and the deletion half of BAR ------------------
  * The mirror image of mmc_batch_widom: the energy each EXISTING molecule is bound with.  The
  * reference has no deletion code; the deletion energy of molecule i of a replica's committed

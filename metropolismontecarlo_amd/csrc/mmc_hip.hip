@@ -11,6 +11,7 @@
 #include "mmc_perbox.inc"
 #include "mmc_units.inc"
 #include "mmc_widom.inc"
+#include "mmc_solute.inc"
 #include "mmc_deletion.inc"
 #include "mmc_forces.inc"
 #include "mmc_struct.inc"

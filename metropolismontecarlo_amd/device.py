@@ -595,6 +595,44 @@ class Batch:
                                          _d(du), _u8(ov)))
         return bs, no, du, ov
 
+    def widom_solute(self, solute, n_insert, temperature, seed, draw0=0, boltz_sum=None, n_overlap=None,
+                     outputs=False):
+        """mmc_batch_widom_solute: n_insert random insertions of the foreign rigid solute
+        (structs.Solute, S sites) into every replica, drawn as widom() draws its molecules: for one
+        (seed, draw0) the reference points are widom()'s COMs.  boltz_sum / n_overlap (R,) accumulate
+        (new zero arrays when None).  Returns (boltz_sum, n_overlap), and with outputs=True also mol
+        (R, M, S + 1, 3) = the sites, then the reference point, du (R, M, 3) and ovl (R, M)."""
+        S = solute.n_sites
+        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
+        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
+        M = int(n_insert)
+        mol = np.zeros((self.R, M, S + 1, 3)) if outputs else None
+        du = np.zeros((self.R, M, 3)) if outputs else None
+        ov = np.zeros((self.R, M), dtype=np.uint8) if outputs else None
+        check(self._L.mmc_batch_widom_solute(self._h, S, _d(solute.offsets), _d(solute.charge), _d(solute.eps),
+                                             _d(solute.sig), M, int(seed) & (2 ** 64 - 1), int(draw0),
+                                             float(temperature), _d(bs), _i(no),
+                                             _d(mol) if outputs else None, _d(du) if outputs else None,
+                                             _u8(ov) if outputs else None))
+        return (bs, no, mol, du, ov) if outputs else (bs, no)
+
+    def widom_solute_at(self, solute, mol, temperature, boltz_sum=None, n_overlap=None):
+        """mmc_batch_widom_solute_at: the caller's solutes mol (R, M, S + 1, 3) = the S sites, then
+        the reference point (the solute's offsets are not used).  Returns (boltz_sum, n_overlap,
+        du (R, M, 3), ovl (R, M))."""
+        S = solute.n_sites
+        mol = _f64(mol)
+        if mol.ndim != 4 or mol.shape[0] != self.R or mol.shape[2:] != (S + 1, 3):
+            raise ValueError("mol must be (R, n_insert, n_sites + 1, 3)")
+        M = mol.shape[1]
+        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
+        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
+        du = np.zeros((self.R, M, 3))
+        ov = np.zeros((self.R, M), dtype=np.uint8)
+        check(self._L.mmc_batch_widom_solute_at(self._h, S, _d(solute.charge), _d(solute.eps), _d(solute.sig), M,
+                                                _d(mol), float(temperature), _d(bs), _i(no), _d(du), _u8(ov)))
+        return bs, no, du, ov
+
     def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
                  n_flagged=None, details=False):
         """mmc_batch_deletion: the deletion (binding) energy dU_i = potential(N) - potential(N

@@ -314,6 +314,28 @@ def system_from_decks(pdb, top):
                 charge=np.array(charge), mass=mass, eps=tab.eps_ij, sig=tab.sig_ij, box=pdb["box"])
 
 
+def solute_from_decks(pdb, top, slot_types):
+    """structs.Solute of the one molecule in `pdb` (a path or ReadPDB's dict) described by `top`
+    (a path or ReadTopFile's dict) for insertion into a batch whose molecule has the atom types
+    `slot_types` (three 1-based indices into [ atomtypes ], or their names): offsets are the
+    coordinates minus the mass COM of system_from_decks, charges the molecule's [ atoms ], and row a
+    of eps / sig the MakeTables entries eps_ij[type_a, slot_types]."""
+    from .structs import Solute
+    pdb = ReadPDB(pdb) if isinstance(pdb, (str, os.PathLike)) else pdb
+    top = ReadTopFile(top, substitutions={"SOLNUMBER": 1}) if isinstance(top, (str, os.PathLike)) else top
+    m = system_from_decks(pdb, top)
+    if m["com"].shape[0] != 1:
+        raise ValueError(f"{pdb['name']}: a solute deck holds one molecule, not {m['com'].shape[0]}")
+    names = [a["name"] for a in top["atomtypes"]]
+    slots = [names.index(t) + 1 if isinstance(t, str) else int(t) for t in slot_types]
+    if len(slots) != 3 or not all(1 <= t <= len(names) for t in slots):
+        raise ValueError("slot_types: the three atom types of the batch's molecule")
+    cols = np.array(slots) - 1
+    rows = m["atype"] - 1
+    return Solute(pdb["name"], m["coords"] - m["com"][0], m["charge"], m["eps"][rows][:, cols],
+                  m["sig"][rows][:, cols])
+
+
 def PrintPDB(filename, step, coords, box, atom_names, mol_names, mol_numbers):
     """Ewald/initialConfigurations.jl:160-181: `<filename>_<step>.pdb` with the reference's
     CRYST1 / ATOM format strings (not strict PDB columns)."""

@@ -587,6 +587,50 @@ function widom_at!(b::Batch, mol_in::Vector{Float64}, n_insert::Integer, tempera
     return boltz_sum, n_overlap
 end
 
+# ---- foreign solutes (include/mmc_hip.h, mmc_batch_widom_solute / mmc_batch_widom_solute_at) --------
+"""
+    widom_solute!(b, offsets, charge, eps, sig, n_insert, seed, draw0, temperature, boltz_sum, n_overlap)
+    widom_solute_at!(b, charge, eps, sig, mol_in, n_insert, temperature, boltz_sum, n_overlap)
+
+`n_insert` insertions into every replica of a rigid solute that is not the batch's molecule: S =
+`length(charge)` sites (1..16) at c + R offsets[a] (`offsets` 3 S Float64, A, site by site), with
+`eps` / `sig` 3 S Float64 (K, A) against the three atom slots of the batch's molecule, already mixed,
+site by site.  The draws are `widom!`'s: for one (seed, draw0) the reference points c are its centres
+of mass.  `boltz_sum[r] += sum exp(-dU / T)` in insertion order, `n_overlap[r] +=` the insertions of
+weight 0; dU as for `widom!`, with the solute's own types.  A solute without charges has no
+Coulomb terms; a net charge gets NO neutralising background (the reference has none).
+`widom_solute_at!` evaluates the caller's solutes, `mol_in` = R * n_insert * (S + 1) * 3 Float64 (the
+sites, then c).  Read-only for the chains.  mu_ex = -T log(boltz_sum / n) in K.
+"""
+function widom_solute!(b::Batch, offsets::Vector{Float64}, charge::Vector{Float64}, eps::Vector{Float64},
+                       sig::Vector{Float64}, n_insert::Integer, seed::Integer, draw0::Integer,
+                       temperature::Float64, boltz_sum::Vector{Float64}, n_overlap::Vector{Int64})
+    S = length(charge)
+    1 <= S <= 16 || error("a solute has 1..16 sites")
+    length(offsets) == 3S && length(eps) == 3S && length(sig) == 3S || error("offsets, eps, sig: S x 3")
+    length(boltz_sum) == b.n_replicas && length(n_overlap) == b.n_replicas || error("one sum per replica")
+    check(ccall((:mmc_batch_widom_solute, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, UInt64, Int64,
+                 Float64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, S, offsets, charge, eps, sig, n_insert, UInt64(seed), draw0, temperature, boltz_sum,
+                n_overlap, C_NULL, C_NULL, C_NULL))
+    return boltz_sum, n_overlap
+end
+function widom_solute_at!(b::Batch, charge::Vector{Float64}, eps::Vector{Float64}, sig::Vector{Float64},
+                          mol_in::Vector{Float64}, n_insert::Integer, temperature::Float64,
+                          boltz_sum::Vector{Float64}, n_overlap::Vector{Int64})
+    S = length(charge)
+    1 <= S <= 16 || error("a solute has 1..16 sites")
+    length(eps) == 3S && length(sig) == 3S || error("eps, sig: S x 3")
+    length(mol_in) == 3 * (S + 1) * n_insert * b.n_replicas || error("mol_in: R x n_insert x (S + 1) x 3")
+    length(boltz_sum) == b.n_replicas && length(n_overlap) == b.n_replicas || error("one sum per replica")
+    check(ccall((:mmc_batch_widom_solute_at, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Float64,
+                 Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, S, charge, eps, sig, n_insert, mol_in, temperature, boltz_sum, n_overlap, C_NULL, C_NULL))
+    return boltz_sum, n_overlap
+end
+
 # ---- deletion energies (include/mmc_hip.h, mmc_batch_deletion) -------------------------------------
 """
     deletion(b, temperature; sel = nothing, bins = nothing, per_replica = false,

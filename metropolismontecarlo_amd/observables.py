@@ -321,7 +321,18 @@ def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
     insertions of one replica.  Draw j uses counter draw0 + j; slots MMC_SLOT_WIDOM + 0, 1, 2 give
     u0..u5: COM = (u0, u1, u2) L, rotation shoemake_rotation(u3, u4, u5), atom a = COM + R off_a."""
     off = np.asarray(offsets, dtype=float).reshape(3, 3)
-    out = np.empty((int(n_insert), 12))
+    return solute_molecules(philox, seed, draw0, n_insert, replica, box, off).reshape(int(n_insert), 12)
+
+
+def solute_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
+    """Host mirror of mmc_batch_widom_solute's generator: [n_insert][S + 1][3] (the S sites, then
+    the reference point c) of the insertions of one replica, offsets (S, 3).  The draws are
+    widom_molecules': counter draw0 + j, slots MMC_SLOT_WIDOM + 0, 1, 2 give u0..u5, c = (u0, u1, u2)
+    L, rotation shoemake_rotation(u3, u4, u5), site a = c + R off_a -- with water's three offsets
+    the same bits as widom_molecules."""
+    off = np.asarray(offsets, dtype=float).reshape(-1, 3)
+    S = off.shape[0]
+    out = np.empty((int(n_insert), S + 1, 3))
     for j in range(int(n_insert)):
         c = int(draw0) + j
         u0, u1 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM, replica)
@@ -329,10 +340,10 @@ def widom_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
         u4, u5 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 2, replica)
         com = np.array([u0 * box, u1 * box, u2 * box])
         R = shoemake_rotation(u3, u4, u5)
-        for a in range(3):
+        for a in range(S):
             for d in range(3):
-                out[j, 3 * a + d] = com[d] + ((R[d, 0] * off[a, 0] + R[d, 1] * off[a, 1]) + R[d, 2] * off[a, 2])
-        out[j, 9:] = com
+                out[j, a, d] = com[d] + ((R[d, 0] * off[a, 0] + R[d, 1] * off[a, 1]) + R[d, 2] * off[a, 2])
+        out[j, S] = com
     return out
 
 

@@ -77,6 +77,32 @@ class Tables:
     σᵢⱼ = property(lambda s: s.sig_ij, lambda s, v: setattr(s, "sig_ij", np.asarray(v, float)))
 
 
+class Solute:
+    """A rigid foreign solute of S sites for Batch.widom_solute (include/mmc_hip.h, "Foreign
+    solutes"): offsets (S, 3) A from its reference point, charge (S,), and eps / sig (S, 3) in K and
+    A against the three atom slots of the batch's molecule, already mixed (the Tables entries
+    eps_ij[type_a, type_slot]).  The reference has no such struct: it is the argument block of
+    mmc_batch_widom_solute."""
+    MAX_SITES = 16  # MMC_SOLUTE_MAX_SITES
+
+    def __init__(self, name, offsets, charge, eps, sig):
+        self.name = str(name)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 3)
+        S = self.offsets.shape[0]
+        self.charge = np.ascontiguousarray(charge, dtype=np.float64).reshape(S)
+        self.eps = np.ascontiguousarray(eps, dtype=np.float64).reshape(S, 3)
+        self.sig = np.ascontiguousarray(sig, dtype=np.float64).reshape(S, 3)
+        if not 1 <= S <= self.MAX_SITES:
+            raise ValueError(f"a solute has 1..{self.MAX_SITES} sites, not {S}")
+
+    @property
+    def n_sites(self):
+        return self.offsets.shape[0]
+
+    def __repr__(self):
+        return f"Solute({self.name!r}, {self.n_sites} sites, net charge {self.charge.sum():+.4f})"
+
+
 class EWALD:
     """mutable struct EWALD{I} (Ewald/ewalds.jl:9-19)."""
 

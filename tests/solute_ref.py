@@ -1,0 +1,190 @@
+"""Helpers of the foreign-solute tests (test_solute_abi.py, test_solute_host.py, test_gpu_solute.py):
+the solutes the tests insert, the deck lattice they insert MEA into, and the oracle's statement of
+the insertion energy -- common.widom_oracle_terms with S sites and the solute's own atom types
+appended to an oracle.System of N + 1 molecules."""
+import os
+
+import numpy as np
+
+import common
+from metropolismontecarlo_amd import io as mio
+from metropolismontecarlo_amd import structs
+
+DECKS = os.path.join(common.GOLDEN, "decks")
+T = 298.15
+# the MEA case of test_gpu_solute.py (and its precondition in test_solute_host.py)
+MEA_RCUT, MEA_SEED, MEA_DRAW0 = 9.0, 2025, 11
+MEA_ALPHA = 5.5   # kappa = alpha / 18.69: the erfc table covers kappa sqrt(r_cut^2 + 100) <= 4, 5.6 gives 4.03
+
+
+# ---- solutes ----------------------------------------------------------------------------------------
+def slot_types(a):
+    """The 1-based atom types of the three slots of the batch's molecule."""
+    return np.asarray(a["atype"][:3], dtype=np.int64)
+
+
+def mixed_rows(a, eps_site, sig_site):
+    """eps / sig (S, 3) of sites with their own LJ parameters against the water slots of system `a`,
+    by the reference's mixing (structs.Tables: sqrt(eps_i eps_j), (sig_i + sig_j) / 2); the slots'
+    own parameters are the diagonal of the system's table."""
+    st = slot_types(a) - 1
+    e_w, s_w = np.diag(np.asarray(a["eps"]))[st], np.diag(np.asarray(a["sig"]))[st]
+    eps_site, sig_site = np.asarray(eps_site, dtype=float), np.asarray(sig_site, dtype=float)
+    return np.sqrt(eps_site[:, None] * e_w[None, :]), (sig_site[:, None] + s_w[None, :]) / 2
+
+
+def water_solute(a, offsets):
+    """The batch's own molecule as a foreign solute: its charges and its rows of the table."""
+    st = slot_types(a) - 1
+    return structs.Solute("water", offsets, np.asarray(a["charge"][:3], dtype=float),
+                          np.asarray(a["eps"])[st][:, st], np.asarray(a["sig"])[st][:, st])
+
+
+def methane(a):
+    """United-atom methane (OPLS-UA: eps = 0.294 kcal/mol = 147.9 K, sig = 3.73 A), uncharged."""
+    eps, sig = mixed_rows(a, [147.9], [3.73])
+    return structs.Solute("methane", np.zeros((1, 3)), [0.0], eps, sig)
+
+
+def cation(a):
+    """A single site with q = +1 (sodium-like LJ: 65.4 K, 2.35 A)."""
+    eps, sig = mixed_rows(a, [65.4], [2.35])
+    return structs.Solute("cation", np.zeros((1, 3)), [1.0], eps, sig)
+
+
+def dipole(a):
+    """Two sites +-0.45 e 1.3 A apart, LJ on the first only; the reference point is the LJ site's
+    neighbour, off the line's middle."""
+    eps, sig = mixed_rows(a, [110.0, 0.0], [3.4, 0.0])
+    return structs.Solute("dipole", [[-0.4, 0.0, 0.0], [0.9, 0.0, 0.0]], [0.45, -0.45], eps, sig)
+
+
+def synthetic(a, S, seed, extent=2.0):
+    """S sites in a ball of radius `extent` about the reference point, random charges that sum to
+    zero (a lone site keeps its charge), every third site without LJ."""
+    rng = np.random.default_rng(seed)
+    off = rng.normal(size=(S, 3))
+    off *= (extent * rng.random(S) ** (1 / 3) / np.linalg.norm(off, axis=1))[:, None]
+    q = rng.normal(size=S) * 0.4
+    if S > 1:
+        q -= q.mean()
+    e_site = 40.0 + 80.0 * rng.random(S)
+    e_site[2::3] = 0.0
+    eps, sig = mixed_rows(a, e_site, 2.4 + rng.random(S))
+    return structs.Solute(f"synthetic{S}", off, q, eps, sig)
+
+
+def deck_top():
+    return mio.ReadTopFile(os.path.join(DECKS, "topol.top"), substitutions={"SOLNUMBER": 1})
+
+
+def mea(slots=(1, 2, 2)):
+    """The deck's monoethanolamine against the deck's water types (O1, H, H)."""
+    return mio.solute_from_decks(os.path.join(DECKS, "mea.pdb"), deck_top(), slots)
+
+
+def tip3p_lattice(n_mol=216, rho=0.0331, seed=4):
+    """n_mol TIP3P waters of the reference's deck (topol.top + tip3p.pdb) on the crystal start at
+    number density rho (216: box 18.69 A), with the water rows of the deck's table."""
+    top = deck_top()
+    one = mio.system_from_decks(mio.ReadPDB(os.path.join(DECKS, "tip3p.pdb")), top)
+    box, com, coords = mio.cubic_lattice_water(n_mol, rho, "tip3p", seed=seed)
+    return dict(com=com, coords=coords, first_atom=3 * np.arange(n_mol, dtype=np.int64) + 1,
+                last_atom=3 * np.arange(n_mol, dtype=np.int64) + 3, atype=np.tile(one["atype"], n_mol),
+                charge=np.tile(one["charge"], n_mol), eps=one["eps"][:2, :2].copy(),
+                sig=one["sig"][:2, :2].copy(), box=float(box))
+
+
+def scan_flushes(com, centre, gate, box):
+    """Whether k_solute_wave's COM scan (mmc_solute.hpp) certainly empties its neighbour list
+    mid-scan and has neighbours left for a later process() call: it scans the molecules in trips of
+    256 and empties the list after a trip when it holds more than SOL_LIST - 256 entries.  Counted
+    is the exact gate by a relative margin of 1e-9 -- a lower bound on the 16-bit prefilter's count
+    (common.scan_flushes is the same argument for mmc_wave_unit.inc's scan)."""
+    import re
+    src = open(os.path.join(common.HERE, "..", "metropolismontecarlo_amd", "csrc", "mmc_solute.hpp")).read()
+    n_list = int(re.search(r"#define SOL_LIST (\d+)", src).group(1))
+    assert "base += 256" in src and "SOL_LIST - 256" in src
+    d = np.asarray(com, dtype=float) - np.asarray(centre, dtype=float)
+    d = d + common.image_shift(d, box)
+    gated = (d * d).sum(1) < gate * gate * (1 - 1e-9)
+    before = np.cumsum(gated)
+    return any(before[b - 1] > n_list - 256 and before[-1] - before[b - 1] > 0
+               for b in range(256, gated.shape[0], 256))
+
+
+# ---- the oracle -------------------------------------------------------------------------------------
+class SoluteOracle:
+    """The insertion energy of `solute` into configurations of the system `a` (topology, tables), by
+    the oracle.  The N + 1 molecule system has 3 + S atom types: the water slots 1..3 and one type
+    per solute site, whose rows against the slots are the solute's eps / sig (its rows against other
+    solute sites stay 0: one solute, no such pair)."""
+
+    def __init__(self, orc, a, solute, lj_rcut, qq_rcut, alpha=5.6):
+        self.orc, self.a, self.sol = orc, a, solute
+        self.lj_rcut, self.qq_rcut, self.alpha = lj_rcut, qq_rcut, alpha
+        S = solute.n_sites
+        st = slot_types(a) - 1
+        self.eps = np.zeros((3 + S, 3 + S))
+        self.sig = np.zeros((3 + S, 3 + S))
+        self.eps[:3, :3] = np.asarray(a["eps"])[st][:, st]
+        self.sig[:3, :3] = np.asarray(a["sig"])[st][:, st]
+        self.eps[3:, :3], self.eps[:3, 3:] = solute.eps, solute.eps.T
+        self.sig[3:, :3], self.sig[:3, 3:] = solute.sig, solute.sig.T
+        self._rl0 = {}
+
+    def terms(self, com, coords, mol, box, key=None):
+        """(d_lj, d_real, d_recip, overlap) of one solute mol [S + 1][3] (sites, then the reference
+        point) appended as molecule N + 1 to (com, coords) in the box `box`:
+          d_lj    == orc.lj_poly_du(N+1)
+          d_real  == orc.ewald_short(N+1)              (0 when it reports an overlap)
+          d_recip == factor (recip_long(N+1) - recip_long(N)) + orc.ewald_self(the solute's charges)
+        `key`: a name under which recip_long(N) of this configuration is kept."""
+        orc, sol = self.orc, self.sol
+        S, n, L = sol.n_sites, com.shape[0], float(box)
+        mol = np.asarray(mol, dtype=float).reshape(S + 1, 3)
+        com1, coords1 = np.vstack([com, mol[S]]), np.vstack([coords, mol[:S]])
+        first = np.concatenate([3 * np.arange(n, dtype=np.int64) + 1, [3 * n + 1]])
+        last = np.concatenate([3 * np.arange(n, dtype=np.int64) + 3, [3 * n + S]])
+        at1 = np.concatenate([np.tile([1, 2, 3], n), 4 + np.arange(S)]).astype(np.int64)
+        q0 = np.asarray(self.a["charge"][:3 * n], dtype=float)
+        q1 = np.concatenate([q0, sol.charge])
+        s1 = orc.System(com1, first, last, coords1, at1, q1, self.eps, self.sig, L)
+        ew = orc.Ewald(self.alpha / L, 5, 27, L, factor=structs.factor)
+        lj, _ = orc.lj_poly_du(n + 1, s1, self.lj_rcut)
+        real, _, ov = orc.ewald_short(n + 1, s1, ew, self.qq_rcut)
+        if key is None or key not in self._rl0:
+            rl0 = orc.recip_long(ew, coords, q0, L)
+            if key is not None:
+                self._rl0[key] = rl0
+        else:
+            rl0 = self._rl0[key]
+        rl1 = orc.recip_long(ew, coords1, q1, L)
+        recip = ew.factor * (rl1 - rl0) + orc.ewald_self(ew, sol.charge)
+        return lj, real, recip, ov
+
+
+def solute_close(x, ref, S):
+    """common.widom_close with its absolute part scaled by S / 3 for S > 3: the number of summed
+    pair terms grows with the sites."""
+    return abs(x - ref) <= 1e-9 * max(1.0, S / 3.0) + 1e-13 * abs(ref)
+
+
+def check_solute(so, b, r, mols, du, ovl, what=""):
+    """Every term and the overlap flag of replica r's insertions mols [M][S + 1][3] against the
+    oracle, on the replica's own coordinates.  Returns the oracle's terms [M][3] and flags [M]."""
+    com, coords, _ = b.get_replica(r)
+    box = float(b.get_boxes()[r])
+    S = so.sol.n_sites
+    bad, ref, flags = [], [], []
+    for j in range(mols.shape[0]):
+        lj, real, recip, ov = so.terms(com, coords, mols[j], box, key=(id(b), r))
+        ref.append((lj, real, recip))
+        flags.append(ov)
+        if bool(ovl[j] & 1) != ov:
+            bad.append((j, "overlap", int(ovl[j]), ov))
+        for name, x, y in (("lj", du[j, 0], lj), ("real", du[j, 1], real), ("recip", du[j, 2], recip)):
+            if not solute_close(x, y, S):
+                bad.append((j, name, x, y))
+    assert not bad, f"{what} {so.sol.name} replica {r}: {bad[:6]}"
+    return np.array(ref), np.array(flags)
