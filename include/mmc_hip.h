@@ -685,7 +685,7 @@ int32_t mmc_chain_block_line(const mmc_chain *chain, int64_t block, int64_t n_mo
  * temperature <= 0 or not finite, non-finite offsets or molecules.
  * mmc_batch_widom_at evaluates the caller's molecules mol_in [R][n_insert][12] (same layout as
  * mol_out) with the same kernel. */
-#define MMC_SLOT_WIDOM 0x50000000u /* Philox slots of an insertion: +0, +1, +2 */
+#define MMC_SLOT_WIDOM 0x50000000u /* Philox slots of an insertion: +0..+5 (+3, +4, +5: B of mmc_batch_widom_pair) */
 int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t draw0,
                         const double *offsets, double temperature, double *boltz_sum,
                         int64_t *n_overlap, double *mol_out, double *du_out, uint8_t *ovl_out);
@@ -744,6 +744,76 @@ int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *c
                                   const double *sig, int64_t n_insert, const double *mol_in,
                                   double temperature, double *boltz_sum, int64_t *n_overlap,
                                   double *du_out, uint8_t *ovl_out);
+
+/* ---- Solute pairs: potentials of mean force at infinite dilution ------------------------------------
+ * How two foreign solutes A and B interact through the solvent -- the methane-methane contact and
+ * solvent-separated minima, an ion pair -- from test particles (potential distribution theorem):
+ *   g_AB(d) = < exp(-dU_AB(d) / T) >_N / ( < exp(-dU_A / T) >_N < exp(-dU_B / T) >_N ),  w(d) = -T ln g_AB(d)
+ * dU_AB(d) is what the reference's potential(..., "ewald") (Ewald/energy.jl:946-1032) changes by when
+ * A and B are appended d apart as molecules N + 1 and N + 2.  One call evaluates, per insertion, A
+ * and B at n_sep = K separations along one random ray: the three averages for all K in one pass.
+ * The solutes: A of n_sites_a = S_A sites, B of S_B, each described as mmc_batch_widom_solute
+ * describes a solute (offsets [S][3] from a reference point, charge [S], eps / sig [S][3] against the
+ * water's three slots), plus the A-B table eps_ab, sig_ab [S_A][S_B], already mixed.
+ * S_A >= 1, S_B >= 1, S_A + S_B <= MMC_SOLUTE_MAX_SITES.  d [K], 1 <= K <= MMC_PAIR_MAX_SEP, each
+ * finite, > 0 and < L / 2.
+ * Draws: insertion j of replica r draws A exactly as mmc_batch_widom_solute (slots MMC_SLOT_WIDOM +
+ * 0, 1, 2): mol_a_out is bit for bit its mol_out for the same (seed, draw0).  Slot +3 (u, v) gives
+ * the ray's direction n = (s cos phi, s sin phi, z), z = 1 - 2 u, s = sqrt(1 - z^2), phi = 2 pi v;
+ * slots +4 (u1, u2) and +5 (u3, its first uniform) give Shoemake's rotation R_B in the expressions
+ * of mmc_batch_widom.  n and R_B serve all K separations of the insertion: c_B,k = c_A + d_k n,
+ * wrapped per axis by the reference's rule (boundaries.jl:16-26: > L -> - L, < 0 -> + L); site b of B
+ * at c_B,k + R_B off_b.
+ * Terms, three rows of (lj, real, recip) per insertion and separation:
+ *   dA    mmc_batch_widom_solute's definition for A against the N waters (the same for every k)
+ *   dB_k  the same for B at placement k
+ *   x_k   the A-B interaction as the reference computes it between molecules N + 1 and N + 2:
+ *     x_lj    LJ_poly_dU restricted to the other solute (energy.jl:209-290): COM gate on
+ *             vector1D(c_A, c_B) against lj_rcut, the per-pair vector1D image, a pair counts when
+ *             r^2 < r_cut^2 + 100 and eps_ab > 0.001, the sum times 4
+ *     x_real  EwaldShort restricted likewise (ewalds.jl:892-910 -> :293-376): gate on qq_rcut, the
+ *             batch's erfc table, times factor; a site pair with r^2 < 0.5 and q_a q_b < 0 is an A-B
+ *             overlap: x_real = 0 and flag bit 2
+ *     x_recip factor sum_k cfac_k 2 Re(conj(s^A_k) s^B_k) on the batch's half-space k list
+ *             (RecipLong(N+2) - RecipLong(N) minus the two single terms, ewalds.jl:538-604)
+ * dU_AB,k = (dU_A + dU_B,k) + x_k, each dU and x_k formed as (lj + real) + recip.  No neutralising
+ * background and no intramolecular term, as for foreign solutes: an ion pair's PMF therefore
+ * INCLUDES the interaction with its periodic images.  With both solutes uncharged every real and
+ * recip entry is exactly +0.0 and S(k) is not read.
+ * flags [R][n_insert][1 + K]: entry 0 is A's (bit 0 overlap with a water, bit 1 dU_A non-finite);
+ * entry 1 + k: bit 0 = B_k overlaps a water, bit 1 = dU_B,k non-finite, bit 2 = A-B overlap, bit 3 =
+ * dU_AB,k non-finite.
+ * Sums, all += in insertion order, bit-identical whatever the grid or option "wave_wgs":
+ *   boltz_a [R], n_zero_a [R]        as mmc_batch_widom_solute's for A
+ *   boltz_b [R][K], n_zero_b [R][K]  the single-solute sums of B at each placement (bits 0, 1)
+ *   boltz_ab [R][K]                  sum exp(-dU_AB,k / T); weight 0, and counted in n_zero_ab
+ *                                    [R][K], when any flag of A or of entry 1 + k is set.
+ * Optional outputs (may be NULL): mol_a_out [R][n_insert][S_A + 1][3], mol_b_out
+ * [R][n_insert][K][S_B + 1][3] (sites, then the reference point), du_out [R][n_insert][1 + 2 K][3]
+ * (A, then B_0 .. B_K-1, then x_0 .. x_K-1), flags_out.  mmc_batch_widom_pair_at evaluates the
+ * caller's mol_a_in and mol_b_in in those layouts with the same kernel; it takes no d.
+ * Read-only for the chains.  MMC_ERR_ARG (in this order; what needs no batch is refused without
+ * one): a site count outside 1..15 or their sum above MMC_SOLUTE_MAX_SITES, n_sep outside
+ * 1..MMC_PAIR_MAX_SEP, a NULL required array (all six sums are required), n_insert < 1, temperature
+ * <= 0 or not finite, a non-finite charge, eps, sig or offset, a negative eps or sig (eps_ab, sig_ab
+ * included), d non-finite or <= 0; then with the batch: d >= L / 2, replicas x n_insert x (1 + K)
+ * above 2^31 - 1, a non-finite coordinate.  MMC_ERR_STATE and MMC_ERR_UNSUPPORTED as
+ * mmc_batch_widom_solute (proposals outstanding, S(k) stale; per-replica boxes, Wolf style, a
+ * system the table kernels do not take).  Nothing is written on a refusal. */
+#define MMC_PAIR_MAX_SEP 32
+int32_t mmc_batch_widom_pair(mmc_batch *b, int32_t n_sites_a, const double *offsets_a, const double *charge_a,
+                             const double *eps_a, const double *sig_a, int32_t n_sites_b, const double *offsets_b,
+                             const double *charge_b, const double *eps_b, const double *sig_b, const double *eps_ab,
+                             const double *sig_ab, int32_t n_sep, const double *d, int64_t n_insert, uint64_t seed,
+                             int64_t draw0, double temperature, double *boltz_a, int64_t *n_zero_a, double *boltz_b,
+                             int64_t *n_zero_b, double *boltz_ab, int64_t *n_zero_ab, double *mol_a_out,
+                             double *mol_b_out, double *du_out, uint8_t *flags_out);
+int32_t mmc_batch_widom_pair_at(mmc_batch *b, int32_t n_sites_a, const double *charge_a, const double *eps_a,
+                                const double *sig_a, int32_t n_sites_b, const double *charge_b, const double *eps_b,
+                                const double *sig_b, const double *eps_ab, const double *sig_ab, int32_t n_sep,
+                                int64_t n_insert, const double *mol_a_in, const double *mol_b_in, double temperature,
+                                double *boltz_a, int64_t *n_zero_a, double *boltz_b, int64_t *n_zero_b,
+                                double *boltz_ab, int64_t *n_zero_ab, double *du_out, uint8_t *flags_out);
 
 /* ---- Deletion energies: binding-energy histograms and the deletion half of BAR ------------------
  * The mirror image of mmc_batch_widom: the energy each EXISTING molecule is bound with.  The

@@ -187,6 +187,11 @@ SIGNATURES = {
                                _dp, _dp, C.POINTER(C.c_uint8)],
     "mmc_batch_widom_solute_at": [_vp, C.c_int32, _dp, _dp, _dp, _i64, _dp, _d, _dp, _i64p, _dp,
                                   C.POINTER(C.c_uint8)],
+    "mmc_batch_widom_pair": [_vp, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32,
+                             _dp, _i64, C.c_uint64, _i64, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _dp, _dp,
+                             C.POINTER(C.c_uint8)],
+    "mmc_batch_widom_pair_at": [_vp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _i64,
+                                _dp, _dp, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
     "mmc_batch_deletion": [_vp, C.c_int32, _i32p, _d, C.c_int32, _d, _d, C.c_int32, C.POINTER(C.c_uint64),
                            _dp, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
     "mmc_batch_forces": [_vp, C.c_int32, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, C.POINTER(C.c_uint8)],

@@ -30,7 +30,7 @@
 #ifndef WIDOM_OCC
 #define WIDOM_OCC 4 // waves per SIMD k_widom_wave is compiled for: 102 VGPRs, no scratch (at 5 = 96 VGPRs
 #endif              // it spilled 5 VGPRs: the test molecule's record and the insertion's bookkeeping)
-#define MMC_WIDOM_SLOT 0x50000000u // == MMC_SLOT_WIDOM (include/mmc_hip.h): slots +0, +1, +2
+#define MMC_WIDOM_SLOT 0x50000000u // == MMC_SLOT_WIDOM (include/mmc_hip.h): slots +0, +1, +2 (+3..+5: mmc_solute_pair.hpp)
 
 struct WidomArgs {
     uint64_t seed;       // Philox key

@@ -633,6 +633,69 @@ class Batch:
                                                 _d(mol), float(temperature), _d(bs), _i(no), _d(du), _u8(ov)))
         return bs, no, du, ov
 
+    def pair_sums(self, sums, K):
+        """The six accumulators of widom_pair: a dict (or None = new zero arrays) with boltz_a (R,),
+        n_zero_a (R,), boltz_b, boltz_ab (R, K), n_zero_b, n_zero_ab (R, K)."""
+        sums = {} if sums is None else sums
+        out = {}
+        for name, dt, shape in (("boltz_a", np.float64, (self.R,)), ("n_zero_a", np.int64, (self.R,)),
+                                ("boltz_b", np.float64, (self.R, K)), ("n_zero_b", np.int64, (self.R, K)),
+                                ("boltz_ab", np.float64, (self.R, K)), ("n_zero_ab", np.int64, (self.R, K))):
+            v = sums.get(name)
+            if v is None:
+                v = np.zeros(shape, dtype=dt)
+            elif not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            out[name] = v
+        return out
+
+    def widom_pair(self, pair, d, n_insert, temperature, seed, draw0=0, sums=None, outputs=False):
+        """mmc_batch_widom_pair: n_insert random insertions of the solute pair (structs.SolutePair)
+        into every replica, B at the K separations d (A) from A along one random ray per insertion;
+        A is drawn as widom_solute() draws it.  `sums`: a dict of the six accumulators (pair_sums;
+        None = new zero arrays), added to in place and returned: boltz_a, n_zero_a (R,), boltz_b,
+        n_zero_b, boltz_ab, n_zero_ab (R, K).  With outputs=True also returns mol_a (R, M, S_A + 1,
+        3), mol_b (R, M, K, S_B + 1, 3), du (R, M, 1 + 2 K, 3) = A, B_0.., x_0.. and flags (R, M,
+        1 + K).  observables.pair_pmf turns the sums into g(d) and w(d)."""
+        a, b = pair.a, pair.b
+        d = _f64(d).ravel()
+        K, M = d.shape[0], int(n_insert)
+        sm = self.pair_sums(sums, K)
+        mol_a = np.zeros((self.R, M, a.n_sites + 1, 3)) if outputs else None
+        mol_b = np.zeros((self.R, M, K, b.n_sites + 1, 3)) if outputs else None
+        du = np.zeros((self.R, M, 1 + 2 * K, 3)) if outputs else None
+        fl = np.zeros((self.R, M, 1 + K), dtype=np.uint8) if outputs else None
+        check(self._L.mmc_batch_widom_pair(
+            self._h, a.n_sites, _d(a.offsets), _d(a.charge), _d(a.eps), _d(a.sig), b.n_sites, _d(b.offsets),
+            _d(b.charge), _d(b.eps), _d(b.sig), _d(pair.eps_ab), _d(pair.sig_ab), K, _d(d), M,
+            int(seed) & (2 ** 64 - 1), int(draw0), float(temperature), _d(sm["boltz_a"]), _i(sm["n_zero_a"]),
+            _d(sm["boltz_b"]), _i(sm["n_zero_b"]), _d(sm["boltz_ab"]), _i(sm["n_zero_ab"]),
+            _d(mol_a) if outputs else None, _d(mol_b) if outputs else None, _d(du) if outputs else None,
+            _u8(fl) if outputs else None))
+        return (sm, mol_a, mol_b, du, fl) if outputs else sm
+
+    def widom_pair_at(self, pair, mol_a, mol_b, temperature, sums=None):
+        """mmc_batch_widom_pair_at: the caller's placements mol_a (R, M, S_A + 1, 3) and mol_b (R, M,
+        K, S_B + 1, 3), sites then the reference point (offsets and separations are not used).
+        Returns (sums, du (R, M, 1 + 2 K, 3), flags (R, M, 1 + K))."""
+        a, b = pair.a, pair.b
+        mol_a, mol_b = _f64(mol_a), _f64(mol_b)
+        if mol_a.ndim != 4 or mol_a.shape[0] != self.R or mol_a.shape[2:] != (a.n_sites + 1, 3):
+            raise ValueError("mol_a must be (R, n_insert, n_sites_a + 1, 3)")
+        M = mol_a.shape[1]
+        if mol_b.ndim != 5 or mol_b.shape[:2] != (self.R, M) or mol_b.shape[3:] != (b.n_sites + 1, 3):
+            raise ValueError("mol_b must be (R, n_insert, n_sep, n_sites_b + 1, 3)")
+        K = mol_b.shape[2]
+        sm = self.pair_sums(sums, K)
+        du = np.zeros((self.R, M, 1 + 2 * K, 3))
+        fl = np.zeros((self.R, M, 1 + K), dtype=np.uint8)
+        check(self._L.mmc_batch_widom_pair_at(
+            self._h, a.n_sites, _d(a.charge), _d(a.eps), _d(a.sig), b.n_sites, _d(b.charge), _d(b.eps), _d(b.sig),
+            _d(pair.eps_ab), _d(pair.sig_ab), K, M, _d(mol_a), _d(mol_b), float(temperature), _d(sm["boltz_a"]),
+            _i(sm["n_zero_a"]), _d(sm["boltz_b"]), _i(sm["n_zero_b"]), _d(sm["boltz_ab"]), _i(sm["n_zero_ab"]),
+            _d(du), _u8(fl)))
+        return sm, du, fl
+
     def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
                  n_flagged=None, details=False):
         """mmc_batch_deletion: the deletion (binding) energy dU_i = potential(N) - potential(N

@@ -631,6 +631,64 @@ function widom_solute_at!(b::Batch, charge::Vector{Float64}, eps::Vector{Float64
     return boltz_sum, n_overlap
 end
 
+# ---- solute pairs (include/mmc_hip.h, mmc_batch_widom_pair / mmc_batch_widom_pair_at) -----------------
+"""
+    widom_pair!(b, A, B, eps_ab, sig_ab, d, n_insert, seed, draw0, temperature, sums)
+    widom_pair_at!(b, A, B, eps_ab, sig_ab, n_sep, mol_a_in, mol_b_in, n_insert, temperature, sums)
+
+`n_insert` insertions into every replica of two rigid foreign solutes, B at the `K = length(d)`
+separations `d` (A, each below half the box) from A along one random ray per insertion: the sums of
+the potential distribution theorem's g_AB(d) = <exp(-dU_AB / T)> / (<exp(-dU_A / T)> <exp(-dU_B / T)>)
+at infinite dilution.  `A` and `B` are named tuples `(offsets, charge, eps, sig)` as `widom_solute!`
+takes them (S_A + S_B <= 16), `eps_ab` / `sig_ab` are S_A * S_B Float64, A's site by A's site.
+`sums` is a named tuple `(boltz_a, n_zero_a, boltz_b, n_zero_b, boltz_ab, n_zero_ab)`: R, R, K * R,
+K * R, K * R, K * R entries (separation fastest), added to in insertion order.  A is drawn as
+`widom_solute!` draws it.  `widom_pair_at!` evaluates the caller's placements: `mol_a_in` = R *
+n_insert * (S_A + 1) * 3 and `mol_b_in` = R * n_insert * K * (S_B + 1) * 3 Float64 (sites, then the
+reference point).  Read-only for the chains.  w(d) = -T log g_AB(d) in K.
+"""
+function widom_pair!(b::Batch, A, B, eps_ab::Vector{Float64}, sig_ab::Vector{Float64}, d::Vector{Float64},
+                     n_insert::Integer, seed::Integer, draw0::Integer, temperature::Float64, sums)
+    SA, SB, K = length(A.charge), length(B.charge), length(d)
+    SA >= 1 && SB >= 1 && SA + SB <= 16 || error("a solute pair has at most 16 sites in all")
+    length(eps_ab) == SA * SB && length(sig_ab) == SA * SB || error("eps_ab, sig_ab: S_A x S_B")
+    pair_sums_ok(b, sums, K)
+    check(ccall((:mmc_batch_widom_pair, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int64,
+                 UInt64, Int64, Float64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, SA, A.offsets, A.charge, A.eps, A.sig, SB, B.offsets, B.charge, B.eps, B.sig, eps_ab, sig_ab, K,
+                d, n_insert, UInt64(seed), draw0, temperature, sums.boltz_a, sums.n_zero_a, sums.boltz_b,
+                sums.n_zero_b, sums.boltz_ab, sums.n_zero_ab, C_NULL, C_NULL, C_NULL, C_NULL))
+    return sums
+end
+function widom_pair_at!(b::Batch, A, B, eps_ab::Vector{Float64}, sig_ab::Vector{Float64}, n_sep::Integer,
+                        mol_a_in::Vector{Float64}, mol_b_in::Vector{Float64}, n_insert::Integer,
+                        temperature::Float64, sums)
+    SA, SB, K = length(A.charge), length(B.charge), Int(n_sep)
+    SA >= 1 && SB >= 1 && SA + SB <= 16 || error("a solute pair has at most 16 sites in all")
+    length(eps_ab) == SA * SB && length(sig_ab) == SA * SB || error("eps_ab, sig_ab: S_A x S_B")
+    length(mol_a_in) == 3 * (SA + 1) * n_insert * b.n_replicas || error("mol_a_in: R x n_insert x (S_A + 1) x 3")
+    length(mol_b_in) == 3 * (SB + 1) * K * n_insert * b.n_replicas || error("mol_b_in: R x n_insert x K x (S_B + 1) x 3")
+    pair_sums_ok(b, sums, K)
+    check(ccall((:mmc_batch_widom_pair_at, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Float64,
+                 Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}),
+                b.h, SA, A.charge, A.eps, A.sig, SB, B.charge, B.eps, B.sig, eps_ab, sig_ab, K, n_insert, mol_a_in,
+                mol_b_in, temperature, sums.boltz_a, sums.n_zero_a, sums.boltz_b, sums.n_zero_b, sums.boltz_ab,
+                sums.n_zero_ab, C_NULL, C_NULL))
+    return sums
+end
+function pair_sums_ok(b::Batch, sums, K::Integer)
+    R = b.n_replicas
+    length(sums.boltz_a) == R && length(sums.n_zero_a) == R || error("boltz_a, n_zero_a: one per replica")
+    all(length(v) == R * K for v in (sums.boltz_b, sums.n_zero_b, sums.boltz_ab, sums.n_zero_ab)) ||
+        error("boltz_b, n_zero_b, boltz_ab, n_zero_ab: R x K")
+    return nothing
+end
+
 # ---- deletion energies (include/mmc_hip.h, mmc_batch_deletion) -------------------------------------
 """
     deletion(b, temperature; sel = nothing, bins = nothing, per_replica = false,

@@ -267,7 +267,7 @@ def normalize_q_hist(q_hist):
 
 
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
-MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2
+MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2 (+3, +4, +5: pair_molecules)
 
 
 def widom_mu_ex(boltz_sum, n_total, temperature):
@@ -345,6 +345,66 @@ def solute_molecules(philox, seed, draw0, n_insert, replica, box, offsets):
                 out[j, a, d] = com[d] + ((R[d, 0] * off[a, 0] + R[d, 1] * off[a, 1]) + R[d, 2] * off[a, 2])
         out[j, S] = com
     return out
+
+
+# ---- solute pairs (include/mmc_hip.h, "Solute pairs") ------------------------------------------------
+def pair_molecules(philox, seed, draw0, n_insert, replica, box, offsets_a, offsets_b, d):
+    """Host mirror of mmc_batch_widom_pair's generator for one replica: (mol_a [n_insert][S_A + 1][3],
+    mol_b [n_insert][K][S_B + 1][3]), sites then the reference point.  A is solute_molecules' (slots
+    MMC_SLOT_WIDOM + 0, 1, 2).  Slot +3 (u, v) gives the ray's direction n = (s cos phi, s sin phi, z),
+    z = 1 - 2 u, s = sqrt(1 - z^2), phi = 2 pi v; slots +4 (u1, u2) and +5 (u3, its first uniform)
+    give shoemake_rotation(u1, u2, u3) = R_B.  c_B,k = c_A + d_k n wrapped per axis (> box: - box,
+    < 0: + box), site b = c_B,k + R_B off_b; n and R_B serve all K separations."""
+    mol_a = solute_molecules(philox, seed, draw0, n_insert, replica, box, offsets_a)
+    off = np.asarray(offsets_b, dtype=float).reshape(-1, 3)
+    d = np.asarray(d, dtype=float).ravel()
+    S, K = off.shape[0], d.shape[0]
+    mol_b = np.empty((int(n_insert), K, S + 1, 3))
+    for j in range(int(n_insert)):
+        c = int(draw0) + j
+        u, v = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 3, replica)
+        u1, u2 = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 4, replica)
+        u3, _ = philox_uniforms(philox, seed, c, MMC_SLOT_WIDOM + 5, replica)
+        z = 1.0 - 2.0 * u
+        s = np.sqrt(1.0 - z * z)
+        phi = 2.0 * np.pi * v
+        n = np.array([s * np.cos(phi), s * np.sin(phi), z])
+        R = shoemake_rotation(u1, u2, u3)
+        ro = np.array([[(R[e, 0] * off[b, 0] + R[e, 1] * off[b, 1]) + R[e, 2] * off[b, 2] for e in range(3)]
+                       for b in range(S)])
+        for k in range(K):
+            cb = mol_a[j, -1] + d[k] * n
+            cb = np.where(cb > box, cb - box, cb)
+            cb = np.where(cb < 0, cb + box, cb)
+            mol_b[j, k, :S] = cb + ro
+            mol_b[j, k, S] = cb
+    return mol_a, mol_b
+
+
+def pair_pmf(boltz_ab, boltz_a, boltz_b, n_insert_total, temperature):
+    """g_AB(d) and the potential of mean force w(d) = -T ln g_AB(d) (K) at infinite dilution from
+    Batch.widom_pair's sums: boltz_ab (R, K), boltz_a (R,), boltz_b (R, K) over n_insert_total
+    insertions per replica,
+        g = <exp(-dU_AB / T)> / (<exp(-dU_A / T)> <exp(-dU_B / T)>).
+    Returns a dict: g, w (K,) pooled over the replicas (the three averages pooled first); g_rep, w_rep
+    (R, K) per replica; g_err, w_err (K,) the standard error of the per-replica values over the
+    replicas (NaN for one replica)."""
+    ab = np.asarray(boltz_ab, dtype=float)
+    ab = ab.reshape(ab.shape[0], -1) if ab.ndim > 1 else ab.reshape(1, -1)
+    R, K = ab.shape
+    a = np.asarray(boltz_a, dtype=float).reshape(R)
+    b = np.asarray(boltz_b, dtype=float).reshape(R, K)
+    n, T = float(n_insert_total), float(temperature)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g_rep = (ab / n) / ((a[:, None] / n) * (b / n))
+        g = (ab.sum(0) / (R * n)) / ((a.sum() / (R * n)) * (b.sum(0) / (R * n)))
+        w_rep, w = -T * np.log(g_rep), -T * np.log(g)
+        if R > 1:
+            g_err = g_rep.std(0, ddof=1) / np.sqrt(R)
+            w_err = w_rep.std(0, ddof=1) / np.sqrt(R)
+        else:
+            g_err = w_err = np.full(K, np.nan)
+    return dict(g=g, w=w, g_rep=g_rep, w_rep=w_rep, g_err=g_err, w_err=w_err)
 
 
 # ---- cavities and occupancy (include/mmc_hip.h, "Cavities and occupancy") ---------------------------

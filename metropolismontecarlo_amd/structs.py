@@ -103,6 +103,33 @@ class Solute:
         return f"Solute({self.name!r}, {self.n_sites} sites, net charge {self.charge.sum():+.4f})"
 
 
+class SolutePair:
+    """Two rigid foreign solutes for Batch.widom_pair (include/mmc_hip.h, "Solute pairs"): Solute a,
+    Solute b and their cross table eps_ab / sig_ab (S_A, S_B) in K and A, already mixed.  S_A + S_B
+    may not exceed Solute.MAX_SITES."""
+    MAX_SEP = 32  # MMC_PAIR_MAX_SEP
+
+    def __init__(self, a, b, eps_ab, sig_ab):
+        if not isinstance(a, Solute) or not isinstance(b, Solute):
+            raise ValueError("a and b must be Solutes")
+        self.a, self.b = a, b
+        self.eps_ab = np.ascontiguousarray(eps_ab, dtype=np.float64).reshape(a.n_sites, b.n_sites)
+        self.sig_ab = np.ascontiguousarray(sig_ab, dtype=np.float64).reshape(a.n_sites, b.n_sites)
+        if a.n_sites + b.n_sites > Solute.MAX_SITES:
+            raise ValueError(f"a solute pair has at most {Solute.MAX_SITES} sites in all, not "
+                             f"{a.n_sites} + {b.n_sites}")
+        for name, t in (("eps_ab", self.eps_ab), ("sig_ab", self.sig_ab)):
+            if not np.all(np.isfinite(t)) or np.any(t < 0):
+                raise ValueError(f"{name} must be finite and >= 0")
+
+    def swapped(self):
+        """The pair with A and B exchanged."""
+        return SolutePair(self.b, self.a, self.eps_ab.T, self.sig_ab.T)
+
+    def __repr__(self):
+        return f"SolutePair({self.a.name!r}, {self.b.name!r})"
+
+
 class EWALD:
     """mutable struct EWALD{I} (Ewald/ewalds.jl:9-19)."""
 

@@ -1,0 +1,166 @@
+"""CPU tests of the boundary of mmc_batch_widom_pair and mmc_batch_widom_pair_at: declared with the
+agreed prototypes, exported, bound with matching ctypes, and loud on a NULL batch and on every
+argument that can be refused without a device -- with the outputs coming back untouched."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from metropolismontecarlo_amd import _lib
+from test_solute_abi import CTYPES, header_code, header_prototype
+
+PROTOTYPES = {
+    "mmc_batch_widom_pair": (
+        "int32_t mmc_batch_widom_pair(mmc_batch *b, int32_t n_sites_a, const double *offsets_a, "
+        "const double *charge_a, const double *eps_a, const double *sig_a, int32_t n_sites_b, "
+        "const double *offsets_b, const double *charge_b, const double *eps_b, const double *sig_b, "
+        "const double *eps_ab, const double *sig_ab, int32_t n_sep, const double *d, int64_t n_insert, "
+        "uint64_t seed, int64_t draw0, double temperature, double *boltz_a, int64_t *n_zero_a, double *boltz_b, "
+        "int64_t *n_zero_b, double *boltz_ab, int64_t *n_zero_ab, double *mol_a_out, double *mol_b_out, "
+        "double *du_out, uint8_t *flags_out);"),
+    "mmc_batch_widom_pair_at": (
+        "int32_t mmc_batch_widom_pair_at(mmc_batch *b, int32_t n_sites_a, const double *charge_a, "
+        "const double *eps_a, const double *sig_a, int32_t n_sites_b, const double *charge_b, const double *eps_b, "
+        "const double *sig_b, const double *eps_ab, const double *sig_ab, int32_t n_sep, int64_t n_insert, "
+        "const double *mol_a_in, const double *mol_b_in, double temperature, double *boltz_a, int64_t *n_zero_a, "
+        "double *boltz_b, int64_t *n_zero_b, double *boltz_ab, int64_t *n_zero_ab, double *du_out, "
+        "uint8_t *flags_out);"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PROTOTYPES))
+def test_symbols_are_declared_exported_and_bound_with_the_header_prototype(name):
+    from test_abi import header_functions
+    proto = PROTOTYPES[name]
+    assert name in header_functions()
+    assert header_prototype(name) == proto
+    assert hasattr(C.CDLL(_lib.LIB_PATH), name)
+    params = proto[proto.index("(") + 1:proto.rindex(")")].split(", ")
+    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
+    assert _lib.SIGNATURES[name] == want
+    fn = getattr(_lib.lib(), name)
+    assert fn.argtypes == want and fn.restype is C.c_int32
+
+
+def test_the_constants_of_the_header_and_their_mirrors():
+    from metropolismontecarlo_amd import observables as obs
+    from metropolismontecarlo_amd import structs
+    code = header_code()
+    assert re.search(r"#define\s+MMC_PAIR_MAX_SEP\s+32\b", code)
+    assert structs.SolutePair.MAX_SEP == 32
+    hpp = open(os.path.join(os.path.dirname(_lib.__file__), "csrc", "mmc_solute_pair.hpp")).read()
+    assert re.search(r"#define\s+PAIR_MAX_SEP\s+32\b", hpp)
+    # the slots of the second solute follow the three of an insertion
+    assert re.search(r"#define\s+MMC_SLOT_WIDOM\s+0x50000000u", code) and obs.MMC_SLOT_WIDOM == 0x50000000
+    assert "+0..+5" in open(os.path.join(os.path.dirname(_lib.__file__), "..", "include", "mmc_hip.h")).read()
+
+
+def call(at=False, b=None, SA=2, SB=1, n_sites_a=None, n_sites_b=None, offsets_a=0.5, offsets_b=0.0,
+         charge_a=(0.4, -0.4), charge_b=(0.3,), eps_a=50.0, sig_a=3.0, eps_b=40.0, sig_b=2.5, eps_ab=45.0, sig_ab=2.8,
+         K=2, d=(3.0, 5.0), n_insert=4, temperature=298.15, sums=(True,) * 6, mol_a=1.0, mol_b=2.0):
+    """One call with sentinel outputs, which must come back untouched.  Array arguments: a fill
+    value, a sequence, or None for a NULL pointer.  Returns (status, message)."""
+    def arr(v, n):
+        if v is None:
+            return None
+        vals = list(v) if isinstance(v, (tuple, list)) else [v] * n
+        return (C.c_double * max(len(vals), 1))(*vals)
+
+    fs = [(C.c_double * 64)(*([7.5] * 64)) for _ in range(3)]
+    ns = [(C.c_int64 * 64)(*([3] * 64)) for _ in range(3)]
+    du = (C.c_double * 512)(*([7.5] * 512))
+    fl = (C.c_uint8 * 64)(*([9] * 64))
+    ma = (C.c_double * 256)(*([7.5] * 256))
+    mb = (C.c_double * 1024)(*([7.5] * 1024))
+    sm = []
+    for i in range(3):
+        sm += [fs[i] if sums[2 * i] else None, ns[i] if sums[2 * i + 1] else None]
+    na = SA if n_sites_a is None else n_sites_a
+    nb = SB if n_sites_b is None else n_sites_b
+    L = _lib.lib()
+    sol_a = (arr(charge_a, SA), arr(eps_a, 3 * SA), arr(sig_a, 3 * SA))
+    sol_b = (arr(charge_b, SB), arr(eps_b, 3 * SB), arr(sig_b, 3 * SB))
+    x = (arr(eps_ab, SA * SB), arr(sig_ab, SA * SB))
+    if at:
+        st = L.mmc_batch_widom_pair_at(b, na, *sol_a, nb, *sol_b, *x, K, n_insert, arr(mol_a, 3 * (SA + 1) * 4),
+                                       arr(mol_b, 3 * (SB + 1) * 4 * max(K, 1)), temperature, *sm, du, fl)
+    else:
+        st = L.mmc_batch_widom_pair(b, na, arr(offsets_a, 3 * SA), *sol_a, nb, arr(offsets_b, 3 * SB), *sol_b, *x, K,
+                                    arr(d, K), n_insert, 1234, 0, temperature, *sm, ma, mb, du, fl)
+    for f in fs:
+        assert all(v == 7.5 for v in f)
+    for n in ns:
+        assert all(v == 3 for v in n)
+    assert all(v == 7.5 for v in du) and all(v == 9 for v in fl)
+    assert all(v == 7.5 for v in ma) and all(v == 7.5 for v in mb)
+    msg = L.mmc_last_error()
+    return st, (msg.decode() if msg else "")
+
+
+@pytest.mark.parametrize("at", [False, True])
+def test_a_null_batch_fails_loudly(at):
+    st, msg = call(at)
+    assert st == _lib.MMC_ERR_ARG and "NULL" in msg and "batch" in msg
+    with pytest.raises(_lib.MMCError, match="MMC_ERR_ARG"):
+        _lib.check(st)
+
+
+NAN, INF = float("nan"), float("inf")
+ONLY = lambda i: tuple(j != i for j in range(6))  # noqa: E731
+
+
+@pytest.mark.parametrize("at", [False, True])
+@pytest.mark.parametrize("kw,word", [
+    (dict(n_sites_a=0), "n_sites_a"), (dict(n_sites_a=-1), "n_sites_a"), (dict(n_sites_a=16), "n_sites_a"),
+    (dict(n_sites_b=0), "n_sites_b"), (dict(n_sites_b=16), "n_sites_b"),
+    (dict(n_sites_a=9, n_sites_b=8), "n_sites_a + n_sites_b"),
+    (dict(K=0), "n_sep"), (dict(K=-3), "n_sep"), (dict(K=33), "n_sep"),
+    (dict(charge_a=None), "charge_a"), (dict(eps_a=None), "eps_a"), (dict(sig_a=None), "sig_a"),
+    (dict(charge_b=None), "charge_b"), (dict(eps_b=None), "eps_b"), (dict(sig_b=None), "sig_b"),
+    (dict(eps_ab=None), "eps_ab"), (dict(sig_ab=None), "sig_ab"),
+    (dict(sums=ONLY(0)), "boltz_a"), (dict(sums=ONLY(1)), "n_zero_a"), (dict(sums=ONLY(2)), "boltz_b"),
+    (dict(sums=ONLY(3)), "n_zero_b"), (dict(sums=ONLY(4)), "boltz_ab"), (dict(sums=ONLY(5)), "n_zero_ab"),
+    (dict(n_insert=0), "n_insert"), (dict(n_insert=-2), "n_insert"),
+    (dict(temperature=0.0), "temperature"), (dict(temperature=NAN), "temperature"),
+    (dict(temperature=INF), "temperature"), (dict(temperature=-1.0), "temperature"),
+    (dict(charge_a=(0.4, NAN)), "charge_a"), (dict(charge_b=(INF,)), "charge_b"),
+    (dict(eps_a=NAN), "eps_a"), (dict(eps_b=(1.0, -1e-300, 1.0)), "eps_b"),
+    (dict(sig_a=INF), "sig_a"), (dict(sig_b=(1.0, 1.0, -3.0)), "sig_b"),
+    (dict(eps_ab=NAN), "eps_ab"), (dict(eps_ab=(1.0, -1.0)), "eps_ab"), (dict(eps_ab=INF), "eps_ab"),
+    (dict(sig_ab=NAN), "sig_ab"), (dict(sig_ab=(-0.5, 1.0)), "sig_ab"),
+])
+def test_arguments_refused_without_a_device(at, kw, word):
+    """These are refused before the batch is looked at: the message names the argument, not the
+    NULL batch, and nothing is written."""
+    st, msg = call(at, **kw)
+    assert st == _lib.MMC_ERR_ARG
+    assert word in msg and "batch is NULL" not in msg, msg
+
+
+@pytest.mark.parametrize("kw,word", [
+    (dict(offsets_a=None), "offsets_a"), (dict(offsets_b=None), "offsets_b"), (dict(offsets_a=NAN), "offsets_a"),
+    (dict(offsets_b=(0.0, -INF, 0.0)), "offsets_b"),
+    (dict(d=None), "NULL d"), (dict(d=(3.0, NAN)), "d must"), (dict(d=(INF, 3.0)), "d must"),
+    (dict(d=(0.0, 3.0)), "d must"), (dict(d=(3.0, -2.0)), "d must"),
+])
+def test_generator_arguments_refused_without_a_device(kw, word):
+    st, msg = call(False, **kw)
+    assert st == _lib.MMC_ERR_ARG and word in msg and "batch is NULL" not in msg, msg
+
+
+@pytest.mark.parametrize("kw,word", [(dict(mol_a=None), "mol_a_in"), (dict(mol_b=None), "mol_b_in")])
+def test_null_placements_are_refused_without_a_device(kw, word):
+    st, msg = call(True, **kw)
+    assert st == _lib.MMC_ERR_ARG and word in msg and "batch is NULL" not in msg, msg
+
+
+@pytest.mark.parametrize("at", [False, True])
+@pytest.mark.parametrize("SA,SB", [(1, 15), (15, 1), (5, 11), (8, 8)])
+def test_sixteen_sites_in_all_and_zero_parameters_get_as_far_as_the_batch(at, SA, SB):
+    """S_A + S_B = 16, zero charges, eps = 0 and sig = 0, one separation and 32 of them are all
+    valid: the call reaches the NULL-batch check."""
+    for K in (1, 32):
+        st, msg = call(at, SA=SA, SB=SB, charge_a=0.0, charge_b=0.0, eps_a=0.0, sig_a=0.0, eps_b=0.0, sig_b=0.0,
+                       eps_ab=0.0, sig_ab=0.0, K=K, d=[1.0 + 0.1 * k for k in range(K)], n_insert=1)
+        assert st == _lib.MMC_ERR_ARG and "batch is NULL" in msg, msg
