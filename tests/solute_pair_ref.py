@@ -1,5 +1,6 @@
 """Helpers of the solute-pair tests (test_solute_pair_abi.py, test_solute_pair_host.py,
-test_gpu_solute_pair.py): the pairs the tests insert and the oracle's statement of every term --
+test_gpu_solute_pair.py, test_solute_paths_host.py, test_gpu_solute_paths.py): the pairs the tests
+insert and the oracle's statement of every term --
 solute_ref.SoluteOracle for A alone and for B alone on N + 1 molecules, and for the A-B term x the
 oracle's lj_poly_du(2), ewald_short(2) and factor (recip_long(A u B) - recip_long(A) - recip_long(B))
 on a System that holds only A and B in the same box, with eps_ab / sig_ab as its type table."""
@@ -187,24 +188,52 @@ class PairOracle:
         return rows, flags
 
 
-def check_pair(po, b, r, mol_a, mol_b, du, flags, what=""):
+def expected_flags(rows, ofl):
+    """The flag bytes [1 + K] k_pair_reduce leaves for an insertion whose rows [1 + 2 K][3] and
+    overlap bits ofl [1 + K] (0 and 2) are the oracle's: bit 1 where dU_A (column 0) or dU_B is
+    non-finite, bit 3 where dU_AB = (dU_A + dU_B) + x is."""
+    K = ofl.shape[0] - 1
+    with np.errstate(invalid="ignore"):
+        du_a, du_b, _, du_ab = du_total(rows)
+    out = np.zeros(1 + K, dtype=np.uint8)
+    out[0] = (int(ofl[0]) & 1) | (0 if np.isfinite(du_a) else 2)
+    for k in range(K):
+        out[1 + k] = (int(ofl[1 + k]) & 5) | (0 if np.isfinite(du_b[k]) else 2) | (0 if np.isfinite(du_ab[k]) else 8)
+    return out
+
+
+def check_pair(po, b, r, mol_a, mol_b, du, flags, what="", cache=True, nonfinite=None):
     """Every term and the overlap bits of replica r's insertions against the oracle, on the replica's
     own coordinates: solute_ref.solute_close with S = S_A for A, S_B for B and S_A + S_B for x.
-    Returns the oracle's rows [M][1 + 2 K][3] and flags [M][1 + K]."""
+    Returns the oracle's rows [M][1 + 2 K][3] and flags [M][1 + K].
+    cache=False: recip_long(N) is recomputed for every placement (after anything that changed the
+    committed state a kept value would hide what is sought).  `nonfinite`: a list; a row (j, row)
+    whose oracle terms are not all finite (a site planted exactly on another) is appended to it, its
+    terms are not compared and the library's dU of the row must be non-finite; and EVERY flag byte
+    must then be expected_flags of the oracle's rows, all four bits."""
     com, coords, _ = b.get_replica(r)
     box = float(b.get_boxes()[r])
     SA, SB = po.pair.a.n_sites, po.pair.b.n_sites
     Mi, K = mol_b.shape[0], mol_b.shape[1]
     bad, ref, rfl = [], [], []
     for j in range(Mi):
-        rows, fl = po.reference(com, coords, mol_a[j], mol_b[j], box, key=(id(b), r))
+        rows, fl = po.reference(com, coords, mol_a[j], mol_b[j], box, key=(id(b), r) if cache else None)
         ref.append(rows)
         rfl.append(fl)
         for e in range(1 + K):
             if (int(flags[j, e]) & 5) != int(fl[e]):
                 bad.append((j, e, "flags", int(flags[j, e]), int(fl[e])))
+        if nonfinite is not None:
+            want = expected_flags(rows, fl)
+            if not np.array_equal(flags[j], want):
+                bad.append((j, "flag bytes", flags[j].tolist(), want.tolist()))
         for row in range(1 + 2 * K):
             S = SA if row == 0 else SB if row <= K else SA + SB
+            if nonfinite is not None and not np.all(np.isfinite(rows[row])):
+                nonfinite.append((j, row))
+                if np.isfinite((du[j, row, 0] + du[j, row, 1]) + du[j, row, 2]):
+                    bad.append((j, row, "finite dU", tuple(du[j, row])))
+                continue
             for c, name in enumerate(("lj", "real", "recip")):
                 if not sr.solute_close(du[j, row, c], rows[row, c], S):
                     bad.append((j, row, name, du[j, row, c], rows[row, c]))
@@ -317,3 +346,207 @@ def flush_cases(a, pair, n=6, d=(3.0, 5.0, 7.0, 9.0, 11.0)):
         rb = pair.b.offsets @ rot().T
         mol_b.append([np.vstack([(ca + dk * nh) % L + rb, (ca + dk * nh) % L]) for dk in d])
     return np.array(mol_a)[None], np.array(mol_b)[None]
+
+
+# ---- inputs shared by test_solute_paths_host.py (preconditions) and test_gpu_solute_paths.py --------
+SUMS = ("boltz_a", "n_zero_a", "boltz_b", "n_zero_b", "boltz_ab", "n_zero_ab")
+PATH_D = (3.0, 5.0, 7.0, 9.0, 11.0)       # two tiles, the last separation beyond both gates (r_cut 10)
+SMALL_D = (2.5, 4.0, 5.5, 7.5, 9.2)       # ... in the 18.7 A boxes (r_cut 7 and 9), below half the box
+SMALL_N = (1, 2, 63, 64, 65, 256, 257)
+GEN_D, GEN_SEED, GEN_DRAW0, GEN_M = (1.0, 7.0, 14.9), 93, 2 ** 32 - 3, 8
+FLAG_SEED, FLAG_M, FLAG_D = 4712, 200, (3.0, 6.0, 11.0)
+
+
+def path_solute(a):
+    return sr.synthetic(a, 5, seed=5)
+
+
+def path_pair(a):
+    return synthetic_pair(a, 3, 4)
+
+
+def flag_pair(a):
+    """The pair of the planted flags: both solutes have a negative site with LJ (a site on a water
+    oxygen then overlaps nothing) and site pairs of either sign of q_a q_b with eps_ab > 0."""
+    return synthetic_pair(a, 5, 4)
+
+
+def full_pair(a, SA=8, SB=8):
+    """synthetic(SA) with synthetic(SB) and a cross table without a zeroed entry."""
+    A, B = sr.synthetic(a, SA, seed=SA), sr.synthetic(a, SB, seed=SB)
+    rng = np.random.default_rng(100 * SA + SB)
+    return structs.SolutePair(A, B, 30.0 + 70.0 * rng.random((SA, SB)), 2.5 + rng.random((SA, SB)))
+
+
+def mixed_pair(a, methane_first):
+    """United-atom methane with solute_ref.dipole: exactly one solute of the pair is charged."""
+    p = structs.SolutePair(sr.methane(a), sr.dipole(a), *cross([147.9], [3.73], [110.0, 0.0], [3.4, 0.0]))
+    return p if methane_first else p.swapped()
+
+
+def separations(K):
+    return (4.0,) if K == 1 else tuple(np.linspace(2.5, 14.9, K))
+
+
+def pair_gate_cases(mol_a, box, pair, lj, qq, seed=17):
+    """For each given A [n][S_A + 1][3] K = 4 placements of B, c_B at (1 - 1e-12) g, (1 + 1e-12) g of
+    the smaller gate and then of the larger, from c_A along solute_ref.GATE_DIRS[i % 3], one random
+    orientation per insertion: separation 0 is inside both gates, 1 and 2 between them, 3 outside."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(mol_a.shape[0]):
+        rot, u = sr.rotation(rng), sr.GATE_DIRS[i % 3]
+        out.append([sr.placed(pair.b.offsets, (mol_a[i, -1] + g * f * u) % box, rot)
+                    for g in sorted((lj, qq)) for f in (1 - 1e-12, 1 + 1e-12)])
+    return np.array(out)
+
+
+def gate_pattern(x, lj, qq):
+    """Whether x [n][4][3], the x rows of pair_gate_cases, switch as the gates say: inside both gates
+    x_lj and x_real are non-zero, outside both they are zero, between them only the term of the
+    larger gate is non-zero."""
+    x_lj, x_real = x[:, :, 0] != 0.0, x[:, :, 1] != 0.0
+    between_lj, between_real = (lj > qq), (qq > lj)
+    return bool(np.all(x_lj[:, 0]) and np.all(x_real[:, 0]) and not x_lj[:, 3].any() and not x_real[:, 3].any()
+                and np.all(x_lj[:, 1:3] == between_lj) and np.all(x_real[:, 1:3] == between_real))
+
+
+def small_cases(a, n, sol, pair, d=PATH_D):
+    """_at placements in the first n molecules of system `a`: the reference point 3 A from molecule
+    n - 1's COM (the index the scans' clamp protects), B along another direction: (mol (1, 1, S + 1,
+    3), mol_a (1, 1, S_A + 1, 3), mol_b (1, 1, K, S_B + 1, 3))."""
+    L = float(a["box"])
+    c = (np.asarray(a["com"])[n - 1] + 3.0 * np.array([2.0, -1.0, 2.0]) / 3.0) % L
+    v = np.array([0.6, 0.0, 0.8])
+    mol_b = np.array([sr.placed(pair.b.offsets, (c + dk * v) % L) for dk in d])
+    return sr.placed(sol.offsets, c)[None, None], sr.placed(pair.a.offsets, c)[None, None], mol_b[None, None]
+
+
+def overlaps_ab(sites_a, q_a, sites_b, q_b, box, ovr=0.5):
+    d = np.asarray(sites_a, dtype=float)[:, None, :] - np.asarray(sites_b, dtype=float)[None, :, :]
+    d = d + common.image_shift(d, box)
+    return bool(np.any(((d * d).sum(2) < ovr) & (np.asarray(q_a)[:, None] * np.asarray(q_b)[None, :] < 0)))
+
+
+HOT_T, HOT_SEED, HOT_M, HOT_D = 5000.0, 4713, 65, (3.0, 6.0)
+
+
+def hot_pair(a):
+    """solute_ref.dipole (its negative site has no LJ) with a ghost: dU_AB is dU_A."""
+    return structs.SolutePair(sr.dipole(a), ghost(2), np.zeros((2, 2)), np.zeros((2, 2)))
+
+
+def light_overlap(a, sol, coords, seed=29):
+    """`sol` [S + 1][3] with its negative LJ-free site 0.5 A from a water H, no other site within
+    sqrt(0.5) A of an opposite charge and every LJ site at least 2.4 A from every oxygen: an overlap
+    (flag bit 0, d_real = 0) whose dU = d_lj + d_recip stays moderate, so that at HOT_T the weight it
+    would have WITHOUT its flag is of the order of the other insertions' weights."""
+    L = float(a["box"])
+    rng = np.random.default_rng(seed)
+    q_w = np.asarray(a["charge"], dtype=float)[:coords.shape[0]]
+    neg = int(np.argmin(sol.charge))
+    assert sol.charge[neg] < 0 < q_w[1] and sol.eps[neg].max() <= 0.001
+    lj = sol.eps[:, 0] > 0.001
+    rest = np.arange(sol.n_sites) != neg
+    oxy = coords[0::3]
+    arm = sol.offsets[lj].mean(0) - sol.offsets[neg]        # from the negative site to the LJ sites
+    arm = arm / np.linalg.norm(arm)
+    for w in rng.permutation(coords.shape[0] // 3)[:200]:
+        for h in (1, 2):
+            out = coords[3 * w + h] - coords[3 * w]
+            out = out + common.image_shift(out, L)
+            out = out / np.linalg.norm(out)                 # O -> H: the way out of this water
+            for _ in range(50):
+                rot, v = sr.rotation(rng), out + 0.4 * rng.normal(size=3)
+                if (rot @ arm) @ out < 0.8:
+                    continue
+                target = coords[3 * w + h] + 0.5 * v / np.linalg.norm(v)
+                m = sr.placed(sol.offsets, target - sol.offsets[neg] @ rot.T, rot)
+                m[neg] = target
+                d = m[:-1][lj][:, None, :] - oxy[None, :, :]
+                d = d + common.image_shift(d, L)
+                if (d * d).sum(2).min() >= 2.4 ** 2 and not sr.overlaps_water(m[:-1][rest], sol.charge[rest], coords, q_w, L):
+                    return m
+    raise AssertionError("no placement found")
+
+
+def flag_plants(a, pair, coords, mol_a, mol_b, r=0, seed=23):
+    """Plants the flagged placements of the test of k_pair_reduce's later blocks into mol_a [M][S_A + 1][3]
+    and mol_b [M][K][S_B + 1][3] (M >= 192, K = 3) of one replica with atoms `coords`, in place.
+    Returns {(j, column): flag byte}; the kinds, each oriented at random until no OTHER flag of the
+    planted placement can arise (no further site within sqrt(0.5) A of an opposite charge):
+      A  a negative site 0.5 A from a water H                    (j = 5, 70)   column 0: bit 0
+      A  a negative LJ site exactly on a water O                 (j = 100)     column 0: bit 1; every
+                                                                               column 1 + k: bit 3 on top
+      B_1 a negative site 0.5 A from a water H                   (j = 128)     column 2: bit 0
+      B_2 a negative LJ site exactly on a water O                (j = 140)     column 3: bits 1 and 3
+      B_0 a site 0.5 A from an A site of the opposite charge     (j = 191)     column 1: bit 2 only
+      B_2 a site exactly on an A site, eps_ab > 0, q_a q_b >= 0  (j = 150)     column 3: bit 3 only
+    For the last two, A is the insertion's own (generated) one, and j moves down from the stated one
+    until B fits among the waters."""
+    L = float(a["box"])
+    rng = np.random.default_rng(seed + r)
+    q_w = np.asarray(a["charge"], dtype=float)[:coords.shape[0]]
+    A, B = pair.a, pair.b
+    SA, SB = A.n_sites, B.n_sites
+
+    def lj_negative(s):
+        i = [k for k in range(s.n_sites) if s.charge[k] < 0 and s.eps[k, 0] > 0.001]
+        assert i, s
+        return i[0]
+
+    def unit():
+        v = rng.normal(size=3)
+        return v / np.linalg.norm(v)
+
+    def at_water(s, site, target, others_free):
+        """s with its `site` on `target`, no other opposite-charge contact with the waters."""
+        for _ in range(400):
+            rot = sr.rotation(rng)
+            m = sr.placed(s.offsets, target - s.offsets[site] @ rot.T, rot)
+            m[site] = target
+            keep = np.arange(s.n_sites) != site if others_free else np.ones(s.n_sites, dtype=bool)
+            if not sr.overlaps_water(m[:-1][keep], s.charge[keep], coords, q_w, L):
+                return m
+        raise AssertionError("no orientation found")
+
+    plant = {}
+    neg_a, neg_b = int(np.argmin(A.charge)), int(np.argmin(B.charge))
+    assert A.charge[neg_a] < 0 and B.charge[neg_b] < 0 < q_w[1]
+    for j, w in ((5, 100), (70, 101)):
+        mol_a[j] = at_water(A, neg_a, coords[3 * (w + r) + 1] + 0.5 * unit(), True)
+        plant[(j, 0)] = 1
+    mol_a[100] = at_water(A, lj_negative(A), coords[3 * (200 + r)].copy(), False)
+    plant[(100, 0)] = 2
+    mol_b[128, 1] = at_water(B, neg_b, coords[3 * (300 + r) + 1] + 0.5 * unit(), True)
+    plant[(128, 2)] = 1
+    mol_b[140, 2] = at_water(B, lj_negative(B), coords[3 * (400 + r)].copy(), False)
+    plant[(140, 3)] = 2 | 8
+    # the A-B plants
+    qq = A.charge[:, None] * B.charge[None, :]
+    ia, ib = np.argwhere(qq < 0)[0]
+    ja, jb = np.argwhere((qq >= 0) & (pair.eps_ab > 0.001))[0]
+    for j0, k, sa, sb, gap, byte in ((191, 0, ia, ib, 0.5, 4), (150, 2, ja, jb, 0.0, 8)):
+        done = False
+        for j in range(j0, j0 - 20, -1):
+            ma = mol_a[j]
+            if sr.overlaps_water(ma[:-1], A.charge, coords, q_w, L):
+                continue                  # (an A that overlaps a water weighs 0 anyway: take a plain one)
+            for _ in range(200):
+                rot = sr.rotation(rng)
+                target = ma[sa] + gap * unit()
+                m = sr.placed(B.offsets, target - B.offsets[sb] @ rot.T, rot)
+                m[sb] = target
+                rest = np.arange(SB) != sb
+                far = np.linalg.norm(m[:-1][rest][None] - ma[:-1][:, None], axis=2).min() > 0.05
+                if (not sr.overlaps_water(m[:-1], B.charge, coords, q_w, L) and far
+                        and np.linalg.norm(m[:-1][:, None] - coords[None], axis=2).min() > 0.8
+                        and overlaps_ab(ma[:-1], A.charge, m[:-1], B.charge, L) == (byte == 4)):
+                    mol_b[j, k] = m
+                    plant[(j, 1 + k)] = byte
+                    done = True
+                    break
+            if done:
+                break
+        assert done, (j0, k)
+    return plant

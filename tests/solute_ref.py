@@ -1,4 +1,5 @@
-"""Helpers of the foreign-solute tests (test_solute_abi.py, test_solute_host.py, test_gpu_solute.py):
+"""Helpers of the foreign-solute tests (test_solute_abi.py, test_solute_host.py, test_gpu_solute.py,
+test_solute_paths_host.py, test_gpu_solute_paths.py):
 the solutes the tests insert, the deck lattice they insert MEA into, and the oracle's statement of
 the insertion energy -- common.widom_oracle_terms with S sites and the solute's own atom types
 appended to an oracle.System of N + 1 molecules."""
@@ -95,6 +96,58 @@ def tip3p_lattice(n_mol=216, rho=0.0331, seed=4):
                 sig=one["sig"][:2, :2].copy(), box=float(box))
 
 
+def rotation(rng):
+    """A random rotation matrix (a normalised Gaussian quaternion)."""
+    q = rng.normal(size=4)
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def placed(off, c, rot=None):
+    """A solute [S + 1][3] with body offsets `off` (S, 3), rotated by `rot`, at the reference point c."""
+    o = np.asarray(off, dtype=float) if rot is None else np.asarray(off, dtype=float) @ rot.T
+    c = np.asarray(c, dtype=float)
+    return np.vstack([c + o, c])
+
+
+def first_molecules(a, n):
+    """The first n molecules of the system `a` in its own box."""
+    out = dict(a)
+    out.update(com=np.asarray(a["com"])[:n].copy(), coords=np.asarray(a["coords"])[:3 * n].copy(),
+               atype=np.asarray(a["atype"])[:3 * n].copy(), charge=np.asarray(a["charge"])[:3 * n].copy(),
+               first_atom=np.asarray(a["first_atom"])[:n].copy(), last_atom=np.asarray(a["last_atom"])[:n].copy())
+    return out
+
+
+# the directions of test_gpu_widom_paths.py's test_separate_cutoffs
+GATE_DIRS = (np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, -1.0]), np.array([1.0, -1.0, 1.0]) / np.sqrt(3.0))
+
+
+def gate_cases(com, box, sol, lj, qq, waters=(3, 250)):
+    """Upright solutes with the reference point at (1 -+ 1e-12) g from the COMs of `waters`, for g in
+    (lj, qq), along GATE_DIRS: (mols [n][S + 1][3], tags [n] = (water, 0 for lj / 1 for qq, direction,
+    inside))."""
+    mols, tags = [], []
+    for j in waters:
+        for gi, g in enumerate((lj, qq)):
+            for di, d in enumerate(GATE_DIRS):
+                for f in (1 - 1e-12, 1 + 1e-12):
+                    mols.append(placed(sol.offsets, (com[j] + g * f * d) % box))
+                    tags.append((j, gi, di, f < 1))
+    return np.array(mols), tags
+
+
+def overlaps_water(sites, q, coords, q_w, box, ovr=0.5):
+    """Whether a site and a water atom of opposite charges lie closer than sqrt(ovr) (ewalds.jl:359;
+    the COM gate is open for any such pair)."""
+    d = np.asarray(sites, dtype=float)[:, None, :] - np.asarray(coords, dtype=float)[None, :, :]
+    d = d + common.image_shift(d, box)
+    u = (d * d).sum(2)
+    return bool(np.any((u < ovr) & (np.asarray(q)[:, None] * np.asarray(q_w)[None, :] < 0)))
+
+
 def scan_flushes(com, centre, gate, box):
     """Whether k_solute_wave's COM scan (mmc_solute.hpp) certainly empties its neighbour list
     mid-scan and has neighbours left for a later process() call: it scans the molecules in trips of
@@ -170,17 +223,31 @@ def solute_close(x, ref, S):
     return abs(x - ref) <= 1e-9 * max(1.0, S / 3.0) + 1e-13 * abs(ref)
 
 
-def check_solute(so, b, r, mols, du, ovl, what=""):
+def check_solute(so, b, r, mols, du, ovl, what="", cache=True, nonfinite=None):
     """Every term and the overlap flag of replica r's insertions mols [M][S + 1][3] against the
-    oracle, on the replica's own coordinates.  Returns the oracle's terms [M][3] and flags [M]."""
+    oracle, on the replica's own coordinates.  Returns the oracle's terms [M][3] and flags [M].
+    cache=False: recip_long(N) is recomputed for every insertion (after anything that changed the
+    committed state a kept value would hide what is sought).  `nonfinite`: a list; an insertion
+    whose oracle terms are not all finite (a site planted exactly on an atom) is appended to it,
+    its terms are not compared, the library's dU of it must be non-finite and its flag must be
+    bit 0 as the oracle states it plus bit 1, and every other flag must be the oracle's bit 0 alone."""
     com, coords, _ = b.get_replica(r)
     box = float(b.get_boxes()[r])
     S = so.sol.n_sites
     bad, ref, flags = [], [], []
     for j in range(mols.shape[0]):
-        lj, real, recip, ov = so.terms(com, coords, mols[j], box, key=(id(b), r))
+        lj, real, recip, ov = so.terms(com, coords, mols[j], box, key=(id(b), r) if cache else None)
         ref.append((lj, real, recip))
         flags.append(ov)
+        if nonfinite is not None:
+            finite = bool(np.all(np.isfinite([lj, real, recip])))
+            if int(ovl[j]) != (1 if ov else 0) | (0 if finite else 2):
+                bad.append((j, "flag", int(ovl[j]), ov, finite))
+            if not finite:
+                nonfinite.append(j)
+                if np.isfinite((du[j, 0] + du[j, 1]) + du[j, 2]):
+                    bad.append((j, "finite dU", tuple(du[j])))
+                continue
         if bool(ovl[j] & 1) != ov:
             bad.append((j, "overlap", int(ovl[j]), ov))
         for name, x, y in (("lj", du[j, 0], lj), ("real", du[j, 1], real), ("recip", du[j, 2], recip)):
