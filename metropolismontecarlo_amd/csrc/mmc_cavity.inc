@@ -1,8 +1,9 @@
 // mmc_cavity.inc -- host side of mmc_batch_cavity and mmc_batch_cavity_at (include/mmc_hip.h,
 // "Cavities and occupancy"; the kernel is in mmc_cavity.hpp).  Included by mmc_hip.hip after
-// mmc_struct.inc, whose state checks it shares, and after mmc_units.inc, whose device scratch
-// (obs_scratch) it uses.
+// mmc_units.inc (ObsCall).
 #include "mmc_cavity.hpp"
+
+static_assert(CV_WAVES == TILE_WAVES && CV_LDS_BYTES == TILE_LDS_BYTES, "tile_waves sizes the workgroup");
 
 static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, const double *points_in,
                           bool at, int32_t site, int32_t n_radii, const double *radii, int32_t n_cap,
@@ -52,27 +53,26 @@ static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t 
     const int K = n_radii;
     const int64_t n_rep = per_replica ? R : 1;
     const size_t n_occ = occ_hist ? (size_t)K * (n_cap + 1) : 0, n_nn = nn_hist ? (size_t)nn_bins + 1 : 0;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t oh_bytes = up16(8 * (size_t)n_rep * n_occ), om_bytes = up16(occ_mom ? 16 * (size_t)n_rep * K : 0);
-    const size_t nh_bytes = up16(8 * (size_t)n_rep * n_nn);
-    const bool want_pts = at || points_out;
-    const size_t pt_bytes = up16(want_pts ? 24 * (size_t)(R * P) : 0), ct_bytes = up16(count_out ? 4 * (size_t)(R * P) * K : 0);
-    const size_t r2_bytes = up16(nn_r2_out ? 8 * (size_t)(R * P) : 0), ix_bytes = up16(nn_idx_out ? 4 * (size_t)(R * P) : 0);
-    char *d_buf = nullptr;
-    MMC_TRY(obs_scratch(b, oh_bytes + om_bytes + nh_bytes + pt_bytes + ct_bytes + r2_bytes + ix_bytes, &d_buf));
-    char *d_oh = d_buf, *d_om = d_oh + oh_bytes, *d_nh = d_om + om_bytes, *d_pt = d_nh + nh_bytes,
-         *d_ct = d_pt + pt_bytes, *d_r2 = d_ct + ct_bytes, *d_ix = d_r2 + r2_bytes;
+    const size_t oh_bytes = 8 * (size_t)n_rep * n_occ, om_bytes = 16 * (size_t)n_rep * K,
+                 nh_bytes = 8 * (size_t)n_rep * n_nn;
+    const size_t pt_bytes = 24 * (size_t)(R * P), ct_bytes = 4 * (size_t)(R * P) * K, r2_bytes = 8 * (size_t)(R * P),
+                 ix_bytes = 4 * (size_t)(R * P);
+    ObsCall oc(b);
+    const size_t o_oh = oc.take(oh_bytes), o_om = oc.take(occ_mom ? om_bytes : 0), o_nh = oc.take(nh_bytes),
+                 o_pt = oc.take(at || points_out ? pt_bytes : 0), o_ct = oc.take(count_out ? ct_bytes : 0),
+                 o_r2 = oc.take(nn_r2_out ? r2_bytes : 0), o_ix = oc.take(nn_idx_out ? ix_bytes : 0);
+    MMC_TRY(oc.alloc());
 
     CavityArgs ca{};
     ca.box_r = s.pb.on ? s.pb.d_box : nullptr;
-    ca.points_in = at ? reinterpret_cast<const double *>(d_pt) : nullptr;
-    ca.points_out = (!at && points_out) ? reinterpret_cast<double *>(d_pt) : nullptr;
-    ca.occ_hist = occ_hist ? reinterpret_cast<unsigned long long *>(d_oh) : nullptr;
-    ca.occ_mom = occ_mom ? reinterpret_cast<unsigned long long *>(d_om) : nullptr;
-    ca.nn_hist = nn_hist ? reinterpret_cast<unsigned long long *>(d_nh) : nullptr;
-    ca.count = count_out ? reinterpret_cast<int32_t *>(d_ct) : nullptr;
-    ca.nn_r2 = nn_r2_out ? reinterpret_cast<double *>(d_r2) : nullptr;
-    ca.nn_idx = nn_idx_out ? reinterpret_cast<int32_t *>(d_ix) : nullptr;
+    ca.points_in = at ? oc.at<double>(o_pt) : nullptr;
+    ca.points_out = (!at && points_out) ? oc.at<double>(o_pt) : nullptr;
+    ca.occ_hist = occ_hist ? oc.at<unsigned long long>(o_oh) : nullptr;
+    ca.occ_mom = occ_mom ? oc.at<unsigned long long>(o_om) : nullptr;
+    ca.nn_hist = nn_hist ? oc.at<unsigned long long>(o_nh) : nullptr;
+    ca.count = count_out ? oc.at<int32_t>(o_ct) : nullptr;
+    ca.nn_r2 = nn_r2_out ? oc.at<double>(o_r2) : nullptr;
+    ca.nn_idx = nn_idx_out ? oc.at<int32_t>(o_ix) : nullptr;
     for (int k = 0; k < CV_MAX_RADII; k++)
         ca.rad2[k] = k < K ? radii[k] * radii[k] : 0.0;
     ca.rmax2 = ca.rad2[K - 1];
@@ -87,60 +87,38 @@ static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t 
     ca.per_replica = per_replica ? 1 : 0;
     ca.R = (int32_t)R;
 
-    // waves per workgroup: as many of CV_WAVES as keep their counters within half of the LDS; the site
-    // positions are staged when they fit in the rest
+    // waves per workgroup: as many as keep their counters within half of the LDS; the site positions
+    // are staged when they fit in the rest
     const size_t per_wave = 4 * (n_occ + n_nn);
-    int nw = CV_WAVES;
-    while (nw > 1 && (size_t)nw * per_wave > CV_LDS_BYTES / 2)
-        nw >>= 1;
-    const size_t lds_w = up16((size_t)nw * per_wave);
+    const int nw = tile_waves(CV_LDS_BYTES / 2, per_wave);
+    const size_t lds_w = ((size_t)nw * per_wave + 15) & ~(size_t)15;
     const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= CV_LDS_BYTES;
     const size_t lds = lds_w + (stage ? 24 * (size_t)N : 0);
-    // persistent workgroups: four waves per SIMD of every compute unit, or option "wave_wgs"; no more
-    // than give every wave a block of 64 probes
-    const int64_t units = R * ((P + 63) / 64);
-    int64_t wgs = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(16 / nw) * b->n_cus;
-    wgs = std::max<int64_t>(1, std::min(wgs, (units + nw - 1) / nw));
+    const unsigned g = obs_grid(b, nw, R * ((P + 63) / 64)), t = (unsigned)nw * 64; // a block of 64 probes is a wave's unit
 
-    hipStream_t st = s.stream;
-    hipError_t e = hipMemsetAsync(d_buf, 0, oh_bytes + om_bytes + nh_bytes, st);
-    if (e == hipSuccess && at)
-        e = hipMemcpyAsync(d_pt, points_in, 24 * (size_t)(R * P), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    oc.zero(o_pt);
+    if (at)
+        oc.to_device(oc.at<double>(o_pt), points_in, pt_bytes);
+    if (oc.e == hipSuccess) {
         const bool use_rec = struct_use_rec(b);
-        const unsigned g = (unsigned)wgs, t = (unsigned)nw * 64;
         if (use_rec && stage)
-            k_cavity_lane<true, true><<<g, t, lds, st>>>(s.bv, s.rec, ca);
+            k_cavity_lane<true, true><<<g, t, lds, oc.st>>>(s.bv, s.rec, ca);
         else if (use_rec)
-            k_cavity_lane<true, false><<<g, t, lds, st>>>(s.bv, s.rec, ca);
+            k_cavity_lane<true, false><<<g, t, lds, oc.st>>>(s.bv, s.rec, ca);
         else if (stage)
-            k_cavity_lane<false, true><<<g, t, lds, st>>>(s.bv, nullptr, ca);
+            k_cavity_lane<false, true><<<g, t, lds, oc.st>>>(s.bv, nullptr, ca);
         else
-            k_cavity_lane<false, false><<<g, t, lds, st>>>(s.bv, nullptr, ca);
-        e = hipGetLastError();
+            k_cavity_lane<false, false><<<g, t, lds, oc.st>>>(s.bv, nullptr, ca);
     }
-    // everything goes through host copies: the caller's arrays are written only on success
-    const size_t out_bytes[7] = { 8 * (size_t)n_rep * n_occ, occ_mom ? 16 * (size_t)n_rep * K : 0, 8 * (size_t)n_rep * n_nn,
-                                  (!at && points_out) ? 24 * (size_t)(R * P) : 0, count_out ? 4 * (size_t)(R * P) * K : 0,
-                                  nn_r2_out ? 8 * (size_t)(R * P) : 0, nn_idx_out ? 4 * (size_t)(R * P) : 0 };
-    const char *d_src[7] = { d_oh, d_om, d_nh, d_pt, d_ct, d_r2, d_ix };
-    void *dst[7] = { occ_hist, occ_mom, nn_hist, points_out, count_out, nn_r2_out, nn_idx_out };
-    std::vector<char> h_out[7];
-    for (int k = 0; k < 7 && e == hipSuccess; k++) {
-        if (!out_bytes[k])
-            continue;
-        h_out[k].resize(out_bytes[k]);
-        e = hipMemcpyAsync(h_out[k].data(), d_src[k], out_bytes[k], hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    else
-        (void)hipStreamSynchronize(st); // (the host buffers of copies already queued outlive them)
-    MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    for (int k = 0; k < 7; k++)
-        if (out_bytes[k])
-            memcpy(dst[k], h_out[k].data(), out_bytes[k]);
-    return MMC_OK;
+    oc.launched();
+    oc.fetch(occ_hist, oc.at<char>(o_oh), oh_bytes);
+    oc.fetch(occ_mom, oc.at<char>(o_om), om_bytes);
+    oc.fetch(nn_hist, oc.at<char>(o_nh), nh_bytes);
+    oc.fetch(at ? nullptr : points_out, oc.at<char>(o_pt), pt_bytes);
+    oc.fetch(count_out, oc.at<char>(o_ct), ct_bytes);
+    oc.fetch(nn_r2_out, oc.at<char>(o_r2), r2_bytes);
+    oc.fetch(nn_idx_out, oc.at<char>(o_ix), ix_bytes);
+    return oc.finish(what);
 }
 
 extern "C" int32_t mmc_batch_cavity(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, int32_t site,

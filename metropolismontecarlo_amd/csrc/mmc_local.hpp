@@ -30,7 +30,7 @@
 // Counters: 32-bit, private to the wave in LDS (27 hydrogen-bond counters, q_bins of q), added to
 // the 64-bit global ones whenever the wave leaves a replica -- integer adds, any order.
 #pragma once
-#include "mmc_wave.hpp"
+#include "mmc_tiles.hpp"
 
 #define LO_WAVES 4              // waves per workgroup (fewer where the histograms would not fit: host)
 #define LO_LDS_BYTES 65536      // dynamic LDS a workgroup may ask for without opting in
@@ -98,21 +98,6 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_local_order_wave(BatchView bv
     const int64_t M = (int64_t)la.R * n_mol;
     const int64_t m0 = M * blockIdx.x / gridDim.x, m1 = M * (blockIdx.x + 1) / gridDim.x;
 
-    // O, H, H of molecule j of replica r
-    auto sites = [&](int r, int j, double *o) {
-        if constexpr (REC) {
-            const double2 *src = reinterpret_cast<const double2 *>(rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE);
-            const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4];
-            o[0] = v0.x; o[1] = v0.y; o[2] = v1.x; o[3] = v1.y; o[4] = v2.x; o[5] = v2.y;
-            o[6] = v3.x; o[7] = v3.y; o[8] = v4.x;
-        } else {
-            const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                o[3 * a] = bv.ax[a0 + a]; o[3 * a + 1] = bv.ay[a0 + a]; o[3 * a + 2] = bv.az[a0 + a];
-            }
-        }
-    };
     // the O of molecule j (j < n_mol) of replica r
     auto oxygen = [&](int r, int j, double &x, double &y, double &z) {
         if constexpr (STAGE) {
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_local_order_wave(BatchView bv
 
         for (int i = i_lo + wv; i < i_hi; i += nw) {
             double ci[9]; // the wave's molecule: wave-uniform
-            sites(r, i, ci);
+            load_sites9<REC>(bv, rec, r, i, ci); // O, H, H
             double ui[2][3]; // d(O_i, H_i,h)
 #pragma unroll
             for (int h = 0; h < 2; h++)
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_local_order_wave(BatchView bv
                 if (lane < n) {
                     const int j = cand[lane];
                     double cj[9];
-                    sites(r, j, cj);
+                    load_sites9<REC>(bv, rec, r, j, cj);
                     const double vx = vector1D(ci[0], cj[0], bc), vy = vector1D(ci[1], cj[1], bc),
                                  vz = vector1D(ci[2], cj[2], bc);
                     const double vv = (vx * vx + vy * vy) + vz * vz;

@@ -3,7 +3,7 @@
 //                        per bin of the slot-0 separation, every pair i < j once
 //
 // The separation and its bin are row (0,0) of k_rdf_sites_wave bit for bit (mmc_struct.hpp: st_image,
-// r^2 = (xx xx + yy yy) + zz zz, the host-built thresholds).  The axis u_i is the unit vector of
+// r^2 = (xx xx + yy yy) + zz zz; mmc_tiles.hpp: tile_bin).  The axis u_i is the unit vector of
 // k_dipoles' mu_i = (q_0 d_0 + q_1 d_1) + q_2 d_2, d_a = vector1D(COM, atom a); u = mu / sqrt(n^2),
 // n^2 = (mu_x^2 + mu_y^2) + mu_z^2, and u = 0 when n^2 is 0 or not finite.  Per pair
 //     c  = (u_i.x u_j.x + u_i.y u_j.y) + u_i.z u_j.z
@@ -13,11 +13,11 @@
 // integer: all four rows are integer sums, so no order of lanes, waves, flushes or atomics can change
 // a bit of the result.
 //
-// The decomposition is k_rdf_sites_wave's: a wave owns a contiguous run of 64 x 64 tiles (k, c <= k)
-// of the i < j triangle; lane n keeps neighbour n of block k across a row of tiles -- here six
-// doubles, site 0 and u, not nine.  u costs a square root and three divisions: it is computed once
-// per (replica, block) by the lane that loads the record.  The chosen side: at the start of a tile
-// the 64 lanes load block c's records and compute their u as well, and the walk over the chosen
+// The tiles of the i < j triangle and a wave's run of them are mmc_tiles.hpp's.  Lane n keeps
+// neighbour n of block k across a row of tiles -- here six doubles, site 0 and u, not nine.  u costs
+// a square root and three divisions: it is computed once per (replica, block) by the lane that loads
+// the record.  The chosen side: at the start of a tile the 64 lanes load block c's records and
+// compute their u as well, and the walk over the chosen
 // molecules pulls the six values out with v_readlane (twelve per chosen molecule, against ~70 vector
 // instructions per pair row), so every vector instruction of the pair has them as scalar operands
 // and the hot loop has no memory load at all.  (The alternative, a [R][N][8] array of site 0 and u
@@ -39,24 +39,16 @@
 #pragma once
 #include "mmc_struct.hpp"
 
-#define OR_WAVES 4                  // waves per workgroup (fewer where the histograms would not fit: host)
-#define OR_LDS_BYTES 65536          // dynamic LDS a workgroup may ask for without opting in
 // MMC_ORIENT_MAX_BINS (include/mmc_hip.h): one wave per workgroup, thresholds 8 (numbins + 2) bytes and
 // four 64-bit rows 32 (numbins + 2) bytes
-static_assert(40 * (MMC_ORIENT_MAX_BINS + 2) <= OR_LDS_BYTES && 40 * (MMC_ORIENT_MAX_BINS + 3) > OR_LDS_BYTES,
+static_assert(40 * (MMC_ORIENT_MAX_BINS + 2) <= TILE_LDS_BYTES && 40 * (MMC_ORIENT_MAX_BINS + 3) > TILE_LDS_BYTES,
               "MMC_ORIENT_MAX_BINS is what one wave fits");
 #define OR_MAGIC 6755399441055744.0 // 1.5 2^52: x + OR_MAGIC has the bits of OR_MAGIC plus rint(x), |x| < 2^51
 #define OR_MAGIC_BITS 0x4338000000000000ULL
 
 struct OrientArgs {
-    const double *thr;        // [numbins + 2]: thr[k] = largest r^2 with bin <= k; thr[numbins + 1] = +inf
-    const double *box_r;      // [R] per-replica boxes, or NULL: bv.box
+    TileArgs ta;
     unsigned long long *hist; // [4][numbins + 2] or [R][4][numbins + 2], zeroed by the host
-    int32_t numbins, per_replica;
-    float inv_dr;
-    int32_t n_blocks;         // K = ceil(n_mol / 64)
-    int32_t tiles_per_rep;    // K (K + 1) / 2: tiles (k, c), c <= k, k-major
-    int64_t n_tiles;          // R * tiles_per_rep
 };
 
 __device__ __forceinline__ unsigned long long or_quant(double v)
@@ -72,22 +64,7 @@ __device__ __forceinline__ void or_molecule(const BatchView &bv, const double *_
     const int f0 = bv.first0[m];
     const double q0 = bv.charge[f0], q1 = bv.charge[f0 + 1], q2 = bv.charge[f0 + 2];
     double t[12];
-    if constexpr (REC) {
-        const double2 *src = reinterpret_cast<const double2 *>(rec + ((int64_t)r * bv.n_mol + m) * MMC_RSTRIDE);
-#pragma unroll
-        for (int q = 0; q < 6; q++) {
-            const double2 v = src[q];
-            t[2 * q] = v.x;
-            t[2 * q + 1] = v.y;
-        }
-    } else {
-        const int64_t mi = (int64_t)r * bv.mol_stride + m, a0 = (int64_t)r * bv.atom_stride + f0;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            t[3 * a] = bv.ax[a0 + a]; t[3 * a + 1] = bv.ay[a0 + a]; t[3 * a + 2] = bv.az[a0 + a];
-        }
-        t[9] = bv.comx[mi]; t[10] = bv.comy[mi]; t[11] = bv.comz[mi];
-    }
+    load_sites12<REC>(bv, rec, r, m, t);
     double mu[3];
 #pragma unroll
     for (int d = 0; d < 3; d++)
@@ -103,31 +80,24 @@ __device__ __forceinline__ void or_molecule(const BatchView &bv, const double *_
     }
 }
 
-// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays (a batch holds
-// three-atom molecules only).
-// grid: any number of workgroups of blockDim.x / 64 waves; wave W of NW takes tiles
-// [n_tiles W / NW, n_tiles (W + 1) / NW).
+// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays (load_sites12).
+// grid and tiles: mmc_tiles.hpp.
 template <bool REC>
-__global__ __launch_bounds__(OR_WAVES * 64) void k_orient_corr_wave(BatchView bv, const double *__restrict__ rec,
+__global__ __launch_bounds__(TILE_WAVES * 64) void k_orient_corr_wave(BatchView bv, const double *__restrict__ rec,
                                                                     OrientArgs oa)
 {
     extern __shared__ __align__(16) unsigned char or_lds[];
-    const int nb = oa.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
+    const TileArgs &ta = oa.ta;
+    const int nb = ta.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
     double *const thr = reinterpret_cast<double *>(or_lds);                                      // [rs]
     unsigned long long *const hall = reinterpret_cast<unsigned long long *>(or_lds + 8 * rs);    // [nw][4][rs]
     unsigned long long *const hw = hall + wv * 4 * rs;
-    for (int q = tid; q < rs; q += (int)blockDim.x)
-        thr[q] = oa.thr[q];
-    for (int q = tid; q < nw * 4 * rs; q += (int)blockDim.x)
-        hall[q] = 0ull;
-    __syncthreads();
+    tile_prologue(thr, ta.thr, rs, hall, nw * 4 * rs);
 
-    const int n_mol = bv.n_mol, K = oa.n_blocks, T = oa.tiles_per_rep;
-    const float inv_dr = oa.inv_dr, e_max = (float)(nb + 1);
-    const int64_t NW = (int64_t)gridDim.x * nw, W = (int64_t)blockIdx.x * nw + wv;
-    const int64_t t0 = oa.n_tiles * W / NW, t1 = oa.n_tiles * (W + 1) / NW;
+    const int n_mol = bv.n_mol;
+    const float inv_dr = ta.inv_dr, e_max = (float)(nb + 1);
 
     // counters src[n_src][4][rs] summed and added to dst[4][rs], the offsets of Q's bit patterns
     // taken off: n lanes added to rows 1..3 of a slot where row 0 of that slot counts n (rows 2 and
@@ -161,35 +131,31 @@ __global__ __launch_bounds__(OR_WAVES * 64) void k_orient_corr_wave(BatchView bv
         wave_sync();
     };
 
-    if (t0 < t1) {
-        int r = (int)(t0 / T), k = 0, c = (int)(t0 - (int64_t)r * T);
-        while (c > k) { // tile index -> (k, c): rows of 1, 2, 3, ... tiles
-            c -= k + 1;
-            k++;
-        }
-        int r_hist = r;
-        bool fresh = true; // (r, k) changed: the lane's neighbour is to be loaded
-        double t[6];       // neighbour j: site 0, u
+    TileCursor tc(ta, gridDim.x, blockIdx.x, nw, wv);
+    if (tc.more()) {
+        int r_hist = tc.r;
+        double t[6]; // neighbour j: site 0, u
         BoxConsts bc = box_consts(bv.box);
-        for (int64_t tile = t0; tile < t1; tile++) {
+        for (; tc.more(); tc.next()) {
+            const int r = tc.r;
             // `lane` is made opaque once per unit (mmc_wave.hpp): lane-derived values are not hoisted
             // out of the persistent loop and held for the kernel's life
             int lane = lane0;
             asm volatile("" : "+v"(lane));
-            if (oa.per_replica && r != r_hist) {
+            if (ta.per_replica && r != r_hist) {
                 flush_wave(oa.hist + (int64_t)r_hist * 4 * rs);
                 r_hist = r;
             }
-            const int j = 64 * k + lane;
-            if (fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
-                bc = box_consts(oa.box_r ? oa.box_r[r] : bv.box);
+            const int j = 64 * tc.k + lane;
+            if (tc.fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
+                bc = box_consts(ta.box_r ? ta.box_r[r] : bv.box);
                 or_molecule<REC>(bv, rec, r, min(j, n_mol - 1), bc, t);
-                fresh = false;
+                tc.fresh = false;
             }
             const double half = bc.half, neg_box = bc.neg;
             // the chosen molecules of block c: lane n computes molecule 64 c + n's six values, the
             // walk below reads them as wave-uniform values
-            const int i_lo = 64 * c, n_i = min(64, n_mol - i_lo);
+            const int i_lo = 64 * tc.c, n_i = min(64, n_mol - i_lo);
             double cs[6];
             or_molecule<REC>(bv, rec, r, min(i_lo + lane, n_mol - 1), bc, cs);
             for (int ii = 0; ii < n_i; ii++) {
@@ -200,12 +166,7 @@ __global__ __launch_bounds__(OR_WAVES * 64) void k_orient_corr_wave(BatchView bv
                 const double yy = st_image(sy - t[1], half, neg_box);
                 const double zz = st_image(sz - t[2], half, neg_box);
                 const double r2 = (xx * xx + yy * yy) + zz * zz;
-                float e = ceilf(__builtin_amdgcn_sqrtf((float)r2) * inv_dr);
-                e = fminf(fmaxf(e, 1.0f), e_max); // 1 .. numbins + 1 (a NaN lands on 1: in bounds)
-                int b = (int)e;
-                const double lo = thr[b - 1], hi = thr[b];
-                b += (r2 > hi) ? 1 : 0;
-                b -= (r2 <= lo) ? 1 : 0;
+                const int b = tile_bin(thr, r2, inv_dr, e_max);
                 const double cc = (ux * t[3] + uy * t[4]) + uz * t[5];
                 const bool pair = j > i && j < n_mol;
                 if (pair) {
@@ -224,20 +185,11 @@ __global__ __launch_bounds__(OR_WAVES * 64) void k_orient_corr_wave(BatchView bv
                     __hip_atomic_fetch_add(&hw[3 * rs + b], or_quant(p2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-            // the next tile: (k, c + 1), then the next row of tiles, then the next replica
-            if (++c > k) {
-                c = 0;
-                fresh = true;
-                if (++k == K) {
-                    k = 0;
-                    r++;
-                }
-            }
         }
-        if (oa.per_replica)
+        if (ta.per_replica)
             flush_wave(oa.hist + (int64_t)r_hist * 4 * rs);
     }
-    if (!oa.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
+    if (!ta.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
         __syncthreads();
         flush(oa.hist, hall, nw, tid, (int)blockDim.x, false);
     }

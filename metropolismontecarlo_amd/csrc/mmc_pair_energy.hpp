@@ -5,9 +5,9 @@
 //                        i < j once
 //   k_pair_energy_nhb    the per-molecule counts -> the distribution of energetic hydrogen bonds
 //
-// The separation and its bin are k_orient_corr_wave's bit for bit (mmc_orient.hpp; row (0,0) of
-// k_rdf_sites_wave).  The energy of a pair in range is that of the nine atom pairs at the MOLECULE's
-// image: with e_a(m) = vector1D(site 0 of m, atom a of m) and D the imaged site-0 difference,
+// The separation and its bin are k_orient_corr_wave's bit for bit (row (0,0) of k_rdf_sites_wave:
+// st_image of mmc_struct.hpp, tile_bin of mmc_tiles.hpp).  The energy of a pair in range is that of
+// the nine atom pairs at the MOLECULE's image: with e_a(m) = vector1D(site 0 of m, atom a of m) and D the imaged site-0 difference,
 //     x_ab = (D + e_a(i)) - e_b(j),   r2_ab = (x x + y y) + z z,
 //     u_C  = factor sum_ab (q_a q_b) / sqrt(r2_ab),
 //     u_LJ = sum_ab (4 eps_ab) (s6 s6 - s6),  s6 = (s2 s2) s2,  s2 = (sig_ab sig_ab) / r2_ab,  eps_ab > 0.001,
@@ -19,10 +19,9 @@
 // and u_LJ of a pair below the 2^20 K flag limit are within ~2^-30 K of it (nine terms of at most
 // ~2^22 K at 2^-51), against the 2^-21 K the quantum allows.
 //
-// The decomposition is k_orient_corr_wave's: a wave owns a contiguous run of 64 x 64 tiles (k, c <= k)
-// of the i < j triangle; lane n keeps neighbour n of block k across a row of tiles -- site 0 and the
-// two offsets e_1, e_2, nine doubles, and in the array instantiation its three charges and atom
-// types.  The chosen side: at the start of a tile the 64 lanes load block c's molecules and form
+// The tiles of the i < j triangle and a wave's run of them are mmc_tiles.hpp's.  Lane n keeps
+// neighbour n of block k across a row of tiles -- site 0 and the two offsets e_1, e_2, nine doubles,
+// and in the array instantiation its three charges and atom types.  The chosen side: at the start of a tile the 64 lanes load block c's molecules and form
 // their offsets as well, and the walk over the chosen molecules pulls the values out with
 // v_readlane -- site 0 for the separation, atom a's offset (and charge and type) at the top of its
 // three atom pairs, so that no more than one atom's worth of scalar registers is live -- so
@@ -49,33 +48,27 @@
 #include "mmc_orient.hpp"
 #include "mmc_deletion.hpp"
 
-#define PE_WAVES 4                  // waves per workgroup (fewer where the counters would not fit: host)
-#define PE_LDS_BYTES 65536          // dynamic LDS a workgroup may ask for without opting in
 // MMC_PAIRE_MAX_BINS (include/mmc_hip.h): one wave per workgroup with the largest energy histogram --
 // thresholds 8 (numbins + 2) bytes, the LJ constants of the nine atom pairs PE_LJ_BYTES, three 64-bit
 // rows 24 (numbins + 2) bytes, 8 (MMC_PAIRE_MAX_EBINS + 2) bytes of energy bins and 8 of the flagged count
 #define PE_LJ_BYTES 144             // (4 eps_ab, sig_ab^2) of ab = 0..8
-static_assert(32 * (MMC_PAIRE_MAX_BINS + 2) + PE_LJ_BYTES + 8 * (MMC_PAIRE_MAX_EBINS + 2) + 8 <= PE_LDS_BYTES &&
-                  32 * (MMC_PAIRE_MAX_BINS + 3) + PE_LJ_BYTES + 8 * (MMC_PAIRE_MAX_EBINS + 2) + 8 > PE_LDS_BYTES,
+static_assert(32 * (MMC_PAIRE_MAX_BINS + 2) + PE_LJ_BYTES + 8 * (MMC_PAIRE_MAX_EBINS + 2) + 8 <= TILE_LDS_BYTES &&
+                  32 * (MMC_PAIRE_MAX_BINS + 3) + PE_LJ_BYTES + 8 * (MMC_PAIRE_MAX_EBINS + 2) + 8 > TILE_LDS_BYTES,
               "MMC_PAIRE_MAX_BINS is what one wave fits");
 #define PE_LIMIT 1048576.0          // 2^20 K: a pair with |u_C| or |u_LJ| at or above it is flagged
 
 struct PairEArgs {
-    const double *thr;        // [numbins + 2]: thr[k] = largest r^2 with bin <= k; thr[numbins + 1] = +inf
-    const double *box_r;      // [R] per-replica boxes, or NULL: bv.box
+    TileArgs ta;
+    // records only: every molecule is a copy of the first (FastConsts)
+    double q3[3];             // the charges of slots 0..2 (ahead of the rest: the kernel's scalar loads
+                              // then fall as they did before TileArgs was split off, and so do its registers)
     unsigned long long *out;  // [wstride] or [R][wstride]: rows [3][numbins + 2], energy bins, flagged; zeroed by the host
     int32_t *cnt;             // [R][n_mol] partners below u_hb, zeroed by the host; NULL: not wanted
-    int32_t numbins, per_replica;
     int32_t e_slots;          // n_ebins + 2, or 0: no energy histogram
     int32_t wstride;          // 3 (numbins + 2) + e_slots + 1
-    float inv_dr;
-    int32_t n_blocks;         // K = ceil(n_mol / 64)
-    int32_t tiles_per_rep;    // K (K + 1) / 2: tiles (k, c), c <= k, k-major
-    int64_t n_tiles;          // R * tiles_per_rep
     double u_lo, u_hi, scale; // scale = n_ebins / (u_hi - u_lo), the host's fp64 (deletion_slot)
     double u_hb, factor;
-    // records only: every molecule is a copy of the first (FastConsts)
-    double q3[3];                    // the charges of slots 0..2
+    // records only
     const double *lj;                // [9][2] device: (4 eps_ab, sig_ab sig_ab), ab = 3 a + b, copied to LDS
     int32_t lj_mask;                 // bit ab: eps_ab > 0.001 (energy.jl:270)
 };
@@ -106,17 +99,11 @@ __device__ __forceinline__ void pe_molecule(const BatchView &bv, const double *_
                                             const BoxConsts &bc, double *o, double *q, int *ty)
 {
     double t[9];
-    if constexpr (REC) {
-        const double2 *src = reinterpret_cast<const double2 *>(rec + ((int64_t)r * bv.n_mol + m) * MMC_RSTRIDE);
-        const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4];
-        t[0] = v0.x; t[1] = v0.y; t[2] = v1.x; t[3] = v1.y; t[4] = v2.x; t[5] = v2.y;
-        t[6] = v3.x; t[7] = v3.y; t[8] = v4.x;
-    } else {
+    load_sites9<REC>(bv, rec, r, m, t);
+    if constexpr (!REC) {
         const int f0 = bv.first0[m];
-        const int64_t a0 = (int64_t)r * bv.atom_stride + f0;
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            t[3 * a] = bv.ax[a0 + a]; t[3 * a + 1] = bv.ay[a0 + a]; t[3 * a + 2] = bv.az[a0 + a];
             q[a] = bv.charge[f0 + a];
             ty[a] = bv.atype[f0 + a];
         }
@@ -131,14 +118,14 @@ __device__ __forceinline__ void pe_molecule(const BatchView &bv, const double *_
 
 // REC: molecules are the 128-byte records of homogeneous batches, charges and LJ constants launch
 // constants; else the SoA arrays with per-atom charges and types (three-atom molecules only).
-// grid: any number of workgroups of blockDim.x / 64 waves; wave W of NW takes tiles
-// [n_tiles W / NW, n_tiles (W + 1) / NW).
+// grid and tiles: mmc_tiles.hpp.
 template <bool REC>
-__global__ __launch_bounds__(PE_WAVES * 64) void k_pair_energy_wave(BatchView bv, const double *__restrict__ rec,
+__global__ __launch_bounds__(TILE_WAVES * 64) void k_pair_energy_wave(BatchView bv, const double *__restrict__ rec,
                                                                     PairEArgs pa)
 {
     extern __shared__ __align__(16) unsigned char pe_lds[];
-    const int nb = pa.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
+    const TileArgs &ta = pa.ta;
+    const int nb = ta.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
     const int ws = pa.wstride, e_slots = pa.e_slots;
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
@@ -148,18 +135,12 @@ __global__ __launch_bounds__(PE_WAVES * 64) void k_pair_energy_wave(BatchView bv
     unsigned long long *const hw = hall + wv * ws;
     unsigned long long *const uh = hw + 3 * rs;          // [e_slots] energy bins
     unsigned long long *const fl = hw + 3 * rs + e_slots; // flagged pairs
-    for (int q = tid; q < rs; q += (int)blockDim.x)
-        thr[q] = pa.thr[q];
     if (REC && tid < 18)
         reinterpret_cast<double *>(pe_lds + 8 * rs)[tid] = pa.lj[tid];
-    for (int q = tid; q < nw * ws; q += (int)blockDim.x)
-        hall[q] = 0ull;
-    __syncthreads();
+    tile_prologue(thr, ta.thr, rs, hall, nw * ws);
 
-    const int n_mol = bv.n_mol, K = pa.n_blocks, T = pa.tiles_per_rep, n_types = bv.n_types;
-    const float inv_dr = pa.inv_dr, e_max = (float)(nb + 1);
-    const int64_t NW = (int64_t)gridDim.x * nw, W = (int64_t)blockIdx.x * nw + wv;
-    const int64_t t0 = pa.n_tiles * W / NW, t1 = pa.n_tiles * (W + 1) / NW;
+    const int n_mol = bv.n_mol, n_types = bv.n_types;
+    const float inv_dr = ta.inv_dr, e_max = (float)(nb + 1);
     const bool want_hb = pa.cnt != nullptr;
     const double u_hb = pa.u_hb, factor = pa.factor;
 
@@ -181,48 +162,44 @@ __global__ __launch_bounds__(PE_WAVES * 64) void k_pair_energy_wave(BatchView bv
         wave_sync();
     };
 
-    if (t0 < t1) {
-        int r = (int)(t0 / T), k = 0, c = (int)(t0 - (int64_t)r * T);
-        while (c > k) { // tile index -> (k, c): rows of 1, 2, 3, ... tiles
-            c -= k + 1;
-            k++;
-        }
-        int r_hist = r;
-        bool fresh = true; // (r, k) changed: the lane's neighbour is to be loaded
-        double t[9];       // neighbour j: site 0, e_1, e_2
-        double qj[3];      // ... and, array instantiation, its charges and types
+    TileCursor tc(ta, gridDim.x, blockIdx.x, nw, wv);
+    if (tc.more()) {
+        int r_hist = tc.r;
+        double t[9];  // neighbour j: site 0, e_1, e_2
+        double qj[3]; // ... and, array instantiation, its charges and types
         int tj[3], tjn[3] = { 0, 0, 0 };
         int cj = 0;          // neighbour j's partners below u_hb in this row of tiles
         int64_t cj_at = 0;   // ... and where they go: r n_mol + j
         BoxConsts bc = box_consts(bv.box);
-        for (int64_t tile = t0; tile < t1; tile++) {
+        for (; tc.more(); tc.next()) {
+            const int r = tc.r;
             // `lane` is made opaque once per unit (mmc_wave.hpp): lane-derived values are not hoisted
             // out of the persistent loop and held for the kernel's life
             int lane = lane0;
             asm volatile("" : "+v"(lane));
-            if (pa.per_replica && r != r_hist) {
+            if (ta.per_replica && r != r_hist) {
                 flush_wave(pa.out + (int64_t)r_hist * ws);
                 r_hist = r;
             }
-            const int j = 64 * k + lane;
-            if (fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
+            const int j = 64 * tc.k + lane;
+            if (tc.fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
                 if (want_hb && cj != 0)
                     atomicAdd(&pa.cnt[cj_at], cj);
                 cj = 0;
                 cj_at = (int64_t)r * n_mol + min(j, n_mol - 1);
-                bc = box_consts(pa.box_r ? pa.box_r[r] : bv.box);
+                bc = box_consts(ta.box_r ? ta.box_r[r] : bv.box);
                 pe_molecule<REC>(bv, rec, r, min(j, n_mol - 1), bc, t, qj, tj);
                 if constexpr (!REC) {
 #pragma unroll
                     for (int a = 0; a < 3; a++)
                         tjn[a] = tj[a] * n_types; // the column of the eps / sig tables
                 }
-                fresh = false;
+                tc.fresh = false;
             }
             const double half = bc.half, neg_box = bc.neg;
             // the chosen molecules of block c: lane n holds molecule 64 c + n's values, the walk below
             // reads them as wave-uniform values
-            const int i_lo = 64 * c, n_i = min(64, n_mol - i_lo);
+            const int i_lo = 64 * tc.c, n_i = min(64, n_mol - i_lo);
             double cs[9], cq[3];
             int cty[3];
             pe_molecule<REC>(bv, rec, r, min(i_lo + lane, n_mol - 1), bc, cs, cq, cty);
@@ -234,12 +211,7 @@ __global__ __launch_bounds__(PE_WAVES * 64) void k_pair_energy_wave(BatchView bv
                 const double yy = st_image(sy - t[1], half, neg_box);
                 const double zz = st_image(sz - t[2], half, neg_box);
                 const double r2 = (xx * xx + yy * yy) + zz * zz;
-                float e = ceilf(__builtin_amdgcn_sqrtf((float)r2) * inv_dr);
-                e = fminf(fmaxf(e, 1.0f), e_max); // 1 .. numbins + 1 (a NaN lands on 1: in bounds)
-                int b = (int)e;
-                const double lo = thr[b - 1], hi = thr[b];
-                b += (r2 > hi) ? 1 : 0;
-                b -= (r2 <= lo) ? 1 : 0;
+                const int b = tile_bin(thr, r2, inv_dr, e_max);
                 const bool pair = j > i && j < n_mol;
                 if (pair)
                     __hip_atomic_fetch_add(&hw[b], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -310,22 +282,13 @@ __global__ __launch_bounds__(PE_WAVES * 64) void k_pair_energy_wave(BatchView bv
             }
             if (want_hb && ci != 0) // (ci != 0 only in lanes below n_i)
                 atomicAdd(&pa.cnt[(int64_t)r * n_mol + i_lo + lane], ci);
-            // the next tile: (k, c + 1), then the next row of tiles, then the next replica
-            if (++c > k) {
-                c = 0;
-                fresh = true;
-                if (++k == K) {
-                    k = 0;
-                    r++;
-                }
-            }
         }
         if (want_hb && cj != 0)
             atomicAdd(&pa.cnt[cj_at], cj);
-        if (pa.per_replica)
+        if (ta.per_replica)
             flush_wave(pa.out + (int64_t)r_hist * ws);
     }
-    if (!pa.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
+    if (!ta.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
         __syncthreads();
         flush(pa.out, hall, nw, tid, (int)blockDim.x, false);
     }

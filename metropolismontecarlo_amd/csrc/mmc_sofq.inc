@@ -1,6 +1,5 @@
 // mmc_sofq.inc -- host side of mmc_batch_structure_factor (include/mmc_hip.h, "Partial structure
-// factors"; the kernels are in mmc_sofq.hpp).  Included by mmc_hip.hip after mmc_orient.inc; it shares
-// the state checks of mmc_struct.inc and the device scratch of mmc_units.inc (obs_scratch).
+// factors"; the kernels are in mmc_sofq.hpp).  Included by mmc_hip.hip after mmc_units.inc (ObsCall).
 #include "mmc_sofq.hpp"
 
 #define SQ_CHUNK_BYTES ((size_t)256 << 20) // device scratch of the per-replica integers of one chunk
@@ -56,32 +55,26 @@ extern "C" int32_t mmc_batch_structure_factor(mmc_batch *b, int32_t n_max, int32
 
     const size_t n_ent = (size_t)6 * S, rep_bytes = sizeof(unsigned long long) * n_ent;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(R, (int64_t)(SQ_CHUNK_BYTES / rep_bytes)));
-    const size_t cnt_bytes = rep_bytes * (size_t)chunk, sum_bytes = sizeof(double) * n_ent;
-    const size_t col_bytes = (sizeof(int32_t) * (size_t)n_cols + 15) & ~(size_t)15;
-    char *d_buf = nullptr;
-    MMC_TRY(obs_scratch(b, cnt_bytes + sum_bytes + col_bytes, &d_buf));
-    std::vector<int64_t> h_sq(per_replica ? (size_t)R * n_ent : 0);
-    std::vector<double> h_sum(per_replica ? 0 : n_ent);
+    const size_t sum_bytes = sizeof(double) * n_ent, col_bytes = sizeof(int32_t) * (size_t)n_cols;
+    ObsCall oc(b);
+    const size_t o_cnt = oc.take(rep_bytes * (size_t)chunk), o_sum = oc.take(sum_bytes), o_cols = oc.take(col_bytes);
+    MMC_TRY(oc.alloc());
 
     SofqArgs sa{};
     sa.box_r = s.pb.on ? s.pb.d_box : nullptr;
-    sa.cnt = reinterpret_cast<unsigned long long *>(d_buf);
-    double *d_sum = reinterpret_cast<double *>(d_buf + cnt_bytes);
-    sa.cols = reinterpret_cast<const int32_t *>(d_buf + cnt_bytes + sum_bytes);
+    sa.cnt = oc.at<unsigned long long>(o_cnt);
+    double *d_sum = oc.at<double>(o_sum);
+    sa.cols = oc.at<int32_t>(o_cols);
     sa.n_cols = n_cols;
     sa.S = S;
 
     const bool use_rec = struct_use_rec(b);
     const void *kern = use_rec ? reinterpret_cast<const void *>(k_sofq_wave<true>)
                                : reinterpret_cast<const void *>(k_sofq_wave<false>);
-    hipStream_t st = s.stream;
-    hipError_t e = hipSuccess;
     if (lds + 64 > 65536) // beyond what a workgroup may ask for without opting in: as k_recip_long_lds
-        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_buf + cnt_bytes + sum_bytes, cols.data(), sizeof(int32_t) * (size_t)n_cols,
-                           hipMemcpyHostToDevice, st);
-    for (int64_t r0 = 0; r0 < R && e == hipSuccess; r0 += chunk) {
+        oc.e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
+    oc.to_device(oc.at<int32_t>(o_cols), cols.data(), col_bytes);
+    for (int64_t r0 = 0; r0 < R && oc.e == hipSuccess; r0 += chunk) {
         const int64_t n_rep = std::min(chunk, R - r0);
         sa.r0 = (int32_t)r0;
         sa.n_rep = (int32_t)n_rep;
@@ -92,38 +85,24 @@ extern "C" int32_t mmc_batch_structure_factor(mmc_batch *b, int32_t n_max, int32
         sa.split = (int32_t)std::max<int64_t>(1, std::min<int64_t>(n_cols, cus / n_rep));
         const int64_t units = n_rep * sa.split;
         const int64_t wgs = std::max<int64_t>(1, std::min(b->wave_wgs > 0 ? (int64_t)b->wave_wgs : cus, units));
-        e = hipMemsetAsync(d_buf, 0, rep_bytes * (size_t)n_rep, st);
-        if (e != hipSuccess)
-            break;
-        if (use_rec)
-            k_sofq_wave<true><<<(unsigned)wgs, SQ_WAVES * 64, lds, st>>>(s.bv, s.rec, sa);
-        else
-            k_sofq_wave<false><<<(unsigned)wgs, SQ_WAVES * 64, lds, st>>>(s.bv, nullptr, sa);
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            break;
-        if (per_replica) {
-            e = hipMemcpyAsync(h_sq.data() + (size_t)r0 * n_ent, d_buf, rep_bytes * (size_t)n_rep,
-                               hipMemcpyDeviceToHost, st);
-        } else {
-            k_sofq_reduce<<<(unsigned)((n_ent + 255) / 256), 256, 0, st>>>(sa.cnt, d_sum, (int)n_rep, (int)n_ent,
-                                                                          r0 == 0 ? 1 : 0);
-            e = hipGetLastError();
+        oc.zero(rep_bytes * (size_t)n_rep);
+        if (oc.e == hipSuccess) {
+            if (use_rec)
+                k_sofq_wave<true><<<(unsigned)wgs, SQ_WAVES * 64, lds, oc.st>>>(s.bv, s.rec, sa);
+            else
+                k_sofq_wave<false><<<(unsigned)wgs, SQ_WAVES * 64, lds, oc.st>>>(s.bv, nullptr, sa);
         }
+        oc.launched();
+        if (per_replica)
+            oc.fetch(sq + (size_t)r0 * n_ent, sa.cnt, rep_bytes * (size_t)n_rep);
+        else if (oc.e == hipSuccess)
+            k_sofq_reduce<<<(unsigned)((n_ent + 255) / 256), 256, 0, oc.st>>>(sa.cnt, d_sum, (int)n_rep, (int)n_ent,
+                                                                             r0 == 0 ? 1 : 0);
+        oc.launched();
     }
-    if (e == hipSuccess && !per_replica)
-        e = hipMemcpyAsync(h_sum.data(), d_sum, sum_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    else
-        (void)hipStreamSynchronize(st); // (cols and the host arrays of copies already queued outlive them)
-    MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "mmc_batch_structure_factor failed: %s", hipGetErrorString(e));
-    // (the caller's arrays are written only on success)
-    if (count)
+    oc.fetch(sq_sum, d_sum, sum_bytes);
+    MMC_TRY(oc.finish("mmc_batch_structure_factor"));
+    if (count) // (as the other arrays of the caller: written only on success)
         memcpy(count, h_count.data(), sizeof(int32_t) * (size_t)S);
-    if (per_replica)
-        memcpy(sq, h_sq.data(), sizeof(int64_t) * h_sq.size());
-    else
-        memcpy(sq_sum, h_sum.data(), sum_bytes);
     return MMC_OK;
 }

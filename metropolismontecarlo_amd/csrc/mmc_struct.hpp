@@ -9,49 +9,33 @@
 // row (a,b), a < b, takes i.a - j.b and i.b - j.a.
 //
 // The scheme is k_move_eval_wave's (mmc_wave.hpp): a wavefront owns a unit and never waits for
-// another wave inside it; lane n holds neighbour n's whole record in registers (six 16-byte loads
-// of one 128-byte line), the chosen molecule's nine coordinates are scalar operands, all lanes work
-// on the same atom pair.  The UNIT is a 64 x 64 tile of the i < j triangle, not k_total_wave's
-// molecule pair (u, N-1-u): a unit of that kind gathers all N records for two chosen molecules,
-// 36 MB of L2 traffic per 750-molecule replica where k_total_wave's COM gate gathers a fifth of
-// them and this pass, which has no gate below L/2, would gather all.  Here the 64 neighbours of
-// block k stay in registers while the wave walks the chosen molecules of block c <= k through
-// scalar loads (issued outside the lane mask, before the previous molecule's nine binnings; scalar
-// loads and LDS share a counter that can only be waited to zero, so the first threshold read of
-// those binnings waits for the load too: its latency is hidden by the other resident waves, not by
-// this one), and consecutive tiles of a
-// wave keep k: the vector loads are one pass over the replica per row of tiles.  Tiles are equal
-// work but for the half-masked diagonal ones, and a wave takes a contiguous run of them, so it
-// stays inside one or two replicas.
-//
-// The bin is found without fp64 sqrt or divide: bin(r^2) = ceil(sqrt(r^2) / dr) is monotone in
-// r^2, so the host builds, with that very fp64 arithmetic, thr[k] = the largest r^2 whose bin is
-// <= k (mmc_struct.inc: rdf_thresholds).  A float estimate e of the bin is within one of it (its
-// relative error ~2e-7 is < 1e-3 bins at the 2046 bins allowed), and two compares against
-// thr[e - 1], thr[e] (one ds_read2_b64) give the exact bin: thr[b - 1] < r^2 <= thr[b].  Slot
-// numbins + 1 of every row is where everything beyond r_max lands, so no lane branches on its bin.
+// another wave inside it; lane n holds neighbour n's nine site coordinates in registers (five 16-byte
+// loads of one 128-byte line), the chosen molecule's nine coordinates are scalar operands, all lanes
+// work on the same atom pair.  The unit is a 64 x 64 tile of the i < j triangle and the bin comes
+// from host-built thresholds: mmc_tiles.hpp has both, for this kernel and the two modelled on it.
+// (Not k_total_wave's molecule pair (u, N-1-u): a unit of that kind gathers all N records for two
+// chosen molecules, 36 MB of L2 traffic per 750-molecule replica where k_total_wave's COM gate
+// gathers a fifth of them and this pass, which has no gate below L/2, would gather all.)  The 64
+// neighbours of block k stay in registers while the wave walks the chosen molecules of block c <= k
+// through scalar loads (issued outside the lane mask, before the previous molecule's nine binnings;
+// scalar loads and LDS share a counter that can only be waited to zero, so the first threshold read
+// of those binnings waits for the load too: its latency is hidden by the other resident waves, not
+// by this one): the vector loads are one pass over the replica per row of tiles.
 //
 // Histograms are 32-bit, privatised per wave in LDS (6 rows x (numbins + 2)), flushed to the 64-bit
 // global counters when the wave's replica changes (per-replica output), once per workgroup at the
 // end (summed output) and before a counter could pass 2^31, bounded by the distances added since
 // the last flush.  Counts are integers: the order of the flushes cannot change them.
 #pragma once
-#include "mmc_wave.hpp"
+#include "mmc_tiles.hpp"
 
-#define ST_WAVES 4            // waves per workgroup (fewer where the histograms would not fit: host)
-#define ST_LDS_BYTES 65536    // dynamic LDS a workgroup may ask for without opting in
+#define ST_WAVES 4            // waves per workgroup of k_dipoles
 #define MMC_RDF_SITES_MAX_BINS 2046 // one wave per workgroup: 32 (numbins + 2) bytes
 #define ST_TILE_DIST (64u * 64u * 9u) // no counter gains more than this in one tile
 
 struct RdfSitesArgs {
-    const double *thr;        // [numbins + 2]: thr[k] = largest r^2 with bin <= k; thr[numbins + 1] = +inf
-    const double *box_r;      // [R] per-replica boxes, or NULL: bv.box
+    TileArgs ta;
     unsigned long long *hist; // [6][numbins + 1] or [R][6][numbins + 1], zeroed by the host
-    int32_t numbins, per_replica;
-    float inv_dr;
-    int32_t n_blocks;         // K = ceil(n_mol / 64)
-    int32_t tiles_per_rep;    // K (K + 1) / 2: tiles (k, c), c <= k, k-major
-    int64_t n_tiles;          // R * tiles_per_rep
 };
 
 // gr.jl:75-80 on one component: |d| > side/2 (strict on both sides) moves d by one side.  -side m
@@ -65,41 +49,28 @@ __device__ __forceinline__ double st_image(double d, double half, double neg_box
 __device__ __forceinline__ void st_count(unsigned *row, const double *thr, double xx, double yy, double zz,
                                          float inv_dr, float e_max)
 {
-    const double r2 = (xx * xx + yy * yy) + zz * zz;
-    float e = ceilf(__builtin_amdgcn_sqrtf((float)r2) * inv_dr);
-    e = fminf(fmaxf(e, 1.0f), e_max); // 1 .. numbins + 1 (a NaN lands on 1: in bounds)
-    int b = (int)e;
-    const double lo = thr[b - 1], hi = thr[b];
-    b += (r2 > hi) ? 1 : 0;
-    b -= (r2 <= lo) ? 1 : 0;
+    const int b = tile_bin(thr, (xx * xx + yy * yy) + zz * zz, inv_dr, e_max);
     __hip_atomic_fetch_add(&row[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays, slot a of
-// molecule j at first0[j] + a (a batch holds three-atom molecules only).
-// grid: any number of workgroups of blockDim.x / 64 waves; wave W of NW takes tiles
-// [n_tiles W / NW, n_tiles (W + 1) / NW).
+// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays (load_sites9).
+// grid and tiles: mmc_tiles.hpp.
 template <bool REC>
-__global__ __launch_bounds__(ST_WAVES * 64) void k_rdf_sites_wave(BatchView bv, const double *__restrict__ rec,
-                                                                  RdfSitesArgs sa)
+__global__ __launch_bounds__(TILE_WAVES * 64) void k_rdf_sites_wave(BatchView bv, const double *__restrict__ rec,
+                                                                    RdfSitesArgs sa)
 {
     extern __shared__ __align__(16) unsigned char st_lds[];
-    const int nb = sa.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
+    const TileArgs &ta = sa.ta;
+    const int nb = ta.numbins, rs = nb + 2; // row stride: bins 0 .. numbins, then the slot beyond r_max
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
     double *const thr = reinterpret_cast<double *>(st_lds);                 // [rs]
     unsigned *const hall = reinterpret_cast<unsigned *>(st_lds + 8 * rs);   // [nw][6][rs]
     unsigned *const hw = hall + wv * 6 * rs;
-    for (int q = tid; q < rs; q += (int)blockDim.x)
-        thr[q] = sa.thr[q];
-    for (int q = tid; q < nw * 6 * rs; q += (int)blockDim.x)
-        hall[q] = 0u;
-    __syncthreads();
+    tile_prologue(thr, ta.thr, rs, hall, nw * 6 * rs);
 
-    const int n_mol = bv.n_mol, K = sa.n_blocks, T = sa.tiles_per_rep;
-    const float inv_dr = sa.inv_dr, e_max = (float)(nb + 1);
-    const int64_t NW = (int64_t)gridDim.x * nw, W = (int64_t)blockIdx.x * nw + wv;
-    const int64_t t0 = sa.n_tiles * W / NW, t1 = sa.n_tiles * (W + 1) / NW;
+    const int n_mol = bv.n_mol;
+    const float inv_dr = ta.inv_dr, e_max = (float)(nb + 1);
     const int64_t row_len = nb + 1;
 
     // this wave's counters added to dst[6][numbins + 1] and cleared
@@ -115,72 +86,43 @@ __global__ __launch_bounds__(ST_WAVES * 64) void k_rdf_sites_wave(BatchView bv, 
         wave_sync();
     };
 
-    if (t0 < t1) {
-        int r = (int)(t0 / T), k = 0, c = (int)(t0 - (int64_t)r * T);
-        while (c > k) { // tile index -> (k, c): rows of 1, 2, 3, ... tiles
-            c -= k + 1;
-            k++;
-        }
-        int r_hist = r;
+    TileCursor tc(ta, gridDim.x, blockIdx.x, nw, wv);
+    if (tc.more()) {
+        int r_hist = tc.r;
         unsigned since = 0u; // distances a counter may have gained since the last flush
-        bool fresh = true;   // (r, k) changed: the lane's neighbour record is to be loaded
         double t[9];
         double half = 0.0, neg_box = 0.0;
-        for (int64_t tile = t0; tile < t1; tile++) {
-            if (sa.per_replica && r != r_hist) {
+        for (; tc.more(); tc.next()) {
+            const int r = tc.r;
+            if (ta.per_replica && r != r_hist) {
                 flush_wave(sa.hist + (int64_t)r_hist * 6 * row_len);
                 r_hist = r;
                 since = 0u;
             }
             if (since > 0x7fffffffu - ST_TILE_DIST) {
-                flush_wave(sa.hist + (sa.per_replica ? (int64_t)r_hist * 6 * row_len : 0));
+                flush_wave(sa.hist + (ta.per_replica ? (int64_t)r_hist * 6 * row_len : 0));
                 since = 0u;
             }
             since += ST_TILE_DIST;
-            const int j = 64 * k + lane;
-            if (fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
-                const int jc = min(j, n_mol - 1);
-                if constexpr (REC) {
-                    const double2 *src = reinterpret_cast<const double2 *>(rec + ((int64_t)r * n_mol + jc) * MMC_RSTRIDE);
-                    const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4];
-                    t[0] = v0.x; t[1] = v0.y; t[2] = v1.x; t[3] = v1.y; t[4] = v2.x; t[5] = v2.y;
-                    t[6] = v3.x; t[7] = v3.y; t[8] = v4.x;
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[jc];
-#pragma unroll
-                    for (int a = 0; a < 3; a++) {
-                        t[3 * a] = bv.ax[a0 + a]; t[3 * a + 1] = bv.ay[a0 + a]; t[3 * a + 2] = bv.az[a0 + a];
-                    }
-                }
-                const double box = sa.box_r ? sa.box_r[r] : bv.box;
+            const int j = 64 * tc.k + lane;
+            if (tc.fresh) { // neighbour j of replica r (a lane beyond the last molecule loads the last)
+                load_sites9<REC>(bv, rec, r, min(j, n_mol - 1), t);
+                const double box = ta.box_r ? ta.box_r[r] : bv.box;
                 half = box / 2.0;
                 neg_box = -box;
-                fresh = false;
+                tc.fresh = false;
             }
             // the chosen molecules i of block c, one after the other: nine wave-uniform coordinates
-            const int i_lo = 64 * c, i_hi = min(i_lo + 64, n_mol);
-            auto chosen = [&](int i, double *o) {
-                if constexpr (REC) {
-                    const double *p = rec + ((int64_t)r * n_mol + i) * MMC_RSTRIDE;
-#pragma unroll
-                    for (int q = 0; q < 9; q++)
-                        o[q] = p[q];
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[i];
-#pragma unroll
-                    for (int a = 0; a < 3; a++) {
-                        o[3 * a] = bv.ax[a0 + a]; o[3 * a + 1] = bv.ay[a0 + a]; o[3 * a + 2] = bv.az[a0 + a];
-                    }
-                }
-            };
+            const int i_lo = 64 * tc.c, i_hi = min(i_lo + 64, n_mol);
             double nx[9];
-            chosen(i_lo, nx);
+            load_sites9<REC>(bv, rec, r, i_lo, nx);
             for (int i = i_lo; i < i_hi; i++) {
                 double s[9];
 #pragma unroll
                 for (int q = 0; q < 9; q++)
                     s[q] = nx[q];
-                chosen(min(i + 1, n_mol - 1), nx); // issued outside the lane mask (see the header on its latency)
+                // issued outside the lane mask (see the header on its latency)
+                load_sites9<REC>(bv, rec, r, min(i + 1, n_mol - 1), nx);
                 if (j > i && j < n_mol) {
 #pragma unroll
                     for (int a = 0; a < 3; a++) {
@@ -195,20 +137,11 @@ __global__ __launch_bounds__(ST_WAVES * 64) void k_rdf_sites_wave(BatchView bv, 
                     }
                 }
             }
-            // the next tile: (k, c + 1), then the next row of tiles, then the next replica
-            if (++c > k) {
-                c = 0;
-                fresh = true;
-                if (++k == K) {
-                    k = 0;
-                    r++;
-                }
-            }
         }
-        if (sa.per_replica)
+        if (ta.per_replica)
             flush_wave(sa.hist + (int64_t)r_hist * 6 * row_len);
     }
-    if (!sa.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
+    if (!ta.per_replica) { // once per workgroup: the waves' counters added up, then added to the total
         __syncthreads();
         for (int q = tid; q < 6 * rs; q += (int)blockDim.x) {
             const int row = q / rs, bin = q - row * rs;
@@ -240,14 +173,8 @@ __global__ __launch_bounds__(ST_WAVES * 64) void k_dipoles(BatchView bv, const d
         const int f0 = bv.first0[i];
         double mu[3];
         if constexpr (REC) {
-            const double2 *src = reinterpret_cast<const double2 *>(rec + ((int64_t)r * n_mol + i) * MMC_RSTRIDE);
-            double t[MMC_REC];
-#pragma unroll
-            for (int q = 0; q < 6; q++) {
-                const double2 v = src[q];
-                t[2 * q] = v.x;
-                t[2 * q + 1] = v.y;
-            }
+            double t[12];
+            load_sites12<true>(bv, rec, r, i, t);
             const double q0 = bv.charge[f0], q1 = bv.charge[f0 + 1], q2 = bv.charge[f0 + 2];
 #pragma unroll
             for (int d = 0; d < 3; d++)

@@ -1,12 +1,26 @@
-// mmc_units.inc -- host side of what the calls with one wavefront per (replica, molecule) share:
-// mmc_batch_widom / _widom_at (mmc_widom.inc), mmc_batch_deletion (mmc_deletion.inc) and
-// mmc_batch_forces (mmc_forces.inc); the kernels' shared part is mmc_unit.hpp.  Included by
-// mmc_hip.hip after mmc_batch.inc and before the three.  DESIGN.md, "Unit kernels".
-//
-// obs_scratch is also the device scratch of mmc_struct.inc, mmc_local.inc and mmc_vperturb.inc: every
-// observable call enqueues on the batch's one stream, drains it before it returns with success and
-// keeps nothing in the buffer between calls, so one buffer (mmc_batch::obs_buf) serves them all.
+// mmc_units.inc -- host side of what the observable calls share.  Every one of them enqueues on the
+// batch's one stream, drains it before it returns and keeps nothing on the device between calls, so
+// one scratch buffer (mmc_batch::obs_buf) and one kind of call (ObsCall) serve them all:
+//   the calls with one wavefront per (replica, molecule): mmc_batch_widom / _widom_at, _solute,
+//   _solute_pair, _deletion and _forces (UnitsCall; the kernels' shared part is mmc_unit.hpp);
+//   the pair passes over the i < j triangle: mmc_batch_rdf_sites, _orient_corr and _pair_energy
+//   (tile_plan, tile_waves; the kernels' shared part is mmc_tiles.hpp);
+//   and mmc_batch_dipoles, _structure_factor, _local_order, _cavity / _cavity_at, _volume_perturb.
+// Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels" and
+// "Tile passes".
 #include "mmc_unit.hpp"
+#include "mmc_tiles.hpp"
+
+// preconditions of the read-only observables (those of mmc_batch_potential_ewald)
+#define STRUCT_STATE(b)                                                                          \
+    MMC_REQUIRE(!(b)->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first"); \
+    BATCH_NO_VOLUME_TRIAL(b)
+
+// the 128-byte records where the batch keeps them in step with the coordinates (as the totals do)
+static inline bool struct_use_rec(const mmc_batch *b)
+{
+    return b->sys.rec && b->sys.homogeneous && (b->sys.pb.on || b->fast_ok);
+}
 
 // Device scratch of the observable calls, kept on the batch and grown on demand (no allocation, and
 // no device-wide synchronisation of a hipFree, per sample).
@@ -97,52 +111,34 @@ template <class Args>
 using units_kernel_t = void (*)(BatchView, const double *, const double *, const int32_t *, FastConsts, PairParams, Args, int);
 
 // One call's device scratch and its queue of work.  The scratch is laid out by take(): regions in the
-// order they are asked for, each aligned to 256 bytes.  Every unit call has rows [R n][row] of
-// doubles first, flags [R n], and the per-replica block: `per_rep` doubles and one count per replica
-// ([R][per_rep] doubles, then [R] long long: sums the reduce kernel adds to or fills), then the
-// S-buffer bits [R].  The block goes each way in one copy through pinned staging of the same layout.
+// order they are asked for, each aligned to 256 bytes; what the kernels want zeroed is taken first
+// and zero(n) clears the first n bytes.  Results come back through fetch(): a copy into host staging
+// the call owns, and a memcpy into the caller's array that finish() makes only after MMC_OK.
 // Between the first enqueue and finish() nothing returns: an error is kept in `e`, skips what
 // follows, and finish() drains the stream whatever happened (the host buffers of copies already
 // queued outlive them).
-struct UnitsCall {
+struct ObsCall {
     mmc_batch *b;
     hipStream_t st;
-    size_t R, nu, row_bytes, sums_bytes, blk_bytes;
-    size_t end = 0, o_rows, o_flags, o_blk;
-    int per_rep;
-    char *base = nullptr, *hblk = nullptr;
+    size_t end = 0;
+    char *base = nullptr;
     hipError_t e = hipSuccess;
+    struct Out {
+        void *dst; // the caller's array, or NULL: read through stage()'s pointer
+        std::vector<char> h;
+    };
+    std::vector<Out> outs; // (growing it moves the vectors: their storage stays where the copies write)
 
-    UnitsCall(mmc_batch *b_, size_t n_units, int row, int per_rep_)
-        : b(b_), st(b_->sys.stream), R((size_t)b_->sys.R), nu(n_units), row_bytes(sizeof(double) * row * n_units),
-          sums_bytes((sizeof(double) * per_rep_ + sizeof(long long)) * R), blk_bytes(sums_bytes + R), per_rep(per_rep_)
-    {
-        o_rows = take(row_bytes);
-        o_flags = take(nu);
-        o_blk = take(blk_bytes);
-    }
+    explicit ObsCall(mmc_batch *b_) : b(b_), st(b_->sys.stream) {}
     size_t take(size_t bytes)
     {
         const size_t o = end;
         end = o + ((bytes + 255) & ~(size_t)255);
         return o;
     }
-    // after the last take(): the buffers, and the S-buffer bits into the staged block
-    int32_t alloc()
-    {
-        MMC_TRY(obs_scratch(b, end, &base));
-        MMC_TRY(obs_staging(b, blk_bytes, &hblk));
-        memcpy(hblk + sums_bytes, b->s_cur.data(), R);
-        return MMC_OK;
-    }
+    // after the last take()
+    int32_t alloc() { return obs_scratch(b, end, &base); }
     template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
-    double *d_rows() const { return at<double>(o_rows); }
-    uint8_t *d_flags() const { return at<uint8_t>(o_flags); }
-    double *d_sums() const { return at<double>(o_blk); }
-    long long *d_counts() const { return reinterpret_cast<long long *>(d_sums() + per_rep * R); }
-    const uint8_t *d_scur() const { return at<uint8_t>(o_blk + sums_bytes); }
-    double *h_sums() const { return reinterpret_cast<double *>(hblk); }
-    long long *h_counts() const { return reinterpret_cast<long long *>(h_sums() + per_rep * R); }
 
     void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
     {
@@ -151,14 +147,163 @@ struct UnitsCall {
     }
     void to_device(void *dst, const void *src, size_t bytes) { copy(dst, src, bytes, hipMemcpyHostToDevice); }
     void to_host(void *dst, const void *src, size_t bytes) { copy(dst, src, bytes, hipMemcpyDeviceToHost); }
-    // the staged block, filled by the caller, to the device
-    void upload_block() { to_device(base + o_blk, hblk, blk_bytes); }
-    // after a launch of the caller's own
+    void zero(size_t n_bytes)
+    {
+        if (e == hipSuccess)
+            e = hipMemsetAsync(base, 0, n_bytes, st);
+    }
+    // after a launch of the caller's own (which it skips unless e == hipSuccess)
     void launched()
     {
         if (e == hipSuccess)
             e = hipGetLastError();
     }
+    // `bytes` at d_src into staging: the host copy, to be read after finish() returned MMC_OK
+    const char *stage(const void *d_src, size_t bytes)
+    {
+        outs.push_back(Out{ nullptr, std::vector<char>(bytes) });
+        to_host(outs.back().h.data(), d_src, bytes);
+        return outs.back().h.data();
+    }
+    // ... and from there into the caller's array, when it gave one
+    void fetch(void *user_dst, const void *d_src, size_t bytes)
+    {
+        if (!user_dst || !bytes)
+            return;
+        stage(d_src, bytes);
+        outs.back().dst = user_dst;
+    }
+    int32_t finish(const char *what)
+    {
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        else
+            (void)hipStreamSynchronize(st);
+        MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        for (const Out &o : outs)
+            if (o.dst)
+                memcpy(o.dst, o.h.data(), o.h.size());
+        return MMC_OK;
+    }
+};
+
+// Waves per workgroup of a pass with per-wave counters in LDS: as many of TILE_WAVES as fit beside
+// `fixed_bytes` in what a workgroup may ask for without opting in.
+static int tile_waves(size_t fixed_bytes, size_t per_wave_bytes)
+{
+    int nw = TILE_WAVES;
+    while (nw > 1 && fixed_bytes + (size_t)nw * per_wave_bytes > TILE_LDS_BYTES)
+        nw >>= 1;
+    return nw;
+}
+
+// Persistent workgroups of nw waves: four waves per SIMD of every compute unit (the passes are bound
+// by vector issue and LDS atomics), or option "wave_wgs"; no more than give every wave a unit.
+static unsigned obs_grid(const mmc_batch *b, int nw, int64_t n_units)
+{
+    const int64_t wgs = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(16 / nw) * b->n_cus;
+    return (unsigned)std::max<int64_t>(1, std::min(wgs, (n_units + nw - 1) / nw));
+}
+
+// gr.jl:87 on r^2, in the arithmetic of k_rdf: the bin of a squared distance
+static inline double rdf_bin_of(double r2, double dr)
+{
+    return std::ceil(std::sqrt(r2) / dr);
+}
+
+// thr[k], k = 0 .. numbins: the largest double r^2 >= 0 with rdf_bin_of(r^2) <= k (the bin is
+// monotone in r^2: sqrt, the division by dr > 0 and ceil are), found by bisection over the bit
+// patterns of the non-negative doubles; thr[numbins + 1] = +inf.
+static void rdf_thresholds(double dr, int numbins, std::vector<double> &thr)
+{
+    auto bits = [](double x) { uint64_t u; memcpy(&u, &x, 8); return u; };
+    auto dbl = [](uint64_t u) { double x; memcpy(&x, &u, 8); return x; };
+    thr.assign((size_t)numbins + 2, INFINITY);
+    for (int k = 0; k <= numbins; k++) {
+        const double e = dr * (k + 1);
+        uint64_t lo = 0, hi = bits(e * e * 1.01); // bin(0) = 0 <= k; bin(hi) >= k + 2
+        if (!(rdf_bin_of(dbl(hi), dr) > k)) {     // (dr so large that the bound overflowed: nothing is beyond)
+            thr[k] = INFINITY;
+            continue;
+        }
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (rdf_bin_of(dbl(mid), dr) <= k)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        thr[k] = dbl(lo);
+    }
+}
+
+// What a pass over the i < j triangle (mmc_tiles.hpp) takes from the batch, after its entry point
+// refused what it can without one: the range against the boxes (MMC_ERR_ARG), the state, the size
+// (MMC_ERR_UNSUPPORTED); then the bins -- gr.jl:5: dr = side / 2 / numbins, else the caller's range
+// -- their thresholds and the tiles.  ta->thr and ta->per_replica are the caller's to set.
+static int32_t tile_plan(const mmc_batch *b, int32_t numbins, double r_max, const char *what, TileArgs *ta,
+                         std::vector<double> *thr)
+{
+    const DeviceSystem &s = b->sys;
+    double min_box = s.bv.box;
+    if (s.pb.on) {
+        MMC_REQUIRE(r_max > 0.0, MMC_ERR_ARG, "%s: per-replica boxes have no common L/2: give r_max > 0", what);
+        min_box = *std::min_element(s.pb.box.begin(), s.pb.box.end());
+    }
+    MMC_REQUIRE(!(r_max > 0.0) || r_max <= min_box / 2.0, MMC_ERR_ARG,
+                "%s: r_max %g exceeds half of the smallest box %g", what, r_max, min_box);
+    STRUCT_STATE(b);
+    MMC_REQUIRE(s.n_mol >= 1 && s.n_mol <= (1 << 21), MMC_ERR_UNSUPPORTED,
+                "%s: 1 .. 2^21 molecules (the tiles of a replica are counted in 32 bits)", what);
+    // (a batch holds three-atom molecules only, mmc_batch_create: slots 0..2 exist in every molecule)
+    const double dr = r_max > 0.0 ? r_max / numbins : (min_box / 2.0) / numbins;
+    rdf_thresholds(dr, numbins, *thr);
+    const int64_t K = (s.n_mol + 63) / 64;
+    ta->box_r = s.pb.on ? s.pb.d_box : nullptr;
+    ta->numbins = numbins;
+    ta->inv_dr = (float)(1.0 / dr);
+    ta->n_blocks = (int32_t)K;
+    ta->tiles_per_rep = (int32_t)(K * (K + 1) / 2);
+    ta->n_tiles = s.R * ta->tiles_per_rep;
+    return MMC_OK;
+}
+
+// A unit call: an ObsCall whose scratch begins with rows [R n][row] of doubles, flags [R n], and the
+// per-replica block: `per_rep` doubles and one count per replica ([R][per_rep] doubles, then [R] long
+// long: sums the reduce kernel adds to or fills), then the S-buffer bits [R].  The block goes each
+// way in one copy through pinned staging of the same layout.
+struct UnitsCall : ObsCall {
+    size_t R, nu, row_bytes, sums_bytes, blk_bytes;
+    size_t o_rows, o_flags, o_blk;
+    int per_rep;
+    char *hblk = nullptr;
+
+    UnitsCall(mmc_batch *b_, size_t n_units, int row, int per_rep_)
+        : ObsCall(b_), R((size_t)b_->sys.R), nu(n_units), row_bytes(sizeof(double) * row * n_units),
+          sums_bytes((sizeof(double) * per_rep_ + sizeof(long long)) * R), blk_bytes(sums_bytes + R), per_rep(per_rep_)
+    {
+        o_rows = take(row_bytes);
+        o_flags = take(nu);
+        o_blk = take(blk_bytes);
+    }
+    // after the last take(): the buffers, and the S-buffer bits into the staged block
+    int32_t alloc()
+    {
+        MMC_TRY(ObsCall::alloc());
+        MMC_TRY(obs_staging(b, blk_bytes, &hblk));
+        memcpy(hblk + sums_bytes, b->s_cur.data(), R);
+        return MMC_OK;
+    }
+    double *d_rows() const { return at<double>(o_rows); }
+    uint8_t *d_flags() const { return at<uint8_t>(o_flags); }
+    double *d_sums() const { return at<double>(o_blk); }
+    long long *d_counts() const { return reinterpret_cast<long long *>(d_sums() + per_rep * R); }
+    const uint8_t *d_scur() const { return at<uint8_t>(o_blk + sums_bytes); }
+    double *h_sums() const { return reinterpret_cast<double *>(hblk); }
+    long long *h_counts() const { return reinterpret_cast<long long *>(h_sums() + per_rep * R); }
+
+    // the staged block, filled by the caller, to the device
+    void upload_block() { to_device(base + o_blk, hblk, blk_bytes); }
     // the unit kernel: its IMG instantiation where img holds
     template <class Args>
     void launch(bool img, units_kernel_t<Args> k_img, units_kernel_t<Args> k_pair, int occ, const PairParams &pp, const Args &a)
@@ -183,11 +328,6 @@ struct UnitsCall {
             h_flags->resize(nu);
             to_host(h_flags->data(), d_flags(), nu);
         }
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        else
-            (void)hipStreamSynchronize(st);
-        MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        return MMC_OK;
+        return ObsCall::finish(what);
     }
 };

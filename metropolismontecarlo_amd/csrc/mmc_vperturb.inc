@@ -1,7 +1,6 @@
 // mmc_vperturb.inc -- host side of mmc_batch_volume_perturb (include/mmc_hip.h, "Virtual volume
-// moves"; the kernels are in mmc_vperturb.hpp).  Included by mmc_hip.hip after mmc_local.inc; shares
-// the state checks of mmc_struct.inc, the device scratch of mmc_units.inc (obs_scratch) and the domain
-// rule of mmc_perbox.inc.
+// moves"; the kernels are in mmc_vperturb.hpp).  Included by mmc_hip.hip after mmc_units.inc (ObsCall)
+// and mmc_perbox.inc, whose domain rule it shares.
 #include "mmc_vperturb.hpp"
 
 #define VP_PARTS_BYTES ((size_t)256 << 20) // tile-pair partials of one chunk of replicas
@@ -64,37 +63,31 @@ extern "C" int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const
 
     // device scratch: box scalars, cfac rows and tables of this call, then results
     const int n_pairs = s.n_tile_pairs;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     int64_t chunk = (int64_t)(VP_PARTS_BYTES / (sizeof(VpPart) * (size_t)n_box * n_pairs));
     chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chunk, R), 32768));
-    const size_t sc_bytes = up16(sizeof(double) * 2 * VP_BOXES), cf_bytes = sizeof(double) * MMC_NK_STRIDE * VP_BOXES,
-                 tb_bytes = up16(sizeof(double) * MMC_QQ_TABLE_DOUBLES * VP_BOXES),
-                 pt_bytes = up16(sizeof(VpPart) * (size_t)chunk * n_box * n_pairs),
-                 sm_bytes = up16(sizeof(VpPart) * (size_t)R * n_box), er_bytes = up16(sizeof(double) * (size_t)R * n_box);
-    char *d_buf = nullptr;
-    MMC_TRY(obs_scratch(b, sc_bytes + cf_bytes + tb_bytes + pt_bytes + sm_bytes + er_bytes, &d_buf));
-    double *d_kappa = reinterpret_cast<double *>(d_buf), *d_box = d_kappa + VP_BOXES;
-    double *d_cfac = reinterpret_cast<double *>(d_buf + sc_bytes);
-    double *d_tabs = reinterpret_cast<double *>(d_buf + sc_bytes + cf_bytes);
-    VpPart *d_parts = reinterpret_cast<VpPart *>(d_buf + sc_bytes + cf_bytes + tb_bytes);
-    VpPart *d_sums = reinterpret_cast<VpPart *>(d_buf + sc_bytes + cf_bytes + tb_bytes + pt_bytes);
-    double *d_erec = reinterpret_cast<double *>(d_buf + sc_bytes + cf_bytes + tb_bytes + pt_bytes + sm_bytes);
+    const size_t sm_bytes = sizeof(VpPart) * (size_t)R * n_box, er_bytes = sizeof(double) * (size_t)R * n_box;
+    ObsCall oc(b);
+    const size_t o_sc = oc.take(sizeof(double) * 2 * VP_BOXES), o_cf = oc.take(sizeof(double) * MMC_NK_STRIDE * VP_BOXES),
+                 o_tb = oc.take(sizeof(double) * MMC_QQ_TABLE_DOUBLES * VP_BOXES),
+                 o_pt = oc.take(sizeof(VpPart) * (size_t)chunk * n_box * n_pairs), o_sm = oc.take(sm_bytes),
+                 o_er = oc.take(er_bytes);
+    MMC_TRY(oc.alloc());
+    double *d_kappa = oc.at<double>(o_sc), *d_box = d_kappa + VP_BOXES;
+    double *d_cfac = oc.at<double>(o_cf), *d_tabs = oc.at<double>(o_tb), *d_erec = oc.at<double>(o_er);
+    VpPart *d_parts = oc.at<VpPart>(o_pt), *d_sums = oc.at<VpPart>(o_sm);
 
-    hipStream_t st = s.stream;
-    std::vector<VpPart> h_sums((size_t)R * n_box);
-    std::vector<double> h_erec((size_t)R * n_box);
-    hipError_t e = hipMemcpyAsync(d_kappa, va.kappa, sizeof(double) * VP_BOXES, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_box, va.box, sizeof(double) * VP_BOXES, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { // PrepareEwaldVariables at (kappa_k, L_k) over the batch's k list (ewalds.jl:45-103)
+    hipStream_t st = oc.st;
+    oc.to_device(d_kappa, va.kappa, sizeof(double) * VP_BOXES);
+    oc.to_device(d_box, va.box, sizeof(double) * VP_BOXES);
+    if (oc.e == hipSuccess) { // PrepareEwaldVariables at (kappa_k, L_k) over the batch's k list (ewalds.jl:45-103)
         k_cfac_pb<<<dim3((unsigned)((s.nkvecs + 63) / 64), (unsigned)n_box), 64, 0, st>>>(
             s.bv.kxyz, (int)s.nkvecs, d_kappa, d_box, d_cfac, nullptr, s.half_k ? 1 : 0);
         k_build_qq_table<<<dim3((MMC_QQ_NROW + 63) / 64, (unsigned)n_box), 64, 0, st>>>(
             0.0, d_tabs, PerBoxTable{ d_kappa, nullptr });
-        e = hipGetLastError();
     }
+    oc.launched();
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
-    for (int64_t r0 = 0; r0 < R && e == hipSuccess; r0 += chunk) {
+    for (int64_t r0 = 0; r0 < R && oc.e == hipSuccess; r0 += chunk) {
         const int64_t nr = std::min(chunk, R - r0);
         va.r0 = (int32_t)r0;
         k_vp_pairs<<<dim3((unsigned)n_pairs, (unsigned)nr), MMC_BLOCK, 0, st>>>(
@@ -103,17 +96,11 @@ extern "C" int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const
                                                                       (int)nr, d_sums);
         k_vp_recip<<<dim3((unsigned)n_box, (unsigned)nr), RL_WAVES * 64, lds, st>>>(s.bv, s.recip_order, va,
                                                                                    d_cfac, d_erec);
-        e = hipGetLastError();
+        oc.launched();
     }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h_sums.data(), d_sums, sizeof(VpPart) * h_sums.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h_erec.data(), d_erec, sizeof(double) * h_erec.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    else
-        (void)hipStreamSynchronize(st);
-    MMC_REQUIRE(e == hipSuccess, MMC_ERR_HIP, "mmc_batch_volume_perturb failed: %s", hipGetErrorString(e));
+    const VpPart *h_sums = reinterpret_cast<const VpPart *>(oc.stage(d_sums, sm_bytes));
+    const double *h_erec = reinterpret_cast<const double *>(oc.stage(d_erec, er_bytes));
+    MMC_TRY(oc.finish("mmc_batch_volume_perturb"));
 
     // the four parts in totals_ewald's arithmetic (energy.jl:978-1021), differences, weights: host, fp64,
     // replica by replica and box by box -- the caller's arrays are written only now

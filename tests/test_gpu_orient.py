@@ -111,6 +111,25 @@ def test_against_the_restatement(n_mol):
             assert not np.array_equal(per[0], per[1])
 
 
+@pytest.mark.parametrize("numbins", [479, 480, 908, 909, 1636])
+def test_the_bin_counts_at_which_a_workgroup_loses_waves(numbins):
+    """The thresholds and a wave's four 64-bit rows, 8 rs + nw 32 rs bytes with rs = numbins + 2, within
+    65536: four waves up to 479 bins, two from 480 to 908, one from 909 to MMC_ORIENT_MAX_BINS.  Three
+    blocks a replica, and with wave_wgs = 1 the waves of one workgroup cross replica boundaries."""
+    assert [nb for nb in range(1, 1637) if (8 + 4 * 32) * (nb + 2) <= 65536][-1] == 479
+    assert [nb for nb in range(1, 1637) if (8 + 2 * 32) * (nb + 2) <= 65536][-1] == 908
+    assert (8 + 32) * (1636 + 2) <= 65536 < (8 + 32) * (1637 + 2)
+    n_mol, R = 129, 3
+    a = truncated(n_mol)
+    with make_batch(a, R) as b:
+        diversify(b, a, seed=9)
+        want = want_rows(b, a["charge"], [a["box"]] * R, numbins, RCUT)
+        for wgs in (1, 0):
+            b.set_option("wave_wgs", wgs)
+            check_against(b.orient_corr(numbins, RCUT, per_replica=True), b.orient_corr(numbins, RCUT), want, n_mol,
+                          f"{numbins} bins, wave_wgs {wgs}")
+
+
 def test_molecules_that_differ_take_the_array_path():
     """A system whose molecules carry different charges has no 128-byte records: the kernel's other
     instantiation, reading the coordinate arrays."""

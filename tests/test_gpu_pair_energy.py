@@ -123,6 +123,46 @@ def test_against_the_restatement(n_mol):
             assert not np.array_equal(per.rows[0], per.rows[1])
 
 
+def wave_boundaries(n_ebins):
+    """The numbins at which a workgroup of k_pair_energy_wave loses waves, from the header's limits: the
+    thresholds, the 144 bytes of LJ constants and a wave's 3 rs + e_slots + 1 64-bit counters,
+    8 rs + 144 + nw 8 (3 rs + e_slots + 1) bytes with rs = numbins + 2, within 65536.  For nw = 4 and 2:
+    the last numbins that fits and the first that does not, where the call allows them; then the
+    largest numbins allowed."""
+    from test_orient_abi import header_define
+    max_bins, max_ebins = int(header_define("MMC_PAIRE_MAX_BINS")), int(header_define("MMC_PAIRE_MAX_EBINS"))
+    assert max_bins == MAX_BINS and n_ebins <= max_ebins
+    e_slots = n_ebins + 2 if n_ebins else 0
+
+    def fits(nw, nb):
+        return 8 * (nb + 2) + 144 + nw * 8 * (3 * (nb + 2) + e_slots + 1) <= 65536
+    assert fits(1, max_bins) and (n_ebins < max_ebins or not fits(1, max_bins + 1))
+    out = set()
+    for nw in (4, 2):
+        last = max([nb for nb in range(1, max_bins + 1) if fits(nw, nb)], default=0)
+        out |= {nb for nb in (last, last + 1) if 1 <= nb <= max_bins}
+    return sorted(out | {max_bins})
+
+
+# without uhist: four waves up to 626 bins, two beyond (MMC_PAIRE_MAX_BINS is below the 1165 that two
+# waves hold); with the largest energy histogram one wave from the first bin on
+@pytest.mark.parametrize("n_ebins,numbins", [(0, 626), (0, 627), (0, MAX_BINS), (4096, 1), (4096, MAX_BINS)])
+def test_the_bin_counts_at_which_a_workgroup_loses_waves(n_ebins, numbins):
+    assert wave_boundaries(0) == [626, 627, MAX_BINS] and wave_boundaries(4096) == [1, MAX_BINS]
+    n_mol, R = 129, 3
+    a = truncated(n_mol)
+    with make_batch(a, R) as b:
+        diversify(b, a, seed=40 + 129)
+        what = f"{numbins} bins, {n_ebins} energy bins"
+        want = want_all(b, a, [a["box"]] * R, numbins, RCUT, n_ebins=max(n_ebins, 1))
+        precondition(want, what)
+        for wgs in (1, 0):
+            b.set_option("wave_wgs", wgs)
+            per, tot = both(b, numbins, RCUT, n_ebins=n_ebins)
+            assert (per.uhist is None) == (n_ebins == 0)
+            check_against(per, tot, want, n_mol, f"{what}, wave_wgs {wgs}")
+
+
 def test_outputs_that_are_not_asked_for_and_the_edges_of_the_arguments():
     n_mol, R = 70, 3
     a = truncated(n_mol)

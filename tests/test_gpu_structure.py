@@ -37,8 +37,9 @@ def want_rows(b, boxes, numbins, r_max=0.0):
                      for r in range(b.R)])
 
 
-def check_batch(b, boxes, numbins, r_max=0.0, what=""):
-    want = want_rows(b, boxes, numbins, r_max)
+def check_batch(b, boxes, numbins, r_max=0.0, what="", want=None):
+    if want is None:
+        want = want_rows(b, boxes, numbins, r_max)
     per = b.rdf_sites(numbins, r_max, per_replica=True)
     tot = b.rdf_sites(numbins, r_max)
     assert per.dtype == np.uint64 and per.shape == (b.R, 6, numbins + 1) and tot.shape == (6, numbins + 1)
@@ -106,6 +107,23 @@ def test_tiny_and_odd_systems(n_mol):
         d = b.dipoles()
         mu = ref.molecule_dipoles(*b.get_replica(0)[:2], a["charge"], box)
         assert np.all(np.abs(d[0] - mu.sum(0)) <= 1e-12 * np.abs(mu).sum(0) + 1e-300)
+
+
+@pytest.mark.parametrize("numbins", [628, 629, 1168, 1169, 2046])
+def test_the_bin_counts_at_which_a_workgroup_loses_waves(numbins):
+    """The thresholds and a wave's six 32-bit rows, 8 rs + nw 24 rs bytes with rs = numbins + 2, within
+    65536: four waves up to 628 bins, two from 629 to 1168, one from 1169 to the 2046 allowed.  Three
+    blocks a replica, and with wave_wgs = 1 the waves of one workgroup cross replica boundaries."""
+    assert [nb for nb in range(1, 2047) if (8 + 4 * 24) * (nb + 2) <= 65536][-1] == 628
+    assert [nb for nb in range(1, 2047) if (8 + 2 * 24) * (nb + 2) <= 65536][-1] == 1168
+    assert (8 + 24) * (2046 + 2) <= 65536 < (8 + 24) * (2047 + 2)
+    box = 22.0
+    a = small_system(129, box, seed=229)
+    with make_batch(a, 3) as b:
+        want = want_rows(b, [box] * 3, numbins)
+        for wgs in (1, 0):
+            b.set_option("wave_wgs", wgs)
+            check_batch(b, [box] * 3, numbins, what=f"{numbins} bins, wave_wgs {wgs}", want=want)
 
 
 def per_box_states(factors):
