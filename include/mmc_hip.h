@@ -1034,6 +1034,59 @@ int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32
  * 40 (numbins + 2) <= 65536  ->  numbins + 2 <= 1638. */
 #define MMC_ORIENT_MAX_BINS 1636
 
+/* ---- Spatial distribution functions: g(x, y, z) around a molecule in its own frame ----------------
+ * The density of the neighbours' sites around a molecule in that molecule's body-fixed frame: the
+ * donor caps in front of the hydrogens, the acceptor band behind the oxygen and the interstitial lobe
+ * of water (Svishchev and Kusalik's maps).  mmc_batch_rdf_sites and mmc_batch_orient_corr integrate
+ * these angles away; only a pass over all pairs with each molecule's frame in hand gives them.  The
+ * reference has no such analysis; the arithmetic is defined here, in unfused fp64 (every operation
+ * below is one fp64 operation in the order written, divisions and square roots IEEE), and restated in
+ * numpy by tests/sdf_ref.py.  dot(a,b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   - Frame of a molecule with sites s0, s1, s2 (slot 0 = O for water): o1 = vector1D(s0, s1) and
+ *     o2 = vector1D(s0, s2) per component (boundaries.jl, the replica's own box; site a minus site 0),
+ *     o0 = 0.  b = o1 + o2, h = o2 - o1.  nb2 = dot(b,b), e_z = b / sqrt(nb2).  t = dot(h, e_z),
+ *     g = h - t e_z (multiply, then subtract).  ng2 = dot(g,g), e_x = g / sqrt(ng2).
+ *     e_y = e_z x e_x, each component a difference of two products (e_y.x = e_z.y e_x.z - e_z.z e_x.y,
+ *     and cyclic).  The molecule has no frame when nb2 or ng2 is 0 or not finite (a NaN included).
+ *   - Per pair i < j of a replica: d = vector1D(s0(i), s0(j)) per component; as seen from j the
+ *     vector is -d bit for bit, it is not recomputed.  For every slot a selected in site_mask (bit a)
+ *     two deposits are made.  Into i's frame: w = d + o_a(j),
+ *     p = (dot(e_x(i), w), dot(e_y(i), w), dot(e_z(i), w)).  Into j's frame: w' = -d + o_a(i),
+ *     projected on j's axes.
+ *   - Folding and cells.  fold bit 0 replaces p.x by |p.x|, bit 1 replaces p.y by |p.y| (both are
+ *     symmetries of C2v water); z is never folded.  The cell edges are e_k = (double)k * cell,
+ *     k = -n_half .. n_half.  Along an unfolded axis p lies in cell k when e_k <= p < e_k+1, stored
+ *     at index k + n_half: 2 n_half cells.  Along a folded axis there are n_half cells,
+ *     k = 0 .. n_half - 1.  A deposit is outside when any coordinate falls in no cell; a NaN counts
+ *     as outside.  Flat index (ix g_y + iy) g_z + iz, with g_z = 2 n_half.
+ *   - Counters: one 64-bit count per cell, then `outside`, then `noframe`: a centre molecule without
+ *     a frame sends all of its deposits there.  So per replica
+ *     cells + outside + noframe = N (N - 1) popcount(site_mask) exactly.
+ *   - All counts are integers: the result does not depend on the grid, on option "wave_wgs", on the
+ *     flush order or on the order of atomics.
+ *   - per_replica == 0: hist[g_x g_y g_z + 2] summed over the replicas; else hist[R][g_x g_y g_z + 2].
+ *     hist is overwritten, not accumulated.
+ *   - Use: g = count / (frames N (N - 1) / V popcount(site_mask) cell^3 2^(folded axes))
+ *     (observables.py: sdf_density, sdf_unfold, sdf_cell_centres).
+ * Both box modes, either Coulomb style, records or arrays: the call reads coordinates only and is
+ * read-only as mmc_batch_orient_corr is, with its preconditions: no proposals outstanding, no volume
+ * trial in flight (MMC_ERR_STATE).  MMC_ERR_ARG: a NULL hist, n_half < 1, cell not finite or <= 0,
+ * fold outside 0..3, site_mask outside 1..7, g_x g_y g_z > MMC_SDF_MAX_CELLS, or a cube that reaches
+ * another periodic image: required is sqrt(3) n_half cell + rho <= L_min / 2 with L_min the smallest
+ * box and rho = 2 r_mol_max, r_mol_max being the batch's bound on the distance of any site from its
+ * molecule's centre of mass (DeviceSystem::r_mol_max: the uploaded and every set configuration, the
+ * body-fixed sites of mmc_batch_set_orientations; unknown, and the call refused, once the caller has
+ * proposed moves of its own).  |o_a| <= rho, so under this condition every site inside the cube
+ * belongs to the minimum image of the O-O vector.  MMC_ERR_UNSUPPORTED: more than 2^21 molecules, or a
+ * device that grants a workgroup less LDS than the grid needs.  The arguments that need no batch are
+ * checked first, then the state, then the cube against the boxes, then the size.  On any error hist
+ * is left untouched. */
+int32_t mmc_batch_sdf(mmc_batch *b, int32_t n_half, double cell, int32_t fold, int32_t site_mask,
+                      int32_t per_replica, uint64_t *hist /* [g_x g_y g_z + 2] or [R][...] */);
+/* 32-bit counters in the LDS of one workgroup: 4 x 32768 = 128 KB of the 160 KB a gfx950 workgroup
+ * may claim, the cell edges and the scaffold beside them. */
+#define MMC_SDF_MAX_CELLS 32768
+
 /* ---- Pair-energy distributions: p(u), <u_C>(r), <u_LJ>(r) and energetic hydrogen bonds -----------
  * The energy of a PAIR of molecules, which no other call exports (mmc_batch_deletion sums over the
  * partners, mmc_batch_rdf_sites has no energies, mmc_batch_local_order counts bonds by geometry): the

@@ -198,6 +198,7 @@ SIGNATURES = {
     "mmc_batch_rdf_sites": [_vp, C.c_int32, _d, C.c_int32, C.POINTER(C.c_uint64)],
     "mmc_batch_dipoles": [_vp, _dp],
     "mmc_batch_orient_corr": [_vp, C.c_int32, _d, C.c_int32, _i64p],
+    "mmc_batch_sdf": [_vp, C.c_int32, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)],
     "mmc_batch_pair_energy": [_vp, C.c_int32, _d, C.c_int32, _d, _d, _d, C.c_int32, _i64p, C.POINTER(C.c_uint64),
                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mmc_batch_structure_factor": [_vp, C.c_int32, C.c_int32, _i32p, _i64p, _dp],

@@ -1,6 +1,7 @@
 // mmc_tiles.hpp -- what the pair passes over the i < j triangle share on the device:
-// k_rdf_sites_wave (mmc_struct.hpp), k_orient_corr_wave (mmc_orient.hpp) and k_pair_energy_wave
-// (mmc_pair_energy.hpp); the host side (tile_plan, tile_waves, obs_grid) is in mmc_units.inc.
+// k_rdf_sites_wave (mmc_struct.hpp), k_orient_corr_wave (mmc_orient.hpp), k_pair_energy_wave
+// (mmc_pair_energy.hpp) and k_sdf_wave (mmc_sdf.hpp, which gives the run of tiles to a workgroup and
+// bins in three dimensions); the host side (tile_plan, tile_waves, obs_grid) is in mmc_units.inc.
 //
 // The decomposition.  The UNIT is a 64 x 64 tile (k, c), c <= k, of a replica's i < j triangle:
 // neighbours j = 64 k + lane, chosen molecules i of block c.  A replica has K (K + 1) / 2 of them,
@@ -40,11 +41,14 @@ struct TileCursor {
     bool fresh; // (r, k) changed: the lane's neighbour is to be loaded (the kernel clears it)
 
     __device__ __forceinline__ TileCursor(const TileArgs &ta, unsigned grid, unsigned block, int nw, int wv)
-        : r(0), k(0), c(0), K(ta.n_blocks), fresh(true)
+        : TileCursor(ta, ta.n_tiles * ((int64_t)block * nw + wv) / ((int64_t)grid * nw),
+                     ta.n_tiles * ((int64_t)block * nw + wv + 1) / ((int64_t)grid * nw))
     {
-        const int64_t NW = (int64_t)grid * nw, W = (int64_t)block * nw + wv;
-        tile = ta.n_tiles * W / NW;
-        end = ta.n_tiles * (W + 1) / NW;
+    }
+    // ... or any run [first, last) of the launch's tiles (k_sdf_wave: a share of its workgroup's run)
+    __device__ __forceinline__ TileCursor(const TileArgs &ta, int64_t first, int64_t last)
+        : tile(first), end(last), r(0), k(0), c(0), K(ta.n_blocks), fresh(true)
+    {
         if (tile < end) {
             const int T = ta.tiles_per_rep;
             r = (int)(tile / T);

@@ -4,7 +4,8 @@
 //   the calls with one wavefront per (replica, molecule): mmc_batch_widom / _widom_at, _solute,
 //   _solute_pair, _deletion and _forces (UnitsCall; the kernels' shared part is mmc_unit.hpp);
 //   the pair passes over the i < j triangle: mmc_batch_rdf_sites, _orient_corr and _pair_energy
-//   (tile_plan, tile_waves; the kernels' shared part is mmc_tiles.hpp);
+//   (tile_plan, tile_waves; the kernels' shared part is mmc_tiles.hpp), and mmc_batch_sdf on the
+//   same tiles with a grid of its own per workgroup;
 //   and mmc_batch_dipoles, _structure_factor, _local_order, _cavity / _cavity_at, _volume_perturb.
 // Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels" and
 // "Tile passes".

@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import CHAIN_DTYPE, TOTALS_DTYPE, Move, MoveResult, RunParams, RunStats, Totals, check
 
 PairEnergy = collections.namedtuple("PairEnergy", "rows uhist nhb flagged")  # Batch.pair_energy
+Sdf = collections.namedtuple("Sdf", "grid outside noframe")  # Batch.sdf
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -843,6 +844,29 @@ class Batch:
         check(self._L.mmc_batch_orient_corr(self._h, int(numbins), float(r_max), int(bool(per_replica)),
                                             _i(out)))
         return out
+
+    def sdf(self, n_half, cell, fold=3, site_mask=1, per_replica=False, out=None):
+        """mmc_batch_sdf: the spatial distribution function's counts, the sites selected in
+        site_mask (bit a = slot a) of every neighbour per cell of a cube of half-width n_half cell
+        in the centre molecule's body-fixed frame (z the bisector, x in the molecular plane);
+        fold bit 0 / 1 folds x / y onto |x| / |y|.  Returns Sdf(grid, outside, noframe): grid
+        uint64 [g_x, g_y, g_z] with g = n_half along a folded axis and 2 n_half otherwise, the
+        deposits outside the cube and those of centres without a frame; summed over the replicas
+        or with a leading [R] axis with per_replica (observables.sdf_density, sdf_unfold,
+        sdf_cell_centres).  `out` (uint64 [g_x g_y g_z + 2] or [R, g_x g_y g_z + 2], contiguous:
+        the library's layout) is overwritten, and the results are views of it."""
+        n, f = max(int(n_half), 0), int(fold)  # (arguments the library refuses still get an array to leave alone)
+        g = (n if f & 1 else 2 * n, n if f & 2 else 2 * n, 2 * n)
+        cells = g[0] * g[1] * g[2]
+        shape = (self.R, cells + 2) if per_replica else (cells + 2,)
+        if out is None:
+            out = np.zeros(shape if cells <= 32768 else shape[:-1] + (2,), dtype=np.uint64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.shape == shape
+                  and out.flags.c_contiguous):
+            raise ValueError(f"out: uint64 {shape}, contiguous")
+        check(self._L.mmc_batch_sdf(self._h, int(n_half), float(cell), f, int(site_mask), int(bool(per_replica)),
+                                    out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return Sdf(out[..., :cells].reshape(shape[:-1] + g), out[..., cells], out[..., cells + 1])
 
     def pair_energy(self, numbins, r_max=0.0, n_ebins=0, u_lo=-4000.0, u_hi=2000.0, u_hb=None, per_replica=False,
                     out=None):

@@ -800,6 +800,34 @@ function orient_corr(b::Batch, numbins::Integer; r_max::Float64 = 0.0, per_repli
     return hist
 end
 
+# ---- spatial distribution functions (include/mmc_hip.h, mmc_batch_sdf) -----------------------------
+"""
+    sdf(b, n_half, cell; fold = 3, site_mask = 1, per_replica = false)
+
+The counts of the spatial distribution function: the sites selected in `site_mask` (bit a = slot a,
+1 = O) of every neighbour per cell of a cube of half-width `n_half * cell` in the centre molecule's
+body-fixed frame (z the bisector, x in the molecular plane); `fold` bit 0 / 1 folds x / y onto
+|x| / |y|.  Returns `(grid, outside, noframe)`: `grid` a `(g_z, g_y, g_x)` UInt64 array (the C layout
+read column-major; g = n_half along a folded axis, 2 n_half otherwise), the deposits outside the cube
+and those of centres without a frame.  Summed over the replicas, or with a trailing replica axis with
+`per_replica`.  Read-only for the chains.
+"""
+function sdf(b::Batch, n_half::Integer, cell::Float64; fold::Integer = 3, site_mask::Integer = 1,
+             per_replica::Bool = false)
+    n_half >= 1 || error("n_half must be >= 1")
+    0 <= fold <= 3 || error("fold must be in 0..3")
+    gx, gy, gz = (fold & 1) != 0 ? n_half : 2n_half, (fold & 2) != 0 ? n_half : 2n_half, 2n_half
+    cells = gx * gy * gz
+    cells <= 32768 || error("the grid has more than 32768 cells")
+    hist = per_replica ? zeros(UInt64, cells + 2, b.n_replicas) : zeros(UInt64, cells + 2)
+    check(ccall((:mmc_batch_sdf, libmmc), Int32, (Ptr{Cvoid}, Int32, Float64, Int32, Int32, Int32, Ptr{UInt64}),
+                b.h, n_half, cell, fold, site_mask, per_replica ? 1 : 0, hist))
+    if per_replica
+        return reshape(hist[1:cells, :], gz, gy, gx, :), hist[cells + 1, :], hist[cells + 2, :]
+    end
+    return reshape(hist[1:cells], gz, gy, gx), hist[cells + 1], hist[cells + 2]
+end
+
 # ---- pair-energy distributions (include/mmc_hip.h, mmc_batch_pair_energy) --------------------------
 """
     pair_energy(b, numbins; r_max = 0.0, ebins = nothing, u_hb = nothing, per_replica = false)

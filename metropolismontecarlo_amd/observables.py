@@ -107,6 +107,55 @@ def orient_projections(hist, n_mol, dr, inv_volume_sum):
     return r, g, h110, h112, p2
 
 
+# ---- spatial distribution functions (include/mmc_hip.h, "Spatial distribution functions") ---------
+def _sdf_folded(fold):
+    fold = int(fold)
+    if not 0 <= fold <= 3:
+        raise ValueError("fold must be 0..3")
+    return bool(fold & 1), bool(fold & 2)
+
+
+def sdf_ideal_count(n_mol, n_frames, volume, cell, fold, site_mask):
+    """What a cell of an mmc_batch_sdf grid counts in an ideal gas of the same density:
+    n_frames N (N - 1) / V popcount(site_mask) cell^3 2^(folded axes).  n_frames: the frames summed
+    into the grid (calls, times the replicas for a summed output); volume: A^3."""
+    n_sel = bin(int(site_mask) & 7).count("1")
+    if n_sel == 0:
+        raise ValueError("site_mask selects no slot")
+    return (float(n_frames) * float(n_mol) * (float(n_mol) - 1.0) / float(volume) * n_sel * float(cell) ** 3
+            * 2.0 ** sum(_sdf_folded(fold)))
+
+
+def sdf_density(grid, n_mol, n_frames, volume, cell, fold, site_mask):
+    """g(x, y, z) from the counts of an mmc_batch_sdf grid ([..., g_x, g_y, g_z]; sums over several
+    calls may be added first): the counts over sdf_ideal_count."""
+    return np.asarray(grid).astype(np.float64) / sdf_ideal_count(n_mol, n_frames, volume, cell, fold, site_mask)
+
+
+def sdf_unfold(grid, fold):
+    """The full mirror-symmetric grid [..., 2 n_half, 2 n_half, 2 n_half] (float64) of a folded
+    one, for plotting: along a folded axis each cell's value is shared equally between the cell and
+    its mirror image, so the total is kept and the result is what fold = 0 would have counted in a
+    symmetric liquid: sdf_density(sdf_unfold(grid, fold), ..., fold=0, ...) equals
+    sdf_density(grid, ..., fold, ...) on both sides."""
+    g = np.asarray(grid).astype(np.float64)
+    if g.ndim < 3:
+        raise ValueError("grid must be [..., g_x, g_y, g_z]")
+    for axis, folded in zip((-3, -2), _sdf_folded(fold)):
+        if folded:
+            g = 0.5 * np.concatenate([np.flip(g, axis=axis), g], axis=axis)
+    return g
+
+
+def sdf_cell_centres(n_half, cell, fold):
+    """(x, y, z): the centres of the cells along each axis of an mmc_batch_sdf grid, (k + 1/2) cell
+    with k = 0 .. n_half - 1 along a folded axis and -n_half .. n_half - 1 otherwise."""
+    n, c = int(n_half), float(cell)
+    full, half = (np.arange(-n, n) + 0.5) * c, (np.arange(n) + 0.5) * c
+    fx, fy = _sdf_folded(fold)
+    return (half if fx else full), (half if fy else full), full
+
+
 # ---- pair-energy distributions (include/mmc_hip.h, "Pair-energy distributions") -------------------
 PAIRE_SCALE = 2.0 ** 20  # MMC_PAIRE_SCALE: one unit of rows 1 and 2 of mmc_batch_pair_energy
 
