@@ -1251,6 +1251,67 @@ int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t 
                               int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist,
                               double *q_sum, int32_t *nbr_out, double *q_out, uint8_t *hb_out);
 
+/* ---- Hydrogen-bond network: clusters, their sizes and percolation ------------------------------
+ * How the hydrogen bonds of mmc_batch_local_order connect: the bond graph of every replica, its
+ * connected components, the cluster-size distribution n_s and whether a cluster spans the periodic
+ * box (Geiger, Stillinger and Rahman, J. Chem. Phys. 70, 4185, 1979; Stanley and Teixeira, J. Chem.
+ * Phys. 73, 3404, 1980).  Up to MMC_NET_MAX_CRIT bond criteria per call, criterion k being
+ * (r_hb[k], cos_hb[k], min_bonds[k]).  The reference has no such analysis; the definitions are
+ * stated here and restated in numpy by tests/network_ref.py.  Every result is an integer: nothing is
+ * left to a tolerance.
+ *   - Bond.  A_k(i, j), i != j, holds when molecule i donates to j or j donates to i through either
+ *     hydrogen; "donates" is exactly the test of "Local order" with (r_hb[k], cos_hb[k]): the same
+ *     unfused fp64 arithmetic, vector1D images and replica box.  A_k is symmetric; two hydrogens to
+ *     one partner, or donation both ways, are one bond.
+ *   - Degree.  deg_k(i) = the number of j with A_k(i, j), over all molecules, before any selection.
+ *   - Flagged.  A (replica, criterion) in which some molecule has deg_k > MMC_NET_MAX_DEG is flagged:
+ *     it enters no histogram, its stats are 0 except stats[7] = 1, its labels are -2 and its partner
+ *     lists -1 throughout (as mmc_batch_pair_energy's `flagged`).  It is not an error; other replicas
+ *     and criteria are unaffected.
+ *   - Sites and edges.  V_k = { i : deg_k(i) >= min_bonds[k] }: every molecule with min_bonds 0, the
+ *     four-bonded ones with 4.  E_k = A_k restricted to V_k x V_k.
+ *   - Clusters.  The connected components of (V_k, E_k); a site without edges is a cluster of size 1.
+ *     The label of a site is the smallest molecule index of its cluster; other molecules have -1.
+ *   - Wrapping.  For an edge (i, j), m_ij is the integer vector of boxes that vector1D adds per
+ *     component to O_j - O_i (each -1, 0 or +1; m_ji = -m_ij bit for bit, because O_i - O_j is the
+ *     exact negative of O_j - O_i).  A cluster wraps along axis a when it contains a closed walk over
+ *     its edges whose sum of m has a nonzero component a; its mask has bit a set (x = 1, y = 2, z = 4).
+ *     With p the sum of m along a spanning tree from the root, the mask is the OR over the edges of
+ *     the nonzero components of p_i + m_ij - p_j.  It does not depend on the tree, on the order of
+ *     traversal or on whether atoms are stored inside the box: the winding vectors of any spanning
+ *     tree's non-tree edges generate the same sublattice (the windings of all closed walks), and
+ *     storing a molecule one box over changes m on all its edges by the same vector, which cancels
+ *     around every closed walk.
+ *   - Outputs, all integers, all overwritten; each may be NULL, but not all three of size_hist,
+ *     deg_hist and stats:
+ *     size_hist uint64 [K][N + 1], [R][K][N + 1] with per_replica: entry s = the number of clusters
+ *       of s sites; entry 0 stays 0.
+ *     deg_hist uint64 [K][MMC_NET_MAX_DEG + 1], [R][K][..] with per_replica: molecules by deg_k, the
+ *       f_j of the percolation papers.
+ *     stats int64 [R][K][MMC_NET_STATS]: 0 bonds |A_k|; 1 sites |V_k|; 2 clusters; 3 the size of the
+ *       largest cluster; 4 the sum of s^2 over the clusters; 5 the OR of the clusters' masks; 6 the
+ *       size of the largest cluster with a nonzero mask (0 if none); 7 flagged (0 or 1).
+ *     label_out int32 [R][K][N].
+ *     nbr_out int32 [R][K][N][MMC_NET_MAX_DEG]: the partners under A_k in ascending j, then -1.
+ *     Nothing depends on the grid, on option "wave_wgs" or on any order of lanes, waves or atomics.
+ *   - Use (observables.py): cluster_size_distribution, percolation_probability, gel_fraction,
+ *     mean_cluster_size, bond_fractions.
+ * Both box modes and either Coulomb style, records or arrays: the call reads coordinates only, and is
+ * read-only exactly as mmc_batch_local_order is, with its preconditions (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: n_crit outside 1..MMC_NET_MAX_CRIT; r_hb, cos_hb or
+ * min_bonds NULL; an r_hb not finite or <= 0; a cos_hb outside (0, 1]; a min_bonds outside
+ * 0..MMC_NET_MAX_DEG; size_hist, deg_hist and stats all NULL.  Checked with the batch: an r_hb above
+ * half of the smallest box.  Then the state; then MMC_ERR_UNSUPPORTED: fewer than 2 molecules, or more
+ * than MMC_NET_MAX_MOL (a replica's graph stays in one workgroup's LDS: 28 bytes per molecule and
+ * 33 per molecule and criterion of a pass).  On any error every output is left untouched. */
+#define MMC_NET_MAX_CRIT 8
+#define MMC_NET_MAX_DEG  16
+#define MMC_NET_STATS    8
+#define MMC_NET_MAX_MOL  2048
+int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const double *r_hb, const double *cos_hb,
+                                const int32_t *min_bonds, int32_t per_replica, uint64_t *size_hist,
+                                uint64_t *deg_hist, int64_t *stats, int32_t *label_out, int32_t *nbr_out);
+
 /* ---- Cavities and occupancy: p_n(R), its moments and the cavity-size distribution ---------------
  * How many sites lie within R of a random point of the liquid, for up to eight radii at once, and
  * how far the nearest site is: the occupancy distribution p_n(R) of scaled-particle and

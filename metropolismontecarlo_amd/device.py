@@ -961,6 +961,52 @@ class Batch:
             ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
         return res
 
+    def hbond_network(self, r_hb=(3.5,), theta_deg=(30.0,), min_bonds=(0,), per_replica=False, details=False,
+                      out=None):
+        """mmc_batch_hbond_network: the hydrogen-bond graph of every replica under K = 1..8 criteria
+        at once (bond: local_order's geometry with r_hb[k], theta_deg[k]; sites: the molecules with
+        at least min_bonds[k] bonds; scalars are broadcast), read-only.  Returns a dict: size_hist
+        uint64 [K, N + 1] (clusters by number of sites), deg_hist uint64 [K, 17] (molecules by number
+        of bonds) -- each [R, ...] with per_replica -- and stats int64 [R, K, 8]: bonds, sites,
+        clusters, the largest cluster, the sum of s^2, the OR of the wrap masks (x = 1, y = 2, z = 4),
+        the largest wrapping cluster, flagged (some molecule with more than 16 bonds: all else 0).
+        details=True adds label int32 [R, K, N] (the lowest index of the molecule's cluster, -1 off
+        the sites, -2 where flagged) and nbr int32 [R, K, N, 16] (the bonded partners, ascending, then
+        -1).  `out`: a dict of arrays under those names to overwrite instead (each of its shape and
+        dtype, contiguous)."""
+        R, N = self.R, self.n_mol
+        crit = np.broadcast_arrays(np.atleast_1d(_f64(r_hb)), np.atleast_1d(_f64(theta_deg)),
+                                   np.atleast_1d(np.asarray(min_bonds)))
+        if crit[0].ndim != 1:
+            raise ValueError("r_hb, theta_deg and min_bonds are scalars or 1-D of one length")
+        rh = np.ascontiguousarray(crit[0], dtype=np.float64)
+        cs = np.ascontiguousarray(np.cos(np.deg2rad(crit[1])), dtype=np.float64)
+        mb = np.ascontiguousarray(crit[2], dtype=np.int32)
+        if not np.array_equal(mb, crit[2]):
+            raise ValueError("min_bonds must be integers")
+        K = rh.shape[0]
+        lead = (R,) if per_replica else ()
+        spec = {"size_hist": (lead + (K, N + 1), np.uint64), "deg_hist": (lead + (K, 17), np.uint64),
+                "stats": ((R, K, 8), np.int64)}
+        if details:
+            spec.update(label=((R, K, N), np.int32), nbr=((R, K, N, 16), np.int32))
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_hbond_network(
+            self._h, K, _d(rh), _d(cs), mb.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(per_replica)),
+            ptr("size_hist", C.c_uint64), ptr("deg_hist", C.c_uint64), ptr("stats", C.c_int64),
+            ptr("label", C.c_int32), ptr("nbr", C.c_int32)))
+        return res
+
     def _cavity(self, points, n_probe, seed, draw0, radii, site, n_cap, nn_bins, nn_max, per_replica, details):
         R, P = self.R, max(int(n_probe), 0)
         rad = _f64(np.atleast_1d(radii)).ravel()

@@ -916,6 +916,35 @@ function local_order(b::Batch; q_bins::Integer = 400, r_hb::Float64 = 3.5, theta
     return hb_hist, q_hist, q_sum
 end
 
+# ---- hydrogen-bond network (include/mmc_hip.h, mmc_batch_hbond_network) -----------------------------
+"""
+    hbond_network(b; r_hb = [3.5], theta_deg = [30.0], min_bonds = [0], per_replica = false)
+
+The hydrogen-bond graph of every replica under K = 1..8 criteria at once, read-only: bonds by
+`local_order`'s geometry with `(r_hb[k], theta_deg[k])`, sites the molecules with at least
+`min_bonds[k]` bonds.  Returns `(size_hist, deg_hist, stats)`: `size_hist` `(N + 1, K)` UInt64
+(clusters by number of sites), `deg_hist` `(17, K)` (molecules by number of bonds) -- each with a
+trailing dimension R with `per_replica` -- and `stats` `(8, K, R)` Int64: bonds, sites, clusters, the
+largest cluster, the sum of s^2, the OR of the wrap masks (x = 1, y = 2, z = 4), the largest wrapping
+cluster, flagged.
+"""
+function hbond_network(b::Batch; r_hb::Vector{Float64} = [3.5], theta_deg::Vector{Float64} = [30.0],
+                       min_bonds::Vector{Int32} = Int32[0], per_replica::Bool = false)
+    K = length(r_hb)
+    1 <= K <= 8 || error("1 to 8 criteria")
+    length(theta_deg) == K && length(min_bonds) == K || error("r_hb, theta_deg and min_bonds have one length")
+    N = b.n_mol
+    size_hist = per_replica ? zeros(UInt64, N + 1, K, b.n_replicas) : zeros(UInt64, N + 1, K)
+    deg_hist = per_replica ? zeros(UInt64, 17, K, b.n_replicas) : zeros(UInt64, 17, K)
+    stats = zeros(Int64, 8, K, b.n_replicas)
+    check(ccall((:mmc_batch_hbond_network, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{UInt64}, Ptr{UInt64},
+                 Ptr{Int64}, Ptr{Int32}, Ptr{Int32}),
+                b.h, K, r_hb, cosd.(theta_deg), min_bonds, per_replica ? 1 : 0, size_hist, deg_hist, stats,
+                C_NULL, C_NULL))
+    return size_hist, deg_hist, stats
+end
+
 # ---- cavities and occupancy (include/mmc_hip.h, mmc_batch_cavity, mmc_batch_cavity_at) --------------
 """
     cavity(b, n_probe, seed; draw0 = 0, radii = [3.3], site = 0, n_cap = 32, nn_bins = 0, nn_max = 0.0,

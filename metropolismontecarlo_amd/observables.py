@@ -315,6 +315,76 @@ def normalize_q_hist(q_hist):
     return centres, h / (h.sum(-1, keepdims=True) * dq)
 
 
+# ---- hydrogen-bond network (include/mmc_hip.h, "Hydrogen-bond network") -----------------------------
+NET_STATS = 8   # bonds, sites, clusters, largest, sum of s^2, wrap mask, largest wrapping, flagged
+NET_MAX_DEG = 16
+
+
+def _net_stats(stats):
+    st = np.asarray(stats)
+    if st.ndim < 2 or st.shape[-1] != NET_STATS:
+        raise ValueError("stats must be [R, ..., 8]")
+    return st
+
+
+def cluster_size_distribution(size_hist):
+    """(n_s, w_s) from mmc_batch_hbond_network's size_hist ([..., N + 1], clusters by number of
+    sites): n_s the counts as floats and w_s = s n_s / sum s n_s, the fraction of the sites that sit
+    in clusters of size s (NaN where there are no sites)."""
+    h = np.asarray(size_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] < 2:
+        raise ValueError("size_hist must be [..., N + 1]")
+    sn = h * np.arange(h.shape[-1], dtype=float)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h, sn / sn.sum(-1, keepdims=True)
+
+
+def percolation_probability(stats):
+    """(P_any, P_all) from stats [R, ..., 8]: the fraction of the unflagged replicas in which some
+    cluster wraps the box along at least one axis, and in which the wrap masks cover all three
+    (NaN where every replica is flagged).  Each [...]: one value per criterion for [R, K, 8]."""
+    st = _net_stats(stats)
+    ok = st[..., 7] == 0
+    n = ok.sum(0).astype(float)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (ok & (st[..., 5] != 0)).sum(0) / n, (ok & (st[..., 5] == 7)).sum(0) / n
+
+
+def gel_fraction(stats):
+    """The largest wrapping cluster over the sites, per replica and criterion, from stats
+    [R, ..., 8] -> [R, ...]: 0 where nothing wraps, NaN where flagged or without sites."""
+    st = _net_stats(stats)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        g = st[..., 6] / st[..., 1].astype(float)
+    return np.where((st[..., 7] == 0) & (st[..., 1] > 0), g, np.nan)
+
+
+def mean_cluster_size(size_hist, stats):
+    """The mean finite-cluster size S = sum' s^2 n_s / sum' s n_s with each replica's largest
+    cluster left out of both sums, from size_hist [K, N + 1] (summed over the replicas) or
+    [R, K, N + 1] and stats [R, K, 8] of the same call.  Returns [K] (NaN where nothing is left)."""
+    h, st = np.asarray(size_hist, dtype=np.int64), _net_stats(stats)
+    if st.ndim != 3 or h.ndim not in (2, 3) or h.shape[-2] != st.shape[1] or (h.ndim == 3 and h.shape[0] != st.shape[0]):
+        raise ValueError("size_hist must be [K, N + 1] or [R, K, N + 1] beside stats [R, K, 8]")
+    if h.ndim == 3:
+        h = h.sum(0)
+    s = np.arange(h.shape[-1], dtype=np.int64)
+    big = st[..., 3]
+    num = (h * s * s).sum(-1) - (big * big).sum(0)
+    den = (h * s).sum(-1) - big.sum(0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den > 0, num / den.astype(float), np.nan)
+
+
+def bond_fractions(deg_hist):
+    """f_j, the fraction of molecules with j = 0..16 bonds, from deg_hist [..., 17]."""
+    h = np.asarray(deg_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] != NET_MAX_DEG + 1:
+        raise ValueError("deg_hist must be [..., 17]")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h / h.sum(-1, keepdims=True)
+
+
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
 MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2 (+3, +4, +5: pair_molecules)
 

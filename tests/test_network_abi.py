@@ -1,0 +1,100 @@
+"""CPU tests of mmc_batch_hbond_network's boundary: declared with the agreed prototype, exported,
+bound with matching ctypes, and loud on a NULL batch and on every argument that can be refused
+without a device."""
+import ctypes as C
+import math
+import re
+
+import pytest
+
+from metropolismontecarlo_amd import _lib
+
+NAME = "mmc_batch_hbond_network"
+PROTOTYPE = ("int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const double *r_hb, "
+             "const double *cos_hb, const int32_t *min_bonds, int32_t per_replica, uint64_t *size_hist, "
+             "uint64_t *deg_hist, int64_t *stats, int32_t *label_out, int32_t *nbr_out);")
+CTYPES = {"mmc_batch *": C.c_void_p, "int32_t": C.c_int32, "const double *": C.POINTER(C.c_double),
+          "const int32_t *": C.POINTER(C.c_int32), "uint64_t *": C.POINTER(C.c_uint64),
+          "int64_t *": C.POINTER(C.c_int64), "int32_t *": C.POINTER(C.c_int32)}
+COS30 = math.cos(math.radians(30.0))
+N = 40   # the size the untouched outputs are laid out for
+
+
+def header_text():
+    from test_abi import HEADER
+    return open(HEADER).read()
+
+
+def header_prototype():
+    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
+    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
+    assert m, f"{NAME} is not declared in mmc_hip.h"
+    return re.sub(r"\s+", " ", m.group(0))
+
+
+def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
+    from test_abi import header_functions
+    assert NAME in header_functions()
+    assert header_prototype() == PROTOTYPE
+    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
+    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
+    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
+    assert _lib.SIGNATURES[NAME] == want
+    fn = getattr(_lib.lib(), NAME)
+    assert fn.argtypes == want and fn.restype is C.c_int32
+
+
+def test_the_header_states_the_limits():
+    text = header_text()
+    for name, value in (("MMC_NET_MAX_CRIT", 8), ("MMC_NET_MAX_DEG", 16), ("MMC_NET_STATS", 8)):
+        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), text), name
+    m = re.search(r"#define\s+MMC_NET_MAX_MOL\s+(\d+)", text)
+    assert m and int(m.group(1)) >= 2048
+
+
+def call(b=None, r_hb=(3.5,), cos_hb=(COS30,), min_bonds=(0,), n_crit=None, outputs=(True, True, True)):
+    k = len(r_hb) if r_hb is not None else 1
+    n_crit = k if n_crit is None else n_crit
+    rh = (C.c_double * len(r_hb))(*r_hb) if r_hb is not None else None
+    cs = (C.c_double * len(cos_hb))(*cos_hb) if cos_hb is not None else None
+    mb = (C.c_int32 * len(min_bonds))(*min_bonds) if min_bonds is not None else None
+    sh = (C.c_uint64 * (8 * (N + 1)))(*([77] * (8 * (N + 1))))
+    dh = (C.c_uint64 * (8 * 17))(*([77] * (8 * 17)))
+    st = (C.c_int64 * 64)(*([-7] * 64))
+    lb = (C.c_int32 * (8 * N))(*([-5] * (8 * N)))
+    status = _lib.lib().mmc_batch_hbond_network(b, n_crit, rh, cs, mb, 0, sh if outputs[0] else None,
+                                                dh if outputs[1] else None, st if outputs[2] else None, lb, None)
+    assert all(v == 77 for v in sh) and all(v == 77 for v in dh) and all(v == -7 for v in st)
+    assert all(v == -5 for v in lb)
+    msg = _lib.lib().mmc_last_error()
+    return status, (msg.decode() if msg else "")
+
+
+def test_a_null_batch_fails_loudly():
+    st, msg = call()
+    assert st == _lib.MMC_ERR_ARG and "NULL" in msg
+    with pytest.raises(_lib.MMCError, match="MMC_ERR_ARG"):
+        _lib.check(st)
+    st, msg = call(r_hb=(2.9, 3.5), cos_hb=(COS30, 1.0), min_bonds=(0, 16))   # the edges of every range pass
+    assert st == _lib.MMC_ERR_ARG and "batch is NULL" in msg
+
+
+@pytest.mark.parametrize("kw,word", [
+    (dict(n_crit=0), "n_crit"), (dict(n_crit=-1), "n_crit"), (dict(n_crit=9), "n_crit"),
+    (dict(r_hb=None), "r_hb is NULL"), (dict(cos_hb=None), "cos_hb is NULL"), (dict(min_bonds=None), "min_bonds is NULL"),
+    (dict(r_hb=(float("nan"),)), "r_hb[0]"), (dict(r_hb=(float("inf"),)), "r_hb[0]"), (dict(r_hb=(0.0,)), "r_hb[0]"),
+    (dict(r_hb=(-3.5,)), "r_hb[0]"),
+    (dict(r_hb=(3.5, -1.0), cos_hb=(COS30, COS30), min_bonds=(0, 0)), "r_hb[1]"),
+    (dict(cos_hb=(0.0,)), "cos_hb[0]"), (dict(cos_hb=(-0.5,)), "cos_hb[0]"),
+    (dict(cos_hb=(math.nextafter(1.0, 2.0),)), "cos_hb[0]"), (dict(cos_hb=(float("nan"),)), "cos_hb[0]"),
+    (dict(r_hb=(3.5, 3.5), cos_hb=(COS30, 1.5), min_bonds=(0, 0)), "cos_hb[1]"),
+    (dict(min_bonds=(-1,)), "min_bonds[0]"), (dict(min_bonds=(17,)), "min_bonds[0]"),
+    (dict(r_hb=(3.5, 3.5), cos_hb=(COS30, COS30), min_bonds=(4, 17)), "min_bonds[1]"),
+    (dict(outputs=(False, False, False)), "at least one"),
+])
+def test_arguments_refused_without_a_device(kw, word):
+    """These are refused before the batch is looked at: the message names the argument, not the
+    NULL batch, and nothing is written."""
+    st, msg = call(**kw)
+    assert st == _lib.MMC_ERR_ARG
+    assert word in msg and "batch is NULL" not in msg, msg
