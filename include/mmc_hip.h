@@ -342,9 +342,9 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *   "inject_torn"      N > 0: the native driver corrupts its first N copies of result records
  *                      before checking them, as a torn PCIe write would (test hook: the check must
  *                      refuse them and read again; mmc_run_stats.torn_records counts them)
- *   "local_stage"      0 = mmc_batch_local_order and mmc_batch_cavity read the site positions from device
- *                      memory even where a replica's fit in LDS (default 1; the path of systems too
- *                      large to stage, same results: a test hook)
+ *   "local_stage"      0 = mmc_batch_local_order, mmc_batch_shell_order and mmc_batch_cavity read the site
+ *                      positions from device memory even where a replica's fit in LDS (default 1; the
+ *                      path of systems too large to stage, same results: a test hook)
  *   "zero_copy_moves"  1 = the kernel reads proposals from pinned host memory instead of an
  *                      H2D copy on the stream (lower latency for one replica, default 0)
  *   "device_moves"     1 = mmc_batch_run / mmc_batch_run_chains generate the trial moves on the
@@ -1311,6 +1311,76 @@ int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t 
 int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const double *r_hb, const double *cos_hb,
                                 const int32_t *min_bonds, int32_t per_replica, uint64_t *size_hist,
                                 uint64_t *deg_hist, int64_t *stats, int32_t *label_out, int32_t *nbr_out);
+
+/* ---- Shell order: ranked neighbours, LSI, zeta and O-O-O angles of 3-site molecules -----------
+ * What lies between the first and the second coordination shell of every molecule of every replica,
+ * in one read-only pass: the neighbour-rank decomposition of g_OO (row 5 is the distribution of the
+ * fifth-neighbour distance d5), the local structure index (Shiratani and Sasai, J. Chem. Phys. 104,
+ * 7671, 1996), zeta (Russo and Tanaka, Nat. Commun. 5, 3556, 2014) and the O-O-O angle distribution.
+ * Slot 0 of a molecule is the heavy atom ("O"), slots 1 and 2 the hydrogens.  The reference has no
+ * such analysis; the arithmetic is defined here, operation by operation, and restated in numpy by
+ * tests/shell_order_ref.py.  + - x / sqrt floor are correctly rounded fp64 and nothing is fused, so
+ * every output is reproducible bit for bit.
+ *   d(x, y) is vector1D as in "Local order", per component, with the replica's own box.  Every r^2
+ *   and every dot product is (x x' + y y') + z z'.  Squares of the radii (r_list r_list, ...) and
+ *   the scales named below are formed once, in fp64, by the host.
+ *   - List.  For molecule i: d_ij = d(O_i, O_j), r2_ij its r^2.  The list holds every j != i with
+ *     r2_ij < r_list r_list, ascending under the key (bit pattern of r2_ij, then j).  m_i is its
+ *     length, rho_k = sqrt(r2_k) the k-th distance, k = 1 .. m_i.  A list has room for
+ *     MMC_SHELL_CAP = 64 neighbours.  A molecule with more in range is FLAGGED: counted in flagged[r],
+ *     in no histogram and no sum; its count_out is -1, its nbr_out -1, its lsi_out and zeta_out NaN.
+ *     A list is never truncated.  (64 neighbours reach to 7.7 A in water at 1 g/cm^3: the second
+ *     shell ends at 5.7 A.)
+ *   - Rank histograms.  For k = 1 .. n_rank the molecule adds one to row k - 1 of rank_hist
+ *     [n_rank][r_bins + 1]: at bin min(r_bins - 1, (int)floor(rho_k inv_dr)), inv_dr = r_bins / r_list,
+ *     or at slot r_bins when m_i < k.
+ *   - LSI.  n = the number of listed neighbours with r2 < r_lsi r_lsi.  Defined when n >= 1 and
+ *     m_i >= n + 1 (the neighbour just beyond r_lsi is in the list).  Delta_k = rho_(k+1) - rho_k,
+ *     k = 1 .. n; mean = (Delta_1 + Delta_2 + ...) / n and I = ((Delta_1 - mean)^2 + (Delta_2 -
+ *     mean)^2 + ...) / n, each sum added one term at a time in rising k, each square one product.
+ *     Bin min(lsi_bins - 1, (int)floor(I lsi_scale)), lsi_scale = lsi_bins / lsi_max; undefined:
+ *     slot lsi_bins of lsi_hist [lsi_bins + 1].
+ *   - zeta.  Neighbour j of the list is bonded when r2_ij < r_hb r_hb and i donates to j or j to i
+ *     through either hydrogen: the test of "Local order" with (r_hb, cos_hb), bit for bit.
+ *     zeta_i = rho of the nearest listed neighbour that is not bonded - rho of the farthest bonded
+ *     one.  Undefined without a bonded neighbour, or when every listed neighbour is bonded.  Bin
+ *     (int)floor((zeta - zeta_lo) zeta_scale) clamped to 0 .. zeta_bins - 1, zeta_scale = zeta_bins /
+ *     (zeta_hi - zeta_lo); undefined: slot zeta_bins of zeta_hist [zeta_bins + 1].
+ *   - O-O-O angles.  Every unordered pair (j, k) of listed neighbours with both r2 < r_ang r_ang, j
+ *     before k in the list: c = ((dj_x dk_x + dj_y dk_y) + dj_z dk_z) / sqrt(r2_j r2_k); bin
+ *     (int)floor((c + 1.0) ang_scale) clamped to 0 .. ang_bins - 1, ang_scale = ang_bins / 2.0; a c
+ *     that is not finite (a coincident oxygen): slot ang_bins of ang_hist [ang_bins + 1].  The
+ *     histogram is in cos(theta) (observables.ooo_angle_distribution converts).
+ *   - Outputs, all overwritten.  Each may be NULL, but not all five of rank_hist, lsi_hist, ang_hist,
+ *     zeta_hist and sums; a histogram that is NULL costs no counters.  The four histograms are
+ *     [R][...] with per_replica.  flagged [R].  sums [R][4] = (sum of the replica's defined I, their
+ *     number, sum of its defined zeta, their number), the numbers as doubles, each sum in the order
+ *     of "Local order"'s q_sum: bitwise reproducible, independent of the launch.  count_out [R][N] =
+ *     m_i; nbr_out [R][N][MMC_SHELL_NBR] = the first 16 of the list, 0-based, then -1; lsi_out and
+ *     zeta_out [R][N], NaN where undefined.  Nothing depends on the grid or option "wave_wgs".
+ *   - Use (observables.py): neighbour_distance_distributions, lsi_distribution, zeta_distribution,
+ *     ooo_angle_distribution, lsi_mean, zeta_mean.
+ * Both box modes and either Coulomb style, records or arrays: the call reads coordinates only, and is
+ * read-only exactly as mmc_batch_local_order is, with its preconditions (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: r_list not finite or <= 0; r_lsi, r_ang or r_hb outside
+ * (0, r_list]; cos_hb outside (0, 1]; n_rank outside 1..MMC_SHELL_MAX_RANK; r_bins, lsi_bins,
+ * ang_bins or zeta_bins outside 1..MMC_SHELL_MAX_BINS; lsi_max not finite or <= 0; zeta_lo >= zeta_hi
+ * or either not finite; the five outputs above all NULL; and the bins of the histograms asked for
+ * together, 1 + n_rank (r_bins + 1) + (lsi_bins + 1) + (ang_bins + 1) + (zeta_bins + 1) counting
+ * only those that are not NULL, above MMC_SHELL_MAX_WORDS (a workgroup's 32-bit counters and a
+ * wave's list, 4 bytes a word and 768 bytes, stay within 32 KiB of LDS).  Checked with the batch: r_list above
+ * half of the smallest box.  Then the state; then MMC_ERR_UNSUPPORTED: fewer than 2 molecules or more
+ * than 2^21.  On any error every output is left untouched. */
+#define MMC_SHELL_CAP       64
+#define MMC_SHELL_NBR       16
+#define MMC_SHELL_MAX_RANK  16
+#define MMC_SHELL_MAX_BINS  1024
+#define MMC_SHELL_MAX_WORDS 8000
+int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double r_lsi, double r_ang, double r_hb, double cos_hb,
+    int32_t n_rank, int32_t r_bins, int32_t lsi_bins, double lsi_max, int32_t ang_bins,
+    int32_t zeta_bins, double zeta_lo, double zeta_hi, int32_t per_replica,
+    uint64_t *rank_hist, uint64_t *lsi_hist, uint64_t *ang_hist, uint64_t *zeta_hist, uint64_t *flagged,
+    double *sums, int32_t *count_out, int32_t *nbr_out, double *lsi_out, double *zeta_out);
 
 /* ---- Cavities and occupancy: p_n(R), its moments and the cavity-size distribution ---------------
  * How many sites lie within R of a random point of the liquid, for up to eight radii at once, and

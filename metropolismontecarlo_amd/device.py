@@ -961,6 +961,53 @@ class Batch:
             ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
         return res
 
+    def shell_order(self, r_list=6.0, r_lsi=3.7, r_ang=3.3, r_hb=3.5, theta_deg=30.0, n_rank=8, r_bins=300,
+                    lsi_bins=200, lsi_max=0.4, ang_bins=180, zeta_bins=200, zeta_lo=-1.5, zeta_hi=2.5,
+                    per_replica=False, details=False, out=None):
+        """mmc_batch_shell_order: every molecule's O-O neighbours inside r_list sorted by distance,
+        and from that list the order between the first and second shell (slot 0 = O, slots 1, 2 = H),
+        read-only.  Returns a dict: rank_hist uint64 [n_rank, r_bins + 1] (row k - 1: the distance to
+        the k-th neighbour in bins of r_list / r_bins; last slot: fewer than k listed), lsi_hist
+        uint64 [lsi_bins + 1] (the local structure index over [0, lsi_max] with r_lsi; last slot:
+        undefined), ang_hist uint64 [ang_bins + 1] (cos of the O-O-O angles between neighbours
+        inside r_ang over [-1, 1]; last slot: not finite), zeta_hist uint64 [zeta_bins + 1] (zeta
+        over [zeta_lo, zeta_hi] with local_order's bonds of (r_hb, theta_deg); last slot: undefined)
+        -- each [R, ...] with per_replica -- flagged uint64 [R] (molecules with more than 64
+        neighbours inside r_list: in no histogram) and sums [R, 4] (sum of the replica's defined
+        LSI, their number, sum of its defined zeta, their number).  details=True adds count int32
+        [R, N] (listed neighbours, -1 where flagged), nbr int32 [R, N, 16] (the nearest 16 by rank,
+        then -1), lsi and zeta [R, N] (NaN where undefined).  `out`: a dict of arrays under those
+        names to overwrite instead (each of its shape and dtype, contiguous)."""
+        R, N = self.R, self.n_mol
+        nk, nr, nl, na, nz = (max(int(v), 0) for v in (n_rank, r_bins, lsi_bins, ang_bins, zeta_bins))
+        lead = (R,) if per_replica else ()
+        # (sizes the library refuses still get arrays to leave alone)
+        spec = {"rank_hist": (lead + (nk, nr + 1), np.uint64), "lsi_hist": (lead + (nl + 1,), np.uint64),
+                "ang_hist": (lead + (na + 1,), np.uint64), "zeta_hist": (lead + (nz + 1,), np.uint64),
+                "flagged": ((R,), np.uint64), "sums": ((R, 4), np.float64)}
+        if details:
+            spec.update(count=((R, N), np.int32), nbr=((R, N, 16), np.int32), lsi=((R, N), np.float64),
+                        zeta=((R, N), np.float64))
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_shell_order(
+            self._h, float(r_list), float(r_lsi), float(r_ang), float(r_hb),
+            float(np.cos(np.deg2rad(float(theta_deg)))), int(n_rank), int(r_bins), int(lsi_bins), float(lsi_max),
+            int(ang_bins), int(zeta_bins), float(zeta_lo), float(zeta_hi), int(bool(per_replica)),
+            ptr("rank_hist", C.c_uint64), ptr("lsi_hist", C.c_uint64), ptr("ang_hist", C.c_uint64),
+            ptr("zeta_hist", C.c_uint64), ptr("flagged", C.c_uint64), ptr("sums", C.c_double),
+            ptr("count", C.c_int32), ptr("nbr", C.c_int32), ptr("lsi", C.c_double), ptr("zeta", C.c_double)))
+        return res
+
     def hbond_network(self, r_hb=(3.5,), theta_deg=(30.0,), min_bonds=(0,), per_replica=False, details=False,
                       out=None):
         """mmc_batch_hbond_network: the hydrogen-bond graph of every replica under K = 1..8 criteria

@@ -916,6 +916,47 @@ function local_order(b::Batch; q_bins::Integer = 400, r_hb::Float64 = 3.5, theta
     return hb_hist, q_hist, q_sum
 end
 
+# ---- shell order (include/mmc_hip.h, mmc_batch_shell_order) ----------------------------------------
+"""
+    shell_order(b; r_list = 6.0, r_lsi = 3.7, r_ang = 3.3, r_hb = 3.5, theta_deg = 30.0, n_rank = 8,
+                r_bins = 300, lsi_bins = 200, lsi_max = 0.4, ang_bins = 180, zeta_bins = 200,
+                zeta_lo = -1.5, zeta_hi = 2.5, per_replica = false)
+
+Every molecule's O-O neighbours inside `r_list` sorted by distance (slot 1 = O, slots 2 and 3 = H), and
+from that list, in one read-only pass: `rank_hist` `(r_bins + 1, n_rank)` UInt64, column k the distance
+to the k-th neighbour in bins of `r_list / r_bins` (last row: fewer than k listed); `lsi_hist`
+`lsi_bins + 1` counts of the local structure index over [0, `lsi_max`]; `ang_hist` `ang_bins + 1`
+counts of the cosine of the O-O-O angles between neighbours inside `r_ang` over [-1, 1]; `zeta_hist`
+`zeta_bins + 1` counts of zeta over [`zeta_lo`, `zeta_hi`] with `local_order`'s bonds; the last entry
+of each is "undefined" -- all with a trailing dimension R with `per_replica`.  Returns
+`(rank_hist, lsi_hist, ang_hist, zeta_hist, flagged, sums)`: `flagged` the molecules per replica with
+more than 64 neighbours inside `r_list` (in no histogram), `sums` `(4, R)`: the sum of the replica's
+defined LSI, their number, the sum of its defined zeta, their number.
+"""
+function shell_order(b::Batch; r_list::Float64 = 6.0, r_lsi::Float64 = 3.7, r_ang::Float64 = 3.3,
+                     r_hb::Float64 = 3.5, theta_deg::Float64 = 30.0, n_rank::Integer = 8, r_bins::Integer = 300,
+                     lsi_bins::Integer = 200, lsi_max::Float64 = 0.4, ang_bins::Integer = 180,
+                     zeta_bins::Integer = 200, zeta_lo::Float64 = -1.5, zeta_hi::Float64 = 2.5,
+                     per_replica::Bool = false)
+    1 <= n_rank <= 16 || error("n_rank must be in 1..16")
+    all(1 <= n <= 1024 for n in (r_bins, lsi_bins, ang_bins, zeta_bins)) || error("bin counts must be in 1..1024")
+    tail = per_replica ? (b.n_replicas,) : ()
+    rank_hist = zeros(UInt64, r_bins + 1, n_rank, tail...)
+    lsi_hist = zeros(UInt64, lsi_bins + 1, tail...)
+    ang_hist = zeros(UInt64, ang_bins + 1, tail...)
+    zeta_hist = zeros(UInt64, zeta_bins + 1, tail...)
+    flagged = zeros(UInt64, b.n_replicas)
+    sums = zeros(Float64, 4, b.n_replicas)
+    check(ccall((:mmc_batch_shell_order, libmmc), Int32,
+                (Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Int32, Int32, Int32, Float64, Int32, Int32,
+                 Float64, Float64, Int32, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64},
+                 Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                b.h, r_list, r_lsi, r_ang, r_hb, cosd(theta_deg), n_rank, r_bins, lsi_bins, lsi_max, ang_bins,
+                zeta_bins, zeta_lo, zeta_hi, per_replica ? 1 : 0, rank_hist, lsi_hist, ang_hist, zeta_hist, flagged,
+                sums, C_NULL, C_NULL, C_NULL, C_NULL))
+    return rank_hist, lsi_hist, ang_hist, zeta_hist, flagged, sums
+end
+
 # ---- hydrogen-bond network (include/mmc_hip.h, mmc_batch_hbond_network) -----------------------------
 """
     hbond_network(b; r_hb = [3.5], theta_deg = [30.0], min_bonds = [0], per_replica = false)

@@ -315,8 +315,91 @@ def normalize_q_hist(q_hist):
     return centres, h / (h.sum(-1, keepdims=True) * dq)
 
 
+# ---- ranked neighbours, LSI, zeta, O-O-O angles (include/mmc_hip.h, "Shell order") -----------------
+def _density(hist, lo, hi, what):
+    """(centres, density, fraction in the last slot) of counts [..., bins + 1] over [lo, hi]."""
+    h = np.asarray(hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] < 2:
+        raise ValueError(f"{what} must be [..., bins + 1]")
+    nb = h.shape[-1] - 1
+    dx = (float(hi) - float(lo)) / nb
+    centres = float(lo) + (np.arange(nb) + 0.5) * dx
+    inside = h[..., :nb]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return centres, inside / (inside.sum(-1, keepdims=True) * dx), h[..., nb] / h.sum(-1)
+
+
+def neighbour_distance_distributions(rank_hist, r_list):
+    """(r, p, beyond) from mmc_batch_shell_order's rank_hist ([..., n_rank, r_bins + 1]): r the bin
+    centres, p[..., k - 1, :] the density of the distance to the k-th neighbour over the molecules
+    that have one inside r_list (each row integrates to 1; NaN where none has), beyond[..., k - 1]
+    the fraction of the molecules whose k-th neighbour is not inside r_list.  Row 5 is the d5
+    distribution; the rows times (1 - beyond), summed over all ranks, are 4 pi r^2 rho g_OO(r)."""
+    if np.ndim(rank_hist) < 2:
+        raise ValueError("rank_hist must be [..., n_rank, r_bins + 1]")
+    return _density(rank_hist, 0.0, r_list, "rank_hist")
+
+
+def lsi_distribution(lsi_hist, lsi_max):
+    """(I, p, undefined) from lsi_hist [..., lsi_bins + 1]: the bin centres over [0, lsi_max], the
+    density of the local structure index over the molecules where it is defined (integrates to 1;
+    the last bin also holds everything at or above lsi_max), and the fraction where it is not."""
+    return _density(lsi_hist, 0.0, lsi_max, "lsi_hist")
+
+
+def zeta_distribution(zeta_hist, lo, hi):
+    """(zeta, p, undefined) from zeta_hist [..., zeta_bins + 1]: the bin centres over [lo, hi], the
+    density of zeta over the molecules where it is defined (integrates to 1; the end bins also hold
+    what lies outside), and the fraction where it is not."""
+    return _density(zeta_hist, lo, hi, "zeta_hist")
+
+
+def ooo_angle_distribution(ang_hist):
+    """(theta, p, mean_cos) from ang_hist [..., ang_bins + 1], counts over equal bins of cos(theta)
+    on [-1, 1] (last slot: not finite, left out): bin k covers theta from acos(c_k + dc) to
+    acos(c_k) degrees, theta[k] is the middle of that span and p[..., k] the fraction of the angles
+    in the bin over the span's width -- the density per degree, P(cos) sin(theta) pi / 180 averaged
+    over the bin, integrating to 1 over the spans.  Both are returned in rising theta.  mean_cos
+    [...] is <cos(theta)> from the bin centres."""
+    h = np.asarray(ang_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] < 2:
+        raise ValueError("ang_hist must be [..., ang_bins + 1]")
+    nb = h.shape[-1] - 1
+    edges = np.degrees(np.arccos(np.clip(-1.0 + np.arange(nb + 1) * (2.0 / nb), -1.0, 1.0)))   # falling: 180 .. 0
+    cos_c = -1.0 + (np.arange(nb) + 0.5) * (2.0 / nb)
+    inside = h[..., :nb]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = inside / inside.sum(-1, keepdims=True)
+        mean_cos = (frac * cos_c).sum(-1)
+    theta = 0.5 * (edges[:-1] + edges[1:])
+    return theta[::-1], (frac / (edges[:-1] - edges[1:]))[..., ::-1], mean_cos
+
+
+def _shell_sums(sums):
+    s = np.asarray(sums, dtype=float)
+    if s.shape[-1] != 4:
+        raise ValueError("sums must be [..., 4]")
+    return s
+
+
+def lsi_mean(sums):
+    """<I> from mmc_batch_shell_order's sums ([..., 4]: sum of the defined I, their number, the same
+    of zeta): per replica for [R, 4] (NaN where none is defined); pass sums.sum(0) for the mean over
+    all molecules."""
+    s = _shell_sums(sums)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s[..., 0] / s[..., 1]
+
+
+def zeta_mean(sums):
+    """<zeta> from mmc_batch_shell_order's sums, as lsi_mean."""
+    s = _shell_sums(sums)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s[..., 2] / s[..., 3]
+
+
 # ---- hydrogen-bond network (include/mmc_hip.h, "Hydrogen-bond network") -----------------------------
-NET_STATS = 8   # bonds, sites, clusters, largest, sum of s^2, wrap mask, largest wrapping, flagged
+NET_STATS = 8  # bonds, sites, clusters, largest, sum of s^2, wrap mask, largest wrapping, flagged
 NET_MAX_DEG = 16
 
 
