@@ -1382,6 +1382,104 @@ int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double r_lsi, double 
     uint64_t *rank_hist, uint64_t *lsi_hist, uint64_t *ang_hist, uint64_t *zeta_hist, uint64_t *flagged,
     double *sums, int32_t *count_out, int32_t *nbr_out, double *lsi_out, double *zeta_out);
 
+/* ---- Bond order: Steinhardt q_l, bond correlations, solid-like molecules and their clusters -----
+ * Is there ice in the box, how much, and how large is the largest crystalline nucleus: Steinhardt's
+ * bond-orientational order q_l (Steinhardt, Nelson and Ronchetti, Phys. Rev. B 28, 784, 1983), the
+ * neighbour-averaged qbar_l (Lechner and Dellago, J. Chem. Phys. 129, 114707, 2008), the bond
+ * correlations c_ij that ten Wolde, Ruiz-Montero and Frenkel (J. Chem. Phys. 104, 9932, 1996) and
+ * CHILL+ (Nguyen and Molinero, J. Phys. Chem. B 119, 9369, 2015) classify molecules with, and the
+ * clusters of solid-like molecules, for every molecule of every replica in one read-only pass over
+ * the O-O neighbours (slot 0 of a molecule is "O").  The reference has no such analysis; the
+ * arithmetic is defined here, operation by operation, and restated in numpy by
+ * tests/bond_order_ref.py.  + - x / sqrt floor are correctly rounded fp64 and nothing is fused, so
+ * every output is reproducible bit for bit.  No trigonometric function is used.
+ *   d(x, y) is vector1D as in "Local order", per component, with the replica's own box.  Every r^2
+ *   is (x x + y y) + z z.
+ *   - Neighbours.  For molecule i: d_ij = d(O_i, O_j), r2_ij its r^2.  In range: every j != i with
+ *     r2_ij < r_nb r_nb (the square formed by the host), ascending under the key (bit pattern of
+ *     r2_ij, then j) -- the list of "Shell order" with r_list = r_nb.  count_i is their number and
+ *     nb(i) the first n_i = min(count_i, n_nb) of them, j_1 .. j_n in that order ("rank order").  A
+ *     molecule with count_i > n_nb is counted in TRUNCATED and processed like any other.  A molecule
+ *     with count_i > MMC_SHELL_CAP = 64 is FLAGGED: it has no nb(i), no q_lm and no bonds of its
+ *     own, and is not counted in truncated.
+ *   - Bond vectors.  rho_k = sqrt(r2_k) and u_k = (d_x / rho_k, d_y / rho_k, d_z / rho_k) of
+ *     neighbour k.  A molecule that is not flagged and has n_i = 0 or some rho_k = 0 is UNDEFINED;
+ *     every other molecule that is not flagged is DEFINED.
+ *   - Constants, formed once by the host in fp64, l in {3, 4, 6}: PI = 3.141592653589793;
+ *     F_m = (l - m + 1)(l - m + 2) ... (l + m), an exact integer (F_0 = 1);
+ *     N_m = sqrt(((2 l + 1) / (4 PI)) / F_m);  K = (4 PI) / (2 l + 1).
+ *   - Harmonics of u = (x, y, z), m = 0 .. l, without the Condon-Shortley sign (it cancels in every
+ *     output; negative m follow from conjugation and enter through the weights w_m):
+ *       c_0 = 1, s_0 = 0;  c_m = x c_(m-1) - y s_(m-1);  s_m = x s_(m-1) + y c_(m-1)
+ *       (the real and imaginary part of (x + i y)^m; each two products, then one sum);
+ *       T_m^m = 1 3 5 ... (2 m - 1), exact (T_0^0 = 1);  T_(m+1)^m = ((2 m + 1) z) T_m^m;
+ *       T_n^m = ((((2 n - 1) z) T_(n-1)^m) - ((n + m - 1) T_(n-2)^m)) / (n - m), n = m + 2 .. l
+ *       (the m-th derivative of the Legendre polynomial P_n);
+ *       A = N_m T_l^m;  Re Y_lm = A c_m;  Im Y_lm = A s_m.
+ *   - Per molecule.  Re q_lm(i) = (Re Y_lm(u_1) + Re Y_lm(u_2) + ...) / n_i, the sum one term at a
+ *     time in rank order, n_i as a double; Im q_lm likewise.  t_m = Re q_lm Re q_lm + Im q_lm Im q_lm;
+ *     Q_i = t_0 + 2 t_1 + 2 t_2 + ... in rising m (w_0 = 1, w_m = 2);  q_l(i) = sqrt(K Q_i).
+ *   - Per directed bond (i, j in nb(i)).  t_m = Re q_lm(i) Re q_lm(j) + Im q_lm(i) Im q_lm(j);
+ *     D = t_0 + 2 t_1 + ... in rising m;  c_ij = D / (sqrt(Q_i) sqrt(Q_j)).  The bond is undefined
+ *     when i or j is not defined, when Q_i or Q_j is 0, or when c_ij is not finite.
+ *   - Averaged.  Re qbar_lm(i) = (Re q_lm(i) + Re q_lm(j_1) + Re q_lm(j_2) + ...) / (n_i + 1), in
+ *     rank order; Im likewise; Qbar_i and qbar_l(i) from qbar_lm as Q_i and q_l(i) from q_lm.
+ *     qbar_l(i) is undefined unless i and every molecule of nb(i) are defined.
+ *   - Windows.  A defined bond is in A when a_lo <= c_ij <= a_hi and in B when b_lo <= c_ij <= b_hi
+ *     (it may be in both); a_lo and b_lo may be -inf, a_hi and b_hi +inf.  n_A(i) and n_B(i) count
+ *     the bonds of i in each.  CHILL+: l = 3, n_nb = 4, r_nb = 3.5 A, A = staggered (-inf, -0.8],
+ *     B = eclipsed [-0.35, 0.25].
+ *   - Solid-like.  i is defined, n_A(i) >= min_a and n_A(i) + n_B(i) >= min_ab.  (3, 4) with the
+ *     CHILL+ windows selects cubic and hexagonal ice; a ten Wolde-Frenkel criterion is l = 6,
+ *     n_nb = 16, A = [0.5, 1], min_a = 7, min_ab = 0.)
+ *   - Clusters.  An undirected edge joins i and j when both are solid-like and j is in nb(i) or i in
+ *     nb(j); clusters are the connected components, a solid-like molecule without edges a cluster
+ *     of 1.  The label of a solid-like molecule is the lowest index of its cluster.
+ *   - Bins: (int)floor(v scale) clamped to 0 .. bins - 1, the clamps made on the double, as "Shell
+ *     order": q_l and qbar_l with v = q, scale = (double)q_bins over [0, 1]; c_ij with v = c + 1.0,
+ *     scale = c_bins / 2.0 over [-1, 1].
+ *   - Outputs, all overwritten, each may be NULL (but not all of them) and a NULL one costs nothing:
+ *     a call that asks for q_hist, q_out and nbr_out only runs the neighbour phase alone, one
+ *     without size_hist, stats and label_out has no cluster phase.  The histograms are [R][...] with
+ *     per_replica.
+ *     q_hist, qbar_hist uint64 [q_bins + 1]: molecules; last slot: q_l (qbar_l) undefined, flagged
+ *       molecules included.
+ *     c_hist uint64 [c_bins + 1]: directed bonds (i, j in nb(i)); last slot: undefined bonds.
+ *     ab_hist uint64 [17][17]: the defined molecules at [n_A][n_B].
+ *     size_hist uint64 [N + 1]: entry s = the number of clusters of s molecules.
+ *     stats int64 [R][MMC_BO_STATS]: 0 defined, 1 undefined, 2 flagged, 3 truncated, 4 solid-like
+ *       molecules, 5 clusters, 6 the largest cluster, 7 the sum of s^2 over the clusters.
+ *     sums double [R][4] = (sum of the replica's defined q_l, their number, sum of its defined
+ *       qbar_l, their number), in the order of "Local order"'s q_sum: bitwise reproducible.
+ *     q_out, qbar_out double [R][N], NaN where undefined.  nbr_out int32 [R][N][MMC_BO_MAX_NB]:
+ *       nb(i) by rank, then -1.  ab_out uint8 [R][N][2] = (n_A, n_B).  label_out int32 [R][N], -1
+ *       where not solid-like.
+ *     Nothing depends on the grid, on options "wave_wgs", "local_stage" and "bond_chunk", or on any
+ *     order of lanes, waves or atomics.
+ *   - Scratch.  q_lm travels between the phases in device scratch (197 bytes per molecule), so the
+ *     replicas are worked off in chunks under a fixed budget (256 MiB), the phases of a chunk
+ *     launched one after the other on the batch's stream.  Option "bond_chunk" = n > 0 sets the
+ *     replicas per chunk (for tests of a ragged last chunk); 0 = by the budget.
+ *   - Use (observables.py): steinhardt_distribution, bond_correlation_distribution, solid_fraction,
+ *     largest_nucleus, nucleus_size_distribution, chill_plus_classes.
+ * Both box modes and either Coulomb style, records or arrays: the call reads coordinates only, and is
+ * read-only exactly as mmc_batch_local_order is, with its preconditions (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: l not 3, 4 or 6; n_nb outside 1..MMC_BO_MAX_NB; r_nb not
+ * finite or <= 0; q_bins or c_bins outside 1..MMC_BO_MAX_BINS; a window bound that is NaN; every
+ * output NULL.  Checked with the batch: r_nb above half of the smallest box.  Then the state; then
+ * MMC_ERR_UNSUPPORTED: fewer than 2 molecules, or more than MMC_BO_MAX_MOL (the labels and sizes of a
+ * replica's clusters, 8 bytes per molecule, stay in one workgroup's LDS).  On any error every output
+ * is left untouched. */
+#define MMC_BO_MAX_NB   16
+#define MMC_BO_MAX_BINS 4096
+#define MMC_BO_STATS    8
+#define MMC_BO_MAX_MOL  8000
+int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb, int32_t n_nb, double a_lo, double a_hi,
+    double b_lo, double b_hi, int32_t min_a, int32_t min_ab, int32_t q_bins, int32_t c_bins,
+    int32_t per_replica, uint64_t *q_hist, uint64_t *qbar_hist, uint64_t *c_hist, uint64_t *ab_hist,
+    uint64_t *size_hist, int64_t *stats, double *sums, double *q_out, double *qbar_out,
+    int32_t *nbr_out, uint8_t *ab_out, int32_t *label_out);
+
 /* ---- Cavities and occupancy: p_n(R), its moments and the cavity-size distribution ---------------
  * How many sites lie within R of a random point of the liquid, for up to eight radii at once, and
  * how far the nearest site is: the occupancy distribution p_n(R) of scaled-particle and

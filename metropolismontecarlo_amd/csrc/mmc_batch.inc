@@ -104,6 +104,7 @@ struct mmc_batch {
                                 // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
     int local_stage = 1;        // mmc_batch_local_order and mmc_batch_cavity copy a replica's site positions to LDS
                                 // where they fit (option "local_stage" = 0: never, the path of systems too large for it)
+    int bond_chunk = 0;         // mmc_batch_bond_order: replicas per chunk of scratch records (0: by its budget)
 
     const MoveRec *dev_moves(int which) const
     {
@@ -332,6 +333,9 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
     } else if (!strcmp(key, "local_stage")) {
         MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "local_stage must be 1 (where the positions fit) or 0 (never)");
         b->local_stage = (int)value;
+    } else if (!strcmp(key, "bond_chunk")) {
+        MMC_REQUIRE(value >= 0 && value <= (1 << 30), MMC_ERR_ARG, "bond_chunk must be 0 (by the scratch budget) or the replicas per chunk");
+        b->bond_chunk = (int)value;
     } else if (!strcmp(key, "trace_steps")) {
         MMC_REQUIRE(value >= 0 && value * b->sys.R <= (1LL << 26), MMC_ERR_ARG, "trace_steps out of range");
         b->trace_steps = value;

@@ -6,7 +6,7 @@
 //   the pair passes over the i < j triangle: mmc_batch_rdf_sites, _orient_corr and _pair_energy
 //   (tile_plan, tile_waves; the kernels' shared part is mmc_tiles.hpp), and mmc_batch_sdf on the
 //   same tiles with a grid of its own per workgroup;
-//   and mmc_batch_dipoles, _structure_factor, _local_order, _shell_order, _hbond_network,
+//   and mmc_batch_dipoles, _structure_factor, _local_order, _shell_order, _bond_order, _hbond_network,
 //   _cavity / _cavity_at, _volume_perturb.
 // Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels" and
 // "Tile passes".

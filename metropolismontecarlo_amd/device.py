@@ -1008,6 +1008,53 @@ class Batch:
             ptr("count", C.c_int32), ptr("nbr", C.c_int32), ptr("lsi", C.c_double), ptr("zeta", C.c_double)))
         return res
 
+    def bond_order(self, l=3, r_nb=3.5, n_nb=4, a=(-np.inf, -0.8), b=(-0.35, 0.25), min_a=3, min_ab=4, q_bins=200,
+                   c_bins=200, per_replica=False, details=False, out=None):
+        """mmc_batch_bond_order: Steinhardt's q_l (l = 3, 4 or 6) of every molecule over its n_nb
+        nearest O-O neighbours inside r_nb, the neighbour-averaged qbar_l, the bond correlations
+        c_ij = q_l(i) . q_l(j)* / (|q_l(i)| |q_l(j)|), the bonds in the closed windows a and b
+        (defaults: CHILL+'s staggered (-inf, -0.8] and eclipsed [-0.35, 0.25]) and the clusters of
+        solid-like molecules (defined, at least min_a bonds in a and min_ab in a and b together),
+        read-only.  Returns a dict: q_hist and qbar_hist uint64 [q_bins + 1] over [0, 1] and c_hist
+        uint64 [c_bins + 1] over [-1, 1] per directed bond (last slot: undefined), ab_hist uint64
+        [17, 17] (defined molecules at [n_a, n_b]), size_hist uint64 [N + 1] (solid clusters by
+        size) -- each [R, ...] with per_replica -- stats int64 [R, 8] (defined, undefined, flagged,
+        truncated, solid molecules, solid clusters, the largest, the sum of s^2) and sums [R, 4] (sum
+        of the replica's defined q_l, their number, sum of its defined qbar_l, their number).
+        details=True adds q and qbar [R, N] (NaN where undefined), nbr int32 [R, N, 16] (the
+        neighbours used, by rank, then -1), ab uint8 [R, N, 2] (n_a, n_b) and label int32 [R, N] (the
+        lowest index of the molecule's cluster, -1 if not solid).  `out`: a dict of arrays under
+        those names to overwrite instead (each of its shape and dtype, contiguous)."""
+        R, N = self.R, self.n_mol
+        nq, nc = (max(int(v), 0) for v in (q_bins, c_bins))
+        lead = (R,) if per_replica else ()
+        # (sizes the library refuses still get arrays to leave alone)
+        spec = {"q_hist": (lead + (nq + 1,), np.uint64), "qbar_hist": (lead + (nq + 1,), np.uint64),
+                "c_hist": (lead + (nc + 1,), np.uint64), "ab_hist": (lead + (17, 17), np.uint64),
+                "size_hist": (lead + (N + 1,), np.uint64), "stats": ((R, 8), np.int64), "sums": ((R, 4), np.float64)}
+        if details:
+            spec.update(q=((R, N), np.float64), qbar=((R, N), np.float64), nbr=((R, N, 16), np.int32),
+                        ab=((R, N, 2), np.uint8), label=((R, N), np.int32))
+        res = {}
+        for k, (shape, dt) in spec.items():
+            arr = None if out is None else out.get(k)
+            if arr is None:
+                arr = np.zeros(shape, dtype=dt)
+            elif not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.shape == shape and arr.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = arr
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_bond_order(
+            self._h, int(l), float(r_nb), int(n_nb), float(a[0]), float(a[1]), float(b[0]), float(b[1]), int(min_a),
+            int(min_ab), int(q_bins), int(c_bins), int(bool(per_replica)),
+            ptr("q_hist", C.c_uint64), ptr("qbar_hist", C.c_uint64), ptr("c_hist", C.c_uint64),
+            ptr("ab_hist", C.c_uint64), ptr("size_hist", C.c_uint64), ptr("stats", C.c_int64), ptr("sums", C.c_double),
+            ptr("q", C.c_double), ptr("qbar", C.c_double), ptr("nbr", C.c_int32), ptr("ab", C.c_uint8),
+            ptr("label", C.c_int32)))
+        return res
+
     def hbond_network(self, r_hb=(3.5,), theta_deg=(30.0,), min_bonds=(0,), per_replica=False, details=False,
                       out=None):
         """mmc_batch_hbond_network: the hydrogen-bond graph of every replica under K = 1..8 criteria

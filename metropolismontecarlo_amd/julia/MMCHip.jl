@@ -957,6 +957,47 @@ function shell_order(b::Batch; r_list::Float64 = 6.0, r_lsi::Float64 = 3.7, r_an
     return rank_hist, lsi_hist, ang_hist, zeta_hist, flagged, sums
 end
 
+# ---- bond order (include/mmc_hip.h, mmc_batch_bond_order) -------------------------------------------
+"""
+    bond_order(b; l = 3, r_nb = 3.5, n_nb = 4, a = (-Inf, -0.8), b_win = (-0.35, 0.25), min_a = 3,
+               min_ab = 4, q_bins = 200, c_bins = 200, per_replica = false)
+
+Steinhardt's q_l of every molecule over its `n_nb` nearest O-O neighbours inside `r_nb` (l = 3, 4 or
+6), the neighbour-averaged qbar_l, the bond correlations c_ij, the bonds in the closed windows `a` and
+`b_win` (defaults: CHILL+'s staggered and eclipsed bonds), and the clusters of solid-like molecules (at
+least `min_a` bonds in `a` and `min_ab` in both), in one read-only pass.  Returns `(q_hist, qbar_hist,
+c_hist, ab_hist, size_hist, stats, sums)`: `q_hist`, `qbar_hist` `q_bins + 1` UInt64 over [0, 1] and
+`c_hist` `c_bins + 1` over [-1, 1] (last entry: undefined), `ab_hist` `(17, 17)` with the molecules at
+`[n_B + 1, n_A + 1]`, `size_hist` `N + 1` clusters by size -- all with a trailing dimension R with
+`per_replica` -- `stats` `(8, R)` Int64 (defined, undefined, flagged, truncated, solid-like molecules,
+clusters, the largest cluster, the sum of s^2) and `sums` `(4, R)`: the sum of the replica's defined
+q_l, their number, the sum of its defined qbar_l, their number.
+"""
+function bond_order(b::Batch; l::Integer = 3, r_nb::Float64 = 3.5, n_nb::Integer = 4,
+                    a::Tuple{Float64,Float64} = (-Inf, -0.8), b_win::Tuple{Float64,Float64} = (-0.35, 0.25),
+                    min_a::Integer = 3, min_ab::Integer = 4, q_bins::Integer = 200, c_bins::Integer = 200,
+                    per_replica::Bool = false)
+    l in (3, 4, 6) || error("l must be 3, 4 or 6")
+    1 <= n_nb <= 16 || error("n_nb must be in 1..16")
+    all(1 <= n <= 4096 for n in (q_bins, c_bins)) || error("bin counts must be in 1..4096")
+    tail = per_replica ? (b.n_replicas,) : ()
+    q_hist = zeros(UInt64, q_bins + 1, tail...)
+    qbar_hist = zeros(UInt64, q_bins + 1, tail...)
+    c_hist = zeros(UInt64, c_bins + 1, tail...)
+    ab_hist = zeros(UInt64, 17, 17, tail...)
+    size_hist = zeros(UInt64, b.n_mol + 1, tail...)
+    stats = zeros(Int64, 8, b.n_replicas)
+    sums = zeros(Float64, 4, b.n_replicas)
+    check(ccall((:mmc_batch_bond_order, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Float64, Int32, Float64, Float64, Float64, Float64, Int32, Int32, Int32, Int32,
+                 Int32, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}),
+                b.h, l, r_nb, n_nb, a[1], a[2], b_win[1], b_win[2], min_a, min_ab, q_bins, c_bins,
+                per_replica ? 1 : 0, q_hist, qbar_hist, c_hist, ab_hist, size_hist, stats, sums,
+                C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
+    return q_hist, qbar_hist, c_hist, ab_hist, size_hist, stats, sums
+end
+
 # ---- hydrogen-bond network (include/mmc_hip.h, mmc_batch_hbond_network) -----------------------------
 """
     hbond_network(b; r_hb = [3.5], theta_deg = [30.0], min_bonds = [0], per_replica = false)

@@ -398,6 +398,90 @@ def zeta_mean(sums):
         return s[..., 2] / s[..., 3]
 
 
+# ---- bond order (include/mmc_hip.h, "Bond order") ---------------------------------------------------
+BO_STATS = 8  # defined, undefined, flagged, truncated, solid molecules, solid clusters, largest, sum of s^2
+CHILL_CLASSES = ("cubic", "hexagonal", "interfacial_ice", "clathrate", "interfacial_clathrate", "liquid")
+
+
+def _bo_stats(stats):
+    st = np.asarray(stats)
+    if st.ndim < 1 or st.shape[-1] != BO_STATS:
+        raise ValueError("stats must be [..., 8]")
+    return st
+
+
+def steinhardt_distribution(q_hist):
+    """(q, p, undefined) from mmc_batch_bond_order's q_hist or qbar_hist ([..., q_bins + 1]): the
+    bin centres over [0, 1], the density of q_l (qbar_l) over the molecules where it is defined
+    (integrates to 1) and the fraction of the molecules where it is not."""
+    return _density(q_hist, 0.0, 1.0, "q_hist")
+
+
+def bond_correlation_distribution(c_hist):
+    """(c, p, undefined) from c_hist [..., c_bins + 1]: the bin centres over [-1, 1], the density of
+    c_ij over the defined directed bonds (integrates to 1) and the fraction of the bonds that are
+    undefined."""
+    return _density(c_hist, -1.0, 1.0, "c_hist")
+
+
+def solid_fraction(stats):
+    """The solid-like molecules over all molecules (defined, undefined and flagged), from stats
+    [..., 8]: per replica for [R, 8]; pass stats.sum(0) for the whole batch."""
+    st = _bo_stats(stats).astype(float)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return st[..., 4] / (st[..., 0] + st[..., 1] + st[..., 2])
+
+
+def largest_nucleus(stats):
+    """The size of the largest cluster of solid-like molecules, per replica, from stats [R, 8]: the
+    reaction coordinate of a nucleation study (0 where nothing is solid-like)."""
+    return _bo_stats(stats)[..., 6].copy()
+
+
+def nucleus_size_distribution(size_hist):
+    """(n_s, w_s) from size_hist ([..., N + 1], solid clusters by size): n_s the counts as floats
+    and w_s = s n_s / sum s n_s, the fraction of the solid-like molecules that sit in clusters of
+    size s (NaN where there are none)."""
+    h = np.asarray(size_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] < 2:
+        raise ValueError("size_hist must be [..., N + 1]")
+    w = h * np.arange(h.shape[-1])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h, w / w.sum(-1, keepdims=True)
+
+
+def chill_plus_classes(details):
+    """Per-replica counts of the CHILL+ classes from a Batch.bond_order(details=True) result taken
+    with the defaults (l = 3, n_nb = 4, a = staggered, b = eclipsed): int64 [R, 6] in the order of
+    CHILL_CLASSES -- cubic, hexagonal, interfacial ice, clathrate, interfacial clathrate, liquid.
+
+    This project's definition, after Nguyen and Molinero, J. Phys. Chem. B 119, 9369 (2015); compare
+    with the paper before relying on a class.  With S = ab[..., 0] the staggered and E = ab[..., 1]
+    the eclipsed bonds of a molecule's (up to) four, tested in this order, the first that holds:
+      cubic                  S = 4
+      hexagonal              S = 3 and E = 1
+      clathrate              E = 4
+      interfacial clathrate  E = 3
+      interfacial ice        S = 2 and some neighbour (nbr) has S > 2; or S = 3 and E = 0 and some
+                             neighbour has S >= 2
+      liquid                 everything else, molecules with undefined q_lm included (S = E = 0)"""
+    ab, nbr = np.asarray(details["ab"]), np.asarray(details["nbr"])
+    if ab.ndim != 3 or ab.shape[-1] != 2 or nbr.shape[:2] != ab.shape[:2]:
+        raise ValueError("details must hold ab [R, N, 2] and nbr [R, N, 16]")
+    S, E = ab[..., 0].astype(np.int64), ab[..., 1].astype(np.int64)
+    R = ab.shape[0]
+    s_nb = np.where(nbr >= 0, np.take_along_axis(S[:, :, None], np.maximum(nbr, 0).reshape(R, -1, 1), axis=1)
+                    .reshape(nbr.shape), -1)                      # S of every neighbour, -1 where none
+    best = s_nb.max(-1)
+    cubic = S == 4
+    hexagonal = (S == 3) & (E == 1)
+    clathrate = ~cubic & ~hexagonal & (E == 4)
+    iclath = ~cubic & ~hexagonal & (E == 3)
+    iice = ~cubic & ~hexagonal & ~clathrate & ~iclath & (((S == 2) & (best > 2)) | ((S == 3) & (E == 0) & (best >= 2)))
+    liquid = ~(cubic | hexagonal | clathrate | iclath | iice)
+    return np.stack([x.sum(1) for x in (cubic, hexagonal, iice, clathrate, iclath, liquid)], axis=1).astype(np.int64)
+
+
 # ---- hydrogen-bond network (include/mmc_hip.h, "Hydrogen-bond network") -----------------------------
 NET_STATS = 8  # bonds, sites, clusters, largest, sum of s^2, wrap mask, largest wrapping, flagged
 NET_MAX_DEG = 16
