@@ -1312,6 +1312,79 @@ int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const double *r_hb
                                 const int32_t *min_bonds, int32_t per_replica, uint64_t *size_hist,
                                 uint64_t *deg_hist, int64_t *stats, int32_t *label_out, int32_t *nbr_out);
 
+/* ---- Hydrogen-bond rings: shortest-path ring statistics -------------------------------------------
+ * The topology of the hydrogen-bond network beyond its connectivity: the closed rings of bonds of
+ * every replica, by size.  Ice Ih and Ic are all six-rings; the liquid shows a mix of 5, 6 and 7 that
+ * shifts on supercooling.  Counted are the shortest-path rings of Franzblau (Phys. Rev. B 44, 4925,
+ * 1991), as used for water by Matsumoto, Baba and Ohmine (J. Chem. Phys. 127, 134504, 2007).  One bond
+ * criterion (r_hb, cos_hb) per call.  The reference has no such analysis; the definitions are stated
+ * here and restated in numpy by tests/rings_ref.py.  Every result is an integer: nothing is left to a
+ * tolerance.
+ *   - Graph.  Exactly mmc_batch_hbond_network's for the criterion (r_hb, cos_hb): A(i, j) is its
+ *     undirected bond (the same unfused fp64 arithmetic, vector1D images and replica box), D(i, j)
+ *     means "i donates to j through either hydrogen" (A(i, j) = D(i, j) or D(j, i)), and m_ij is the
+ *     bond's integer box vector (m_ji = -m_ij).  deg(i) = the number of j with A(i, j).
+ *   - Flagged.  A replica in which some molecule has deg > MMC_RING_MAX_DEG is flagged: it enters no
+ *     histogram, its stats are 0 except stats[7] = 1, its count_out entries are 65535 (-1 as uint16)
+ *     and its ring_out rows -1.  It is not an error; other replicas are unaffected.  (The cap is below
+ *     the network's 16 because the search grows with deg^(n/2); liquid water at the usual criteria has
+ *     at most 5 or 6 bonds per molecule.)
+ *   - Ring.  A cyclic sequence p_0 .. p_(n-1) of n distinct molecules, 3 <= n <= n_max <=
+ *     MMC_RING_MAX_SIZE, with A(p_k, p_(k+1)) for every k cyclically.  It is a shortest-path ring when
+ *     it has no shortcut: for every two members p_a, p_b the distance in the replica's finite graph
+ *     of N molecules (the fewest bonds of any path, through members or not) equals their distance
+ *     round the ring, min(|a - b|, n - |a - b|).  Each ring counts once, whatever its start and
+ *     direction.  Only shortest-path rings are counted, here called rings.
+ *   - Wrapping.  A ring wraps when the sum of m_(p_k p_(k+1)) round it is not (0, 0, 0): it closes
+ *     through the periodic box and is an artefact of the box size.  Such rings are counted apart (row
+ *     1, stats[2]) and enter nothing else.  The sum does not depend on whether atoms are stored
+ *     inside the box (see "Hydrogen-bond network").
+ *   - Homodromic.  A ring that does not wrap is homodromic when D(p_k, p_(k+1)) holds for every k
+ *     cyclically, or D(p_(k+1), p_k) holds for every k: the donations run round it one way.
+ *   - Canonical form.  The lowest member first, then the smaller of its two ring neighbours, then
+ *     onward round the ring.
+ *   - Outputs, all integers, all overwritten; each may be NULL, but not all three of ring_hist,
+ *     member_hist and stats:
+ *     ring_hist uint64 [3][MMC_RING_MAX_SIZE + 1], [R][3][..] with per_replica: row 0 the rings that
+ *       do not wrap, by size; row 1 the wrapping rings by size; row 2 the homodromic ones among row 0.
+ *       Entries 0, 1, 2 and those above n_max are 0.
+ *     member_hist uint64 [MMC_RING_MAX_SIZE + 1][MMC_RING_MEMBER_BINS], [R][..] with per_replica: row
+ *       n, bin c = the number of molecules that are members of c row-0 rings of size n; row 0 counts
+ *       rings of any size; the last bin means "32 or more".  Rows 1, 2 and those above n_max are 0.
+ *     stats int64 [R][MMC_RING_STATS]: 0 bonds |A|; 1 rings (row 0 summed); 2 wrapping rings; 3
+ *       homodromic rings; 4 molecules in no row-0 ring; 5 the largest number of row-0 rings one
+ *       molecule is a member of; 6 the row-0 rings that did not fit into ring_out (0 without
+ *       ring_out); 7 flagged (0 or 1).
+ *     count_out uint16 [R][N][MMC_RING_MAX_SIZE + 1]: per molecule the number of row-0 rings of each
+ *       size it is a member of; entry 0 their total, entries 1 and 2 zero; saturating at 65535.
+ *     ring_out int32 [R][max_rings][MMC_RING_MAX_SIZE]: the row-0 rings of replica r in canonical
+ *       form, padded with -1; unused rows are -1 throughout.  Rings beyond max_rings are dropped and
+ *       counted in stats[6]; which ones are dropped, and the order of the rows, is the one thing in
+ *       the call that may depend on the launch.  max_rings is ignored when ring_out is NULL.
+ *     Everything else is independent of the grid, of options "wave_wgs" and "ring_chunk" and of any
+ *     order of lanes, waves or atomics.
+ *   - Staging.  With count_out or ring_out the replicas are worked off in launches whose details
+ *     stay under a fixed budget of device memory (256 MiB), one after the other on the batch's
+ *     stream.  Option "ring_chunk" = n > 0 sets the replicas per launch (for tests of a ragged last
+ *     one); 0 = by the budget.
+ *   - Use (observables.py): ring_size_distribution, ring_fractions, homodromic_fraction,
+ *     ring_membership.
+ * Both box modes and either Coulomb style, records or arrays: the call reads coordinates only, and is
+ * read-only exactly as mmc_batch_local_order is, with its preconditions (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: r_hb not finite or <= 0; cos_hb outside (0, 1]; n_max outside
+ * 3..MMC_RING_MAX_SIZE; ring_hist, member_hist and stats all NULL; ring_out with max_rings < 1.
+ * Checked with the batch: r_hb above half of the smallest box.  Then the state; then
+ * MMC_ERR_UNSUPPORTED: fewer than 2 molecules, more than MMC_NET_MAX_MOL, or a device that does not
+ * grant the LDS a replica's graph needs (57 bytes per molecule, and one more per molecule for each
+ * of the workgroup's at least four waves).  On any error every output is left untouched. */
+#define MMC_RING_MAX_SIZE    8
+#define MMC_RING_MAX_DEG     8
+#define MMC_RING_STATS       8
+#define MMC_RING_MEMBER_BINS 33
+int32_t mmc_batch_hbond_rings(mmc_batch *b, double r_hb, double cos_hb, int32_t n_max, int32_t per_replica,
+                              uint64_t *ring_hist, uint64_t *member_hist, int64_t *stats,
+                              uint16_t *count_out, int64_t max_rings, int32_t *ring_out);
+
 /* ---- Shell order: ranked neighbours, LSI, zeta and O-O-O angles of 3-site molecules -----------
  * What lies between the first and the second coordination shell of every molecule of every replica,
  * in one read-only pass: the neighbour-rank decomposition of g_OO (row 5 is the distribution of the

@@ -213,6 +213,8 @@ SIGNATURES = {
                              C.POINTER(C.c_uint8), _i32p],
     "mmc_batch_hbond_network": [_vp, C.c_int32, _dp, _dp, _i32p, C.c_int32, C.POINTER(C.c_uint64),
                                 C.POINTER(C.c_uint64), _i64p, _i32p, _i32p],
+    "mmc_batch_hbond_rings": [_vp, _d, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i64p,
+                              C.POINTER(C.c_uint16), _i64, _i32p],
     "mmc_batch_cavity": [_vp, _i64, C.c_uint64, _i64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,
                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _i32p, _dp, _i32p],
     "mmc_batch_cavity_at": [_vp, _i64, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,

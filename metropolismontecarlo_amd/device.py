@@ -1101,6 +1101,45 @@ class Batch:
             ptr("label", C.c_int32), ptr("nbr", C.c_int32)))
         return res
 
+    def hbond_rings(self, r_hb=3.5, theta_deg=30.0, n_max=8, per_replica=False, details=False, max_rings=0, out=None):
+        """mmc_batch_hbond_rings: the shortest-path rings (Franzblau) of 3 .. n_max <= 8 molecules in
+        the hydrogen-bond graph of every replica under one criterion (hbond_network's bond with r_hb,
+        theta_deg), read-only.  Returns a dict: ring_hist uint64 [3, 9] (by size: the rings that do
+        not wrap the box, those that do, the homodromic ones among the first), member_hist uint64
+        [9, 33] (row n: molecules by the number of n-rings they are in, row 0 by rings of any size,
+        last bin 32 or more) -- each [R, ...] with per_replica -- and stats int64 [R, 8]: bonds,
+        rings, wrapping rings, homodromic rings, molecules in no ring, the most rings one molecule
+        is in, rings that did not fit into `ring`, flagged (some molecule with more than 8 bonds: all
+        else 0).  details=True adds count uint16 [R, N, 9] (per molecule the rings of each size,
+        entry 0 their total; 65535 where flagged) and, with max_rings > 0, ring int32
+        [R, max_rings, 8]: the rings in canonical form (lowest member, the smaller of its two ring
+        neighbours, onward), padded with -1, in no particular order.  `out`: a dict of arrays under
+        those names to overwrite instead (each of its shape and dtype, contiguous)."""
+        R, N = self.R, self.n_mol
+        lead = (R,) if per_replica else ()
+        spec = {"ring_hist": (lead + (3, 9), np.uint64), "member_hist": (lead + (9, 33), np.uint64),
+                "stats": ((R, 8), np.int64)}
+        if details:
+            spec["count"] = ((R, N, 9), np.uint16)
+            if int(max_rings) > 0:
+                spec["ring"] = ((R, int(max_rings), 8), np.int32)
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_hbond_rings(
+            self._h, float(r_hb), float(np.cos(np.deg2rad(float(theta_deg)))), int(n_max), int(bool(per_replica)),
+            ptr("ring_hist", C.c_uint64), ptr("member_hist", C.c_uint64), ptr("stats", C.c_int64),
+            ptr("count", C.c_uint16), int(max_rings), ptr("ring", C.c_int32)))
+        return res
+
     def _cavity(self, points, n_probe, seed, draw0, radii, site, n_cap, nn_bins, nn_max, per_replica, details):
         R, P = self.R, max(int(n_probe), 0)
         rad = _f64(np.atleast_1d(radii)).ravel()

@@ -1027,6 +1027,33 @@ function hbond_network(b::Batch; r_hb::Vector{Float64} = [3.5], theta_deg::Vecto
     return size_hist, deg_hist, stats
 end
 
+# ---- hydrogen-bond rings (include/mmc_hip.h, mmc_batch_hbond_rings) ---------------------------------
+"""
+    hbond_rings(b; r_hb = 3.5, theta_deg = 30.0, n_max = 8, per_replica = false)
+
+The shortest-path rings (Franzblau) of 3 to `n_max` <= 8 molecules in the hydrogen-bond graph of every
+replica under one criterion (`hbond_network`'s bond), read-only.  Returns `(ring_hist, member_hist,
+stats)`: `ring_hist` `(9, 3)` UInt64 (by size: the rings that do not wrap the box, those that do, the
+homodromic ones among the first), `member_hist` `(33, 9)` (molecules by the number of n-rings they are
+members of; row 0: rings of any size; the last bin 32 or more) -- each with a trailing dimension R with
+`per_replica` -- and `stats` `(8, R)` Int64: bonds, rings, wrapping rings, homodromic rings, molecules
+in no ring, the most rings one molecule is in, rings dropped from a ring list (0 here), flagged.
+"""
+function hbond_rings(b::Batch; r_hb::Float64 = 3.5, theta_deg::Float64 = 30.0, n_max::Integer = 8,
+                     per_replica::Bool = false)
+    3 <= n_max <= 8 || error("n_max is 3 to 8")
+    ring_hist = per_replica ? zeros(UInt64, 9, 3, b.n_replicas) : zeros(UInt64, 9, 3)
+    member_hist = per_replica ? zeros(UInt64, 33, 9, b.n_replicas) : zeros(UInt64, 33, 9)
+    stats = zeros(Int64, 8, b.n_replicas)
+    # (the macro form: count_out is the only 16-bit pointer of the interface, NULL here)
+    check(@ccall libmmc.mmc_batch_hbond_rings(b.h::Ptr{Cvoid}, r_hb::Float64, cosd(theta_deg)::Float64,
+                                              n_max::Int32, (per_replica ? 1 : 0)::Int32,
+                                              ring_hist::Ptr{UInt64}, member_hist::Ptr{UInt64},
+                                              stats::Ptr{Int64}, C_NULL::Ptr{UInt16}, 0::Int64,
+                                              C_NULL::Ptr{Int32})::Int32)
+    return ring_hist, member_hist, stats
+end
+
 # ---- cavities and occupancy (include/mmc_hip.h, mmc_batch_cavity, mmc_batch_cavity_at) --------------
 """
     cavity(b, n_probe, seed; draw0 = 0, radii = [3.3], site = 0, n_cap = 32, nn_bins = 0, nn_max = 0.0,

@@ -552,6 +552,54 @@ def bond_fractions(deg_hist):
         return h / h.sum(-1, keepdims=True)
 
 
+# ---- hydrogen-bond rings (include/mmc_hip.h, "Hydrogen-bond rings") ----------------------------------
+RING_MAX_SIZE = 8
+RING_MEMBER_BINS = 33
+
+
+def _ring_hist(ring_hist):
+    h = np.asarray(ring_hist, dtype=float)
+    if h.ndim < 2 or h.shape[-2:] != (3, RING_MAX_SIZE + 1):
+        raise ValueError("ring_hist must be [..., 3, 9]")
+    return h
+
+
+def ring_size_distribution(ring_hist, n_mol, n_samples=1):
+    """Rings per molecule by size, [..., 9], from mmc_batch_hbond_rings' ring_hist ([..., 3, 9]; row 0,
+    the rings that do not wrap the box): counts / (n_mol n_samples), n_samples the replicas (times
+    frames) a summed histogram holds.  Ice Ih and Ic have 2 six-rings per molecule and nothing else."""
+    h = _ring_hist(ring_hist)
+    if not (n_mol > 0 and n_samples > 0):
+        raise ValueError("n_mol and n_samples must be positive")
+    return h[..., 0, :] / (float(n_mol) * float(n_samples))
+
+
+def ring_fractions(ring_hist):
+    """The fraction of the rings (row 0) that have n = 0..8 members, [..., 9]; NaN without rings."""
+    h = _ring_hist(ring_hist)[..., 0, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h / h.sum(-1, keepdims=True)
+
+
+def homodromic_fraction(ring_hist):
+    """By size, [..., 9]: the fraction of the rings (row 0) round which the donations run one way
+    (row 2); NaN where there is no ring of that size."""
+    h = _ring_hist(ring_hist)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return h[..., 2, :] / h[..., 0, :]
+
+
+def ring_membership(member_hist):
+    """The mean number of n-rings a molecule is a member of, [..., 9] (entry 0: rings of any size),
+    from member_hist [..., 9, 33] (molecules by membership; the last bin, "32 or more", counts as
+    32); NaN for the rows that are empty (1, 2 and those above n_max)."""
+    h = np.asarray(member_hist, dtype=float)
+    if h.ndim < 2 or h.shape[-2:] != (RING_MAX_SIZE + 1, RING_MEMBER_BINS):
+        raise ValueError("member_hist must be [..., 9, 33]")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (h * np.arange(RING_MEMBER_BINS)).sum(-1) / h.sum(-1)
+
+
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom) ----------------------------
 MMC_SLOT_WIDOM = 0x50000000  # Philox slots of an insertion: +0, +1, +2 (+3, +4, +5: pair_molecules)
 
