@@ -345,6 +345,8 @@ int32_t mmc_batch_set_parts(mmc_batch *b, int32_t n_parts);
  *   "local_stage"      0 = mmc_batch_local_order, mmc_batch_shell_order and mmc_batch_cavity read the site
  *                      positions from device memory even where a replica's fit in LDS (default 1; the
  *                      path of systems too large to stage, same results: a test hook)
+ *   "voronoi_prune"    0 = mmc_batch_voronoi clips every face against every listed plane instead of
+ *                      stopping at the first one out of its reach (default 1; same bits, for timing)
  *   "zero_copy_moves"  1 = the kernel reads proposals from pinned host memory instead of an
  *                      H2D copy on the stream (lower latency for one replica, default 0)
  *   "device_moves"     1 = mmc_batch_run / mmc_batch_run_chains generate the trial moves on the
@@ -1454,6 +1456,98 @@ int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double r_lsi, double 
     int32_t zeta_bins, double zeta_lo, double zeta_hi, int32_t per_replica,
     uint64_t *rank_hist, uint64_t *lsi_hist, uint64_t *ang_hist, uint64_t *zeta_hist, uint64_t *flagged,
     double *sums, int32_t *count_out, int32_t *nbr_out, double *lsi_out, double *zeta_out);
+
+/* ---- Voronoi cells: volumes, asphericity and geometric neighbours of 3-site molecules ------------
+ * The cutoff-free side of the local structure: the Voronoi cell of every oxygen of every replica in
+ * one read-only pass -- its volume V (the local density of the two-state picture), its surface S, its
+ * asphericity eta = S^3 / (36 pi V^2) (Ruocco, Sampoli and Vallauri, J. Chem. Phys. 96, 6167, 1992:
+ * 2.25 in ice Ih and Ic, about 1.6 - 1.7 in the liquid), its faces (the geometric coordination number
+ * and neighbour list) and the sums for <V> and <V^2> - <V>^2.  The reference has no such analysis; the
+ * arithmetic is defined here, operation by operation, and restated in numpy by tests/voronoi_ref.py.
+ * + - x / sqrt floor are correctly rounded fp64 and nothing is fused, so every output is reproducible
+ * bit for bit.  Every dot product and every r^2 is (x x' + y y') + z z'; r_list r_list and the scales
+ * named below are formed once, in fp64, by the host.
+ *   - List.  The list of "Shell order" with the same r_list: neighbour k = 0 .. n - 1 of molecule i
+ *     in rising (bits of rho_k^2, j), d_k = d(O_i, O_j) the signed image and rho_k^2 its r^2.  More
+ *     than MMC_VORONOI_CAP = 64 in range: flag bit 0 (CAP), nothing else is done.  n = 0, or
+ *     rho_0^2 = 0 (a coincident oxygen has no bisector plane): flag bit 1 (OPEN), nothing else is done.
+ *     Two LISTED neighbours that coincide with each other are not looked for: they own bit-equal
+ *     planes, each face is clipped by the other's plane with e(p) of rounding size and either sign,
+ *     so one or both faces may vanish while the cell stays certified, its V short of that face's
+ *     A rho / 6.  The outputs are still the ones this arithmetic defines, bit for bit; they are not
+ *     the cell of the distinct sites.  Coincident oxygens do not occur in a chain (the overlap test).
+ *   - Face k lies in the plane x . d_k = rho_k^2 / 2 around m_k = 0.5 d_k.  Its in-plane basis: with
+ *     a the axis of the smallest |component| of d_k (the first of equal ones), w = d_k x e_a written
+ *     out -- a = x: (0, d_z, -d_y); a = y: (-d_z, 0, d_x); a = z: (d_y, -d_x, 0) -- u = w / sqrt(w . w)
+ *     (three divisions), q = d_k x u = (d_y u_z - d_z u_y, d_z u_x - d_x u_z, d_x u_y - d_y u_x),
+ *     v = q / sqrt(q . q).  A point of the plane is x = m_k + s u + t v, and |x|^2 is taken as
+ *     0.25 rho_k^2 + (s s + t t).
+ *   - Polygon.  Face k starts as the vertices (s, t) = (-r, -r), (r, -r), (r, r), (-r, r), r = r_list,
+ *     and is clipped by the planes m = 0, 1, ..., n - 1, m != k, in that order: a = u . d_m,
+ *     b = v . d_m, c = 0.5 rho_m^2 - m_k . d_m; e(p) = (a s_p + b t_p) - c; p is inside when
+ *     e(p) <= 0.  One clip makes a new vertex list from the old one p_0 .. p_(N-1): for j = 0 .. N - 1
+ *     with q = p_(j+1), or p_0 after the last: if p_j is inside, p_j is appended; then, if exactly one
+ *     of p_j and q is inside (a cut edge), w = e(p_j) / (e(p_j) - e(q)) and the vertex
+ *     (s_p + w (s_q - s_p), t_p + w (t_q - t_p)) is appended.  A list that ends with fewer than three
+ *     vertices is no face: the lane is done.  An append to a list that holds MMC_VORONOI_MAXV = 16
+ *     vertices, or a third cut edge in one clip (rounding made the polygon non-convex), sets flag bit
+ *     2 (POLY) and ends the face.  (With at most two cut edges the new list is never longer than
+ *     j + 2 once p_j has been handled: a clip can be made in place.)  The largest polygon met on
+ *     water and on lattices had 13 vertices.
+ *   - Pruning.  g = the largest s s + t t of the face's current vertices.  Before plane m is applied,
+ *     a face stops for good when 0.25 rho_m^2 > (0.25 rho_k^2 + g) MMC_VORONOI_PRUNE, PRUNE = 1 + 2^-20:
+ *     a plane cuts a vertex x only if |x| > rho_m / 2, the ranks are in rising rho, and the margin is
+ *     10^9 times the rounding of e(p), so neither this nor any later plane changes the list.  The
+ *     rule changes no bit (option "voronoi_prune" = 0 walks every plane; tests compare the two).
+ *   - Cell.  A_k = 0.5 |sum over j of (s_j t_(j+1) - s_(j+1) t_j)|, the sum from zero in rising j with
+ *     p_N = p_0; 0 for no face.  S = sum of A_k, T = sum of A_k rho_k (rho_k = sqrt(rho_k^2)), each
+ *     from zero in rising k; V = T / 6.0; eta = ((S S) S) / ((K V) V), K = 36.0 x 3.141592653589793.
+ *     Face k is COUNTED when A_k > area_min: it is a geometric neighbour.  Every face enters S and V.
+ *     (On perfect lattices rounding leaves faces of area ~ 1e-15 between second neighbours: area_min =
+ *     1e-6 A^2 gives the textbook 6, 14, 12 and 16 faces of sc, bcc, fcc and diamond.)
+ *   - Closure.  The cell is certified when a face is left and 4.0 (0.25 rho_k^2 + g_k) <= r_list r_list
+ *     for every face left: an oxygen that could cut off a vertex at |x| lies within 2 |x| of O_i,
+ *     and the list is complete to r_list.  Otherwise flag bit 1 (OPEN).  POLY and OPEN may both be set.
+ *   - A molecule with a flag bit set enters no histogram and no sum.  Others add: vol_hist [v_bins +
+ *     1] at (int)floor(V v_scale) clamped to 0 .. v_bins, v_scale = v_bins / v_max (last slot:
+ *     beyond v_max); eta_hist [eta_bins + 1] at (int)floor((eta - 1.0) eta_scale) clamped to 0 ..
+ *     eta_bins, eta_scale = eta_bins / (eta_max - 1.0), a value that is not finite to the last slot;
+ *     face_hist [65] at the number of counted faces; per counted face side_hist [MMC_VORONOI_MAXV + 1]
+ *     at its number of vertices and nbr_hist [r_bins + 1] at (int)floor(rho_k inv_dr) clamped to 0 ..
+ *     r_bins, inv_dr = r_bins / r_list (the geometric-neighbour part of g_OO).
+ *   - Outputs, all overwritten, each may be NULL but not all.  The five histograms are [R][...] with
+ *     per_replica.  flagged [R][3]: molecules per flag bit (CAP, OPEN, POLY).  sums [R][8] = (number
+ *     summed, sum V, sum V V, sum S, sum eta, sum of counted faces, sum of counted-face area, 0) over
+ *     the replica's unflagged molecules in the order of "Local order"'s q_sum (lane l the molecules
+ *     l, l + 64, ...; the lane sums in wave_sum_rows' order): bitwise reproducible, independent of the
+ *     launch.  vol_out, area_out [R][N]: V and S, NaN where flagged; faces_out [R][N]: counted faces,
+ *     or minus the flag bits; nbr_out [R][N][64]: the molecules (0-based) of the counted faces in
+ *     rising rank, then -1; face_area_out [R][N][64]: their areas, then 0.  Nothing depends on the
+ *     grid or on options "wave_wgs", "local_stage" and "voronoi_prune".
+ *   - Use (observables.py): voronoi_volume_distribution, asphericity_distribution,
+ *     voronoi_coordination, face_side_fractions, voronoi_neighbour_gr, voronoi_means,
+ *     volume_fluctuation.
+ *   - Limits.  64 neighbours reach to about 7.7 A at 1 g/cm^3, and a cell whose farthest vertex lies
+ *     beyond r_list / 2 is OPEN and left out.  At low density (NIST configuration 4, 0.83 g/cm^3:
+ *     3.5 % at r_list = 7.5 A) the cells left out are the largest, so the high-V tail and <V> are
+ *     biased low; flagged says by how much.  r_list is bounded by half the smallest box: beyond it
+ *     the minimum image is not the only image that can cut a cell.
+ * Both box modes and either Coulomb style, records or arrays: the call reads O positions only, and is
+ * read-only exactly as mmc_batch_shell_order is, with its preconditions (MMC_ERR_STATE).
+ * MMC_ERR_ARG, checked before the batch: r_list or v_max not finite or <= 0; area_min not finite or
+ * < 0; eta_max not finite or <= 1; v_bins, eta_bins or r_bins outside 1..MMC_VORONOI_MAX_BINS (which
+ * keeps a workgroup's 32-bit counters, at most 3157 words, beside its waves' lists and polygons in
+ * LDS); every output NULL.  Checked with the batch: r_list above half of the smallest box.  Then the
+ * state; then MMC_ERR_UNSUPPORTED: fewer than 2 molecules or more than 2^21.  On any error every
+ * output is left untouched. */
+#define MMC_VORONOI_CAP      64
+#define MMC_VORONOI_MAXV     16
+#define MMC_VORONOI_MAX_BINS 1024
+int32_t mmc_batch_voronoi(mmc_batch *b, double r_list, double area_min, int32_t v_bins, double v_max,
+    int32_t eta_bins, double eta_max, int32_t r_bins, int32_t per_replica,
+    uint64_t *vol_hist, uint64_t *eta_hist, uint64_t *face_hist, uint64_t *side_hist, uint64_t *nbr_hist,
+    uint64_t *flagged, double *sums,
+    double *vol_out, double *area_out, int32_t *faces_out, int32_t *nbr_out, double *face_area_out);
 
 /* ---- Bond order: Steinhardt q_l, bond correlations, solid-like molecules and their clusters -----
  * Is there ice in the box, how much, and how large is the largest crystalline nucleus: Steinhardt's

@@ -207,6 +207,9 @@ SIGNATURES = {
     "mmc_batch_shell_order": [_vp, _d, _d, _d, _d, _d, C.c_int32, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32, _d, _d,
                               C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _i32p, _i32p, _dp, _dp],
+    "mmc_batch_voronoi": [_vp, _d, _d, C.c_int32, _d, C.c_int32, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                          C.POINTER(C.c_uint64), _dp, _dp, _dp, _i32p, _i32p, _dp],
     "mmc_batch_bond_order": [_vp, C.c_int32, _d, C.c_int32, _d, _d, _d, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                              C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i64p, _dp, _dp, _dp, _i32p,

@@ -106,6 +106,7 @@ struct mmc_batch {
                                 // where they fit (option "local_stage" = 0: never, the path of systems too large for it)
     int bond_chunk = 0;         // mmc_batch_bond_order: replicas per chunk of scratch records (0: by its budget)
     int ring_chunk = 0;         // mmc_batch_hbond_rings: replicas per launch with count_out or ring_out (0: by its budget)
+    int voronoi_prune = 1;      // mmc_batch_voronoi: a face stops at the first plane that cannot reach it (0: walks them all; same bits)
 
     const MoveRec *dev_moves(int which) const
     {
@@ -340,6 +341,9 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
     } else if (!strcmp(key, "ring_chunk")) {
         MMC_REQUIRE(value >= 0 && value <= (1 << 30), MMC_ERR_ARG, "ring_chunk must be 0 (by the staging budget) or the replicas per launch");
         b->ring_chunk = (int)value;
+    } else if (!strcmp(key, "voronoi_prune")) {
+        MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "voronoi_prune must be 1 (stop at the first plane out of reach) or 0 (never)");
+        b->voronoi_prune = (int)value;
     } else if (!strcmp(key, "trace_steps")) {
         MMC_REQUIRE(value >= 0 && value * b->sys.R <= (1LL << 26), MMC_ERR_ARG, "trace_steps out of range");
         b->trace_steps = value;

@@ -1008,6 +1008,51 @@ class Batch:
             ptr("count", C.c_int32), ptr("nbr", C.c_int32), ptr("lsi", C.c_double), ptr("zeta", C.c_double)))
         return res
 
+    def voronoi(self, r_list=7.0, area_min=0.0, v_bins=200, v_max=80.0, eta_bins=200, eta_max=3.0, r_bins=280,
+                per_replica=False, details=False, out=None):
+        """mmc_batch_voronoi: the Voronoi cell of every molecule's O from its O-O neighbours inside
+        r_list (at most 64, at most half the smallest box), read-only.  Returns a dict: vol_hist
+        uint64 [v_bins + 1] (cell volume over [0, v_max); last slot: beyond), eta_hist uint64
+        [eta_bins + 1] (asphericity S^3 / (36 pi V^2) over [1, eta_max); last slot: beyond), face_hist
+        uint64 [65] (molecules by their number of counted faces: those with area > area_min),
+        side_hist uint64 [17] (counted faces by number of sides), nbr_hist uint64 [r_bins + 1] (O-O
+        distance of counted faces over [0, r_list)) -- each [R, ...] with per_replica -- flagged
+        uint64 [R, 3] (molecules with more than 64 neighbours in range; whose cell is not certified
+        closed inside the list; whose polygon passed 16 vertices: in no histogram and no sum) and sums
+        [R, 8] (number summed, sum V, sum V^2, sum S, sum eta, sum of counted faces, sum of their
+        area, 0).  details=True adds vol and area [R, N] (NaN where flagged), faces int32 [R, N]
+        (counted faces, or minus the flag bits), nbr int32 [R, N, 64] (the geometric neighbours by
+        rank, then -1) and face_area [R, N, 64] (their face areas, then 0).  `out`: a dict of arrays
+        under those names to overwrite instead (each of its shape and dtype, contiguous)."""
+        R, N = self.R, self.n_mol
+        nv, ne, nr = (max(int(v), 0) for v in (v_bins, eta_bins, r_bins))
+        lead = (R,) if per_replica else ()
+        # (sizes the library refuses still get arrays to leave alone)
+        spec = {"vol_hist": (lead + (nv + 1,), np.uint64), "eta_hist": (lead + (ne + 1,), np.uint64),
+                "face_hist": (lead + (65,), np.uint64), "side_hist": (lead + (17,), np.uint64),
+                "nbr_hist": (lead + (nr + 1,), np.uint64), "flagged": ((R, 3), np.uint64), "sums": ((R, 8), np.float64)}
+        if details:
+            spec.update(vol=((R, N), np.float64), area=((R, N), np.float64), faces=((R, N), np.int32),
+                        nbr=((R, N, 64), np.int32), face_area=((R, N, 64), np.float64))
+        res = {}
+        for k, (shape, dt) in spec.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dtype=dt)
+            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
+            res[k] = a
+
+        def ptr(k, ct):
+            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        check(self._L.mmc_batch_voronoi(
+            self._h, float(r_list), float(area_min), int(v_bins), float(v_max), int(eta_bins), float(eta_max),
+            int(r_bins), int(bool(per_replica)), ptr("vol_hist", C.c_uint64), ptr("eta_hist", C.c_uint64),
+            ptr("face_hist", C.c_uint64), ptr("side_hist", C.c_uint64), ptr("nbr_hist", C.c_uint64),
+            ptr("flagged", C.c_uint64), ptr("sums", C.c_double), ptr("vol", C.c_double), ptr("area", C.c_double),
+            ptr("faces", C.c_int32), ptr("nbr", C.c_int32), ptr("face_area", C.c_double)))
+        return res
+
     def bond_order(self, l=3, r_nb=3.5, n_nb=4, a=(-np.inf, -0.8), b=(-0.35, 0.25), min_a=3, min_ab=4, q_bins=200,
                    c_bins=200, per_replica=False, details=False, out=None):
         """mmc_batch_bond_order: Steinhardt's q_l (l = 3, 4 or 6) of every molecule over its n_nb

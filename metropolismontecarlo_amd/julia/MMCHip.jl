@@ -957,6 +957,44 @@ function shell_order(b::Batch; r_list::Float64 = 6.0, r_lsi::Float64 = 3.7, r_an
     return rank_hist, lsi_hist, ang_hist, zeta_hist, flagged, sums
 end
 
+# ---- Voronoi cells (include/mmc_hip.h, mmc_batch_voronoi) -------------------------------------------
+"""
+    voronoi(b; r_list = 7.0, area_min = 0.0, v_bins = 200, v_max = 80.0, eta_bins = 200, eta_max = 3.0,
+            r_bins = 280, per_replica = false)
+
+The Voronoi cell of every molecule's O (slot 1) from its O-O neighbours inside `r_list` (at most 64, at
+most half the smallest box), in one read-only pass: `vol_hist` `v_bins + 1` UInt64 counts of the cell
+volume over [0, `v_max`); `eta_hist` `eta_bins + 1` counts of the asphericity S^3 / (36 pi V^2) over
+[1, `eta_max`); the last entry of each is "beyond"; `face_hist` 65 counts of molecules by their number
+of counted faces (area > `area_min`); `side_hist` 17 counts of counted faces by number of sides;
+`nbr_hist` `r_bins + 1` counts of the O-O distance of counted faces over [0, `r_list`) -- all with a
+trailing dimension R with `per_replica`.  Returns `(vol_hist, eta_hist, face_hist, side_hist, nbr_hist,
+flagged, sums)`: `flagged` `(3, R)` the molecules per replica with more than 64 neighbours in range,
+with a cell that is not certified closed, with a polygon beyond 16 vertices (in no histogram and no
+sum); `sums` `(8, R)`: the number summed, sum V, sum V^2, sum S, sum eta, sum of counted faces, sum of
+their area, 0.
+"""
+function voronoi(b::Batch; r_list::Float64 = 7.0, area_min::Float64 = 0.0, v_bins::Integer = 200,
+                 v_max::Float64 = 80.0, eta_bins::Integer = 200, eta_max::Float64 = 3.0, r_bins::Integer = 280,
+                 per_replica::Bool = false)
+    all(1 <= n <= 1024 for n in (v_bins, eta_bins, r_bins)) || error("bin counts must be in 1..1024")
+    tail = per_replica ? (b.n_replicas,) : ()
+    vol_hist = zeros(UInt64, v_bins + 1, tail...)
+    eta_hist = zeros(UInt64, eta_bins + 1, tail...)
+    face_hist = zeros(UInt64, 65, tail...)
+    side_hist = zeros(UInt64, 17, tail...)
+    nbr_hist = zeros(UInt64, r_bins + 1, tail...)
+    flagged = zeros(UInt64, 3, b.n_replicas)
+    sums = zeros(Float64, 8, b.n_replicas)
+    check(ccall((:mmc_batch_voronoi, libmmc), Int32,
+                (Ptr{Cvoid}, Float64, Float64, Int32, Float64, Int32, Float64, Int32, Int32, Ptr{UInt64}, Ptr{UInt64},
+                 Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                b.h, r_list, area_min, v_bins, v_max, eta_bins, eta_max, r_bins, per_replica ? 1 : 0, vol_hist,
+                eta_hist, face_hist, side_hist, nbr_hist, flagged, sums, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
+    return vol_hist, eta_hist, face_hist, side_hist, nbr_hist, flagged, sums
+end
+
 # ---- bond order (include/mmc_hip.h, mmc_batch_bond_order) -------------------------------------------
 """
     bond_order(b; l = 3, r_nb = 3.5, n_nb = 4, a = (-Inf, -0.8), b_win = (-0.35, 0.25), min_a = 3,

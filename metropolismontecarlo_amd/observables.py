@@ -398,6 +398,86 @@ def zeta_mean(sums):
         return s[..., 2] / s[..., 3]
 
 
+# ---- Voronoi cells (include/mmc_hip.h, "Voronoi cells") ---------------------------------------------
+def voronoi_volume_distribution(vol_hist, v_max):
+    """(V, p, beyond) from mmc_batch_voronoi's vol_hist [..., v_bins + 1]: the bin centres over
+    [0, v_max), the density of the cell volume over the unflagged molecules inside it (integrates to
+    1) and the fraction at or beyond v_max."""
+    return _density(vol_hist, 0.0, v_max, "vol_hist")
+
+
+def asphericity_distribution(eta_hist, eta_max):
+    """(eta, p, beyond) from eta_hist [..., eta_bins + 1]: the bin centres over [1, eta_max), the
+    density of eta = S^3 / (36 pi V^2) (1 for a sphere, 2.25 in ice Ih) and the fraction at or beyond
+    eta_max."""
+    return _density(eta_hist, 1.0, eta_max, "eta_hist")
+
+
+def voronoi_coordination(face_hist):
+    """(n, p, mean) from face_hist [..., 65]: n = 0 .. 64, p[..., n] the fraction of the unflagged
+    molecules with n counted faces (geometric neighbours), mean [...] their mean number."""
+    h = np.asarray(face_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] != 65:
+        raise ValueError("face_hist must be [..., 65]")
+    n = np.arange(65)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = h / h.sum(-1, keepdims=True)
+    return n, p, (p * n).sum(-1)
+
+
+def face_side_fractions(side_hist):
+    """(sides, p, mean) from side_hist [..., 17]: sides = 0 .. 16, p[..., k] the fraction of the
+    counted faces with k sides, mean [...] the mean number of sides (Euler: 6 - 12 / <faces>
+    when every vertex joins three faces)."""
+    h = np.asarray(side_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] != 17:
+        raise ValueError("side_hist must be [..., 17]")
+    k = np.arange(17)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = h / h.sum(-1, keepdims=True)
+    return k, p, (p * k).sum(-1)
+
+
+def voronoi_neighbour_gr(nbr_hist, r_list, n_summed, density):
+    """(r, g) from nbr_hist [..., r_bins + 1]: the part of g_OO(r) that geometric neighbours make
+    up, counts / (n_summed 4 pi r^2 dr density) at the bin centres over [0, r_list).  n_summed: the
+    unflagged molecules behind the histogram (sums[..., 0], summed over what nbr_hist is summed
+    over); density: molecules per volume."""
+    h = np.asarray(nbr_hist, dtype=float)
+    if h.ndim < 1 or h.shape[-1] < 2:
+        raise ValueError("nbr_hist must be [..., r_bins + 1]")
+    nb = h.shape[-1] - 1
+    dr = float(r_list) / nb
+    r = (np.arange(nb) + 0.5) * dr
+    shell = 4.0 * np.pi * r * r * dr * float(density)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return r, h[..., :nb] / (np.asarray(n_summed, dtype=float)[..., None] * shell)
+
+
+def _voronoi_sums(sums):
+    s = np.asarray(sums, dtype=float)
+    if s.shape[-1] != 8:
+        raise ValueError("sums must be [..., 8]")
+    return s
+
+
+def voronoi_means(sums):
+    """(<V>, <eta>, <faces>) from mmc_batch_voronoi's sums ([..., 8]: number summed, sum V, sum V^2,
+    sum S, sum eta, sum of counted faces, sum of counted-face area, 0) over the unflagged molecules:
+    per replica for [R, 8] (NaN where none); pass sums.sum(0) for the mean over all molecules."""
+    s = _voronoi_sums(sums)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s[..., 1] / s[..., 0], s[..., 4] / s[..., 0], s[..., 5] / s[..., 0]
+
+
+def volume_fluctuation(sums):
+    """<V^2> - <V>^2 of the cell volume over the unflagged molecules, from sums as voronoi_means."""
+    s = _voronoi_sums(sums)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = s[..., 1] / s[..., 0]
+        return s[..., 2] / s[..., 0] - mean * mean
+
+
 # ---- bond order (include/mmc_hip.h, "Bond order") ---------------------------------------------------
 BO_STATS = 8  # defined, undefined, flagged, truncated, solid molecules, solid clusters, largest, sum of s^2
 CHILL_CLASSES = ("cubic", "hexagonal", "interfacial_ice", "clathrate", "interfacial_clathrate", "liquid")
