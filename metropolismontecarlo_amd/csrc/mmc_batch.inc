@@ -102,7 +102,8 @@ struct mmc_batch {
     int coulomb_style = MMC_COULOMB_EWALD; // mmc_batch_set_coulomb_style (main.jl:75)
     bool s_stale = false;       // the style went from Wolf back to Ewald: S(k) does not describe the
                                 // coordinates until mmc_batch_recip_long / _potential_ewald rebuild it
-    int local_stage = 1;        // mmc_batch_local_order and mmc_batch_cavity copy a replica's site positions to LDS
+    int local_stage = 1;        // the neighbour scans (local order, cavities, shell order, bond order, Voronoi cells and,
+                                // always, network and rings: mmc_nbr.hpp) copy a replica's site positions to LDS
                                 // where they fit (option "local_stage" = 0: never, the path of systems too large for it)
     int bond_chunk = 0;         // mmc_batch_bond_order: replicas per chunk of scratch records (0: by its budget)
     int ring_chunk = 0;         // mmc_batch_hbond_rings: replicas per launch with count_out or ring_out (0: by its budget)

@@ -13,7 +13,7 @@
 // with the replica's O positions staged in LDS where they fit), and 32-bit counters in LDS, one set
 // per workgroup, are added to the 64-bit global ones whenever the workgroup leaves a replica.
 //
-// Phase A, one molecule, one wave: scan and rank sort as k_shell_order_wave, then
+// Phase A, one molecule, one wave: scan_list and rank_sort (mmc_nbr.hpp), then
 //   harmonics  lane k < n_i takes neighbour k: u = d / rho and, for m = 0 .. l, T_l^m(z) by the
 //              header's recurrence and (x + i y)^m one complex product at a time -- scalars only, no
 //              indexed registers -- written to the wave's [16][14] block in LDS
@@ -66,106 +66,52 @@ __device__ __forceinline__ double bo_norm2(double q, int lane, int l)
 {
     const double im = wave_pick(q, min(lane + l + 1, 63));
     const double t = q * q + im * im; // lanes 0 .. l: t_m
-    double Q = sh_read(t, 0);
+    double Q = lane_f64(t, 0);
     for (int m = 1; m <= l; m++)
-        Q = Q + 2.0 * sh_read(t, m);
+        Q = Q + 2.0 * lane_f64(t, m);
     return Q;
 }
 
 // REC, STAGE, grid: as k_shell_order_wave.
-// dynamic LDS: [nw] lists of SH_LIST_BYTES, [nw] blocks of BO_Y_BYTES, [hs] counters (defined,
+// dynamic LDS: [nw] lists of NBR_LIST_BYTES, [nw] blocks of BO_Y_BYTES, [hs] counters (defined,
 // undefined, flagged, truncated, then q_hist's), then (STAGE) 3 N doubles at the next multiple of 16.
 template <bool REC, bool STAGE>
-__global__ __launch_bounds__(LO_WAVES * 64) void k_bond_qlm(BatchView bv, const double *__restrict__ rec, BondArgs ba)
+__global__ __launch_bounds__(NBR_WAVES * 64) void k_bond_qlm(BatchView bv, const double *__restrict__ rec, BondArgs ba)
 {
     extern __shared__ __align__(16) unsigned char bo_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
     const int n_mol = bv.n_mol, l = ba.l, cols = 2 * (l + 1);
     const int hs = 4 + (ba.q_hist ? ba.q_bins + 1 : 0);
-    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(bo_lds + (size_t)wv * SH_LIST_BYTES);
+    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(bo_lds + (size_t)wv * NBR_LIST_BYTES);
     int *const idx = reinterpret_cast<int *>(keys + MMC_SHELL_CAP);
-    double *const yb = reinterpret_cast<double *>(bo_lds + (size_t)nw * SH_LIST_BYTES + (size_t)wv * BO_Y_BYTES);
-    unsigned *const hw = reinterpret_cast<unsigned *>(bo_lds + (size_t)nw * (SH_LIST_BYTES + BO_Y_BYTES));
+    double *const yb = reinterpret_cast<double *>(bo_lds + (size_t)nw * NBR_LIST_BYTES + (size_t)wv * BO_Y_BYTES);
+    unsigned *const hw = reinterpret_cast<unsigned *>(bo_lds + (size_t)nw * (NBR_LIST_BYTES + BO_Y_BYTES));
     double *const pos = reinterpret_cast<double *>(
-        bo_lds + (((size_t)nw * (SH_LIST_BYTES + BO_Y_BYTES) + 4 * (size_t)hs + 15) & ~(size_t)15));
+        bo_lds + (((size_t)nw * (NBR_LIST_BYTES + BO_Y_BYTES) + 4 * (size_t)hs + 15) & ~(size_t)15));
     for (int q = tid; q < hs; q += (int)blockDim.x)
         hw[q] = 0u;
     __syncthreads();
 
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    const int64_t M = (int64_t)ba.nr * n_mol;
-    const int64_t m0 = M * blockIdx.x / gridDim.x, m1 = M * (blockIdx.x + 1) / gridDim.x;
+    const Sites<REC, STAGE> sites{ bv, rec, pos };
 
-    auto oxygen = [&](int r, int j, double &x, double &y, double &z) {
-        if constexpr (STAGE) {
-            x = pos[j]; y = pos[n_mol + j]; z = pos[2 * n_mol + j];
-        } else if constexpr (REC) {
-            const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-            const double2 v0 = *reinterpret_cast<const double2 *>(p);
-            x = v0.x; y = v0.y; z = p[2];
-        } else {
-            const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-            x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-        }
-    };
-
-    for (int64_t s0 = m0; s0 < m1;) { // the run's molecules of one replica: [i_lo, i_hi) of replica r
-        const int rl = (int)(s0 / n_mol), r = ba.r0 + rl;
-        const int i_lo = (int)(s0 - (int64_t)rl * n_mol);
-        const int i_hi = (int)min((int64_t)n_mol, (int64_t)i_lo + (m1 - s0));
-        s0 += i_hi - i_lo;
-        if constexpr (STAGE) {
-            __syncthreads(); // every wave has left the previous replica's positions
-            for (int j = tid; j < n_mol; j += (int)blockDim.x) {
-                double x, y, z;
-                if constexpr (REC) {
-                    const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-                    const double2 v0 = *reinterpret_cast<const double2 *>(p);
-                    x = v0.x; y = v0.y; z = p[2];
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-                    x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-                }
-                pos[j] = x; pos[n_mol + j] = y; pos[2 * n_mol + j] = z;
-            }
-            __syncthreads();
-        }
+    for (RunCursor rc(ba.nr, n_mol); rc.next();) { // the run's molecules of one replica of the chunk: [rc.lo, rc.hi)
+        const int rl = rc.r, r = ba.r0 + rl;
+        if constexpr (STAGE)
+            stage_sites(sites, r);
         const BoxConsts bc = box_consts(ba.box_r ? ba.box_r[r] : bv.box);
 
-        for (int i = i_lo + wv; i < i_hi; i += nw) {
+        for (int i = rc.lo + wv; i < rc.hi; i += nw) {
             const int64_t g = (int64_t)rl * n_mol + i;      // in the chunk's scratch
             const int64_t go = (int64_t)r * n_mol + i;      // in the batch's outputs
             const int64_t gq = (int64_t)(r - ba.q_r0) * n_mol + i;
             double cx, cy, cz; // the wave's molecule: wave-uniform
-            oxygen(r, i, cx, cy, cz);
+            sites.get(r, i, cx, cy, cz);
 
-            // ---- scan: the list, unsorted, in rising j (k_shell_order_wave's)
-            int m = 0;
-            bool over = false;
-            for (int jb = 0; jb < n_mol; jb += 64) {
-                const int j = jb + lane;
-                double x, y, z;
-                oxygen(r, min(j, n_mol - 1), x, y, z);
-                const double dx = vector1D_abs(cx, x, bc), dy = vector1D_abs(cy, y, bc), dz = vector1D_abs(cz, z, bc);
-                const double r2 = (dx * dx + dy * dy) + dz * dz;
-                const bool near = j < n_mol && j != i && r2 < ba.rnb2;
-                const unsigned long long nm = wave_ballot(near);
-                if (nm != 0ULL) { // wave-uniform
-                    const int add = __popcll(nm);
-                    if (m + add > MMC_SHELL_CAP) { // more than the lanes can own: flagged, nothing written
-                        over = true;
-                        break;
-                    }
-                    if (near) {
-                        const int slot = m + lanes_below(nm); // < MMC_SHELL_CAP
-                        keys[slot] = (unsigned long long)__double_as_longlong(r2);
-                        idx[slot] = j;
-                    }
-                    m += add;
-                }
-            }
-            wave_sync();
+            // ---- scan: the list, unsorted, in rising j
+            int m;
+            const bool over = !scan_list(sites, r, i, cx, cy, cz, bc, ba.rnb2, keys, idx, lane, m);
 
             if (over) { // wave-uniform
                 if (lane == 0) {
@@ -185,25 +131,9 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_bond_qlm(BatchView bv, const 
             }
 
             // ---- sort: lane n's entry to slot rank(n); lane k then reads slot k
-            const bool mine = lane < m;
-            unsigned long long key = mine ? keys[lane] : ~0ULL;
-            int jn = mine ? idx[lane] : -1;
-            int rank = 0;
-            for (int e = 0; e < m; e++) {
-                const unsigned long long ke = keys[e]; // one address for the wave: a broadcast
-                rank += (ke < key || (ke == key && e < lane)) ? 1 : 0;
-            }
-            wave_sync(); // every lane has read the unsorted list
-            if (mine) {
-                keys[rank] = key;
-                idx[rank] = jn;
-            }
-            wave_sync();
-            if (mine) {
-                key = keys[lane];
-                jn = idx[lane];
-            }
-            wave_sync(); // the list is rewritten by the wave's next molecule
+            unsigned long long key;
+            int jn;
+            rank_sort(keys, idx, m, lane, key, jn);
 
             // ---- harmonics: lane k < n is neighbour k of nb(i)
             const int n = min(m, ba.n_nb);
@@ -215,7 +145,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_bond_qlm(BatchView bv, const 
             if (nbk) {
                 const double rho = sqrt(r2);
                 double ox, oy, oz;
-                oxygen(r, jn, ox, oy, oz);
+                sites.get(r, jn, ox, oy, oz);
                 const double x = vector1D(cx, ox, bc) / rho, y = vector1D(cy, oy, bc) / rho, z = vector1D(cz, oz, bc) / rho;
                 double c = 1.0, s = 0.0, tmm = 1.0; // (x + i y)^m and T_m^m
                 for (int mm = 0; mm <= l; mm++) {
@@ -292,7 +222,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_bond_qlm(BatchView bv, const 
 }
 
 // dynamic LDS: [hs] counters: qbar_hist's, c_hist's, ab_hist's, each only where asked for
-__global__ __launch_bounds__(LO_WAVES * 64) void k_bond_corr(BondArgs ba, int n_mol)
+__global__ __launch_bounds__(NBR_WAVES * 64) void k_bond_corr(BondArgs ba, int n_mol)
 {
     extern __shared__ __align__(16) unsigned char bo_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -306,24 +236,18 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_bond_corr(BondArgs ba, int n_
     __syncthreads();
 
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    const int64_t M = (int64_t)ba.nr * n_mol;
-    const int64_t m0 = M * blockIdx.x / gridDim.x, m1 = M * (blockIdx.x + 1) / gridDim.x;
-
-    for (int64_t s0 = m0; s0 < m1;) {
-        const int rl = (int)(s0 / n_mol), r = ba.r0 + rl;
-        const int i_lo = (int)(s0 - (int64_t)rl * n_mol);
-        const int i_hi = (int)min((int64_t)n_mol, (int64_t)i_lo + (m1 - s0));
-        s0 += i_hi - i_lo;
+    for (RunCursor rc(ba.nr, n_mol); rc.next();) {
+        const int rl = rc.r, r = ba.r0 + rl;
         const int64_t gr = (int64_t)rl * n_mol; // the replica in the chunk's scratch
 
-        for (int i = i_lo + wv; i < i_hi; i += nw) {
+        for (int i = rc.lo + wv; i < rc.hi; i += nw) {
             const int64_t g = gr + i, go = (int64_t)r * n_mol + i;
             const int64_t gq = (int64_t)(r - ba.q_r0) * n_mol + i;
             const int sti = __builtin_amdgcn_readfirstlane(ba.st[g]);
             const int n = sti & 0xff;
             const bool def_i = (sti & (BO_UNDEF | BO_FLAGGED)) == 0;
             const double qi = lane < BO_REC ? ba.rec[BO_REC * g + lane] : 0.0; // lane t: component t; lane 14: Q_i
-            const double Qi = sh_read(qi, BO_Q);
+            const double Qi = lane_f64(qi, BO_Q);
 
             // ---- bonds: lane k < n is (i, j_k)
             const bool nbk = lane < n;
@@ -333,7 +257,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_bond_corr(BondArgs ba, int n_
             const double *const rj = ba.rec + BO_REC * (gr + jn);
             double D = 0.0;
             for (int m = 0; m <= l; m++) {
-                const double t = sh_read(qi, m) * (nbk ? rj[m] : 0.0) + sh_read(qi, l + 1 + m) * (nbk ? rj[l + 1 + m] : 0.0);
+                const double t = lane_f64(qi, m) * (nbk ? rj[m] : 0.0) + lane_f64(qi, l + 1 + m) * (nbk ? rj[l + 1 + m] : 0.0);
                 D = m == 0 ? t : D + 2.0 * t;
             }
             const double Qj = nbk ? rj[BO_Q] : 0.0;

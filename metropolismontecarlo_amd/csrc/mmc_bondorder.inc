@@ -3,7 +3,7 @@
 #include "mmc_bondorder.hpp"
 
 static_assert(MMC_BO_MAX_NB == 16 && MMC_BO_MAX_NB <= BO_REC, "one lane per neighbour and per record slot");
-static_assert(8 * (size_t)MMC_BO_MAX_MOL + 16 <= LO_LDS_BYTES, "labels and sizes of a replica in one workgroup's LDS");
+static_assert(8 * (size_t)MMC_BO_MAX_MOL + 16 <= NBR_LDS_BYTES, "labels and sizes of a replica in one workgroup's LDS");
 static_assert(MMC_BO_STATS == 8, "four counters of phase A, four of phase C");
 
 #define BO_SCRATCH_BYTES ((size_t)256 << 20) // the chunk's records: see DESIGN.md, "Bond order"
@@ -32,9 +32,9 @@ extern "C" int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb, in
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(r_nb <= min_box / 2.0, MMC_ERR_ARG, "mmc_batch_bond_order: r_nb %g exceeds half of the smallest box %g",
-                r_nb, min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(r_nb <= box_min / 2.0, MMC_ERR_ARG, "mmc_batch_bond_order: r_nb %g exceeds half of the smallest box %g",
+                r_nb, box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 2 && N <= MMC_BO_MAX_MOL, MMC_ERR_UNSUPPORTED,
@@ -118,15 +118,14 @@ extern "C" int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb, in
     ba.per_replica = per_replica ? 1 : 0;
 
     // phase A: four waves, their lists and blocks beside the counters; the O positions where they fit
-    const int nw = LO_WAVES;
+    const int nw = NBR_WAVES;
     const size_t hs_a = 4 + (q_hist ? (size_t)q_bins + 1 : 0);
-    const size_t lds_w = ((size_t)nw * (SH_LIST_BYTES + BO_Y_BYTES) + 4 * hs_a + 15) & ~(size_t)15;
-    const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= LO_LDS_BYTES;
+    const size_t lds_w = ((size_t)nw * (NBR_LIST_BYTES + BO_Y_BYTES) + 4 * hs_a + 15) & ~(size_t)15;
+    const bool stage = stage_fits(b, lds_w, N, NBR_LDS_BYTES);
     const size_t lds_a = lds_w + (stage ? 24 * (size_t)N : 0);
     const size_t lds_b = 4 * ((qbar_hist ? (size_t)q_bins + 1 : 0) + (c_hist ? (size_t)c_bins + 1 : 0) + (ab_hist ? 289 : 0));
     const size_t lds_c = 8 * (size_t)N + 16;
     const unsigned t = (unsigned)nw * 64;
-    const bool use_rec = struct_use_rec(b);
 
     oc.zero(o_zero_end); // every counter
     oc.to_device(oc.at<double>(o_nm), norm, sizeof norm); // (norm outlives the copy: finish() drains the stream)
@@ -135,21 +134,12 @@ extern "C" int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb, in
         ba.r0 = (int32_t)r0;
         ba.nr = (int32_t)nr;
         const unsigned g = obs_grid(b, nw, nr * N); // a molecule is a wave's unit
-        if (oc.e == hipSuccess) {
-            ba.q_r0 = q_out ? 0 : (int32_t)r0;
-            if (use_rec && stage)
-                k_bond_qlm<true, true><<<g, t, lds_a, oc.st>>>(s.bv, s.rec, ba);
-            else if (use_rec)
-                k_bond_qlm<true, false><<<g, t, lds_a, oc.st>>>(s.bv, s.rec, ba);
-            else if (stage)
-                k_bond_qlm<false, true><<<g, t, lds_a, oc.st>>>(s.bv, nullptr, ba);
-            else
-                k_bond_qlm<false, false><<<g, t, lds_a, oc.st>>>(s.bv, nullptr, ba);
-        }
-        oc.launched();
-        const unsigned gq = (unsigned)((nr + LO_WAVES - 1) / LO_WAVES);
+        ba.q_r0 = q_out ? 0 : (int32_t)r0;
+        nbr_launch(oc, [](auto rec, auto st) { return k_bond_qlm<decltype(rec)::value, decltype(st)::value>; }, stage, g, t, lds_a,
+                   lds_a, ba);
+        const unsigned gq = (unsigned)((nr + NBR_WAVES - 1) / NBR_WAVES);
         if (oc.e == hipSuccess && sums)
-            k_local_qsum<<<gq, LO_WAVES * 64, 0, oc.st>>>(ba.q_all + (q_out ? r0 * N : 0), oc.at<double>(o_s1) + 2 * r0, (int)N,
+            k_local_qsum<<<gq, NBR_WAVES * 64, 0, oc.st>>>(ba.q_all + (q_out ? r0 * N : 0), oc.at<double>(o_s1) + 2 * r0, (int)N,
                                                           (int)nr);
         oc.launched();
         if (oc.e == hipSuccess && phase_b) {
@@ -158,7 +148,7 @@ extern "C" int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb, in
         }
         oc.launched();
         if (oc.e == hipSuccess && sums)
-            k_local_qsum<<<gq, LO_WAVES * 64, 0, oc.st>>>(ba.qbar_all + (qbar_out ? r0 * N : 0), oc.at<double>(o_s2) + 2 * r0,
+            k_local_qsum<<<gq, NBR_WAVES * 64, 0, oc.st>>>(ba.qbar_all + (qbar_out ? r0 * N : 0), oc.at<double>(o_s2) + 2 * r0,
                                                           (int)N, (int)nr);
         oc.launched();
         if (oc.e == hipSuccess && phase_c)

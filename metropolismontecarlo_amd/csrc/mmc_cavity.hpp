@@ -2,7 +2,9 @@
 // in every replica, read-only beside the chains.  The arithmetic is stated in include/mmc_hip.h
 // ("Cavities and occupancy") and restated in numpy by tests/cavity_ref.py.
 //
-// The scheme is mmc_local.hpp's with a block of 64 probes as the unit and a LANE per probe.  A
+// The scheme is mmc_nbr.hpp's with a block of 64 probes as the unit and a LANE per probe -- in a copy of
+// this kernel's own (site read, staging, run walk): on Sites, stage_sites and RunCursor its walk over
+// the sites compiled to code that ran 1.7 % slower (profiles/nbr_scaffold_bench.json).  A
 // persistent workgroup takes a contiguous run of the R ceil(n_probe / 64) blocks; for every replica
 // its run touches it copies the replica's site positions into LDS once (24 bytes per molecule, SoA),
 // and its waves then take the run's blocks of that replica in turn.  The only workgroup barriers are
@@ -27,11 +29,9 @@
 // nearest site), added to the 64-bit global ones whenever the wave leaves a replica, where the lanes'
 // 64-bit moment sums are reduced and added too -- integer adds, any order.
 #pragma once
-#include "mmc_local.hpp"
+#include "mmc_nbr.hpp"
 #include "mmc_propose.hpp"
 
-#define CV_WAVES 4                    // waves per workgroup (fewer where the counters would not fit: host)
-#define CV_LDS_BYTES 65536            // dynamic LDS a workgroup may ask for without opting in
 #define CV_MAX_RADII 8                // == MMC_CAVITY_MAX_RADII (include/mmc_hip.h)
 #define CV_SLOT 0x50000000u           // == MMC_SLOT_CAVITY == MMC_SLOT_WIDOM: slots +0 and +1
 
@@ -60,7 +60,7 @@ __device__ __forceinline__ unsigned long long cv_wave_sum(unsigned long long v)
 {
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1)
-        v += lo_shfl_xor(v, m);
+        v += wave_shfl_xor_u64(v, m);
     return v; // in every lane
 }
 
@@ -72,7 +72,7 @@ __device__ __forceinline__ unsigned long long cv_wave_sum(unsigned long long v)
 // dynamic LDS: [nw][K (n_cap + 1) + nn_bins + 1] counters (without occ_hist no occupancy bins, without
 // nn_hist none of the nearest site), rounded up to 16 bytes, then (STAGE) 3 N doubles.
 template <bool REC, bool STAGE>
-__global__ __launch_bounds__(CV_WAVES * 64) void k_cavity_lane(BatchView bv, const double *__restrict__ rec,
+__global__ __launch_bounds__(NBR_WAVES * 64) void k_cavity_lane(BatchView bv, const double *__restrict__ rec,
                                                                CavityArgs ca)
 {
     extern __shared__ __align__(16) unsigned char cv_lds[];

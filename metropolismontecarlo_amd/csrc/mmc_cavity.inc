@@ -3,8 +3,6 @@
 // mmc_units.inc (ObsCall).
 #include "mmc_cavity.hpp"
 
-static_assert(CV_WAVES == TILE_WAVES && CV_LDS_BYTES == TILE_LDS_BYTES, "tile_waves sizes the workgroup");
-
 static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t draw0, const double *points_in,
                           bool at, int32_t site, int32_t n_radii, const double *radii, int32_t n_cap,
                           int32_t nn_bins, double nn_max, int32_t per_replica, uint64_t *occ_hist,
@@ -37,9 +35,9 @@ static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t 
     if (at)
         for (int64_t q = 0; q < 3 * R * P; q++)
             MMC_REQUIRE(std::isfinite(points_in[q]), MMC_ERR_ARG, "%s: non-finite points_in", what);
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(radii[n_radii - 1] <= min_box / 2.0, MMC_ERR_ARG,
-                "%s: radius %g exceeds half of the smallest box %g", what, radii[n_radii - 1], min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(radii[n_radii - 1] <= box_min / 2.0, MMC_ERR_ARG,
+                "%s: radius %g exceeds half of the smallest box %g", what, radii[n_radii - 1], box_min);
     // the moment sums: a probe adds at most N^2
     MMC_REQUIRE((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)R * (unsigned __int128)P
                     < ((unsigned __int128)1 << 63),
@@ -90,27 +88,17 @@ static int32_t cavity_run(mmc_batch *b, int64_t n_probe, uint64_t seed, int64_t 
     // waves per workgroup: as many as keep their counters within half of the LDS; the site positions
     // are staged when they fit in the rest
     const size_t per_wave = 4 * (n_occ + n_nn);
-    const int nw = tile_waves(CV_LDS_BYTES / 2, per_wave);
+    const int nw = tile_waves(NBR_LDS_BYTES / 2, per_wave);
     const size_t lds_w = ((size_t)nw * per_wave + 15) & ~(size_t)15;
-    const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= CV_LDS_BYTES;
+    const bool stage = stage_fits(b, lds_w, N, NBR_LDS_BYTES);
     const size_t lds = lds_w + (stage ? 24 * (size_t)N : 0);
     const unsigned g = obs_grid(b, nw, R * ((P + 63) / 64)), t = (unsigned)nw * 64; // a block of 64 probes is a wave's unit
 
     oc.zero(o_pt);
     if (at)
         oc.to_device(oc.at<double>(o_pt), points_in, pt_bytes);
-    if (oc.e == hipSuccess) {
-        const bool use_rec = struct_use_rec(b);
-        if (use_rec && stage)
-            k_cavity_lane<true, true><<<g, t, lds, oc.st>>>(s.bv, s.rec, ca);
-        else if (use_rec)
-            k_cavity_lane<true, false><<<g, t, lds, oc.st>>>(s.bv, s.rec, ca);
-        else if (stage)
-            k_cavity_lane<false, true><<<g, t, lds, oc.st>>>(s.bv, nullptr, ca);
-        else
-            k_cavity_lane<false, false><<<g, t, lds, oc.st>>>(s.bv, nullptr, ca);
-    }
-    oc.launched();
+    nbr_launch(oc, [](auto rec, auto st) { return k_cavity_lane<decltype(rec)::value, decltype(st)::value>; }, stage, g, t, lds, lds,
+               ca);
     oc.fetch(occ_hist, oc.at<char>(o_oh), oh_bytes);
     oc.fetch(occ_mom, oc.at<char>(o_om), om_bytes);
     oc.fetch(nn_hist, oc.at<char>(o_nh), nh_bytes);

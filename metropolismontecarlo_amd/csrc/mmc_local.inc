@@ -2,8 +2,6 @@
 // kernels are in mmc_local.hpp).  Included by mmc_hip.hip after mmc_units.inc (ObsCall).
 #include "mmc_local.hpp"
 
-static_assert(LO_WAVES == TILE_WAVES && LO_LDS_BYTES == TILE_LDS_BYTES, "tile_waves sizes the workgroup");
-
 extern "C" int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t q_bins,
                                          int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist,
                                          double *q_sum, int32_t *nbr_out, double *q_out, uint8_t *hb_out)
@@ -19,9 +17,9 @@ extern "C" int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_h
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(r_hb <= min_box / 2.0, MMC_ERR_ARG,
-                "mmc_batch_local_order: r_hb %g exceeds half of the smallest box %g", r_hb, min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(r_hb <= box_min / 2.0, MMC_ERR_ARG,
+                "mmc_batch_local_order: r_hb %g exceeds half of the smallest box %g", r_hb, box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 5 && N <= (1 << 21), MMC_ERR_UNSUPPORTED,
@@ -56,28 +54,18 @@ extern "C" int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_h
 
     // waves per workgroup: as many as keep their counters and candidate lists within half of the LDS;
     // the O positions are staged when they fit in the rest
-    const size_t per_wave = 4 * ((size_t)q_bins + LO_HB_ROWS + LO_CAND);
-    const int nw = tile_waves(LO_LDS_BYTES / 2, per_wave);
+    const size_t per_wave = 4 * ((size_t)q_bins + LO_HB_ROWS + NBR_CAND);
+    const int nw = tile_waves(NBR_LDS_BYTES / 2, per_wave);
     const size_t lds_w = ((size_t)nw * per_wave + 15) & ~(size_t)15;
-    const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= LO_LDS_BYTES;
+    const bool stage = stage_fits(b, lds_w, N, NBR_LDS_BYTES);
     const size_t lds = lds_w + (stage ? 24 * (size_t)N : 0);
     const unsigned g = obs_grid(b, nw, R * N), t = (unsigned)nw * 64; // a molecule is a wave's unit
 
     oc.zero(o_qs);
-    if (oc.e == hipSuccess) {
-        const bool use_rec = struct_use_rec(b);
-        if (use_rec && stage)
-            k_local_order_wave<true, true><<<g, t, lds, oc.st>>>(s.bv, s.rec, la);
-        else if (use_rec)
-            k_local_order_wave<true, false><<<g, t, lds, oc.st>>>(s.bv, s.rec, la);
-        else if (stage)
-            k_local_order_wave<false, true><<<g, t, lds, oc.st>>>(s.bv, nullptr, la);
-        else
-            k_local_order_wave<false, false><<<g, t, lds, oc.st>>>(s.bv, nullptr, la);
-    }
-    oc.launched();
+    nbr_launch(oc, [](auto rec, auto st) { return k_local_order_wave<decltype(rec)::value, decltype(st)::value>; }, stage, g, t,
+               lds, lds, la);
     if (oc.e == hipSuccess && q_sum)
-        k_local_qsum<<<(unsigned)((R + LO_WAVES - 1) / LO_WAVES), LO_WAVES * 64, 0, oc.st>>>(
+        k_local_qsum<<<(unsigned)((R + NBR_WAVES - 1) / NBR_WAVES), NBR_WAVES * 64, 0, oc.st>>>(
             la.q_all, oc.at<double>(o_qs), (int)N, (int)R);
     oc.launched();
     oc.fetch(hb_hist, oc.at<char>(o_hb), hb_bytes);

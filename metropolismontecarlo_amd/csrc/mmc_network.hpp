@@ -3,12 +3,13 @@
 //                     of the bond graph on the selected sites, their sizes and the axes along which
 //                     they wrap the periodic box
 // The definitions are stated in include/mmc_hip.h ("Hydrogen-bond network") and restated in numpy by
-// tests/network_ref.py; the bond test is k_local_order_wave's (lo_bond, mmc_local.hpp).
+// tests/network_ref.py; staging, scan and bond test are mmc_nbr.hpp's
+// (stage_sites, scan_candidates, HbPair).
 //
 // One persistent workgroup per replica, whole replicas in turn.  The criteria of a call are worked
 // off in groups of `group`: as many as have their adjacency lists in the workgroup's LDS at once.
 // One group, one replica:
-//   stage    the replica's O positions into LDS (24 bytes per molecule, SoA), as k_local_order_wave.
+//   stage    the replica's O positions into LDS (stage_sites).
 //   bonds    every wave takes molecules i = wave, wave + nw, ...; lane l scans j = l, l + 64, ... and
 //            lanes with r^2 < max r_hb^2 of the group append j to the wave's candidate list (ballot +
 //            prefix count), worked off 64 at a time in ascending j: lane n loads candidate n's sites,
@@ -35,10 +36,9 @@
 // or workgroups can change a bit.  Global atomics: the nonzero bins of the two histograms, once per
 // (replica, criterion).
 #pragma once
-#include "mmc_local.hpp"
+#include "mmc_nbr.hpp"
 
 #define NET_THREADS 1024        // the largest workgroup (the host launches 4, 8 or 16 waves)
-#define NET_CAND 128            // candidate slots per wave: at most 63 pending + 64 appended
 #define NET_NONE 0xFFFFu        // the label of a molecule that is no site
 #define NET_RED 32              // [0..16] molecules by degree, then NET_R_*
 #define NET_R_FLAG 17
@@ -77,7 +77,7 @@ __host__ __device__ inline NetLds net_lds(int n_mol, int group, int nw)
     l.deg = l.adj + 2 * (size_t)MMC_NET_MAX_DEG * group * n_mol;     // lists [group][16][N] of 16 bits
     l.hist = up(l.deg + (size_t)group * n_mol);                      // degrees [group][N] of 8 bits
     l.cand = up(l.hist + 4 * ((size_t)n_mol + 1));                   // clusters by size [N + 1]
-    l.red = l.cand + 4 * (size_t)nw * NET_CAND;
+    l.red = l.cand + 4 * (size_t)nw * NBR_CAND;
     l.bytes = l.red + 4 * NET_RED;
     return l;
 }
@@ -97,8 +97,10 @@ __global__ __launch_bounds__(NET_THREADS) void k_hbond_network(BatchView bv, con
     unsigned short *const adj = reinterpret_cast<unsigned short *>(nt_lds + lo.adj);
     unsigned char *const degc = nt_lds + lo.deg;
     unsigned *const shist = reinterpret_cast<unsigned *>(nt_lds + lo.hist);
-    int *const cand = reinterpret_cast<int *>(nt_lds + lo.cand) + wv * NET_CAND;
+    int *const cand = reinterpret_cast<int *>(nt_lds + lo.cand) + wv * NBR_CAND;
     unsigned *const red = reinterpret_cast<unsigned *>(nt_lds + lo.red);
+
+    const Sites<REC, true> sites{ bv, rec, pos };
 
     for (int r = (int)blockIdx.x; r < na.R; r += (int)gridDim.x) {
         const BoxConsts bc = box_consts(na.box_r ? na.box_r[r] : bv.box);
@@ -110,36 +112,18 @@ __global__ __launch_bounds__(NET_THREADS) void k_hbond_network(BatchView bv, con
             for (int k = 0; k < g; k++)
                 rmax2 = fmax(rmax2, na.rhb2[k0 + k]);
 
-            __syncthreads(); // every thread has left the labels of the pass before
-            for (int j = tid; j < n_mol; j += nt) {
-                double x, y, z;
-                if constexpr (REC) {
-                    const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-                    const double2 v0 = *reinterpret_cast<const double2 *>(p);
-                    x = v0.x; y = v0.y; z = p[2];
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-                    x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-                }
-                pos[j] = x; pos[n_mol + j] = y; pos[2 * n_mol + j] = z;
-            }
-            __syncthreads();
+            stage_sites(sites, r); // (its first barrier: every thread has left the labels of the pass before)
 
             // ---- bonds: a wave per molecule i ------------------------------------------------------
             for (int i = wv; i < n_mol; i += nw) {
                 double ci[9]; // the wave's molecule: wave-uniform
                 load_sites9<REC>(bv, rec, r, i, ci);
                 double ui[2][3]; // d(O_i, H_i,h)
-#pragma unroll
-                for (int h = 0; h < 2; h++)
-#pragma unroll
-                    for (int d = 0; d < 3; d++)
-                        ui[h][d] = vector1D(ci[d], ci[3 + 3 * h + d], bc);
+                hb_arms(ci, bc, ui);
                 int dg[MMC_NET_MAX_CRIT]; // the degrees so far: wave-uniform
 #pragma unroll
                 for (int k = 0; k < MMC_NET_MAX_CRIT; k++)
                     dg[k] = 0;
-                int n_cand = 0;
 
                 // candidates [0, n) of the list, one per lane (n <= 64), in ascending j
                 auto bonds = [&](int n) {
@@ -148,40 +132,17 @@ __global__ __launch_bounds__(NET_THREADS) void k_hbond_network(BatchView bv, con
                         const int j = cand[lane];
                         double cj[9];
                         load_sites9<REC>(bv, rec, r, j, cj);
-                        const double vx = vector1D(ci[0], cj[0], bc), vy = vector1D(ci[1], cj[1], bc),
-                                     vz = vector1D(ci[2], cj[2], bc);
-                        const double vv = (vx * vx + vy * vy) + vz * vz;
-                        const double wx = vector1D(cj[0], ci[0], bc), wy = vector1D(cj[1], ci[1], bc),
-                                     wz = vector1D(cj[2], ci[2], bc);
-                        const double ww = (wx * wx + wy * wy) + wz * wz;
-                        // the boxes vector1D added to O_j - O_i, per component, + 1
-                        unsigned code = 0u;
-#pragma unroll
-                        for (int d = 2; d >= 0; d--) {
-                            const double dd = cj[d] - ci[d];
-                            const unsigned m1 = fabs(dd) < bc.half ? 1u : (dd > 0.0 ? 0u : 2u);
-                            code = 3u * code + m1;
-                        }
-                        entry = (unsigned)j | (code << 11);
-                        double t[4], q[4]; // u . v and |u|^2 |v|^2: i's hydrogens, then j's
-#pragma unroll
-                        for (int h = 0; h < 2; h++) {
-                            t[h] = (ui[h][0] * vx + ui[h][1] * vy) + ui[h][2] * vz;
-                            q[h] = ((ui[h][0] * ui[h][0] + ui[h][1] * ui[h][1]) + ui[h][2] * ui[h][2]) * vv;
-                            const double ux = vector1D(cj[0], cj[3 + 3 * h], bc), uy = vector1D(cj[1], cj[4 + 3 * h], bc),
-                                         uz = vector1D(cj[2], cj[5 + 3 * h], bc);
-                            t[2 + h] = (ux * wx + uy * wy) + uz * wz;
-                            q[2 + h] = ((ux * ux + uy * uy) + uz * uz) * ww;
-                        }
+                        const HbPair hp(ci, ui, cj, bc);
+                        entry = (unsigned)j | (hp.code << 11);
 #pragma unroll
                         for (int k = 0; k < MMC_NET_MAX_CRIT; k++)
-                            if (k < g) { // lo_bond with criterion k0 + k, four times
+                            if (k < g) { // criterion k0 + k: any of the four hydrogens, inside its own radius
                                 const double c2 = na.cos2[k0 + k];
                                 bool b = false;
 #pragma unroll
                                 for (int h = 0; h < 4; h++)
-                                    b = b || (t[h] > 0.0 && t[h] * t[h] >= c2 * q[h]);
-                                if (b && vv < na.rhb2[k0 + k])
+                                    b = b || hp.bonded(h, c2);
+                                if (b && hp.vv < na.rhb2[k0 + k])
                                     bm |= 1u << k;
                             }
                     }
@@ -197,35 +158,7 @@ __global__ __launch_bounds__(NET_THREADS) void k_hbond_network(BatchView bv, con
                         }
                 };
 
-                for (int jb = 0; jb < n_mol; jb += 64) {
-                    const int j = jb + lane;
-                    const bool valid = j < n_mol && j != i;
-                    const int jj = min(j, n_mol - 1);
-                    const double dx = vector1D_abs(ci[0], pos[jj], bc), dy = vector1D_abs(ci[1], pos[n_mol + jj], bc),
-                                 dz = vector1D_abs(ci[2], pos[2 * n_mol + jj], bc);
-                    const double r2 = (dx * dx + dy * dy) + dz * dz;
-                    const bool near = valid && r2 < rmax2;
-                    const unsigned long long nm = wave_ballot(near);
-                    if (nm != 0ULL) { // wave-uniform
-                        if (near)
-                            cand[n_cand + lanes_below(nm)] = j; // n_cand <= 63 here: the slot is < NET_CAND
-                        n_cand += __popcll(nm);
-                        wave_sync();
-                        if (n_cand >= 64) {
-                            bonds(64);
-                            const int rest = n_cand - 64; // <= 63: one lane each
-                            const int mv = lane < rest ? cand[64 + lane] : 0;
-                            wave_sync();
-                            if (lane < rest)
-                                cand[lane] = mv;
-                            wave_sync();
-                            n_cand = rest;
-                        }
-                    }
-                }
-                if (n_cand > 0)
-                    bonds(n_cand);
-                wave_sync(); // the candidate list is rewritten by the wave's next molecule
+                scan_candidates(sites, r, i, ci[0], ci[1], ci[2], bc, rmax2, cand, lane, [](int, bool, double) {}, bonds);
                 if (lane == 0) {
 #pragma unroll
                     for (int k = 0; k < MMC_NET_MAX_CRIT; k++)

@@ -26,10 +26,10 @@ extern "C" int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const d
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol, K = n_crit;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
+    const double box_min = min_box(s);
     for (int k = 0; k < n_crit; k++)
-        MMC_REQUIRE(r_hb[k] <= min_box / 2.0, MMC_ERR_ARG,
-                    "mmc_batch_hbond_network: r_hb[%d] = %g exceeds half of the smallest box %g", k, r_hb[k], min_box);
+        MMC_REQUIRE(r_hb[k] <= box_min / 2.0, MMC_ERR_ARG,
+                    "mmc_batch_hbond_network: r_hb[%d] = %g exceeds half of the smallest box %g", k, r_hb[k], box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 2 && N <= MMC_NET_MAX_MOL, MMC_ERR_UNSUPPORTED,
@@ -82,20 +82,9 @@ extern "C" int32_t mmc_batch_hbond_network(mmc_batch *b, int32_t n_crit, const d
     na.per_replica = per_replica ? 1 : 0;
     na.R = (int32_t)R;
 
-    const bool use_rec = struct_use_rec(b);
-    if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_sdf_wave
-        oc.e = hipFuncSetAttribute(use_rec ? reinterpret_cast<const void *>(k_hbond_network<true>)
-                                           : reinterpret_cast<const void *>(k_hbond_network<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
     if (o_st > 0)
         oc.zero(o_st);
-    if (oc.e == hipSuccess) {
-        if (use_rec)
-            k_hbond_network<true><<<wgs, nw * 64, lds, oc.st>>>(s.bv, s.rec, na);
-        else
-            k_hbond_network<false><<<wgs, nw * 64, lds, oc.st>>>(s.bv, nullptr, na);
-    }
-    oc.launched();
+    nbr_launch(oc, [](auto rec) { return k_hbond_network<decltype(rec)::value>; }, wgs, (unsigned)nw * 64, lds, lds_max, na);
     oc.fetch(size_hist, oc.at<char>(o_sh), sh_bytes);
     oc.fetch(deg_hist, oc.at<char>(o_dh), dh_bytes);
     oc.fetch(stats, oc.at<char>(o_st), st_bytes);

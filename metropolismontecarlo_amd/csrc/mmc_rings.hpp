@@ -5,7 +5,10 @@
 //                   homodromic or not, and per molecule
 // The definitions are stated in include/mmc_hip.h ("Hydrogen-bond rings") and restated in numpy by
 // tests/rings_ref.py.  The graph is k_hbond_network's for one criterion; this kernel carries its own
-// copy of that scan (mmc_network.hpp stays as it is), which also keeps the two donation bits.
+// copy of mmc_nbr.hpp's staging, scan (scan_candidates) and bond test (HbPair), which also keeps the two
+// donation bits: on the shared helpers its ring search, untouched, compiled to code that ran 0.5 to
+// 0.9 % slower at n_max = 6 and 8 (profiles/nbr_scaffold_bench.json), so the copy stays.  A change to
+// either is to be made in both.
 //
 // One persistent workgroup per replica, whole replicas in turn.  One replica:
 //   stage    the O positions into LDS, as k_hbond_network.
@@ -80,7 +83,7 @@ __host__ __device__ inline RingLds ring_lds(int n_mol, int nw)
     l.lev = up(l.deg + (size_t)n_mol);                                // degrees [N] of 8 bits
     l.lev_stride = (int)up((size_t)n_mol);
     l.cand = l.lev + (size_t)nw * l.lev_stride;                       // levels [nw][N] of 8 bits
-    l.red = l.cand + 4 * (size_t)nw * NET_CAND;
+    l.red = l.cand + 4 * (size_t)nw * NBR_CAND;
     l.bytes = l.red + 4 * RG_RED;
     return l;
 }
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_hbond_rings(BatchView bv, const 
     unsigned *const adj = reinterpret_cast<unsigned *>(rg_lds + lo.adj);
     unsigned char *const degc = rg_lds + lo.deg;
     unsigned char *const lev = rg_lds + lo.lev + (size_t)wv * lo.lev_stride;
-    int *const cand = reinterpret_cast<int *>(rg_lds + lo.cand) + wv * NET_CAND;
+    int *const cand = reinterpret_cast<int *>(rg_lds + lo.cand) + wv * NBR_CAND;
     unsigned *const red = reinterpret_cast<unsigned *>(rg_lds + lo.red);
 
     for (int rl = (int)blockIdx.x; rl < ra.nr; rl += (int)gridDim.x) {
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_hbond_rings(BatchView bv, const 
                                      uz = vector1D(cj[2], cj[5 + 3 * h], bc);
                         const double t1 = (ux * wx + uy * wy) + uz * wz;
                         const double q1 = ((ux * ux + uy * uy) + uz * uz) * ww;
-                        don[0] = don[0] || (t0 > 0.0 && t0 * t0 >= ra.cos2 * q0); // lo_bond
+                        don[0] = don[0] || (t0 > 0.0 && t0 * t0 >= ra.cos2 * q0); // HbPair::bonded
                         don[1] = don[1] || (t1 > 0.0 && t1 * t1 >= ra.cos2 * q1);
                     }
                     const bool in = vv < ra.rhb2;
@@ -243,7 +246,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_hbond_rings(BatchView bv, const 
                 const unsigned long long nm = wave_ballot(near);
                 if (nm != 0ULL) { // wave-uniform
                     if (near)
-                        cand[n_cand + lanes_below(nm)] = j; // n_cand <= 63 here: the slot is < NET_CAND
+                        cand[n_cand + lanes_below(nm)] = j; // n_cand <= 63 here: the slot is < NBR_CAND
                     n_cand += __popcll(nm);
                     wave_sync();
                     if (n_cand >= 64) {

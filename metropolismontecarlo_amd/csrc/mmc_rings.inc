@@ -19,9 +19,9 @@ extern "C" int32_t mmc_batch_hbond_rings(mmc_batch *b, double r_hb, double cos_h
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(r_hb <= min_box / 2.0, MMC_ERR_ARG, "mmc_batch_hbond_rings: r_hb = %g exceeds half of the smallest box %g",
-                r_hb, min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(r_hb <= box_min / 2.0, MMC_ERR_ARG, "mmc_batch_hbond_rings: r_hb = %g exceeds half of the smallest box %g",
+                r_hb, box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 2 && N <= MMC_NET_MAX_MOL, MMC_ERR_UNSUPPORTED,
@@ -69,11 +69,6 @@ extern "C" int32_t mmc_batch_hbond_rings(mmc_batch *b, double r_hb, double cos_h
     ra.n_max = n_max;
     ra.per_replica = per_replica ? 1 : 0;
 
-    const bool use_rec = struct_use_rec(b);
-    if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_hbond_network
-        oc.e = hipFuncSetAttribute(use_rec ? reinterpret_cast<const void *>(k_hbond_rings<true>)
-                                           : reinterpret_cast<const void *>(k_hbond_rings<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
     oc.zero(o_zero_end);
     for (int64_t r0 = 0; r0 < R; r0 += chunk) {
         const int64_t nr = std::min(chunk, R - r0);
@@ -82,13 +77,7 @@ extern "C" int32_t mmc_batch_hbond_rings(mmc_batch *b, double r_hb, double cos_h
         const unsigned wgs = obs_grid(b, nw, nr * nw); // a replica is a workgroup's unit
         if (oc.e == hipSuccess && ring_out) // unused rows are -1
             oc.e = hipMemsetAsync(ra.ring, 0xFF, rg_rep * (size_t)nr, oc.st);
-        if (oc.e == hipSuccess) {
-            if (use_rec)
-                k_hbond_rings<true><<<wgs, nw * 64, lds, oc.st>>>(s.bv, s.rec, ra);
-            else
-                k_hbond_rings<false><<<wgs, nw * 64, lds, oc.st>>>(s.bv, nullptr, ra);
-        }
-        oc.launched();
+        nbr_launch(oc, [](auto rec) { return k_hbond_rings<decltype(rec)::value>; }, wgs, (unsigned)nw * 64, lds, lds_max, ra);
         // (the copies run on the launch's stream: the next launch overwrites the staging after them)
         if (count_out)
             oc.fetch(reinterpret_cast<char *>(count_out) + cn_rep * (size_t)r0, oc.at<char>(o_cn), cn_rep * (size_t)nr);

@@ -8,21 +8,18 @@
 // tests/shell_order_ref.py; slot 0 of a molecule is the heavy atom, slots 1 and 2 the hydrogens.
 // The per-replica sums are k_local_qsum's (mmc_local.hpp) over the per-molecule arrays.
 //
-// The scheme is k_local_order_wave's: a persistent workgroup takes a contiguous run of the R N
-// molecules, stages the O positions of every replica its run touches in LDS (STAGE), and its waves
+// The scheme is mmc_nbr.hpp's: a persistent workgroup takes a contiguous run of the R N molecules
+// (RunCursor), stages the O positions of every replica its run touches in LDS (STAGE), and its waves
 // take the run's molecules of that replica in turn; inside a molecule a wave waits for nobody.
 //
 // One molecule i, one wave:
-//   scan     lane l takes j = l, l + 64, ...: r^2 of d(O_i, O_j) through vector1D_abs (the same bits as
-//            the signed image squared).  Lanes with r^2 < r_list^2 append (bits of r^2, j) to the
-//            wave's list in LDS (ballot + prefix count), in rising j.  A pass that would take the
-//            list beyond MMC_SHELL_CAP flags the molecule and ends its scan: nothing is truncated.
-//   sort     lane n takes entry n and counts the entries with a smaller key, and those before it
-//            with an equal one (the list is in rising j, so that is the order (key, j)): its rank.
-//            It writes its entry to that slot; lane k then owns neighbour k, and the lanes hold the
-//            list in rising r^2 -- every radius selects a prefix of the lanes.
+//   scan     scan_list: (bits of r^2, j) of the O inside r_list to the wave's list in LDS.  A pass
+//            that would take the list beyond MMC_SHELL_CAP flags the molecule and ends its scan:
+//            nothing is truncated.
+//   sort     rank_sort: lane k then owns neighbour k, and the lanes hold the list in rising r^2 --
+//            every radius selects a prefix of the lanes.
 //   bonds    lanes with r^2 < r_hb^2 load their neighbour's nine coordinates and make
-//            k_local_order_wave's four lo_bond tests (only where zeta is asked for).
+//            the four tests of the pair (HbPair; only where zeta is asked for).
 //   reduce   rank bins by lanes < n_rank; LSI and zeta by lane reads and serial sums in rising k;
 //            angles by an outer loop over j < m_ang with lanes k > j taking one cosine each.
 // Counters: 32-bit, in LDS, one set per workgroup that its waves add to with LDS atomics, added to the
@@ -36,7 +33,7 @@
 
 // MMC_SHELL_CAP (64 neighbours in a list: one lane each once sorted) and MMC_SHELL_NBR (16 of them in
 // nbr_out) are include/mmc_hip.h's
-#define SH_LIST_BYTES (12 * MMC_SHELL_CAP) // a wave's list: 64 keys, then 64 indices
+static_assert(MMC_SHELL_CAP == NBR_CAP, "the list of scan_list: one lane per listed neighbour");
 
 struct ShellArgs {
     const double *box_r;            // [R] per-replica boxes, or NULL: bv.box
@@ -55,14 +52,6 @@ struct ShellArgs {
     int32_t per_replica, R;
 };
 
-// lane k's value (k wave-uniform) in a scalar register pair
-__device__ __forceinline__ double sh_read(double v, int k)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, k);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), k);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 // (int)floor(x) clamped to [0, top]; x finite or +-inf
 __device__ __forceinline__ int sh_bin(double x, int top)
 {
@@ -70,99 +59,43 @@ __device__ __forceinline__ int sh_bin(double x, int top)
 }
 
 // REC, STAGE, grid: as k_local_order_wave.
-// dynamic LDS: [nw] lists of SH_LIST_BYTES, [hs] counters, then (STAGE) 3 N doubles at the next
+// dynamic LDS: [nw] lists of NBR_LIST_BYTES, [hs] counters, then (STAGE) 3 N doubles at the next
 // multiple of 16 bytes.
 template <bool REC, bool STAGE>
-__global__ __launch_bounds__(LO_WAVES * 64) void k_shell_order_wave(BatchView bv, const double *__restrict__ rec,
+__global__ __launch_bounds__(NBR_WAVES * 64) void k_shell_order_wave(BatchView bv, const double *__restrict__ rec,
                                                                     ShellArgs sa)
 {
     extern __shared__ __align__(16) unsigned char sh_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
     const int n_mol = bv.n_mol, hs = sa.hs;
-    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(sh_lds + (size_t)wv * SH_LIST_BYTES);
+    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(sh_lds + (size_t)wv * NBR_LIST_BYTES);
     int *const idx = reinterpret_cast<int *>(keys + MMC_SHELL_CAP);
-    unsigned *const hw = reinterpret_cast<unsigned *>(sh_lds + (size_t)nw * SH_LIST_BYTES); // the workgroup's
+    unsigned *const hw = reinterpret_cast<unsigned *>(sh_lds + (size_t)nw * NBR_LIST_BYTES); // the workgroup's
     double *const pos = reinterpret_cast<double *>(
-        sh_lds + (((size_t)nw * SH_LIST_BYTES + 4 * (size_t)hs + 15) & ~(size_t)15));
+        sh_lds + (((size_t)nw * NBR_LIST_BYTES + 4 * (size_t)hs + 15) & ~(size_t)15));
     for (int q = tid; q < hs; q += (int)blockDim.x)
         hw[q] = 0u;
     __syncthreads();
 
     const bool want_lsi = sa.lsi_hist || sa.lsi_all, want_zeta = sa.zeta_hist || sa.zeta_all;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    const int64_t M = (int64_t)sa.R * n_mol;
-    const int64_t m0 = M * blockIdx.x / gridDim.x, m1 = M * (blockIdx.x + 1) / gridDim.x;
+    const Sites<REC, STAGE> sites{ bv, rec, pos };
 
-    // the O of molecule j (j < n_mol) of replica r
-    auto oxygen = [&](int r, int j, double &x, double &y, double &z) {
-        if constexpr (STAGE) {
-            x = pos[j]; y = pos[n_mol + j]; z = pos[2 * n_mol + j];
-        } else if constexpr (REC) {
-            const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-            const double2 v0 = *reinterpret_cast<const double2 *>(p);
-            x = v0.x; y = v0.y; z = p[2];
-        } else {
-            const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-            x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-        }
-    };
-
-    for (int64_t s0 = m0; s0 < m1;) { // the run's molecules of one replica: [i_lo, i_hi) of replica r
-        const int r = (int)(s0 / n_mol);
-        const int i_lo = (int)(s0 - (int64_t)r * n_mol);
-        const int i_hi = (int)min((int64_t)n_mol, (int64_t)i_lo + (m1 - s0));
-        s0 += i_hi - i_lo;
-        if constexpr (STAGE) {
-            __syncthreads(); // every wave has left the previous replica's positions
-            for (int j = tid; j < n_mol; j += (int)blockDim.x) {
-                double x, y, z;
-                if constexpr (REC) {
-                    const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-                    const double2 v0 = *reinterpret_cast<const double2 *>(p);
-                    x = v0.x; y = v0.y; z = p[2];
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-                    x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-                }
-                pos[j] = x; pos[n_mol + j] = y; pos[2 * n_mol + j] = z;
-            }
-            __syncthreads();
-        }
+    for (RunCursor rc(sa.R, n_mol); rc.next();) { // the run's molecules of one replica: [rc.lo, rc.hi) of replica r
+        const int r = rc.r;
+        if constexpr (STAGE)
+            stage_sites(sites, r);
         const BoxConsts bc = box_consts(sa.box_r ? sa.box_r[r] : bv.box);
 
-        for (int i = i_lo + wv; i < i_hi; i += nw) {
+        for (int i = rc.lo + wv; i < rc.hi; i += nw) {
             const int64_t g = (int64_t)r * n_mol + i;
             double ci[9]; // the wave's molecule: wave-uniform
             load_sites9<REC>(bv, rec, r, i, ci); // O, H, H
 
             // ---- scan: the list, unsorted, in rising j
-            int m = 0;
-            bool over = false;
-            for (int jb = 0; jb < n_mol; jb += 64) {
-                const int j = jb + lane;
-                double x, y, z;
-                oxygen(r, min(j, n_mol - 1), x, y, z);
-                const double dx = vector1D_abs(ci[0], x, bc), dy = vector1D_abs(ci[1], y, bc),
-                             dz = vector1D_abs(ci[2], z, bc);
-                const double r2 = (dx * dx + dy * dy) + dz * dz;
-                const bool near = j < n_mol && j != i && r2 < sa.rl2;
-                const unsigned long long nm = wave_ballot(near);
-                if (nm != 0ULL) { // wave-uniform
-                    const int add = __popcll(nm);
-                    if (m + add > MMC_SHELL_CAP) { // more than the lanes can own: flagged, nothing written
-                        over = true;
-                        break;
-                    }
-                    if (near) {
-                        const int slot = m + lanes_below(nm); // < MMC_SHELL_CAP
-                        keys[slot] = (unsigned long long)__double_as_longlong(r2);
-                        idx[slot] = j;
-                    }
-                    m += add;
-                }
-            }
-            wave_sync();
+            int m;
+            const bool over = !scan_list(sites, r, i, ci[0], ci[1], ci[2], bc, sa.rl2, keys, idx, lane, m);
 
             if (over) { // wave-uniform: in no histogram
                 if (lane == 0) {
@@ -181,30 +114,15 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_shell_order_wave(BatchView bv
 
             // ---- sort: lane n's entry to slot rank(n); lane k then reads slot k
             const bool mine = lane < m;
-            unsigned long long key = mine ? keys[lane] : ~0ULL;
-            int jn = mine ? idx[lane] : -1;
-            int rank = 0;
-            for (int e = 0; e < m; e++) {
-                const unsigned long long ke = keys[e]; // one address for the wave: a broadcast
-                rank += (ke < key || (ke == key && e < lane)) ? 1 : 0;
-            }
-            wave_sync(); // every lane has read the unsorted list
-            if (mine) {
-                keys[rank] = key;
-                idx[rank] = jn;
-            }
-            wave_sync();
-            if (mine) {
-                key = keys[lane];
-                jn = idx[lane];
-            }
-            wave_sync(); // the list is rewritten by the wave's next molecule
+            unsigned long long key;
+            int jn;
+            rank_sort(keys, idx, m, lane, key, jn);
 
             // lane k < m: neighbour k.  r^2 from the key; the signed image for the angles
             const double r2 = mine ? __longlong_as_double((long long)key) : 0.0;
             const double rho = sqrt(r2);
             double ox, oy, oz;
-            oxygen(r, mine ? jn : i, ox, oy, oz);
+            sites.get(r, mine ? jn : i, ox, oy, oz);
             const double ex = vector1D(ci[0], ox, bc), ey = vector1D(ci[1], oy, bc), ez = vector1D(ci[2], oz, bc);
 
             // ---- rank histograms: lane k is rank k + 1
@@ -219,14 +137,14 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_shell_order_wave(BatchView bv
                 double lsi = nan;
                 if (n >= 1 && m >= n + 1) { // wave-uniform
                     const double delta = wave_pick(rho, min(lane + 1, 63)) - rho; // lanes < n: gap k + 1
-                    double s = sh_read(delta, 0);
+                    double s = lane_f64(delta, 0);
                     for (int k = 1; k < n; k++)
-                        s = s + sh_read(delta, k);
+                        s = s + lane_f64(delta, k);
                     const double mean = s / (double)n;
                     const double dev = (delta - mean) * (delta - mean);
-                    double v = sh_read(dev, 0);
+                    double v = lane_f64(dev, 0);
                     for (int k = 1; k < n; k++)
-                        v = v + sh_read(dev, k);
+                        v = v + lane_f64(dev, k);
                     lsi = v / (double)n;
                 }
                 if (lane == 0) {
@@ -243,25 +161,15 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_shell_order_wave(BatchView bv
                 if (mine && r2 < sa.rhb2) {
                     double cj[9];
                     load_sites9<REC>(bv, rec, r, jn, cj);
-                    const double vx = vector1D(ci[0], cj[0], bc), vy = vector1D(ci[1], cj[1], bc),
-                                 vz = vector1D(ci[2], cj[2], bc);
-                    const double vv = (vx * vx + vy * vy) + vz * vz;
-                    const double wx = vector1D(cj[0], ci[0], bc), wy = vector1D(cj[1], ci[1], bc),
-                                 wz = vector1D(cj[2], ci[2], bc);
-                    const double ww = (wx * wx + wy * wy) + wz * wz;
-                    bonded = lo_bond(vector1D(ci[0], ci[3], bc), vector1D(ci[1], ci[4], bc), vector1D(ci[2], ci[5], bc),
-                                     vx, vy, vz, vv, sa.cos2) ||
-                             lo_bond(vector1D(ci[0], ci[6], bc), vector1D(ci[1], ci[7], bc), vector1D(ci[2], ci[8], bc),
-                                     vx, vy, vz, vv, sa.cos2) ||
-                             lo_bond(vector1D(cj[0], cj[3], bc), vector1D(cj[1], cj[4], bc), vector1D(cj[2], cj[5], bc),
-                                     wx, wy, wz, ww, sa.cos2) ||
-                             lo_bond(vector1D(cj[0], cj[6], bc), vector1D(cj[1], cj[7], bc), vector1D(cj[2], cj[8], bc),
-                                     wx, wy, wz, ww, sa.cos2);
+                    double ui[2][3];
+                    hb_arms(ci, bc, ui);
+                    const HbPair hp(ci, ui, cj, bc);
+                    bonded = hp.bonded(0, sa.cos2) || hp.bonded(1, sa.cos2) || hp.bonded(2, sa.cos2) || hp.bonded(3, sa.cos2);
                 }
                 const unsigned long long bm = wave_ballot(bonded), fm = wave_ballot(mine && !bonded);
                 double zeta = nan;
                 if (bm != 0ULL && fm != 0ULL) // wave-uniform
-                    zeta = sh_read(rho, __builtin_ctzll(fm)) - sh_read(rho, 63 - __builtin_clzll(bm));
+                    zeta = lane_f64(rho, __builtin_ctzll(fm)) - lane_f64(rho, 63 - __builtin_clzll(bm));
                 if (lane == 0) {
                     if (sa.zeta_hist)
                         atomicAdd(&hw[sa.o_zeta + (bm != 0ULL && fm != 0ULL
@@ -276,7 +184,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void k_shell_order_wave(BatchView bv
             if (sa.ang_hist) { // wave-uniform
                 const int m_ang = __popcll(wave_ballot(mine && r2 < sa.rang2)); // a prefix of the lanes
                 for (int j = 0; j + 1 < m_ang; j++) {
-                    const double jx = sh_read(ex, j), jy = sh_read(ey, j), jz = sh_read(ez, j), j2 = sh_read(r2, j);
+                    const double jx = lane_f64(ex, j), jy = lane_f64(ey, j), jz = lane_f64(ez, j), j2 = lane_f64(r2, j);
                     if (lane > j && lane < m_ang) {
                         const double c = ((jx * ex + jy * ey) + jz * ez) / sqrt(j2 * r2);
                         const int kb = __builtin_isfinite(c) ? sh_bin((c + 1.0) * sa.ang_scale, sa.ang_bins - 1) : sa.ang_bins;

@@ -46,9 +46,9 @@ extern "C" int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double r_l
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(r_list <= min_box / 2.0, MMC_ERR_ARG,
-                "mmc_batch_shell_order: r_list %g exceeds half of the smallest box %g", r_list, min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(r_list <= box_min / 2.0, MMC_ERR_ARG,
+                "mmc_batch_shell_order: r_list %g exceeds half of the smallest box %g", r_list, box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 2 && N <= (1 << 21), MMC_ERR_UNSUPPORTED, "mmc_batch_shell_order: 2 .. 2^21 molecules");
@@ -103,29 +103,19 @@ extern "C" int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double r_l
 
     // waves per workgroup: as many as keep their lists beside the counters within half of the LDS; the
     // O positions are staged when they fit in the rest
-    const int nw = tile_waves(LO_LDS_BYTES / 2 + 4 * hs, SH_LIST_BYTES);
-    const size_t lds_w = ((size_t)nw * SH_LIST_BYTES + 4 * hs + 15) & ~(size_t)15;
-    const bool stage = b->local_stage && lds_w + 24 * (size_t)N <= LO_LDS_BYTES;
+    const int nw = tile_waves(NBR_LDS_BYTES / 2 + 4 * hs, NBR_LIST_BYTES);
+    const size_t lds_w = ((size_t)nw * NBR_LIST_BYTES + 4 * hs + 15) & ~(size_t)15;
+    const bool stage = stage_fits(b, lds_w, N, NBR_LDS_BYTES);
     const size_t lds = lds_w + (stage ? 24 * (size_t)N : 0);
     const unsigned g = obs_grid(b, nw, R * N), t = (unsigned)nw * 64; // a molecule is a wave's unit
 
     oc.zero(o_s1); // every counter
-    if (oc.e == hipSuccess) {
-        const bool use_rec = struct_use_rec(b);
-        if (use_rec && stage)
-            k_shell_order_wave<true, true><<<g, t, lds, oc.st>>>(s.bv, s.rec, sa);
-        else if (use_rec)
-            k_shell_order_wave<true, false><<<g, t, lds, oc.st>>>(s.bv, s.rec, sa);
-        else if (stage)
-            k_shell_order_wave<false, true><<<g, t, lds, oc.st>>>(s.bv, nullptr, sa);
-        else
-            k_shell_order_wave<false, false><<<g, t, lds, oc.st>>>(s.bv, nullptr, sa);
-    }
-    oc.launched();
-    const unsigned gq = (unsigned)((R + LO_WAVES - 1) / LO_WAVES);
+    nbr_launch(oc, [](auto rec, auto st) { return k_shell_order_wave<decltype(rec)::value, decltype(st)::value>; }, stage, g, t,
+               lds, lds, sa);
+    const unsigned gq = (unsigned)((R + NBR_WAVES - 1) / NBR_WAVES);
     if (oc.e == hipSuccess && sums) {
-        k_local_qsum<<<gq, LO_WAVES * 64, 0, oc.st>>>(sa.lsi_all, oc.at<double>(o_s1), (int)N, (int)R);
-        k_local_qsum<<<gq, LO_WAVES * 64, 0, oc.st>>>(sa.zeta_all, oc.at<double>(o_s2), (int)N, (int)R);
+        k_local_qsum<<<gq, NBR_WAVES * 64, 0, oc.st>>>(sa.lsi_all, oc.at<double>(o_s1), (int)N, (int)R);
+        k_local_qsum<<<gq, NBR_WAVES * 64, 0, oc.st>>>(sa.zeta_all, oc.at<double>(o_s2), (int)N, (int)R);
     }
     oc.launched();
     oc.fetch(flagged, oc.at<char>(o_fl), fl_bytes);

@@ -6,10 +6,12 @@
 //   the pair passes over the i < j triangle: mmc_batch_rdf_sites, _orient_corr and _pair_energy
 //   (tile_plan, tile_waves; the kernels' shared part is mmc_tiles.hpp), and mmc_batch_sdf on the
 //   same tiles with a grid of its own per workgroup;
-//   and mmc_batch_dipoles, _structure_factor, _local_order, _shell_order, _bond_order, _hbond_network,
-//   _cavity / _cavity_at, _volume_perturb.
-// Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels" and
-// "Tile passes".
+//   the neighbour scans: mmc_batch_local_order, _shell_order, _bond_order, _voronoi, _hbond_network,
+//   _hbond_rings and _cavity / _cavity_at (min_box, stage_fits, nbr_launch; the kernels' shared part is
+//   mmc_nbr.hpp);
+//   and mmc_batch_dipoles, _structure_factor, _volume_perturb.
+// Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels",
+// "Tile passes" and "Neighbour scans".
 #include "mmc_unit.hpp"
 #include "mmc_tiles.hpp"
 
@@ -205,6 +207,56 @@ static unsigned obs_grid(const mmc_batch *b, int nw, int64_t n_units)
 {
     const int64_t wgs = b->wave_wgs > 0 ? b->wave_wgs : (int64_t)(16 / nw) * b->n_cus;
     return (unsigned)std::max<int64_t>(1, std::min(wgs, (n_units + nw - 1) / nw));
+}
+
+// ---- the neighbour scans (mmc_nbr.hpp): local order, cavities, network, shell order, bond order,
+// rings, Voronoi cells
+
+// The smallest box of the batch's replicas: no radius of a scan may exceed half of it.
+static double min_box(const DeviceSystem &s)
+{
+    return s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
+}
+
+// Are a replica's sites staged in LDS (24 bytes per molecule behind a workgroup's `fixed_bytes`)?
+// Where they fit in `limit`, unless option "local_stage" is 0.
+static bool stage_fits(const mmc_batch *b, size_t fixed_bytes, int64_t N, size_t limit)
+{
+    return b->local_stage && fixed_bytes + 24 * (size_t)N <= limit;
+}
+
+template <class Args>
+using nbr_kernel_t = void (*)(BatchView, const double *, Args);
+
+// One launch of a scan kernel on the call's stream: the records where the batch keeps them in step
+// (struct_use_rec), dynamic LDS beyond what needs no opting in raised to lds_opt_in first.
+template <class Args>
+static void nbr_launch_one(ObsCall &oc, nbr_kernel_t<Args> k, bool use_rec, unsigned g, unsigned t, size_t lds, size_t lds_opt_in,
+                           const Args &a)
+{
+    if (oc.e == hipSuccess && lds > TILE_LDS_BYTES)
+        oc.e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_opt_in);
+    if (oc.e == hipSuccess)
+        k<<<g, t, lds, oc.st>>>(oc.b->sys.bv, use_rec ? oc.b->sys.rec : nullptr, a);
+    oc.launched();
+}
+// K<REC, STAGE> of a kernel template K, given as pick(rec, stage) = K<decltype(rec)::value, decltype(stage)::value> ...
+template <class Args, class Pick>
+static void nbr_launch(ObsCall &oc, Pick pick, bool stage, unsigned g, unsigned t, size_t lds, size_t lds_opt_in, const Args &a)
+{
+    const bool use_rec = struct_use_rec(oc.b);
+    const std::true_type T;
+    const std::false_type F;
+    const nbr_kernel_t<Args> k = use_rec ? (stage ? pick(T, T) : pick(T, F)) : (stage ? pick(F, T) : pick(F, F));
+    nbr_launch_one(oc, k, use_rec, g, t, lds, lds_opt_in, a);
+}
+// ... and K<REC>, given as pick(rec)
+template <class Args, class Pick>
+static void nbr_launch(ObsCall &oc, Pick pick, unsigned g, unsigned t, size_t lds, size_t lds_opt_in, const Args &a)
+{
+    const bool use_rec = struct_use_rec(oc.b);
+    const nbr_kernel_t<Args> k = use_rec ? pick(std::true_type()) : pick(std::false_type());
+    nbr_launch_one(oc, k, use_rec, g, t, lds, lds_opt_in, a);
 }
 
 // gr.jl:87 on r^2, in the arithmetic of k_rdf: the bin of a squared distance

@@ -7,12 +7,12 @@
 // The arithmetic is stated in include/mmc_hip.h ("Voronoi cells") and restated in numpy by
 // tests/voronoi_ref.py; slot 0 of a molecule is the heavy atom.
 //
-// The scheme is k_shell_order_wave's (mmc_shell.hpp): a persistent workgroup takes a contiguous run of
+// The scheme is mmc_nbr.hpp's, as k_shell_order_wave (mmc_shell.hpp): a persistent workgroup takes a contiguous run of
 // the R N molecules, stages the O positions of every replica its run touches in LDS (STAGE), and its
 // waves take the run's molecules of that replica in turn; inside a molecule a wave waits for nobody.
 //
 // One molecule i, one wave:
-//   scan, sort   k_shell_order_wave's, statement for statement: lane k then owns neighbour k.
+//   scan, sort   scan_list and rank_sort (mmc_nbr.hpp): lane k then owns neighbour k.
 //   clip     lane k's polygon lives in LDS, vertex j of lane l at slot 64 j + l (16 bytes a vertex:
 //            a wave's lanes read and write consecutive slots).  The planes m = 0, 1, ... come by
 //            readlane from the sorted lanes; a lane sits a plane out when it is lane m, has no
@@ -63,7 +63,7 @@ __device__ __forceinline__ int vo_bin(double x, int top)
 }
 
 // REC, STAGE, grid: as k_shell_order_wave.
-// dynamic LDS: [nw] lists of SH_LIST_BYTES, [nw] polygon sets of VO_POLY_BYTES, [hs] counters, then
+// dynamic LDS: [nw] lists of NBR_LIST_BYTES, [nw] polygon sets of VO_POLY_BYTES, [hs] counters, then
 // (STAGE) 3 N doubles at the next multiple of 16 bytes.
 template <bool REC, bool STAGE>
 __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, const double *__restrict__ rec,
@@ -73,10 +73,10 @@ __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, co
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
     const int n_mol = bv.n_mol, hs = va.hs;
-    const size_t per_wave = SH_LIST_BYTES + VO_POLY_BYTES;
-    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(vo_lds + (size_t)wv * SH_LIST_BYTES);
+    const size_t per_wave = NBR_LIST_BYTES + VO_POLY_BYTES;
+    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(vo_lds + (size_t)wv * NBR_LIST_BYTES);
     int *const idx = reinterpret_cast<int *>(keys + MMC_VORONOI_CAP);
-    double2 *const poly = reinterpret_cast<double2 *>(vo_lds + (size_t)nw * SH_LIST_BYTES + (size_t)wv * VO_POLY_BYTES) + lane;
+    double2 *const poly = reinterpret_cast<double2 *>(vo_lds + (size_t)nw * NBR_LIST_BYTES + (size_t)wv * VO_POLY_BYTES) + lane;
     unsigned *const hw = reinterpret_cast<unsigned *>(vo_lds + (size_t)nw * per_wave); // the workgroup's
     double *const pos = reinterpret_cast<double *>(vo_lds + (((size_t)nw * per_wave + 4 * (size_t)hs + 15) & ~(size_t)15));
     for (int q = tid; q < hs; q += (int)blockDim.x)
@@ -85,109 +85,36 @@ __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, co
 
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     const double prune_margin = 1.0 + 0x1p-20; // MMC_VORONOI_PRUNE
-    const int64_t M = (int64_t)va.R * n_mol;
-    const int64_t m0 = M * blockIdx.x / gridDim.x, m1 = M * (blockIdx.x + 1) / gridDim.x;
+    const Sites<REC, STAGE> sites{ bv, rec, pos };
 
-    // the O of molecule j (j < n_mol) of replica r
-    auto oxygen = [&](int r, int j, double &x, double &y, double &z) {
-        if constexpr (STAGE) {
-            x = pos[j]; y = pos[n_mol + j]; z = pos[2 * n_mol + j];
-        } else if constexpr (REC) {
-            const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-            const double2 v0 = *reinterpret_cast<const double2 *>(p);
-            x = v0.x; y = v0.y; z = p[2];
-        } else {
-            const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-            x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-        }
-    };
-
-    for (int64_t s0 = m0; s0 < m1;) { // the run's molecules of one replica: [i_lo, i_hi) of replica r
-        const int r = (int)(s0 / n_mol);
-        const int i_lo = (int)(s0 - (int64_t)r * n_mol);
-        const int i_hi = (int)min((int64_t)n_mol, (int64_t)i_lo + (m1 - s0));
-        s0 += i_hi - i_lo;
-        if constexpr (STAGE) {
-            __syncthreads(); // every wave has left the previous replica's positions
-            for (int j = tid; j < n_mol; j += (int)blockDim.x) {
-                double x, y, z;
-                if constexpr (REC) {
-                    const double *p = rec + ((int64_t)r * n_mol + j) * MMC_RSTRIDE;
-                    const double2 v0 = *reinterpret_cast<const double2 *>(p);
-                    x = v0.x; y = v0.y; z = p[2];
-                } else {
-                    const int64_t a0 = (int64_t)r * bv.atom_stride + bv.first0[j];
-                    x = bv.ax[a0]; y = bv.ay[a0]; z = bv.az[a0];
-                }
-                pos[j] = x; pos[n_mol + j] = y; pos[2 * n_mol + j] = z;
-            }
-            __syncthreads();
-        }
+    for (RunCursor rc(va.R, n_mol); rc.next();) { // the run's molecules of one replica: [rc.lo, rc.hi) of replica r
+        const int r = rc.r;
+        if constexpr (STAGE)
+            stage_sites(sites, r);
         const BoxConsts bc = box_consts(va.box_r ? va.box_r[r] : bv.box);
 
-        for (int i = i_lo + wv; i < i_hi; i += nw) {
+        for (int i = rc.lo + wv; i < rc.hi; i += nw) {
             const int64_t g = (int64_t)r * n_mol + i;
             double cx, cy, cz; // the wave's oxygen: wave-uniform
-            oxygen(r, i, cx, cy, cz);
+            sites.get(r, i, cx, cy, cz);
 
-            // ---- scan: the list, unsorted, in rising j (k_shell_order_wave's)
-            int m = 0;
-            bool over = false;
-            for (int jb = 0; jb < n_mol; jb += 64) {
-                const int j = jb + lane;
-                double x, y, z;
-                oxygen(r, min(j, n_mol - 1), x, y, z);
-                const double ax = vector1D_abs(cx, x, bc), ay = vector1D_abs(cy, y, bc), az = vector1D_abs(cz, z, bc);
-                const double r2 = (ax * ax + ay * ay) + az * az;
-                const bool near = j < n_mol && j != i && r2 < va.rl2;
-                const unsigned long long nm = wave_ballot(near);
-                if (nm != 0ULL) { // wave-uniform
-                    const int add = __popcll(nm);
-                    if (m + add > MMC_VORONOI_CAP) { // more than the lanes can own: flagged, nothing written
-                        over = true;
-                        break;
-                    }
-                    if (near) {
-                        const int slot = m + lanes_below(nm); // < MMC_VORONOI_CAP
-                        keys[slot] = (unsigned long long)__double_as_longlong(r2);
-                        idx[slot] = j;
-                    }
-                    m += add;
-                }
-            }
-            wave_sync();
-
-            // ---- sort: lane n's entry to slot rank(n); lane k then reads slot k (k_shell_order_wave's)
+            // ---- scan, then sort: lane k owns neighbour k
+            int m;
+            const bool over = !scan_list(sites, r, i, cx, cy, cz, bc, va.rl2, keys, idx, lane, m);
             const bool mine = !over && lane < m;
-            unsigned long long key = mine ? keys[lane] : ~0ULL;
-            int jn = mine ? idx[lane] : -1;
-            if (!over) { // wave-uniform
-                int rank = 0;
-                for (int e = 0; e < m; e++) {
-                    const unsigned long long ke = keys[e]; // one address for the wave: a broadcast
-                    rank += (ke < key || (ke == key && e < lane)) ? 1 : 0;
-                }
-                wave_sync(); // every lane has read the unsorted list
-                if (mine) {
-                    keys[rank] = key;
-                    idx[rank] = jn;
-                }
-                wave_sync();
-                if (mine) {
-                    key = keys[lane];
-                    jn = idx[lane];
-                }
-                wave_sync(); // the list is rewritten by the wave's next molecule
-            }
+            unsigned long long key = ~0ULL;
+            int jn = -1;
+            if (!over) // wave-uniform
+                rank_sort(keys, idx, m, lane, key, jn);
 
             // lane k < m: neighbour k.  rho^2 from the key (the bits of the signed image's), d the signed image
             const double r2 = mine ? __longlong_as_double((long long)key) : 0.0;
             double ox, oy, oz;
-            oxygen(r, mine ? jn : i, ox, oy, oz);
+            sites.get(r, mine ? jn : i, ox, oy, oz);
             const double dx = vector1D(cx, ox, bc), dy = vector1D(cy, oy, bc), dz = vector1D(cz, oz, bc);
 
             int flags = over ? VO_CAP : 0;
-            if (!over && (m == 0 || sh_read(r2, 0) == 0.0)) // no neighbour, or a coincident one: no cell
+            if (!over && (m == 0 || lane_f64(r2, 0) == 0.0)) // no neighbour, or a coincident one: no cell
                 flags = VO_OPEN;
 
             int cnt = 0;         // the vertices of lane k's polygon; 0: no face
@@ -217,14 +144,14 @@ __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, co
                 g2 = rl * rl + rl * rl;
                 bool stopped = false, bad_face = false;
                 for (int pm = 0; pm < m; pm++) {
-                    const double r2m = sh_read(r2, pm);
+                    const double r2m = lane_f64(r2, pm);
                     if (va.prune)
                         stopped = stopped || 0.25 * r2m > (h + g2) * prune_margin;
                     const bool left = cnt > 0 && !stopped;
                     if (wave_ballot(left) == 0ULL)
                         break; // no later plane reaches any polygon
                     const bool act = left && lane != pm;
-                    const double ex = sh_read(dx, pm), ey = sh_read(dy, pm), ez = sh_read(dz, pm);
+                    const double ex = lane_f64(dx, pm), ey = lane_f64(dy, pm), ez = lane_f64(dz, pm);
                     if (act) {
                         const double a = (ux * ex + uy * ey) + uz * ez, b = (vx * ex + vy * ey) + vz * ez;
                         const double c = 0.5 * r2m - ((mx * ex + my * ey) + mz * ez);
@@ -320,9 +247,9 @@ __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, co
             const double Ar = A * rho, Ac = counted ? A : 0.0;
             double S = 0.0, T = 0.0, C = 0.0;
             for (int k = 0; k < m; k++) {
-                S = S + sh_read(A, k);
-                T = T + sh_read(Ar, k);
-                C = C + sh_read(Ac, k);
+                S = S + lane_f64(A, k);
+                T = T + lane_f64(Ar, k);
+                C = C + lane_f64(Ac, k);
             }
             const double V = T / 6.0;
             const double eta = ((S * S) * S) / ((va.k36pi * V) * V);
@@ -399,13 +326,13 @@ __global__ __launch_bounds__(VO_WAVES * 64) void k_voronoi_wave(BatchView bv, co
 // One wave per replica, k_local_qsum's order: lane l adds the terms of the unflagged molecules
 // i = l, l + 64, ... in that order, then the 64 lane sums are added by wave_sum_rows.
 // out[r][8] = (number summed, sum V, sum V V, sum S, sum eta, sum counted faces, sum counted area, 0).
-__global__ __launch_bounds__(LO_WAVES * 64) void k_voronoi_sums(const double *__restrict__ vol, const double *__restrict__ area,
+__global__ __launch_bounds__(NBR_WAVES * 64) void k_voronoi_sums(const double *__restrict__ vol, const double *__restrict__ area,
                                                                 const double *__restrict__ carea,
                                                                 const int32_t *__restrict__ faces, double k36pi,
                                                                 double *out, int n_mol, int R)
 {
     const int lane = threadIdx.x & 63;
-    const int r = (int)blockIdx.x * LO_WAVES + (int)(threadIdx.x >> 6);
+    const int r = (int)blockIdx.x * NBR_WAVES + (int)(threadIdx.x >> 6);
     if (r >= R)
         return;
     double a[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };

@@ -33,18 +33,18 @@ extern "C" int32_t mmc_batch_voronoi(mmc_batch *b, double r_list, double area_mi
     BATCH_CHECK(b);
     DeviceSystem &s = b->sys;
     const int64_t R = s.R, N = s.n_mol;
-    const double min_box = s.pb.on ? *std::min_element(s.pb.box.begin(), s.pb.box.end()) : s.bv.box;
-    MMC_REQUIRE(r_list <= min_box / 2.0, MMC_ERR_ARG, "mmc_batch_voronoi: r_list %g exceeds half of the smallest box %g",
-                r_list, min_box);
+    const double box_min = min_box(s);
+    MMC_REQUIRE(r_list <= box_min / 2.0, MMC_ERR_ARG, "mmc_batch_voronoi: r_list %g exceeds half of the smallest box %g",
+                r_list, box_min);
     STRUCT_STATE(b);
     BATCH_USABLE(b);
     MMC_REQUIRE(N >= 2 && N <= (1 << 21), MMC_ERR_UNSUPPORTED, "mmc_batch_voronoi: 2 .. 2^21 molecules");
 
     // waves per workgroup: as many of VO_WAVES as the device's LDS holds beside the counters and the
     // staged O positions (one workgroup per compute unit then); without staging where even one does not
-    const size_t lds_max = (size_t)std::max<int64_t>(0, s.lds_per_block - 64), per_wave = SH_LIST_BYTES + VO_POLY_BYTES;
+    const size_t lds_max = (size_t)std::max<int64_t>(0, s.lds_per_block - 64), per_wave = NBR_LIST_BYTES + VO_POLY_BYTES;
     auto lds_of = [&](int nw, bool st) { return (((size_t)nw * per_wave + 4 * hs + 15) & ~(size_t)15) + (st ? 24 * (size_t)N : 0); };
-    bool stage = b->local_stage && lds_of(1, true) <= lds_max;
+    const bool stage = stage_fits(b, lds_of(1, false), N, lds_max);
     int nw = VO_WAVES;
     while (nw > 1 && lds_of(nw, stage) > lds_max)
         nw--;
@@ -107,27 +107,11 @@ extern "C" int32_t mmc_batch_voronoi(mmc_batch *b, double r_list, double area_mi
     const int64_t want = b->wave_wgs > 0 ? b->wave_wgs : resident;
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min(want, (R * N + nw - 1) / nw)), t = (unsigned)nw * 64;
 
-    const bool use_rec = struct_use_rec(b);
-    const void *kern = use_rec ? (stage ? reinterpret_cast<const void *>(k_voronoi_wave<true, true>)
-                                        : reinterpret_cast<const void *>(k_voronoi_wave<true, false>))
-                               : (stage ? reinterpret_cast<const void *>(k_voronoi_wave<false, true>)
-                                        : reinterpret_cast<const void *>(k_voronoi_wave<false, false>));
-    if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_sofq_wave
-        oc.e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
     oc.zero(o_zero_end); // every counter
-    if (oc.e == hipSuccess) {
-        if (use_rec && stage)
-            k_voronoi_wave<true, true><<<g, t, lds, oc.st>>>(s.bv, s.rec, va);
-        else if (use_rec)
-            k_voronoi_wave<true, false><<<g, t, lds, oc.st>>>(s.bv, s.rec, va);
-        else if (stage)
-            k_voronoi_wave<false, true><<<g, t, lds, oc.st>>>(s.bv, nullptr, va);
-        else
-            k_voronoi_wave<false, false><<<g, t, lds, oc.st>>>(s.bv, nullptr, va);
-    }
-    oc.launched();
+    nbr_launch(oc, [](auto rec, auto st) { return k_voronoi_wave<decltype(rec)::value, decltype(st)::value>; }, stage, g, t, lds,
+               lds_max, va);
     if (oc.e == hipSuccess && sums)
-        k_voronoi_sums<<<(unsigned)((R + LO_WAVES - 1) / LO_WAVES), LO_WAVES * 64, 0, oc.st>>>(
+        k_voronoi_sums<<<(unsigned)((R + NBR_WAVES - 1) / NBR_WAVES), NBR_WAVES * 64, 0, oc.st>>>(
             va.vol, va.area, va.carea, va.faces, va.k36pi, oc.at<double>(o_sm), (int)N, (int)R);
     oc.launched();
     oc.fetch(flagged, oc.at<char>(o_fl), fl_bytes);

@@ -211,6 +211,23 @@ __device__ __forceinline__ double lane_f64(double v, int src)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// lane ^ m's 64-bit word, and the minimum of the wave's words in every lane
+__device__ __forceinline__ unsigned long long wave_shfl_xor_u64(unsigned long long v, int m)
+{
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const unsigned long long o = wave_shfl_xor_u64(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // phase_row (mmc_device.hpp) on sincos_moderate: the recurrence of ewalds.jl:564-585 unchanged.
 __device__ __forceinline__ void phase_row_moderate(double x, double L, cplx *row /* [MMC_NKTAB] */)
 {

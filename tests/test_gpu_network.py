@@ -106,6 +106,23 @@ def test_small_and_odd_systems(n_mol):
             assert wants[0, 1]["A"].sum() > 0 and np.all(per["stats"][:, 0, 7] == 0)
 
 
+def test_candidate_lists_longer_than_a_wave():
+    """129 molecules in a 22 A box and r_hb = L / 2: most molecules have more than 64 oxygens inside
+    the gate (up to 90), so a candidate list is worked off inside the scan and its rest moved down.
+    A cone of 12 degrees leaves at most 9 partners: nothing is flagged, and the lists are compared
+    entry by entry -- beside a criterion of 3.5 A in the same pass over the molecules."""
+    import local_order_ref
+    box = 22.0
+    a = small_system(129, box, seed=429)
+    with make_batch(a, 3) as b:
+        shifted_replicas(b, a, box)
+        for r in range(3):
+            _, r2 = local_order_ref.oo_vectors(b.get_replica(r)[1], box)
+            assert ((r2 < 121.0).sum(1) - 1).max() > 64
+        per, _, wants = check_batch(b, [box] * 3, ((11.0, 12.0, 0), (3.5, 30.0, 0)), what="r_hb L/2")
+        assert np.all(per["stats"][:, :, 7] == 0) and wants[0, 0]["A"].sum(1).max() > 4
+
+
 def test_one_molecule_is_refused():
     a = small_system(1, 22.0, seed=7)
     with make_batch(a, 2) as b:

@@ -117,6 +117,23 @@ def test_small_and_odd_systems(n_mol, wgs):
             assert np.all(per6["stats"][:, 7] == 1) and per5["stats"][0, 1] > 20
 
 
+def test_candidate_lists_longer_than_a_wave():
+    """129 molecules in a 22 A box and r_hb = L / 2: most molecules have more than 64 oxygens inside
+    the gate (up to 90), so a candidate list is worked off inside the scan and its rest moved down.
+    A cone of 10 degrees leaves at most 6 partners: nothing is flagged, and lists, donations and
+    rings are compared with the restatement's."""
+    import local_order_ref
+    box = 22.0
+    a = small_system(129, box, seed=429)
+    with make_batch(a, 3) as b:
+        shifted_replicas(b, a, box)
+        for r in range(3):
+            _, r2 = local_order_ref.oo_vectors(b.get_replica(r)[1], box)
+            assert ((r2 < 121.0).sum(1) - 1).max() > 64
+        per, _, _ = check_batch(b, [box] * 3, 11.0, 10.0, what="r_hb L/2")
+        assert np.all(per["stats"][:, 7] == 0) and np.all(per["stats"][:, 0] > 100) and np.all(per["stats"][:, 1] > 0)
+
+
 def test_one_molecule_is_refused():
     a = small_system(1, 22.0, seed=7)
     with make_batch(a, 2) as b:
