@@ -478,6 +478,10 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #endif
 #define WV_XY WV_XY_MOVE
 #define WV_PASSES 2 // (105-111 VGPRs unconstrained instead of 137-151: what makes WV_OCC = 5 possible)
+#ifndef WV_ONE_CALL_MOVE
+#define WV_ONE_CALL_MOVE 1
+#endif
+#define WV_ONE_CALL WV_ONE_CALL_MOVE
     // (n_parts == 1: every unit has the reciprocal part, and the commit's stores, issued before the
     // phase tables were computed, have mostly landed when those are done)
 #define WV_AFTER_PHASE_TABLES                                                                    \
@@ -489,6 +493,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #undef WV_WOLF
 #undef WV_VIRIAL
 #undef WV_PASSES
+#undef WV_ONE_CALL
 #undef WV_XY
 #undef WV_SUBST
 #undef WV_ZERO

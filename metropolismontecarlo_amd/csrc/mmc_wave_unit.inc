@@ -50,6 +50,10 @@
 #define WV_PASSES 1
 #define WV_PASSES_DEFAULTED
 #endif
+#ifndef WV_ONE_CALL // 1: the pair loops have one call site, the scan is restarted per list (see the COM scan)
+#define WV_ONE_CALL 0
+#define WV_ONE_CALL_DEFAULTED
+#endif
 #ifndef WV_XY // 1: the (kx, ky) products of the moved atoms once per column of k-vectors (see the k loop)
 #define WV_XY 0
 #define WV_XY_DEFAULTED
@@ -333,9 +337,22 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                     // temporaries of the both-states form are live at a time, which is what lets the
                     // kernel be compiled for more waves per SIMD.  Same arithmetic, same order of
                     // the sums within a state.
-                    auto pass = [&](auto stc, bool g, bool l, unsigned long long gm, unsigned long long &ovm,
+                    //
+                    // WHAT AN ATOM PAIR CLOSER THAN sqrt(ovr) CHANGES IS DECIDED ONCE PER ROUND AND STATE,
+                    // not per atom pair.  The nine pairs are evaluated with the gate as their only mask
+                    // and a running minimum of r^2 per lane; one test after them asks whether any gated
+                    // lane came below ovr.  If none did -- every round of a healthy
+                    // liquid -- the sums are bit for bit those of the exact body: the same fma chain in
+                    // the same order, row 0 for the lanes outside the gate.  If one did, the Coulomb sum
+                    // is put back to what it was when the round began and the round runs again through
+                    // the exact body (overlap sentinel, series below the table), which leaves the LJ
+                    // terms alone: those do not depend on it and have been added once already.
+                    // Nothing is assumed about the system; only the speed depends on overlaps being rare.
+                    auto pass = [&](auto stc, bool l, unsigned long long gm, unsigned long long &ovm,
                                     double &a_lj, double &a_v, double &a_q) {
                         constexpr int ST = decltype(stc)::value;
+                        auto atoms = [&](auto exc, uint32_t &umin) {
+                        constexpr bool EXACT = decltype(exc)::value;
 #pragma unroll 1 // (unrolled: the per-pair constants are hoisted into VGPRs and spilled: 394 spills in round 4)
                         for (int a = 0; a < 3; a++) {
                             const int base_w = (ST ? MV_AT_NEW : MV_AT_OLD) + 3 * a;
@@ -343,25 +360,33 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                                          az = lane_f64(w, base_w + 2);
                             auto pair1 = [&](int ab, double bx, double by, double bz) {
                                 const double qq = fc.qq9[ab];
-                                const bool qneg = (fc.qneg_mask >> ab) & 1; // uniform
                                 const double px = WV_MIN1(ST, 0, ax, bx), py = WV_MIN1(ST, 1, ay, by),
                                              pz = WV_MIN1(ST, 2, az, bz);
                                 const double u = px * px + py * py + pz * pz;
-                                const unsigned long long cm = wave_ballot(u < pp.ovr) & gm;
                                 // (WV_IMG also promises (gate + 2 r_mol)^2 < r_cut^2 + 100: every atom pair of a gated
                                 // molecule pair is inside the slack of ewalds.jl:362 / energy.jl:270, no need to look)
-                                // opposite charges that close: the overlap sentinel (qm); like charges that
-                                // close: below r^2 = 0.25 the table ends (cold; practically never).  Branch-free
-                                // mask arithmetic but for the cold path: a uniform branch per pair on qneg cost
-                                // more scalar instructions than the masks it saved
-                                const unsigned long long qm = qneg ? cm : 0ULL, cold = cm & ~qm;
-                                const unsigned long long im = (wv_img ? ~0ULL : wave_ballot(u < pp.qq_slack_sq)) & gm & ~qm;
-                                double e = qq_table_eval_lanes(sm.qtab, u, im);
-                                ovm |= qm;
-                                if (cold != 0ULL) {
-                                    if (((im >> lane) & 1) && u < MMC_QQ_UMIN) e = qq_pair_cold(u, pp.kappa);
-                                }
+                                const unsigned long long km = (wv_img ? ~0ULL : wave_ballot(u < pp.qq_slack_sq)) & gm;
+                                if constexpr (EXACT) {
+                                    // opposite charges that close: the overlap sentinel (qm); like charges that
+                                    // close: below r^2 = 0.25 the table ends (cold; practically never)
+                                    const bool qneg = (fc.qneg_mask >> ab) & 1; // uniform
+                                    const unsigned long long cm = wave_ballot(u < pp.ovr) & gm;
+                                    const unsigned long long qm = qneg ? cm : 0ULL, cold = cm & ~qm;
+                                    const unsigned long long im = km & ~qm;
+                                    double e = qq_table_eval_lanes(sm.qtab, u, im);
+                                    ovm |= qm;
+                                    if (cold != 0ULL) {
+                                        if (((im >> lane) & 1) && u < MMC_QQ_UMIN) e = qq_pair_cold(u, pp.kappa);
+                                    }
+                                    a_q = fma(e, qq, a_q); // ewalds.jl:365-367
+                                } else {
+                                umin = min(umin, (uint32_t)(__double_as_longlong(u) >> 32));
+                                const double e = qq_table_eval_lanes(sm.qtab, u, km);
                                 a_q = fma(e, qq, a_q); // ewalds.jl:365-367
+                                // (the sum is pinned HERE: with no branch that needs e the compiler sinks the three
+                                // Horner chains of an atom below the LJ branches, 60 registers of coefficients
+                                // live at once, and spills the gathered records)
+                                asm volatile("" : "+v"(a_q));
                                 if ((fc.lj_mask >> ab) & 1) { // uniform (energy.jl:270: eps > 0.001); same r^2
                                     const double eps = fc.eps9[ab], sg = fc.sig9[ab];
                                     if (l && (wv_img || u < pp.lj_slack_sq)) {
@@ -384,6 +409,7 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                                         }
                                     }
                                 }
+                                } // !EXACT
                             };
                             pair1(3 * a, t[0], t[1], t[2]);
                             WV_PAIR_FENCE
@@ -392,10 +418,26 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                             pair1(3 * a + 2, t[6], t[7], t[8]);
                             WV_PAIR_FENCE
                         }
-                        (void)g;
+                        };
+                        // The minimum is kept of the HIGH WORD of r^2 (r^2 >= +0: as an unsigned integer
+                        // it orders as r^2 does; a NaN lies above every threshold, as in `u < ovr`) --
+                        // one register and one 32-bit minimum per pair.  r^2 < ovr implies
+                        // hi(r^2) <= hi(ovr): the test errs only towards the exact body.  The threshold
+                        // is ovr itself: the exact body looks below the table's end (MMC_QQ_UMIN) only
+                        // where r^2 < ovr (`cold` is a part of `cm`), so with no gated r^2 below ovr it
+                        // does what the fast body did.  (max(ovr, MMC_QQ_UMIN) here is one more scalar
+                        // register live across the pair loop: 151 spilled SGPRs, the parent has 150.)
+                        const double a_q_in = a_q;
+                        uint32_t umin = ~0u;
+                        atoms(std::false_type{}, umin);
+                        const uint32_t thr_hi = (uint32_t)(__double_as_longlong(pp.ovr) >> 32);
+                        if (__builtin_expect((wave_ballot(umin <= thr_hi) & gm) != 0ULL, 0)) {
+                            a_q = a_q_in;
+                            atoms(std::true_type{}, umin);
+                        }
                     };
-                    WV_IF2(pass(std::integral_constant<int, 0>{}, g0, l0, gm0, ovm0, a_lj0, a_v0, a_q0);)
-                    pass(std::integral_constant<int, 1>{}, g1, l1, gm1, ovm1, a_lj1, a_v1, a_q1);
+                    WV_IF2(pass(std::integral_constant<int, 0>{}, l0, gm0, ovm0, a_lj0, a_v0, a_q0);)
+                    pass(std::integral_constant<int, 1>{}, l1, gm1, ovm1, a_lj1, a_v1, a_q1);
                 }
 #else
                     // one atom pair (a, b), both states.  The Coulomb term needs only r^2, and
@@ -545,12 +587,26 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
             }
             int base = j_begin, cnt = 0;
             uint32_t fxy[WV_PF], fz[WV_PF];
+#if WV_ONE_CALL
+            // ONE call site of process(): scan until the list has no room for another WV_PF blocks or
+            // the range ends, take the list through the pair loops, and again while molecules remain
+            // (the same neighbours in the same order and the same trips as with a call inside the scan
+            // and one behind it, one copy of the pair loops instead of two).  The prefetch starts anew
+            // with every list -- the blocks it re-reads were requested by the trip before -- so its
+            // registers are not live across the pair loops.
+            while (base < j_end) {
+            cnt = 0;
+#endif
 #pragma unroll
             for (int b = 0; b < WV_PF; b++) {
                 fxy[b] = *reinterpret_cast<const uint32_t *>(pxy + 256 * b + ul4);
                 fz[b] = *reinterpret_cast<const uint16_t *>(pz + 128 * b + ul2);
             }
+#if WV_ONE_CALL
+            while (base < j_end && cnt <= WV_LIST - 64 * WV_PF) { // (no room for another WV_PF blocks: empty the list)
+#else
             while (base < j_end) {
+#endif
 #pragma unroll
                 for (int b = 0; b < WV_PF; b++) {
                     const int j = base + lane;
@@ -575,6 +631,13 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                 }
                 pxy += 256 * WV_PF;
                 pz += 128 * WV_PF;
+#if WV_ONE_CALL
+            }
+            WV_STAMP(4); // scan done (the last list's, where there are several)
+            if (cnt)
+                process(cnt);
+            }
+#else
                 if (cnt > WV_LIST - 64 * WV_PF) { // no room for another WV_PF blocks: empty the list
                     process(cnt);
                     cnt = 0;
@@ -583,6 +646,7 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
             WV_STAMP(4); // scan done
             if (cnt)
                 process(cnt);
+#endif
             WV_STAMP(6); // pair loops done
         } else if (lane < 6) {
             outw[lane] = WV_ZERO;
@@ -646,6 +710,10 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
 #ifdef WV_XY_DEFAULTED
 #undef WV_XY
 #undef WV_XY_DEFAULTED
+#endif
+#ifdef WV_ONE_CALL_DEFAULTED
+#undef WV_ONE_CALL
+#undef WV_ONE_CALL_DEFAULTED
 #endif
 #ifdef WV_PASSES_DEFAULTED
 #undef WV_PASSES
