@@ -98,6 +98,9 @@ CHAIN_DTYPE = np.dtype([("dr_max", "f8"), ("dphi_max", "f8"), ("energy", "f8"), 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
+_u64p = C.POINTER(C.c_uint64)
+_u16p = C.POINTER(C.c_uint16)
+_u8p = C.POINTER(C.c_uint8)
 _vp = C.c_void_p
 _d = C.c_double
 _i64 = C.c_int64
@@ -170,60 +173,48 @@ SIGNATURES = {
     "mmc_batch_qq_table": [_vp, _dp, _i64, _dp],
     "mmc_batch_qq_table_replica": [_vp, _i64, _dp, _i64, _dp],
     "mmc_batch_settle": [_vp, _i32p],
-    "mmc_batch_get_trace": [_vp, _dp, C.POINTER(C.c_uint8)],
+    "mmc_batch_get_trace": [_vp, _dp, _u8p],
     "mmc_batch_set_orientations": [_vp, _dp, _dp, _i32],
     "mmc_batch_get_orientations": [_vp, _i64, _dp],
     "mmc_part_validate": [_vp, C.c_uint32],
     "mmc_batch_peek_part": [_vp, _i64, _i32, _vp, C.POINTER(C.c_uint32)],
-    "mmc_batch_rdf": [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)],
+    "mmc_batch_rdf": [_vp, _i32, _i32, _u64p],
     "mmc_batch_run": [_vp, C.POINTER(RunParams), _dp, C.POINTER(RunStats)],
-    "mmc_study_f32_total": [_vp, C.c_double, C.c_double, C.c_int32, _dp],
-    "mmc_study_f32_move": [_vp, _i64, _dp, _dp, C.c_double, C.c_double, C.c_int32, _dp, _i32p],
+    "mmc_study_f32_total": [_vp, _d, _d, _i32, _dp],
+    "mmc_study_f32_move": [_vp, _i64, _dp, _dp, _d, _d, _i32, _dp, _i32p],
     "mmc_philox4x32": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
-    "mmc_batch_widom": [_vp, _i64, C.c_uint64, _i64, _dp, _d, _dp, _i64p, _dp, _dp,
-                        C.POINTER(C.c_uint8)],
-    "mmc_batch_widom_at": [_vp, _i64, _dp, _d, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
-    "mmc_batch_widom_solute": [_vp, C.c_int32, _dp, _dp, _dp, _dp, _i64, C.c_uint64, _i64, _d, _dp, _i64p,
-                               _dp, _dp, C.POINTER(C.c_uint8)],
-    "mmc_batch_widom_solute_at": [_vp, C.c_int32, _dp, _dp, _dp, _i64, _dp, _d, _dp, _i64p, _dp,
-                                  C.POINTER(C.c_uint8)],
-    "mmc_batch_widom_pair": [_vp, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32,
-                             _dp, _i64, C.c_uint64, _i64, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _dp, _dp,
-                             C.POINTER(C.c_uint8)],
-    "mmc_batch_widom_pair_at": [_vp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _i64,
-                                _dp, _dp, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
-    "mmc_batch_deletion": [_vp, C.c_int32, _i32p, _d, C.c_int32, _d, _d, C.c_int32, C.POINTER(C.c_uint64),
-                           _dp, _dp, _i64p, _dp, C.POINTER(C.c_uint8)],
-    "mmc_batch_forces": [_vp, C.c_int32, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, C.POINTER(C.c_uint8)],
-    "mmc_batch_rdf_sites": [_vp, C.c_int32, _d, C.c_int32, C.POINTER(C.c_uint64)],
+    "mmc_batch_widom": [_vp, _i64, C.c_uint64, _i64, _dp, _d, _dp, _i64p, _dp, _dp, _u8p],
+    "mmc_batch_widom_at": [_vp, _i64, _dp, _d, _dp, _i64p, _dp, _u8p],
+    "mmc_batch_widom_solute": [_vp, _i32, _dp, _dp, _dp, _dp, _i64, C.c_uint64, _i64, _d, _dp, _i64p, _dp, _dp,
+                               _u8p],
+    "mmc_batch_widom_solute_at": [_vp, _i32, _dp, _dp, _dp, _i64, _dp, _d, _dp, _i64p, _dp, _u8p],
+    "mmc_batch_widom_pair": [_vp, _i32, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _i32, _dp, _i64,
+                             C.c_uint64, _i64, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _dp, _dp, _u8p],
+    "mmc_batch_widom_pair_at": [_vp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _i32, _i64, _dp, _dp, _d,
+                                _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _u8p],
+    "mmc_batch_deletion": [_vp, _i32, _i32p, _d, _i32, _d, _d, _i32, _u64p, _dp, _dp, _i64p, _dp, _u8p],
+    "mmc_batch_forces": [_vp, _i32, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, _u8p],
+    "mmc_batch_rdf_sites": [_vp, _i32, _d, _i32, _u64p],
     "mmc_batch_dipoles": [_vp, _dp],
-    "mmc_batch_orient_corr": [_vp, C.c_int32, _d, C.c_int32, _i64p],
-    "mmc_batch_sdf": [_vp, C.c_int32, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)],
-    "mmc_batch_pair_energy": [_vp, C.c_int32, _d, C.c_int32, _d, _d, _d, C.c_int32, _i64p, C.POINTER(C.c_uint64),
-                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
-    "mmc_batch_structure_factor": [_vp, C.c_int32, C.c_int32, _i32p, _i64p, _dp],
-    "mmc_batch_local_order": [_vp, _d, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                              _dp, _i32p, _dp, C.POINTER(C.c_uint8)],
-    "mmc_batch_shell_order": [_vp, _d, _d, _d, _d, _d, C.c_int32, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32, _d, _d,
-                              C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _i32p, _i32p, _dp, _dp],
-    "mmc_batch_voronoi": [_vp, _d, _d, C.c_int32, _d, C.c_int32, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
-                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                          C.POINTER(C.c_uint64), _dp, _dp, _dp, _i32p, _i32p, _dp],
-    "mmc_batch_bond_order": [_vp, C.c_int32, _d, C.c_int32, _d, _d, _d, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                             C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i64p, _dp, _dp, _dp, _i32p,
-                             C.POINTER(C.c_uint8), _i32p],
-    "mmc_batch_hbond_network": [_vp, C.c_int32, _dp, _dp, _i32p, C.c_int32, C.POINTER(C.c_uint64),
-                                C.POINTER(C.c_uint64), _i64p, _i32p, _i32p],
-    "mmc_batch_hbond_rings": [_vp, _d, _d, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i64p,
-                              C.POINTER(C.c_uint16), _i64, _i32p],
-    "mmc_batch_cavity": [_vp, _i64, C.c_uint64, _i64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,
-                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _i32p, _dp, _i32p],
-    "mmc_batch_cavity_at": [_vp, _i64, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _d, C.c_int32,
-                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, _dp, _i32p],
-    "mmc_batch_volume_perturb": [_vp, C.c_int32, _dp, _d, _dp, _i64p, _dp, _dp],
-    "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, C.c_int32, C.POINTER(RunStats)],
+    "mmc_batch_orient_corr": [_vp, _i32, _d, _i32, _i64p],
+    "mmc_batch_sdf": [_vp, _i32, _d, _i32, _i32, _i32, _u64p],
+    "mmc_batch_pair_energy": [_vp, _i32, _d, _i32, _d, _d, _d, _i32, _i64p, _u64p, _u64p, _u64p],
+    "mmc_batch_structure_factor": [_vp, _i32, _i32, _i32p, _i64p, _dp],
+    "mmc_batch_local_order": [_vp, _d, _d, _i32, _i32, _u64p, _u64p, _dp, _i32p, _dp, _u8p],
+    "mmc_batch_shell_order": [_vp, _d, _d, _d, _d, _d, _i32, _i32, _i32, _d, _i32, _i32, _d, _d, _i32, _u64p, _u64p,
+                              _u64p, _u64p, _u64p, _dp, _i32p, _i32p, _dp, _dp],
+    "mmc_batch_voronoi": [_vp, _d, _d, _i32, _d, _i32, _d, _i32, _i32, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p,
+                          _dp, _dp, _dp, _i32p, _i32p, _dp],
+    "mmc_batch_bond_order": [_vp, _i32, _d, _i32, _d, _d, _d, _d, _i32, _i32, _i32, _i32, _i32, _u64p, _u64p, _u64p,
+                             _u64p, _u64p, _i64p, _dp, _dp, _dp, _i32p, _u8p, _i32p],
+    "mmc_batch_hbond_network": [_vp, _i32, _dp, _dp, _i32p, _i32, _u64p, _u64p, _i64p, _i32p, _i32p],
+    "mmc_batch_hbond_rings": [_vp, _d, _d, _i32, _i32, _u64p, _u64p, _i64p, _u16p, _i64, _i32p],
+    "mmc_batch_cavity": [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _dp, _i32, _i32, _d, _i32, _u64p, _u64p, _u64p,
+                         _dp, _i32p, _dp, _i32p],
+    "mmc_batch_cavity_at": [_vp, _i64, _dp, _i32, _i32, _dp, _i32, _i32, _d, _i32, _u64p, _u64p, _u64p, _i32p, _dp,
+                            _i32p],
+    "mmc_batch_volume_perturb": [_vp, _i32, _dp, _d, _dp, _i64p, _dp, _dp],
+    "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, _i32, C.POINTER(RunStats)],
     "mmc_chain_block_line": [_vp, _i64, _i64, _d, _d, C.c_char_p, _i64],
     "mmc_dist_unique_id": [C.c_char_p],                      # uint8_t[128]
     "mmc_dist_init": [_i32, _i32, C.c_char_p, _i32, C.POINTER(_vp)],

@@ -10,14 +10,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CHAIN_DTYPE, TOTALS_DTYPE, Move, MoveResult, RunParams, RunStats, Totals, check
+from ._lib import (CHAIN_DTYPE, TOTALS_DTYPE, Move, MoveResult, RunParams, RunStats, Totals, _dp, _i32p, _i64p,
+                   check)
 
 PairEnergy = collections.namedtuple("PairEnergy", "rows uhist nhb flagged")  # Batch.pair_energy
 Sdf = collections.namedtuple("Sdf", "grid outside noframe")  # Batch.sdf
-
-_dp = C.POINTER(C.c_double)
-_i64p = C.POINTER(C.c_int64)
-_i32p = C.POINTER(C.c_int32)
 
 
 def _f64(a):
@@ -30,10 +27,6 @@ def _i64(a):
 
 def _d(a):
     return a.ctypes.data_as(_dp)
-
-
-def _u8(a):
-    return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
 def philox4x32(ctr, key):
@@ -61,13 +54,49 @@ def _selection(sel, n_mol):
     return sel_a, sel_a.shape[0]
 
 
-def _accumulator(a, R, dtype, name):
-    """A per-replica sum the library adds to in place: the caller's array, or a new zero one."""
+def _output(a, shape, dtype, name="out"):
+    """An array the library writes or adds to in place: the caller's `a`, which must be exactly a
+    C-contiguous ndarray of that shape and dtype, or a new zero one when `a` is None."""
     if a is None:
-        return np.zeros(R, dtype=dtype)
-    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == (R,) and a.flags.c_contiguous):
-        raise ValueError(f"{name}: {np.dtype(dtype).name} (R,), contiguous (updated in place)")
+        return np.zeros(shape, dtype=dtype)
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == shape and a.flags.c_contiguous):
+        raise ValueError(f"{name}: a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
     return a
+
+
+def _outputs(spec, given, where="out", known_only=False):
+    """{name: array} for a spec {name: (shape, dtype)}: _output() of every entry, taken from the dict
+    `given` (None = none given; `where` names it in a refusal, None for separate arguments).  Keys
+    of `given` that are not in the spec are ignored, or refused with known_only."""
+    given = {} if given is None else given
+    if not isinstance(given, dict):
+        raise ValueError(f"{where}: a dict of arrays under names among {sorted(spec)}, not a {type(given).__name__}")
+    if known_only and not set(given) <= set(spec):
+        raise ValueError(f"{where}: {[k for k in given if k not in spec]} are no outputs of this call; "
+                         f"those are {sorted(spec)}")
+    return {k: _output(given.get(k), shape, dt, f"{where}[{k!r}]" if where else k)
+            for k, (shape, dt) in spec.items()}
+
+
+def _insertion_outputs(R, M, boltz_sum, n_overlap, mol, du):
+    """The outputs of the widom family: the sums boltz_sum and n_overlap (R,), the caller's or new,
+    then new arrays: mol (R, M) + `mol` unless that is None, and du (R, M, 3), ovl (R, M) if `du`."""
+    spec = {"boltz_sum": ((R,), np.float64), "n_overlap": ((R,), np.int64)}
+    if mol is not None:
+        spec["mol"] = ((R, M) + mol, np.float64)
+    if du:
+        spec.update(du=((R, M, 3), np.float64), ovl=((R, M), np.uint8))
+    return _outputs(spec, dict(boltz_sum=boltz_sum, n_overlap=n_overlap), where=None)
+
+
+def _ptr(a):
+    """The ctypes pointer to a's data; its element type is a's dtype's."""
+    return a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
+def _ptrs(res, *names):
+    """The pointers to res[name] in the order named; None for a name res does not hold."""
+    return [_ptr(res[k]) if k in res else None for k in names]
 
 
 REFERENCE_IDEAL_TERM = 4.60453   # the ideal-gas term Loop() hard-codes in its block line (main.jl:677)
@@ -92,21 +121,13 @@ def device_count():
     return n.value
 
 
-class Context:
-    """mmc_ctx: one system (one Markov chain) on one GPU."""
-
-    def __init__(self, device=0, stream=None):
-        self._L = _lib.lib()
-        h = C.c_void_p()
-        check(self._L.mmc_ctx_create(device, C.c_void_p(stream or 0), C.byref(h)))
-        self._h = h
-        self.n_mol = self.n_atoms = 0
-        self.nkvecs = 0
-        self.factor = None
+class _Handle:
+    """Owns one library handle self._h, destroyed by the call self._L.<_destroy>."""
+    _destroy = None
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.mmc_ctx_destroy(self._h)
+            getattr(self._L, self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -120,6 +141,20 @@ class Context:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Context(_Handle):
+    """mmc_ctx: one system (one Markov chain) on one GPU."""
+    _destroy = "mmc_ctx_destroy"
+
+    def __init__(self, device=0, stream=None):
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        check(self._L.mmc_ctx_create(device, C.c_void_p(stream or 0), C.byref(h)))
+        self._h = h
+        self.n_mol = self.n_atoms = 0
+        self.nkvecs = 0
+        self.factor = None
 
     # -- state ---------------------------------------------------------------------------------
     def upload_system(self, com, first_atom, last_atom, coords, atype, charge, eps, sig, box):
@@ -192,7 +227,7 @@ class Context:
     def get_kvectors(self):
         kxyz = np.empty((self.nkvecs, 3), dtype=np.int32)
         cfac = np.empty(self.nkvecs)
-        check(self._L.mmc_get_kvectors(self._h, kxyz.ctypes.data_as(_i32p), _d(cfac)))
+        check(self._L.mmc_get_kvectors(self._h, _ptr(kxyz), _d(cfac)))
         return kxyz, cfac
 
     def get_sumqexp(self):
@@ -314,8 +349,9 @@ class Context:
         check(self._L.mmc_reject_move(self._h))
 
 
-class Batch:
+class Batch(_Handle):
     """mmc_batch: R replicas of one 3-atoms-per-molecule system on one GPU."""
+    _destroy = "mmc_batch_destroy"
 
     def __init__(self, n_replicas, com, coords, atype, charge, eps, sig, box, kappa, factor,
                  lj_rcut, qq_rcut, nk=5, k_sq_max=27, device=0, stream=None):
@@ -344,23 +380,6 @@ class Batch:
         d = coords[:3] - com[0]
         self.widom_offsets = d - self.box * np.round(d / self.box)
         self.nkvecs = 337
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mmc_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_replica(self, r, com, coords):
         com, coords = _f64(com).reshape(-1, 3), _f64(coords).reshape(-1, 3)
@@ -569,17 +588,11 @@ class Batch:
         Returns (boltz_sum, n_overlap), and with outputs=True also mol (R, M, 12), du (R, M, 3)
         and ovl (R, M)."""
         off = _f64(self.widom_offsets if offsets is None else offsets).reshape(3, 3)
-        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
-        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
         M = int(n_insert)
-        mol = np.zeros((self.R, M, 12)) if outputs else None
-        du = np.zeros((self.R, M, 3)) if outputs else None
-        ov = np.zeros((self.R, M), dtype=np.uint8) if outputs else None
+        res = _insertion_outputs(self.R, M, boltz_sum, n_overlap, (12,) if outputs else None, outputs)
         check(self._L.mmc_batch_widom(self._h, M, int(seed) & (2 ** 64 - 1), int(draw0), _d(off),
-                                      float(temperature), _d(bs), _i(no),
-                                      _d(mol) if outputs else None, _d(du) if outputs else None,
-                                      _u8(ov) if outputs else None))
-        return (bs, no, mol, du, ov) if outputs else (bs, no)
+                                      float(temperature), *_ptrs(res, "boltz_sum", "n_overlap", "mol", "du", "ovl")))
+        return tuple(res.values())
 
     def widom_at(self, mol, temperature, boltz_sum=None, n_overlap=None):
         """mmc_batch_widom_at: the caller's test molecules mol (R, M, 12) = atoms (9), COM (3).
@@ -588,13 +601,10 @@ class Batch:
         if mol.ndim != 3 or mol.shape[0] != self.R or mol.shape[2] != 12:
             raise ValueError("mol must be (R, n_insert, 12)")
         M = mol.shape[1]
-        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
-        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
-        du = np.zeros((self.R, M, 3))
-        ov = np.zeros((self.R, M), dtype=np.uint8)
-        check(self._L.mmc_batch_widom_at(self._h, M, _d(mol), float(temperature), _d(bs), _i(no),
-                                         _d(du), _u8(ov)))
-        return bs, no, du, ov
+        res = _insertion_outputs(self.R, M, boltz_sum, n_overlap, None, True)
+        check(self._L.mmc_batch_widom_at(self._h, M, _d(mol), float(temperature),
+                                         *_ptrs(res, "boltz_sum", "n_overlap", "du", "ovl")))
+        return tuple(res.values())
 
     def widom_solute(self, solute, n_insert, temperature, seed, draw0=0, boltz_sum=None, n_overlap=None,
                      outputs=False):
@@ -604,18 +614,13 @@ class Batch:
         (new zero arrays when None).  Returns (boltz_sum, n_overlap), and with outputs=True also mol
         (R, M, S + 1, 3) = the sites, then the reference point, du (R, M, 3) and ovl (R, M)."""
         S = solute.n_sites
-        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
-        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
         M = int(n_insert)
-        mol = np.zeros((self.R, M, S + 1, 3)) if outputs else None
-        du = np.zeros((self.R, M, 3)) if outputs else None
-        ov = np.zeros((self.R, M), dtype=np.uint8) if outputs else None
+        res = _insertion_outputs(self.R, M, boltz_sum, n_overlap, (S + 1, 3) if outputs else None, outputs)
         check(self._L.mmc_batch_widom_solute(self._h, S, _d(solute.offsets), _d(solute.charge), _d(solute.eps),
                                              _d(solute.sig), M, int(seed) & (2 ** 64 - 1), int(draw0),
-                                             float(temperature), _d(bs), _i(no),
-                                             _d(mol) if outputs else None, _d(du) if outputs else None,
-                                             _u8(ov) if outputs else None))
-        return (bs, no, mol, du, ov) if outputs else (bs, no)
+                                             float(temperature),
+                                             *_ptrs(res, "boltz_sum", "n_overlap", "mol", "du", "ovl")))
+        return tuple(res.values())
 
     def widom_solute_at(self, solute, mol, temperature, boltz_sum=None, n_overlap=None):
         """mmc_batch_widom_solute_at: the caller's solutes mol (R, M, S + 1, 3) = the S sites, then
@@ -626,29 +631,19 @@ class Batch:
         if mol.ndim != 4 or mol.shape[0] != self.R or mol.shape[2:] != (S + 1, 3):
             raise ValueError("mol must be (R, n_insert, n_sites + 1, 3)")
         M = mol.shape[1]
-        bs = _accumulator(boltz_sum, self.R, np.float64, "boltz_sum")
-        no = _accumulator(n_overlap, self.R, np.int64, "n_overlap")
-        du = np.zeros((self.R, M, 3))
-        ov = np.zeros((self.R, M), dtype=np.uint8)
+        res = _insertion_outputs(self.R, M, boltz_sum, n_overlap, None, True)
         check(self._L.mmc_batch_widom_solute_at(self._h, S, _d(solute.charge), _d(solute.eps), _d(solute.sig), M,
-                                                _d(mol), float(temperature), _d(bs), _i(no), _d(du), _u8(ov)))
-        return bs, no, du, ov
+                                                _d(mol), float(temperature),
+                                                *_ptrs(res, "boltz_sum", "n_overlap", "du", "ovl")))
+        return tuple(res.values())
 
     def pair_sums(self, sums, K):
         """The six accumulators of widom_pair: a dict (or None = new zero arrays) with boltz_a (R,),
         n_zero_a (R,), boltz_b, boltz_ab (R, K), n_zero_b, n_zero_ab (R, K)."""
-        sums = {} if sums is None else sums
-        out = {}
-        for name, dt, shape in (("boltz_a", np.float64, (self.R,)), ("n_zero_a", np.int64, (self.R,)),
-                                ("boltz_b", np.float64, (self.R, K)), ("n_zero_b", np.int64, (self.R, K)),
-                                ("boltz_ab", np.float64, (self.R, K)), ("n_zero_ab", np.int64, (self.R, K))):
-            v = sums.get(name)
-            if v is None:
-                v = np.zeros(shape, dtype=dt)
-            elif not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            out[name] = v
-        return out
+        f8, i8, one, per_d = np.float64, np.int64, (self.R,), (self.R, K)
+        # (in the order mmc_batch_widom_pair and _pair_at take them)
+        return _outputs({"boltz_a": (one, f8), "n_zero_a": (one, i8), "boltz_b": (per_d, f8), "n_zero_b": (per_d, i8),
+                         "boltz_ab": (per_d, f8), "n_zero_ab": (per_d, i8)}, sums, where="sums")
 
     def widom_pair(self, pair, d, n_insert, temperature, seed, draw0=0, sums=None, outputs=False):
         """mmc_batch_widom_pair: n_insert random insertions of the solute pair (structs.SolutePair)
@@ -661,19 +656,18 @@ class Batch:
         a, b = pair.a, pair.b
         d = _f64(d).ravel()
         K, M = d.shape[0], int(n_insert)
-        sm = self.pair_sums(sums, K)
-        mol_a = np.zeros((self.R, M, a.n_sites + 1, 3)) if outputs else None
-        mol_b = np.zeros((self.R, M, K, b.n_sites + 1, 3)) if outputs else None
-        du = np.zeros((self.R, M, 1 + 2 * K, 3)) if outputs else None
-        fl = np.zeros((self.R, M, 1 + K), dtype=np.uint8) if outputs else None
+        R, sm = self.R, self.pair_sums(sums, K)
+        spec = {}
+        if outputs:
+            spec = {"mol_a": ((R, M, a.n_sites + 1, 3), np.float64), "mol_b": ((R, M, K, b.n_sites + 1, 3), np.float64),
+                    "du": ((R, M, 1 + 2 * K, 3), np.float64), "flags": ((R, M, 1 + K), np.uint8)}
+        new = _outputs(spec, None)
         check(self._L.mmc_batch_widom_pair(
             self._h, a.n_sites, _d(a.offsets), _d(a.charge), _d(a.eps), _d(a.sig), b.n_sites, _d(b.offsets),
             _d(b.charge), _d(b.eps), _d(b.sig), _d(pair.eps_ab), _d(pair.sig_ab), K, _d(d), M,
-            int(seed) & (2 ** 64 - 1), int(draw0), float(temperature), _d(sm["boltz_a"]), _i(sm["n_zero_a"]),
-            _d(sm["boltz_b"]), _i(sm["n_zero_b"]), _d(sm["boltz_ab"]), _i(sm["n_zero_ab"]),
-            _d(mol_a) if outputs else None, _d(mol_b) if outputs else None, _d(du) if outputs else None,
-            _u8(fl) if outputs else None))
-        return (sm, mol_a, mol_b, du, fl) if outputs else sm
+            int(seed) & (2 ** 64 - 1), int(draw0), float(temperature), *_ptrs(sm, *sm),
+            *_ptrs(new, "mol_a", "mol_b", "du", "flags")))
+        return (sm, *new.values()) if outputs else sm
 
     def widom_pair_at(self, pair, mol_a, mol_b, temperature, sums=None):
         """mmc_batch_widom_pair_at: the caller's placements mol_a (R, M, S_A + 1, 3) and mol_b (R, M,
@@ -692,9 +686,8 @@ class Batch:
         fl = np.zeros((self.R, M, 1 + K), dtype=np.uint8)
         check(self._L.mmc_batch_widom_pair_at(
             self._h, a.n_sites, _d(a.charge), _d(a.eps), _d(a.sig), b.n_sites, _d(b.charge), _d(b.eps), _d(b.sig),
-            _d(pair.eps_ab), _d(pair.sig_ab), K, M, _d(mol_a), _d(mol_b), float(temperature), _d(sm["boltz_a"]),
-            _i(sm["n_zero_a"]), _d(sm["boltz_b"]), _i(sm["n_zero_b"]), _d(sm["boltz_ab"]), _i(sm["n_zero_ab"]),
-            _d(du), _u8(fl)))
+            _d(pair.eps_ab), _d(pair.sig_ab), K, M, _d(mol_a), _d(mol_b), float(temperature), *_ptrs(sm, *sm),
+            _ptr(du), _ptr(fl)))
         return sm, du, fl
 
     def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
@@ -710,23 +703,18 @@ class Batch:
         (R, n, 3) and ovl uint8 (R, n) (bit 0 overlap, bit 1 non-finite dU)."""
         R = self.R
         sel_a, n = _selection(sel, self.n_mol)
-        bs = _accumulator(boltz_sum, R, np.float64, "boltz_sum")
-        nf = _accumulator(n_flagged, R, np.int64, "n_flagged")
-        res = {"esum": np.zeros((R, 4)), "boltz_sum": bs, "n_flagged": nf}
+        spec = {"esum": ((R, 4), np.float64), "boltz_sum": ((R,), np.float64), "n_flagged": ((R,), np.int64)}
         n_bins, u_lo, u_hi = 0, 0.0, 0.0
         if bins is not None:
             n_bins, u_lo, u_hi = int(bins[0]), float(bins[1]), float(bins[2])
             slots = max(n_bins, 0) + 2   # (an n_bins the library refuses still gets an array to leave alone)
-            res["hist"] = np.zeros((R, slots) if per_replica else (slots,), dtype=np.uint64)
+            spec["hist"] = ((R, slots) if per_replica else (slots,), np.uint64)
         if details:
-            res["du"] = np.zeros((R, n, 3))
-            res["ovl"] = np.zeros((R, n), dtype=np.uint8)
+            spec.update(du=((R, n, 3), np.float64), ovl=((R, n), np.uint8))
+        res = _outputs(spec, dict(boltz_sum=boltz_sum, n_flagged=n_flagged), where=None)
         check(self._L.mmc_batch_deletion(
-            self._h, n, None if sel_a is None else sel_a.ctypes.data_as(C.POINTER(C.c_int32)),
-            float(temperature), n_bins, u_lo, u_hi, int(bool(per_replica)),
-            res["hist"].ctypes.data_as(C.POINTER(C.c_uint64)) if bins is not None else None,
-            _d(res["esum"]), _d(bs), _i(nf), _d(res["du"]) if details else None,
-            _u8(res["ovl"]) if details else None))
+            self._h, n, None if sel_a is None else _ptr(sel_a), float(temperature), n_bins, u_lo, u_hi,
+            int(bool(per_replica)), *_ptrs(res, "hist", "esum", "boltz_sum", "n_flagged", "du", "ovl")))
         return res
 
     def forces(self, sel=None, mass=None, details=False, n_flagged=None):
@@ -745,17 +733,14 @@ class Batch:
             mass_a = np.ascontiguousarray(mass, dtype=np.float64)
             if mass_a.shape != (3,):
                 raise ValueError("mass: three values, one per atom slot")
-        nf = _accumulator(n_flagged, R, np.int64, "n_flagged")
-        res = {"fsum": np.zeros((R, 9)), "n_flagged": nf}
+        spec = {"fsum": ((R, 9), np.float64), "n_flagged": ((R,), np.int64)}
         if details:
-            res.update(force=np.zeros((R, n, 3)), torque=np.zeros((R, n, 3)), vir=np.zeros((R, n, 3)),
-                       atom=np.zeros((R, n, 3, 3)), ovl=np.zeros((R, n), dtype=np.uint8))
+            spec.update(force=((R, n, 3), np.float64), torque=((R, n, 3), np.float64), vir=((R, n, 3), np.float64),
+                        atom=((R, n, 3, 3), np.float64), ovl=((R, n), np.uint8))
+        res = _outputs(spec, dict(n_flagged=n_flagged), where=None)
         check(self._L.mmc_batch_forces(
-            self._h, n, None if sel_a is None else sel_a.ctypes.data_as(C.POINTER(C.c_int32)),
-            None if mass_a is None else _d(mass_a),
-            _d(res["force"]) if details else None, _d(res["torque"]) if details else None,
-            _d(res["vir"]) if details else None, _d(res["atom"]) if details else None,
-            _d(res["fsum"]), _i(nf), _u8(res["ovl"]) if details else None))
+            self._h, n, None if sel_a is None else _ptr(sel_a), None if mass_a is None else _d(mass_a),
+            *_ptrs(res, "force", "torque", "vir", "atom", "fsum", "n_flagged", "ovl")))
         return res
 
     def get_trace(self, n_steps):
@@ -763,7 +748,7 @@ class Batch:
         flags bit 0 accepted, bit 1 overlap, bit 2 rotation."""
         d = np.zeros((self.R, int(n_steps)))
         f = np.zeros((self.R, int(n_steps)), dtype=np.uint8)
-        check(self._L.mmc_batch_get_trace(self._h, _d(d), f.ctypes.data_as(C.POINTER(C.c_uint8))))
+        check(self._L.mmc_batch_get_trace(self._h, _d(d), _ptr(f)))
         return d, f
 
     def set_orientations(self, quat, db, faithful=True):
@@ -795,8 +780,7 @@ class Batch:
     def rdf(self, site, numbins):
         """mmc_batch_rdf: histogram hist[0..numbins] of gr.jl's makeRDF over all replicas."""
         hist = np.zeros(int(numbins) + 1, dtype=np.uint64)
-        check(self._L.mmc_batch_rdf(self._h, int(site), int(numbins),
-                                    hist.ctypes.data_as(C.POINTER(C.c_uint64))))
+        check(self._L.mmc_batch_rdf(self._h, int(site), int(numbins), _ptr(hist)))
         return hist
 
     def rdf_sites(self, numbins, r_max=0.0, per_replica=False, out=None):
@@ -806,24 +790,14 @@ class Batch:
         box only), else of r_max / numbins.  `out` (that shape, uint64, contiguous) is overwritten
         and returned."""
         n1 = max(int(numbins), 0) + 1  # (a numbins the library refuses still gets an array to leave alone)
-        shape = (self.R, 6, n1) if per_replica else (6, n1)
-        if out is None:
-            out = np.zeros(shape, dtype=np.uint64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.shape == shape
-                  and out.flags.c_contiguous):
-            raise ValueError(f"out: uint64 {shape}, contiguous")
-        check(self._L.mmc_batch_rdf_sites(self._h, int(numbins), float(r_max), int(bool(per_replica)),
-                                          out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        out = _output(out, (self.R, 6, n1) if per_replica else (6, n1), np.uint64)
+        check(self._L.mmc_batch_rdf_sites(self._h, int(numbins), float(r_max), int(bool(per_replica)), _ptr(out)))
         return out
 
     def dipoles(self, out=None):
         """mmc_batch_dipoles: the total dipole moment of every replica, [R, 3] in e A."""
-        if out is None:
-            out = np.zeros((self.R, 3))
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (self.R, 3)
-                  and out.flags.c_contiguous):
-            raise ValueError(f"out: float64 ({self.R}, 3), contiguous")
-        check(self._L.mmc_batch_dipoles(self._h, _d(out)))
+        out = _output(out, (self.R, 3), np.float64)
+        check(self._L.mmc_batch_dipoles(self._h, _ptr(out)))
         return out
 
     def orient_corr(self, numbins, r_max=0.0, per_replica=False, out=None):
@@ -835,14 +809,8 @@ class Batch:
         vector of the molecule's dipole.  `out` (that shape, int64, contiguous) is overwritten and
         returned."""
         n2 = max(int(numbins), 0) + 2  # (a numbins the library refuses still gets an array to leave alone)
-        shape = (self.R, 4, n2) if per_replica else (4, n2)
-        if out is None:
-            out = np.zeros(shape, dtype=np.int64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.shape == shape
-                  and out.flags.c_contiguous):
-            raise ValueError(f"out: int64 {shape}, contiguous")
-        check(self._L.mmc_batch_orient_corr(self._h, int(numbins), float(r_max), int(bool(per_replica)),
-                                            _i(out)))
+        out = _output(out, (self.R, 4, n2) if per_replica else (4, n2), np.int64)
+        check(self._L.mmc_batch_orient_corr(self._h, int(numbins), float(r_max), int(bool(per_replica)), _ptr(out)))
         return out
 
     def sdf(self, n_half, cell, fold=3, site_mask=1, per_replica=False, out=None):
@@ -859,13 +827,12 @@ class Batch:
         g = (n if f & 1 else 2 * n, n if f & 2 else 2 * n, 2 * n)
         cells = g[0] * g[1] * g[2]
         shape = (self.R, cells + 2) if per_replica else (cells + 2,)
-        if out is None:
-            out = np.zeros(shape if cells <= 32768 else shape[:-1] + (2,), dtype=np.uint64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.shape == shape
-                  and out.flags.c_contiguous):
-            raise ValueError(f"out: uint64 {shape}, contiguous")
+        if out is None and cells > 32768:   # (a grid the library refuses: two slots to leave alone, not cells + 2)
+            out = np.zeros(shape[:-1] + (2,), dtype=np.uint64)
+        else:
+            out = _output(out, shape, np.uint64)
         check(self._L.mmc_batch_sdf(self._h, int(n_half), float(cell), f, int(site_mask), int(bool(per_replica)),
-                                    out.ctypes.data_as(C.POINTER(C.c_uint64))))
+                                    _ptr(out)))
         return Sdf(out[..., :cells].reshape(shape[:-1] + g), out[..., cells], out[..., cells + 1])
 
     def pair_energy(self, numbins, r_max=0.0, n_ebins=0, u_lo=-4000.0, u_hi=2000.0, u_hb=None, per_replica=False,
@@ -888,23 +855,11 @@ class Batch:
             spec["uhist"] = (lead + (max(ne, 0) + 2,), np.uint64)
         if u_hb is not None:
             spec["nhb"] = (lead + (9,), np.uint64)
-        if out is not None and not (isinstance(out, dict) and set(out) <= set(spec)):
-            raise ValueError(f"out: a dict with keys among {sorted(spec)}")
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k):
-            return res[k].ctypes.data_as(C.POINTER(C.c_uint64)) if k in res else None
+        res = _outputs(spec, out, known_only=True)
         check(self._L.mmc_batch_pair_energy(
             self._h, int(numbins), float(r_max), ne, float(u_lo), float(u_hi),
-            0.0 if u_hb is None else float(u_hb), int(bool(per_replica)), _i(res["rows"]), ptr("uhist"),
-            ptr("nhb"), ptr("flagged")))
+            0.0 if u_hb is None else float(u_hb), int(bool(per_replica)),
+            *_ptrs(res, "rows", "uhist", "nhb", "flagged")))
         return PairEnergy(res["rows"], res.get("uhist"), res.get("nhb"), res["flagged"])
 
     def structure_factor(self, n_max, per_replica=False, out=None):
@@ -918,15 +873,11 @@ class Batch:
         returned.  With per-replica boxes only per_replica=True."""
         S = max(int(n_max), 0) ** 2 + 1  # (an n_max the library refuses still gets arrays to leave alone)
         shape, dt = ((self.R, 6, S), np.int64) if per_replica else ((6, S), np.float64)
-        if out is None:
-            out = np.zeros(shape, dtype=dt)
-        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.shape == shape and out.flags.c_contiguous):
-            raise ValueError(f"out: {np.dtype(dt).name} {shape}, contiguous")
+        out = _output(out, shape, dt)
         count = np.zeros(S, dtype=np.int32)
-        check(self._L.mmc_batch_structure_factor(self._h, int(n_max), int(bool(per_replica)),
-                                                 count.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                 _i(out) if per_replica else None,
-                                                 None if per_replica else _d(out)))
+        check(self._L.mmc_batch_structure_factor(self._h, int(n_max), int(bool(per_replica)), _ptr(count),
+                                                 _ptr(out) if per_replica else None,
+                                                 None if per_replica else _ptr(out)))
         return count, out
 
     def local_order(self, q_bins=400, r_hb=3.5, theta_deg=30.0, per_replica=False, details=False, out=None):
@@ -944,21 +895,10 @@ class Batch:
                 "q_sum": ((R, 2), np.float64)}
         if details:
             spec.update(nbr=((R, N, 4), np.int32), q=((R, N), np.float64), hb=((R, N, 2), np.uint8))
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_local_order(
             self._h, float(r_hb), float(np.cos(np.deg2rad(float(theta_deg)))), int(q_bins),
-            int(bool(per_replica)), ptr("hb_hist", C.c_uint64), ptr("q_hist", C.c_uint64),
-            ptr("q_sum", C.c_double), ptr("nbr", C.c_int32), ptr("q", C.c_double), ptr("hb", C.c_uint8)))
+            int(bool(per_replica)), *_ptrs(res, "hb_hist", "q_hist", "q_sum", "nbr", "q", "hb")))
         return res
 
     def shell_order(self, r_list=6.0, r_lsi=3.7, r_ang=3.3, r_hb=3.5, theta_deg=30.0, n_rank=8, r_bins=300,
@@ -988,24 +928,13 @@ class Batch:
         if details:
             spec.update(count=((R, N), np.int32), nbr=((R, N, 16), np.int32), lsi=((R, N), np.float64),
                         zeta=((R, N), np.float64))
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_shell_order(
             self._h, float(r_list), float(r_lsi), float(r_ang), float(r_hb),
             float(np.cos(np.deg2rad(float(theta_deg)))), int(n_rank), int(r_bins), int(lsi_bins), float(lsi_max),
             int(ang_bins), int(zeta_bins), float(zeta_lo), float(zeta_hi), int(bool(per_replica)),
-            ptr("rank_hist", C.c_uint64), ptr("lsi_hist", C.c_uint64), ptr("ang_hist", C.c_uint64),
-            ptr("zeta_hist", C.c_uint64), ptr("flagged", C.c_uint64), ptr("sums", C.c_double),
-            ptr("count", C.c_int32), ptr("nbr", C.c_int32), ptr("lsi", C.c_double), ptr("zeta", C.c_double)))
+            *_ptrs(res, "rank_hist", "lsi_hist", "ang_hist", "zeta_hist", "flagged", "sums", "count", "nbr", "lsi",
+                   "zeta")))
         return res
 
     def voronoi(self, r_list=7.0, area_min=0.0, v_bins=200, v_max=80.0, eta_bins=200, eta_max=3.0, r_bins=280,
@@ -1034,23 +963,12 @@ class Batch:
         if details:
             spec.update(vol=((R, N), np.float64), area=((R, N), np.float64), faces=((R, N), np.int32),
                         nbr=((R, N, 64), np.int32), face_area=((R, N, 64), np.float64))
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_voronoi(
             self._h, float(r_list), float(area_min), int(v_bins), float(v_max), int(eta_bins), float(eta_max),
-            int(r_bins), int(bool(per_replica)), ptr("vol_hist", C.c_uint64), ptr("eta_hist", C.c_uint64),
-            ptr("face_hist", C.c_uint64), ptr("side_hist", C.c_uint64), ptr("nbr_hist", C.c_uint64),
-            ptr("flagged", C.c_uint64), ptr("sums", C.c_double), ptr("vol", C.c_double), ptr("area", C.c_double),
-            ptr("faces", C.c_int32), ptr("nbr", C.c_int32), ptr("face_area", C.c_double)))
+            int(r_bins), int(bool(per_replica)),
+            *_ptrs(res, "vol_hist", "eta_hist", "face_hist", "side_hist", "nbr_hist", "flagged", "sums", "vol", "area",
+                   "faces", "nbr", "face_area")))
         return res
 
     def bond_order(self, l=3, r_nb=3.5, n_nb=4, a=(-np.inf, -0.8), b=(-0.35, 0.25), min_a=3, min_ab=4, q_bins=200,
@@ -1080,24 +998,12 @@ class Batch:
         if details:
             spec.update(q=((R, N), np.float64), qbar=((R, N), np.float64), nbr=((R, N, 16), np.int32),
                         ab=((R, N, 2), np.uint8), label=((R, N), np.int32))
-        res = {}
-        for k, (shape, dt) in spec.items():
-            arr = None if out is None else out.get(k)
-            if arr is None:
-                arr = np.zeros(shape, dtype=dt)
-            elif not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.shape == shape and arr.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = arr
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_bond_order(
             self._h, int(l), float(r_nb), int(n_nb), float(a[0]), float(a[1]), float(b[0]), float(b[1]), int(min_a),
             int(min_ab), int(q_bins), int(c_bins), int(bool(per_replica)),
-            ptr("q_hist", C.c_uint64), ptr("qbar_hist", C.c_uint64), ptr("c_hist", C.c_uint64),
-            ptr("ab_hist", C.c_uint64), ptr("size_hist", C.c_uint64), ptr("stats", C.c_int64), ptr("sums", C.c_double),
-            ptr("q", C.c_double), ptr("qbar", C.c_double), ptr("nbr", C.c_int32), ptr("ab", C.c_uint8),
-            ptr("label", C.c_int32)))
+            *_ptrs(res, "q_hist", "qbar_hist", "c_hist", "ab_hist", "size_hist", "stats", "sums", "q", "qbar", "nbr",
+                   "ab", "label")))
         return res
 
     def hbond_network(self, r_hb=(3.5,), theta_deg=(30.0,), min_bonds=(0,), per_replica=False, details=False,
@@ -1129,21 +1035,10 @@ class Batch:
                 "stats": ((R, K, 8), np.int64)}
         if details:
             spec.update(label=((R, K, N), np.int32), nbr=((R, K, N, 16), np.int32))
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_hbond_network(
-            self._h, K, _d(rh), _d(cs), mb.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(per_replica)),
-            ptr("size_hist", C.c_uint64), ptr("deg_hist", C.c_uint64), ptr("stats", C.c_int64),
-            ptr("label", C.c_int32), ptr("nbr", C.c_int32)))
+            self._h, K, _d(rh), _d(cs), _ptr(mb), int(bool(per_replica)),
+            *_ptrs(res, "size_hist", "deg_hist", "stats", "label", "nbr")))
         return res
 
     def hbond_rings(self, r_hb=3.5, theta_deg=30.0, n_max=8, per_replica=False, details=False, max_rings=0, out=None):
@@ -1168,21 +1063,10 @@ class Batch:
             spec["count"] = ((R, N, 9), np.uint16)
             if int(max_rings) > 0:
                 spec["ring"] = ((R, int(max_rings), 8), np.int32)
-        res = {}
-        for k, (shape, dt) in spec.items():
-            a = None if out is None else out.get(k)
-            if a is None:
-                a = np.zeros(shape, dtype=dt)
-            elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError(f"out[{k!r}]: {np.dtype(dt).name} {shape}, contiguous")
-            res[k] = a
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+        res = _outputs(spec, out)
         check(self._L.mmc_batch_hbond_rings(
             self._h, float(r_hb), float(np.cos(np.deg2rad(float(theta_deg)))), int(n_max), int(bool(per_replica)),
-            ptr("ring_hist", C.c_uint64), ptr("member_hist", C.c_uint64), ptr("stats", C.c_int64),
-            ptr("count", C.c_uint16), int(max_rings), ptr("ring", C.c_int32)))
+            *_ptrs(res, "ring_hist", "member_hist", "stats", "count"), int(max_rings), *_ptrs(res, "ring")))
         return res
 
     def _cavity(self, points, n_probe, seed, draw0, radii, site, n_cap, nn_bins, nn_max, per_replica, details):
@@ -1191,26 +1075,22 @@ class Batch:
         K, cap, nb = rad.shape[0], max(int(n_cap), 0), max(int(nn_bins), 0)
         lead = (R,) if per_replica else ()
         # (sizes the library refuses still get arrays to leave alone)
-        res = {"occ_hist": np.zeros(lead + (K, cap + 1), dtype=np.uint64),
-               "occ_mom": np.zeros(lead + (K, 2), dtype=np.uint64)}
+        spec = {"occ_hist": (lead + (K, cap + 1), np.uint64), "occ_mom": (lead + (K, 2), np.uint64)}
         if nb > 0:
-            res["nn_hist"] = np.zeros(lead + (nb + 1,), dtype=np.uint64)
+            spec["nn_hist"] = (lead + (nb + 1,), np.uint64)
             if nn_max is None:
                 raise ValueError("nn_bins > 0 needs nn_max")
         if details:
             if points is None:
-                res["points"] = np.zeros((R, P, 3))
-            res.update(count=np.zeros((R, P, K), dtype=np.int32), nn_r2=np.zeros((R, P)),
-                       nn_idx=np.zeros((R, P), dtype=np.int32))
-
-        def ptr(k, ct):
-            return res[k].ctypes.data_as(C.POINTER(ct)) if k in res else None
+                spec["points"] = ((R, P, 3), np.float64)
+            spec.update(count=((R, P, K), np.int32), nn_r2=((R, P), np.float64), nn_idx=((R, P), np.int32))
+        res = _outputs(spec, None)
         common = (int(site), K, _d(rad), int(n_cap), nb, float(nn_max) if nb > 0 else 0.0, int(bool(per_replica)),
-                  ptr("occ_hist", C.c_uint64), ptr("occ_mom", C.c_uint64), ptr("nn_hist", C.c_uint64))
-        tail = (ptr("count", C.c_int32), ptr("nn_r2", C.c_double), ptr("nn_idx", C.c_int32))
+                  *_ptrs(res, "occ_hist", "occ_mom", "nn_hist"))
+        tail = _ptrs(res, "count", "nn_r2", "nn_idx")
         if points is None:
             check(self._L.mmc_batch_cavity(self._h, int(n_probe), int(seed) & (2 ** 64 - 1), int(draw0), *common,
-                                           ptr("points", C.c_double), *tail))
+                                           *_ptrs(res, "points"), *tail))
         else:
             check(self._L.mmc_batch_cavity_at(self._h, int(n_probe), _d(points), *common, *tail))
             if details:
@@ -1255,17 +1135,13 @@ class Batch:
         else:
             sc = _f64(np.atleast_1d(scales)).ravel()
         K = sc.shape[0]
-        bs = np.zeros((self.R, K)) if boltz_sum is None else boltz_sum
-        no = np.zeros((self.R, K), dtype=np.int64) if n_overlap is None else n_overlap
-        if not (isinstance(bs, np.ndarray) and bs.dtype == np.float64 and bs.shape == (self.R, K)
-                and bs.flags.c_contiguous and isinstance(no, np.ndarray) and no.dtype == np.int64
-                and no.shape == (self.R, K) and no.flags.c_contiguous):
-            raise ValueError("boltz_sum: float64 (R, K), n_overlap: int64 (R, K), contiguous (updated in place)")
-        du = np.zeros((self.R, K, 4)) if details else None
-        base = np.zeros((self.R, 4)) if details else None
-        check(self._L.mmc_batch_volume_perturb(self._h, K, _d(sc), float(temperature), _d(bs), _i(no),
-                                               _d(du) if details else None, _d(base) if details else None))
-        return (bs, no, du, base) if details else (bs, no)
+        spec = {"boltz_sum": ((self.R, K), np.float64), "n_overlap": ((self.R, K), np.int64)}
+        if details:
+            spec.update(du=((self.R, K, 4), np.float64), base=((self.R, 4), np.float64))
+        res = _outputs(spec, dict(boltz_sum=boltz_sum, n_overlap=n_overlap), where=None)
+        check(self._L.mmc_batch_volume_perturb(self._h, K, _d(sc), float(temperature),
+                                               *_ptrs(res, "boltz_sum", "n_overlap", "du", "base")))
+        return tuple(res.values())
 
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the

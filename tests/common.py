@@ -363,3 +363,36 @@ def widom_host_sums(du, ovl, boltz0, novl0, temperature):
         bs = np.where(flagged[:, j], bs, bs + w[:, j])
     no += flagged.sum(1)
     return bs, no
+
+
+def header_define(name):
+    """The value of `#define name value` in include/mmc_hip.h, as text."""
+    from test_abi import HEADER
+    m = re.search(r"^#define\s+%s\s+(\S+)" % name, open(HEADER).read(), flags=re.M)
+    assert m, f"{name} is not defined in mmc_hip.h"
+    return m.group(1)
+
+
+class _UnreachableLibrary:
+    """Stands where a wrapper's library handle does: any call through it fails the test."""
+
+    def __getattr__(self, name):
+        def reached(*args):
+            raise AssertionError("the library was reached")
+        return reached
+
+
+def fake_batch(method_name, R=2, n_mol=10, **attrs):
+    """An object with device.Batch's `method_name` (several names: separate them with blanks) bound
+    to it and the attributes the wrappers read: R, n_mol, _h = None, and an _L that fails the test
+    when a wrapper's own argument checks let a call through.  `attrs` adds or replaces attributes,
+    _L among them.  Needs no built library."""
+    from metropolismontecarlo_amd.device import Batch
+
+    class Fake:
+        pass
+    fake = Fake()
+    fake.__dict__.update(dict(R=R, n_mol=n_mol, _h=None, _L=_UnreachableLibrary()), **attrs)
+    for name in method_name.split():
+        setattr(fake, name, getattr(Batch, name).__get__(fake))
+    return fake

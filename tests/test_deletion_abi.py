@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from metropolismontecarlo_amd import _lib
+from common import fake_batch
 
 NAME = "mmc_batch_deletion"
 PROTOTYPE = ("int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t *sel, double temperature, "
@@ -105,22 +106,7 @@ def test_a_grid_is_not_looked_at_without_a_histogram():
     assert st == _lib.MMC_ERR_ARG and "batch is NULL" in msg
 
 
-class _FakeBatch:
-    """device.Batch.deletion's own argument checks run before the library is called."""
-    R, n_mol = 2, 10
-
-    def __init__(self):
-        from metropolismontecarlo_amd.device import Batch
-        self.deletion = Batch.deletion.__get__(self)
-        self._h = None
-
-        class _L:
-            @staticmethod
-            def mmc_batch_deletion(*args):
-                raise AssertionError("the library was reached")
-        self._L = _L
-
-
+# (device.Batch.deletion's own argument checks run before the library is called.)
 @pytest.mark.parametrize("kw", [
     dict(sel=np.zeros((2, 2), dtype=np.int64)), dict(sel=np.array([0.5, 1.0])), dict(sel=np.array([2 ** 40])),
     dict(boltz_sum=np.zeros(3)), dict(boltz_sum=np.zeros(2, dtype=np.float32)), dict(boltz_sum=[0.0, 0.0]),
@@ -128,4 +114,4 @@ class _FakeBatch:
 ])
 def test_the_wrapper_checks_its_arguments(kw):
     with pytest.raises(ValueError):
-        _FakeBatch().deletion(298.15, **kw)
+        fake_batch("deletion").deletion(298.15, **kw)

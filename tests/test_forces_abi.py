@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from metropolismontecarlo_amd import _lib
+from common import fake_batch
 
 NAME = "mmc_batch_forces"
 PROTOTYPE = ("int32_t mmc_batch_forces(mmc_batch *b, int32_t n_sel, const int32_t *sel, const double *mass , "
@@ -101,22 +102,7 @@ def test_arguments_refused_without_a_device(kw, word):
     assert word in msg and "batch is NULL" not in msg, msg
 
 
-class _FakeBatch:
-    """device.Batch.forces' own argument checks run before the library is called."""
-    R, n_mol = 2, 10
-
-    def __init__(self):
-        from metropolismontecarlo_amd.device import Batch
-        self.forces = Batch.forces.__get__(self)
-        self._h = None
-
-        class _L:
-            @staticmethod
-            def mmc_batch_forces(*args):
-                raise AssertionError("the library was reached")
-        self._L = _L
-
-
+# (device.Batch.forces' own argument checks run before the library is called.)
 @pytest.mark.parametrize("kw", [
     dict(sel=np.zeros((2, 2), dtype=np.int64)), dict(sel=np.array([0.5, 1.0])), dict(sel=np.array([2 ** 40])),
     dict(mass=np.ones(2)), dict(mass=np.ones((3, 1))),
@@ -124,4 +110,4 @@ class _FakeBatch:
 ])
 def test_the_wrapper_checks_its_arguments(kw):
     with pytest.raises(ValueError):
-        _FakeBatch().forces(**kw)
+        fake_batch("forces").forces(**kw)

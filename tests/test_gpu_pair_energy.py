@@ -129,7 +129,7 @@ def wave_boundaries(n_ebins):
     8 rs + 144 + nw 8 (3 rs + e_slots + 1) bytes with rs = numbins + 2, within 65536.  For nw = 4 and 2:
     the last numbins that fits and the first that does not, where the call allows them; then the
     largest numbins allowed."""
-    from test_orient_abi import header_define
+    from common import header_define
     max_bins, max_ebins = int(header_define("MMC_PAIRE_MAX_BINS")), int(header_define("MMC_PAIRE_MAX_EBINS"))
     assert max_bins == MAX_BINS and n_ebins <= max_ebins
     e_slots = n_ebins + 2 if n_ebins else 0

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from metropolismontecarlo_amd import _lib
+from common import fake_batch, header_define
 
 NAME = "mmc_batch_orient_corr"
 PROTOTYPE = ("int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica, "
@@ -19,12 +20,6 @@ SENTINEL = -0x0123456789abcdef
 def header_text():
     from test_abi import HEADER
     return open(HEADER).read()
-
-
-def header_define(name):
-    m = re.search(r"^#define\s+%s\s+(\S+)" % name, header_text(), flags=re.M)
-    assert m, f"{name} is not defined in mmc_hip.h"
-    return m.group(1)
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
@@ -96,22 +91,7 @@ def test_arguments_refused_without_a_device(kw, word):
     assert word in msg and "batch is NULL" not in msg, msg
 
 
-class _FakeBatch:
-    """device.Batch.orient_corr's own check of `out` runs before the library is called."""
-    R, n_mol = 2, 10
-
-    def __init__(self):
-        from metropolismontecarlo_amd.device import Batch
-        self.orient_corr = Batch.orient_corr.__get__(self)
-        self._h = None
-
-        class _L:
-            @staticmethod
-            def mmc_batch_orient_corr(*args):
-                raise AssertionError("the library was reached")
-        self._L = _L
-
-
+# (device.Batch.orient_corr's own check of `out` runs before the library is called.)
 @pytest.mark.parametrize("kw", [
     dict(out=np.zeros((4, 12), dtype=np.uint64)), dict(out=np.zeros((4, 11), dtype=np.int64)),
     dict(out=np.zeros((2, 4, 12), dtype=np.int64)), dict(out=np.zeros((4, 24), dtype=np.int64)[:, ::2]),
@@ -119,6 +99,6 @@ class _FakeBatch:
 ])
 def test_the_wrapper_checks_its_arguments(kw):
     with pytest.raises(ValueError):
-        _FakeBatch().orient_corr(10, **kw)
+        fake_batch("orient_corr").orient_corr(10, **kw)
     with pytest.raises(AssertionError, match="the library was reached"):
-        _FakeBatch().orient_corr(10, out=np.zeros((4, 12), dtype=np.int64))
+        fake_batch("orient_corr").orient_corr(10, out=np.zeros((4, 12), dtype=np.int64))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from metropolismontecarlo_amd import _lib
+from common import fake_batch, header_define
 
 NAME = "mmc_batch_sdf"
 PROTOTYPE = ("int32_t mmc_batch_sdf(mmc_batch *b, int32_t n_half, double cell, int32_t fold, int32_t site_mask, "
@@ -19,12 +20,6 @@ SENTINEL = 0xfedcba9876543210
 def header_text():
     from test_abi import HEADER
     return open(HEADER).read()
-
-
-def header_define(name):
-    m = re.search(r"^#define\s+%s\s+(\S+)" % name, header_text(), flags=re.M)
-    assert m, f"{name} is not defined in mmc_hip.h"
-    return m.group(1)
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
@@ -107,22 +102,7 @@ def test_arguments_refused_without_a_device(kw, word):
     assert word in msg and "batch is NULL" not in msg, msg
 
 
-class _FakeBatch:
-    """device.Batch.sdf's own check of `out` runs before the library is called."""
-    R, n_mol = 2, 10
-
-    def __init__(self):
-        from metropolismontecarlo_amd.device import Batch
-        self.sdf = Batch.sdf.__get__(self)
-        self._h = None
-
-        class _L:
-            @staticmethod
-            def mmc_batch_sdf(*args):
-                raise AssertionError("the library was reached")
-        self._L = _L
-
-
+# (device.Batch.sdf's own check of `out` runs before the library is called.)
 @pytest.mark.parametrize("kw", [
     dict(out=np.zeros(18, dtype=np.int64)), dict(out=np.zeros(17, dtype=np.uint64)),
     dict(out=np.zeros((2, 18), dtype=np.uint64)), dict(out=np.zeros(36, dtype=np.uint64)[::2]),
@@ -131,8 +111,8 @@ class _FakeBatch:
 ])
 def test_the_wrapper_checks_its_arguments(kw):
     with pytest.raises(ValueError):
-        _FakeBatch().sdf(2, 0.5, **kw)                      # fold 3: 2 x 2 x 4 cells + 2
+        fake_batch("sdf").sdf(2, 0.5, **kw)                 # fold 3: 2 x 2 x 4 cells + 2
     with pytest.raises(AssertionError, match="the library was reached"):
-        _FakeBatch().sdf(2, 0.5, out=np.zeros(18, dtype=np.uint64))
+        fake_batch("sdf").sdf(2, 0.5, out=np.zeros(18, dtype=np.uint64))
     with pytest.raises(AssertionError, match="the library was reached"):
-        _FakeBatch().sdf(2, 0.5, fold=0, per_replica=True, out=np.zeros((2, 66), dtype=np.uint64))
+        fake_batch("sdf").sdf(2, 0.5, fold=0, per_replica=True, out=np.zeros((2, 66), dtype=np.uint64))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from metropolismontecarlo_amd import _lib
+from common import fake_batch, header_define
 
 NAME = "mmc_batch_structure_factor"
 PROTOTYPE = ("int32_t mmc_batch_structure_factor(mmc_batch *b, int32_t n_max, int32_t per_replica, "
@@ -20,12 +21,6 @@ SENTINEL = -0x0123456789abcdef
 def header_text():
     from test_abi import HEADER
     return open(HEADER).read()
-
-
-def header_define(name):
-    m = re.search(r"^#define\s+%s\s+(\S+)" % name, header_text(), flags=re.M)
-    assert m, f"{name} is not defined in mmc_hip.h"
-    return m.group(1)
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
@@ -105,22 +100,7 @@ def test_arguments_refused_without_a_device(kw, word):
     assert word in msg and "batch is NULL" not in msg, msg
 
 
-class _FakeBatch:
-    """device.Batch.structure_factor's own check of `out` runs before the library is called."""
-    R, n_mol = 2, 10
-
-    def __init__(self):
-        from metropolismontecarlo_amd.device import Batch
-        self.structure_factor = Batch.structure_factor.__get__(self)
-        self._h = None
-
-        class _L:
-            @staticmethod
-            def mmc_batch_structure_factor(*args):
-                raise AssertionError("the library was reached")
-        self._L = _L
-
-
+# (device.Batch.structure_factor's own check of `out` runs before the library is called.)
 @pytest.mark.parametrize("kw", [
     dict(out=np.zeros((6, 10), dtype=np.int64)), dict(out=np.zeros((6, 9), dtype=np.float64)),
     dict(out=np.zeros((2, 6, 10), dtype=np.float64)), dict(out=np.zeros((6, 20), dtype=np.float64)[:, ::2]),
@@ -130,8 +110,8 @@ class _FakeBatch:
 ])
 def test_the_wrapper_checks_its_arguments(kw):
     with pytest.raises(ValueError):
-        _FakeBatch().structure_factor(3, **kw)
+        fake_batch("structure_factor").structure_factor(3, **kw)
     with pytest.raises(AssertionError, match="the library was reached"):
-        _FakeBatch().structure_factor(3, out=np.zeros((6, 10), dtype=np.float64))
+        fake_batch("structure_factor").structure_factor(3, out=np.zeros((6, 10), dtype=np.float64))
     with pytest.raises(AssertionError, match="the library was reached"):
-        _FakeBatch().structure_factor(3, per_replica=True, out=np.zeros((2, 6, 10), dtype=np.int64))
+        fake_batch("structure_factor").structure_factor(3, per_replica=True, out=np.zeros((2, 6, 10), dtype=np.int64))
