@@ -1,19 +1,29 @@
 """numpy restatement of mmc_batch_structure_factor for the structure-factor tests (not a test
-module): the definitions of include/mmc_hip.h, "Partial structure factors", in unfused fp64 -- the
-phase factors of every atom, their powers by repeated complex products from 1, the product order
-(x y) z, lane l of 64 adding the molecules l, l + 64, ... in that order, the 64 lane sums by
-wave_sum's tree, Q and the doubling of the half space.  The one thing not restated is
-sincos_moderate: numpy's cos and sin stand for it (both within an ulp of the exact value; what a
-last-place difference of a phase factor can do to an entry is far inside the tests' bound of one
-unit per vector).
+module): the definitions of include/mmc_hip.h, "Partial structure factors", operation by operation
+in unfused fp64, so that the device (built with -ffp-contract=off) can be asked to agree BIT FOR
+BIT.  Nothing is left unrestated:
+
+  phase factors   (cos, sin) of (MMC_TWOPI x) / L by sincos_moderate, both from
+                  tests/elementary_ref.py (its fma is exact; both argument branches), one scalar
+                  call per coordinate (phase_factors);
+  powers          p_0 = 1, p_k = c_mul(p_{k-1}, e1): sq_pow's first product is 1 e1, which is
+                  exact, and a block's first power z1^k0 is the same k0 products from 1;
+  negative ny     the conjugate of y1^|ny|, taken after the power;
+  the term        c_mul(c_mul(ex, ey), p_k) for nz = k, c_mul(c_mul(ex, ey), conj(p_k)) for nz = -k;
+  the sums        lane l of 64 adds the molecules l, l + 64, ... in that order from 0.0, the 64 lane
+                  sums go through wave_sum's tree (lane_sum);
+  a row's value   re_a re_b + im_a im_b: two products and one add;
+  Q               v 2^24 (exact) rounded to the nearest integer, ties to even -- the device's
+                  1.5 2^52 add; np.rint rounds the same way -- and the doubling of the half space.
 
 sofq_rows_direct is a second, independent form: np.longdouble, cos and sin of 2 pi n . r / L taken
 directly, plain sums."""
 import numpy as np
 
+import elementary_ref as er
+
 SCALE = 2.0 ** 24
 SLOT_PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
-TWOPI = 2.0 * 3.141592653589793
 
 
 def shell_counts(n_max):
@@ -93,14 +103,20 @@ def _slots(coords):
     return c.reshape(-1, 3, 3).transpose(1, 0, 2)     # [slot, molecule, component]
 
 
+def phase_factors(coords, box):
+    """[(re, im)] for the axes x, y, z, each float64 [slot, molecule]: elementary_ref.phase of every
+    coordinate -- the device's sincos_moderate at the device's argument, one scalar call each."""
+    x = _slots(coords)
+    L = float(box)
+    ph = np.array([er.phase(float(v), L) for v in x.ravel()], dtype=np.float64).reshape(x.shape + (2,))
+    return [(ph[..., d, 0].copy(), ph[..., d, 1].copy()) for d in range(3)]
+
+
 def sofq_rows(coords, box, n_max):
     """int64 [6, n_max^2 + 1] of one frame of 3-site molecules (coords [3 N, 3]) in a box of side
     `box`: sq[row][s] = 2 sum over the half-space vectors of shell s of Q(rho_a.re rho_b.re +
     rho_a.im rho_b.im)."""
-    x = _slots(coords)
-    ang = TWOPI * x / float(box)
-    e1 = [(np.cos(ang[..., d]), np.sin(ang[..., d])) for d in range(3)]       # each [slot, molecule]
-    px, py, pz = (powers(e, n_max) for e in e1)
+    px, py, pz = (powers(e, n_max) for e in phase_factors(coords, box))
     out = np.zeros((6, n_max * n_max + 1), dtype=np.int64)
     for nx, ny, nzs in half_space_columns(n_max):
         ex, ey = px[nx], py[abs(ny)]
