@@ -647,6 +647,69 @@ int32_t mmc_batch_run_chains(mmc_batch *b, const mmc_run_params *p, mmc_chain *c
 int32_t mmc_chain_block_line(const mmc_chain *chain, int64_t block, int64_t n_mol, double box,
                              double ideal_term, char *buf, int64_t len);
 
+/* ---- Parallel tempering: per-replica temperatures and ladder exchanges ---------------------------
+ * mmc_batch_set_temperatures gives replica r its own temperature temps[r] (K): mmc_batch_run,
+ * mmc_batch_run_chains and mmc_batch_run_npt_replicas then decide replica r's trial moves with
+ * Metropolis(dU / temps[r]) on every path (host decisions and the move kernel's own), and
+ * mmc_batch_run_npt_replicas uses beta_r = 1 / temps[r] in the volume criterion as well;
+ * p->temperature is ignored but must still be > 0.  temps == NULL switches the array off again.
+ * An array of R equal values is the scalar chain bit for bit: the decision is the same expression
+ * dU / T with the same draws.  mmc_batch_run_npt (the one-replica chain) returns
+ * MMC_ERR_UNSUPPORTED while temperatures are set.  MMC_ERR_ARG, no state changed: a value <= 0 or
+ * not finite.  MMC_ERR_STATE: proposals outstanding (mmc_batch_settle) or a volume trial open.
+ * The entry points that take their own `temperature` argument (mmc_batch_widom*,
+ * mmc_batch_deletion, mmc_batch_volume_perturb) never read the batch's array.
+ * mmc_batch_get_temperatures: the array as it stands (exchanges permute it), 0.0 everywhere when
+ * off; it does not depend on any run's p->temperature. */
+int32_t mmc_batch_set_temperatures(mmc_batch *b, const double *temps /* [R]; NULL = off */);
+int32_t mmc_batch_get_temperatures(mmc_batch *b, double *temps /* [R]; run-independent: 0.0 when off */);
+
+/* One round of ladder exchanges, decided on the host: a pure function of its arguments -- no
+ * device, no batch.  A swap exchanges TEMPERATURES, not configurations: no replica state moves.
+ * Layout: ladder l is replicas [l n_rungs, (l + 1) n_rungs); rung[r] in 0..n_rungs-1 is the rung
+ * of its ladder that replica r holds now (a permutation within every ladder).  For every ladder l
+ * and k = parity, parity + 2, ... with k + 1 < n_rungs:
+ *   a = the replica of the ladder holding rung k, b = the one holding rung k + 1
+ *   attempt[k]++
+ *   D = (1 / temps[a] - 1 / temps[b]) * ((energies[a] - energies[b]) + pressure * (volumes[a] - volumes[b]))
+ *       (volumes == NULL, NVT:  D = (1 / temps[a] - 1 / temps[b]) * (energies[a] - energies[b]))
+ *   u = the first uniform of the Philox draw with key = seed, counter = (round (64 bit),
+ *       MMC_SLOT_EXCHANGE, (uint32_t)(replica0 + l n_rungs + k)) -- "Random streams" above:
+ *       ((x0 << 32 | x1) >> 11) * 2^-53 of the four output words x0..x3
+ *   accepted if and only if energies[a], energies[b] and D are all finite and (D >= 0 or
+ *       u < exp(D)) -- exp of the host's libm
+ *   on acceptance: temps[a] <-> temps[b], rung[a] <-> rung[b], accept[k]++
+ * A replica whose energy is +inf (an overlapping start: mmc_batch_potential_ewald's convention)
+ * never swaps.  attempt / accept: [n_rungs - 1], accumulated over calls and ladders.
+ * MMC_ERR_ARG, nothing changed: n_ladders < 1, n_rungs < 2, parity not 0 or 1, a NULL array other
+ * than volumes, rung not a permutation of 0..n_rungs-1 within a ladder, a temperature that is not
+ * positive and finite.
+ * Sharding: a rank's share of a larger ensemble holds whole ladders, so its replica0 is a multiple
+ * of n_rungs (sharding.shard / shard_total check it when given n_rungs). */
+#define MMC_SLOT_EXCHANGE 0x60000000u /* Philox slot of a ladder exchange's uniform */
+int32_t mmc_exchange_round(int64_t n_ladders, int32_t n_rungs, int32_t parity, uint64_t seed,
+                           uint64_t replica0, uint64_t round, double pressure,
+                           const double *energies, const double *volumes /* NULL: NVT */,
+                           double *temps /* in/out */, int32_t *rung /* in/out */,
+                           int64_t *attempt, int64_t *accept /* [n_rungs - 1], accumulated */);
+/* mmc_exchange_round on the batch's own temperatures (R / n_rungs ladders), which are then uploaded
+ * again.  With per-replica boxes the volumes are box^3 of mmc_batch_get_boxes; otherwise NVT, and
+ * `pressure` is ignored.  MMC_ERR_STATE: no temperatures set, proposals outstanding or a volume
+ * trial open.  MMC_ERR_ARG: R is not a multiple of n_rungs, and mmc_exchange_round's. */
+int32_t mmc_batch_exchange(mmc_batch *b, int32_t n_rungs, int32_t parity, uint64_t seed, uint64_t replica0,
+                           uint64_t round, double pressure, const double *energies, int32_t *rung,
+                           int64_t *attempt, int64_t *accept);
+/* n_rounds x { p->n_steps trial moves for every replica (mmc_batch_run), one exchange }: round i
+ * uses round = round0 + i and parity = (round0 + i) & 1, with p->seed and p->replica0.  energies:
+ * in/out [R] running totals (in Wolf style the Wolf totals).  stats: summed over the rounds as
+ * mmc_batch_run_npt_replicas sums them.  One-box batches only (MMC_ERR_UNSUPPORTED with
+ * per-replica boxes: drive an NPT ladder as mmc_batch_run_npt_replicas of one sweep followed by
+ * mmc_batch_exchange).  Errors otherwise as mmc_batch_exchange and mmc_batch_run; the arguments of
+ * the exchange are checked before the first move. */
+int32_t mmc_batch_run_exchange(mmc_batch *b, const mmc_run_params *p, int64_t n_rounds, int32_t n_rungs,
+                               uint64_t round0, double *energies, int32_t *rung,
+                               int64_t *attempt, int64_t *accept, mmc_run_stats *stats);
+
 /* ---- Widom test-particle insertion: the excess chemical potential of every replica ------------
  * The reference has no insertion code (its README names free energies and adsorption as goals);
  * the insertion energy is DEFINED through its own total energy, potential(..., "ewald")
@@ -688,9 +751,13 @@ int32_t mmc_chain_block_line(const mmc_chain *chain, int64_t block, int64_t n_mo
  * mmc_batch_widom_at evaluates the caller's molecules mol_in [R][n_insert][12] (same layout as
  * mol_out) with the same kernel. */
 #define MMC_SLOT_WIDOM 0x50000000u /* Philox slots of an insertion: +0..+5 (+3, +4, +5: B of mmc_batch_widom_pair) */
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t draw0,
                         const double *offsets, double temperature, double *boltz_sum,
                         int64_t *n_overlap, double *mol_out, double *du_out, uint8_t *ovl_out);
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in, double temperature,
                            double *boltz_sum, int64_t *n_overlap, double *du_out, uint8_t *ovl_out);
 
@@ -738,10 +805,14 @@ int32_t mmc_batch_widom_at(mmc_batch *b, int64_t n_insert, const double *mol_in,
  * stale; per-replica boxes, Wolf style, a system the table kernels do not take).  Nothing is
  * written on a refusal. */
 #define MMC_SOLUTE_MAX_SITES 16
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom_solute(mmc_batch *b, int32_t n_sites, const double *offsets, const double *charge,
                                const double *eps, const double *sig, int64_t n_insert, uint64_t seed,
                                int64_t draw0, double temperature, double *boltz_sum, int64_t *n_overlap,
                                double *mol_out, double *du_out, uint8_t *ovl_out);
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *charge, const double *eps,
                                   const double *sig, int64_t n_insert, const double *mol_in,
                                   double temperature, double *boltz_sum, int64_t *n_overlap,
@@ -803,6 +874,8 @@ int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *c
  * mmc_batch_widom_solute (proposals outstanding, S(k) stale; per-replica boxes, Wolf style, a
  * system the table kernels do not take).  Nothing is written on a refusal. */
 #define MMC_PAIR_MAX_SEP 32
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom_pair(mmc_batch *b, int32_t n_sites_a, const double *offsets_a, const double *charge_a,
                              const double *eps_a, const double *sig_a, int32_t n_sites_b, const double *offsets_b,
                              const double *charge_b, const double *eps_b, const double *sig_b, const double *eps_ab,
@@ -810,6 +883,8 @@ int32_t mmc_batch_widom_pair(mmc_batch *b, int32_t n_sites_a, const double *offs
                              int64_t draw0, double temperature, double *boltz_a, int64_t *n_zero_a, double *boltz_b,
                              int64_t *n_zero_b, double *boltz_ab, int64_t *n_zero_ab, double *mol_a_out,
                              double *mol_b_out, double *du_out, uint8_t *flags_out);
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_widom_pair_at(mmc_batch *b, int32_t n_sites_a, const double *charge_a, const double *eps_a,
                                 const double *sig_a, int32_t n_sites_b, const double *charge_b, const double *eps_b,
                                 const double *sig_b, const double *eps_ab, const double *sig_ab, int32_t n_sep,
@@ -869,6 +944,8 @@ int32_t mmc_batch_widom_pair_at(mmc_batch *b, int32_t n_sites_a, const double *c
  * outside the erfc table), fewer than 2 molecules.  MMC_ERR_ARG: temperature <= 0 or not finite;
  * every output NULL; hist given with n_bins outside 1..4096, u_lo >= u_hi or a bound not finite;
  * sel given with n_sel < 1 or an index outside 0..N-1.  On any error every output is untouched. */
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t *sel, double temperature,
                            int32_t n_bins, double u_lo, double u_hi, int32_t per_replica,
                            uint64_t *hist      /* [n_bins + 2] or [R][n_bins + 2]; may be NULL */,
@@ -1759,6 +1836,8 @@ int32_t mmc_batch_cavity_at(mmc_batch *b, int64_t n_probe, const double *points_
  * identical 3-atom molecules); (kappa_k, r_cut) outside the erfc table's domain at the smallest L_k
  * (kappa <= 0.5 and kappa sqrt(r_cut^2 + 100) <= 4); a replica whose atoms' phases do not fit one
  * workgroup's LDS (56 bytes per atom: about 2800 atoms).  On any error every output is untouched. */
+/* (`temperature` is this call's own argument: the batch's per-replica temperatures,
+ * mmc_batch_set_temperatures, are not read) */
 int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *scale /* [K] */,
                                  double temperature,
                                  double *boltz_sum  /* [R][K] in/out, may be NULL */,

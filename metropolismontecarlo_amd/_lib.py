@@ -180,6 +180,13 @@ SIGNATURES = {
     "mmc_batch_peek_part": [_vp, _i64, _i32, _vp, C.POINTER(C.c_uint32)],
     "mmc_batch_rdf": [_vp, _i32, _i32, _u64p],
     "mmc_batch_run": [_vp, C.POINTER(RunParams), _dp, C.POINTER(RunStats)],
+    "mmc_batch_set_temperatures": [_vp, _dp],
+    "mmc_batch_get_temperatures": [_vp, _dp],
+    "mmc_exchange_round": [_i64, _i32, _i32, C.c_uint64, C.c_uint64, C.c_uint64, _d, _dp, _dp, _dp, _i32p, _i64p,
+                           _i64p],
+    "mmc_batch_exchange": [_vp, _i32, _i32, C.c_uint64, C.c_uint64, C.c_uint64, _d, _dp, _i32p, _i64p, _i64p],
+    "mmc_batch_run_exchange": [_vp, C.POINTER(RunParams), _i64, _i32, C.c_uint64, _dp, _i32p, _i64p, _i64p,
+                               C.POINTER(RunStats)],
     "mmc_study_f32_total": [_vp, _d, _d, _i32, _dp],
     "mmc_study_f32_move": [_vp, _i64, _dp, _dp, _d, _d, _i32, _dp, _i32p],
     "mmc_philox4x32": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],

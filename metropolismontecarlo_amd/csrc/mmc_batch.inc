@@ -75,6 +75,8 @@ struct mmc_batch {
     int accept_on_device = -1;         // option "accept_on_device": -1 by host threads per launch, 0 host, 1 kernel          // option "accept_on_device": 0 keeps the decision on the host
     DecideConsts *d_decide = nullptr;  // what the kernel's own accept decision needs (Driver, device-side decisions)
     DecideConsts decide_host{};        // ... as last uploaded
+    std::vector<double> temps;         // per-replica temperatures (mmc_batch_set_temperatures); empty = off
+    double *d_temps = nullptr;         // ... on the device, [R] (DecideConsts::temps), allocated on first use
     unsigned *d_queue = nullptr;       // unit tickets of the kernel's multi-step launches: group g's at [MMC_QUEUE_STRIDE g]
     unsigned queue_base[MMC_MAX_GROUPS] = {}; // ... tickets taken so far (a launch takes one per unit)
     bool queue_reset = false;          // a run failed: tickets and counts may disagree
@@ -691,21 +693,31 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
 #define MMC_WAVE_LAUNCH(SUBST, IMG) MMC_WAVE_LAUNCH3(SUBST, IMG, false)
 #define MMC_WAVE_LAUNCH3(SUBST, IMG, MULTI)                                                      \
     if (wolf) MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, true); else MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, false)
-#define MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, WOLF)                                                \
-    k_move_eval_wave<SUBST, IMG, MULTI, WOLF><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>(      \
+#define MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, WOLF) MMC_WAVE_LAUNCH5(SUBST, IMG, MULTI, WOLF, false)
+#define MMC_WAVE_LAUNCH5(SUBST, IMG, MULTI, WOLF, LADDER)                                        \
+    k_move_eval_wave<SUBST, IMG, MULTI, WOLF, LADDER><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>( \
         s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,     \
         (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,      \
         dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,      \
         dd ? dd->queue_base : 0u)
+// the forms that decide (one part per move, SUBST = false): under per-replica temperatures their
+// LADDER twins, which read DecideConsts::temps[r]
+#define MMC_WAVE_DECIDES(IMG, MULTI)                                                             \
+    if (ladder && wolf) MMC_WAVE_LAUNCH5(false, IMG, MULTI, true, true);                         \
+    else if (ladder) MMC_WAVE_LAUNCH5(false, IMG, MULTI, false, true);                           \
+    else MMC_WAVE_LAUNCH3(false, IMG, MULTI)
+        const bool ladder = dd && !b->temps.empty(); // (run_impl has put d_temps into *dd->dc)
         if (P == 1 && dd && dd->n_sub > 1) {
-            if (img) { MMC_WAVE_LAUNCH3(false, true, true); } else { MMC_WAVE_LAUNCH3(false, false, true); }
+            if (img) { MMC_WAVE_DECIDES(true, true); } else { MMC_WAVE_DECIDES(false, true); }
         } else if (P == 1) {
-            if (img) { MMC_WAVE_LAUNCH(false, true); } else { MMC_WAVE_LAUNCH(false, false); }
+            if (img) { MMC_WAVE_DECIDES(true, false); } else { MMC_WAVE_DECIDES(false, false); }
         } else {
             if (img) { MMC_WAVE_LAUNCH(true, true); } else { MMC_WAVE_LAUNCH(true, false); }
         }
+#undef MMC_WAVE_DECIDES
 #undef MMC_WAVE_LAUNCH
 #undef MMC_WAVE_LAUNCH3
+#undef MMC_WAVE_LAUNCH5
 #undef MMC_WAVE_LAUNCH4
     } else if (kernel == 1 && s.pb.on)
         k_move_eval_fast<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, nullptr, s.kpack, s.fc, cur, prev,

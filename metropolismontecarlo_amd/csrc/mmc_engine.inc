@@ -165,6 +165,7 @@ struct Driver {
     mmc_batch *b;
     const mmc_run_params *p;
     double *energies;          // mmc_batch_run
+    const double *temps = nullptr; // per-replica temperatures (mmc_batch_set_temperatures), or null: p->temperature
     mmc_chain *chains = nullptr; // mmc_batch_run_chains
     int adjust = 0;
     uint8_t s_flip = 1;          // an accepted move hands the S buffers over (main.jl:621); 0 in Wolf style,
@@ -257,7 +258,7 @@ struct Driver {
     void decide(int64_t r, const PartOut *parts, int64_t step_done, mmc_run_stats &st, const RepView &v,
                 int dev_accept = -1)
     {
-        const double T_ = p->temperature, factor = b->sys.bv.factor;
+        const double T_ = temps ? temps[r] : p->temperature, factor = b->sys.bv.factor;
         const bool sweep_end = (step_done % b->sys.n_mol) == b->sys.n_mol - 1;
         mmc_move_result res;
         mmc_combine_parts(parts, P, factor, &res);
@@ -1040,6 +1041,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     Driver d;
     d.b = b; d.p = p; d.energies = energies; d.chains = chains; d.adjust = adjust;
     d.devgen = b->device_moves != 0;
+    d.temps = b->temps.empty() ? nullptr : b->temps.data();
     d.s_flip = wolf ? 0 : 1;
     d.rng_off = b->steps_done;
     d.inject_left.store(b->inject_torn);
@@ -1176,6 +1178,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         dc.temperature = p->temperature; dc.factor = s.bv.factor;
         dc.seed = p->seed; dc.replica0 = (uint32_t)p->replica0;
         dc.flags = b->d_flags;
+        dc.temps = d.temps ? b->d_temps : nullptr; // (part of the memcmp below: switching the ladder on or off uploads again)
         dc.ring = b->d_ring; dc.ring_slots = b->ring_slots; dc.ring_stride = s.R;
         if (!b->d_decide)
             MMC_TRY(s.dmalloc((void **)&b->d_decide, sizeof(DecideConsts)));
@@ -1366,6 +1369,9 @@ extern "C" int32_t mmc_batch_run_npt(mmc_batch *b, const mmc_run_params *p, cons
     MMC_REQUIRE(p && q && energy && stats && ns, MMC_ERR_ARG, "NULL argument");
     MMC_REQUIRE(b->sys.R == 1, MMC_ERR_UNSUPPORTED,
                 "a batch has one box: an NPT chain needs a batch of ONE replica");
+    MMC_REQUIRE(b->temps.empty(), MMC_ERR_UNSUPPORTED,
+                "mmc_batch_run_npt: per-replica temperatures are set (mmc_batch_set_temperatures); a ladder "
+                "of NPT chains is mmc_batch_run_npt_replicas");
     MMC_REQUIRE(q->n_sweeps >= 0 && q->moves_per_sweep >= 0 && q->vmax >= 0 && q->alpha > 0
                     && p->temperature > 0, MMC_ERR_ARG, "bad NPT parameters");
     memset(stats, 0, sizeof(*stats));

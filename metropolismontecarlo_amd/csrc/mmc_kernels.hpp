@@ -511,6 +511,8 @@ struct DecideConsts {
     const MoveRec *ring;    // [ring_slots][ring_stride], by step % ring_slots
     int64_t ring_stride;
     uint8_t *flags; // [R]
+    const double *temps; // [R] per-replica temperatures (mmc_batch_set_temperatures), or null: read by the
+                         // LADDER instantiations of k_move_eval_wave only, in place of `temperature`
 };
 // Several steps of a chain in ONE launch (the same wave takes the replica through them: what it
 // wrote and read in one step is in the caches for the next): the launch sends ONE record per

@@ -191,7 +191,6 @@ extern "C" int32_t mmc_batch_run_npt_replicas(mmc_batch *b, const mmc_run_params
     const int64_t R = s.R, n_mol = s.n_mol;
     memset(stats, 0, sizeof(*stats));
     memset(per_replica, 0, sizeof(mmc_npt_stats) * R);
-    const double beta = 1.0 / p->temperature;
     mmc_run_params pp = *p;
     pp.n_steps = q->moves_per_sweep > 0 ? q->moves_per_sweep : n_mol;
     std::vector<double> new_boxes(R), vol_new(R), u_b(R);
@@ -235,6 +234,8 @@ extern "C" int32_t mmc_batch_run_npt_replicas(mmc_batch *b, const mmc_run_params
                 if (new_boxes[r] == 0.0)
                     continue;
                 const double P = pressures ? pressures[r] : q->pressure;
+                // (re-read every sweep: the caller's exchanges between calls permute the temperatures)
+                const double beta = 1.0 / (b->temps.empty() ? p->temperature : b->temps[r]);
                 const double arg = -beta * (P * (vol_new[r] - vol_old[r])
                                             - (double)n_mol * log(vol_new[r] / vol_old[r]) / beta
                                             + (tot[r].energy - energies[r])); // :129-130

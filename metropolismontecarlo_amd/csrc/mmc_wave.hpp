@@ -248,6 +248,9 @@ __device__ __forceinline__ void phase_row_moderate(double x, double L, cplx *row
 
 // The kernel's own Metropolis decision (DecideConsts, mmc_kernels.hpp): every lane computes it from
 // the unit's seven sums in LDS; lane 0 rewrites the replica's flag byte.  Returns accept (0 / 1).
+// LADDER = true (parallel tempering, mmc_batch_set_temperatures): the replica's own temperature
+// dc->temps[r] in place of dc->temperature -- r is uniform over the wave, so one scalar load per step.
+template <bool LADDER = false>
 __device__ __forceinline__ int wave_decide(const double *outw, bool ov_old, bool ov_new,
                                            const DecideConsts *__restrict__ dc, long long step, int r,
                                            int scur, int lane, double *delta_out = nullptr, bool store_flags = true,
@@ -256,7 +259,7 @@ __device__ __forceinline__ int wave_decide(const double *outw, bool ov_old, bool
     const double delta = mmc_move_delta(outw, ov_old, ov_new, dc->factor);
     if (delta_out)
         *delta_out = delta;
-    const double x = delta / dc->temperature;
+    const double x = delta / (LADDER ? dc->temps[r] : dc->temperature);
     const double u = mmc_metropolis_uniform(ChainKey{ dc->seed, dc->replica0 + (uint32_t)r }, (uint64_t)step);
     // exp(-x) > u, decided without the exponential where 1 - x <= exp(-x) <= 1 / (1 + x) (x >= 0)
     // already says which (the margins are far above the rounding of the two bounds): every lane of
@@ -302,7 +305,10 @@ __device__ __forceinline__ int wave_ticket(unsigned *queue, unsigned base, int n
 // (main.jl:580-590): no phase tables, no k loop, neither S(k) buffer read or written, every part of
 // n_parts > 1 a pair part, the record's reciprocal sum 0.  Its own instantiations again, compiled for
 // WV_OCC_WOLF waves per SIMD; the Ewald forms compile exactly as they did.
-template <bool SUBST, bool IMG, bool MULTI = false, bool WOLF = false>
+// LADDER = true: the decision at the replica's own temperature (wave_decide<true>, DecideConsts::temps)
+// -- instantiated for the forms that decide only (SUBST = false); every other form compiles exactly
+// as it did.
+template <bool SUBST, bool IMG, bool MULTI = false, bool WOLF = false, bool LADDER = false>
 __global__ __launch_bounds__(WV_MWAVES * 64)
 __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WOLF : WV_OCC))) void k_move_eval_wave(
     BatchView bv, double *rec, const double *__restrict__ qq_tab,
@@ -440,10 +446,10 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
             if (!dc)
                 return 0;
             if (n_sub <= 1)
-                return wave_decide(sm.outw[wv], o0, o1, dc, dec_step, r, scur, lane, nullptr, true, !WOLF);
+                return wave_decide<LADDER>(sm.outw[wv], o0, o1, dc, dec_step, r, scur, lane, nullptr, true, !WOLF);
             double delta;
             const bool last = sub + 1 == n_sub;
-            const int acc = wave_decide(sm.outw[wv], o0, o1, dc, dec_step + sub, r, scur, lane, &delta, last, !WOLF);
+            const int acc = wave_decide<LADDER>(sm.outw[wv], o0, o1, dc, dec_step + sub, r, scur, lane, &delta, last, !WOLF);
             if (acc) {
                 e_sum += delta;
                 acc_mask |= 1u << sub;

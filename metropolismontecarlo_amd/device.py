@@ -121,6 +121,32 @@ def device_count():
     return n.value
 
 
+def exchange_round(n_rungs, energies, temps, rung, seed, round, parity=None, pressure=0.0, volumes=None, replica0=0,
+                   attempt=None, accept=None):
+    """mmc_exchange_round, the pure host function (no device, no batch): one round of ladder
+    exchanges over energies (R,), R = n_ladders * n_rungs.  temps (R,) float64 and rung (R,) int32
+    are updated in place; volumes (R,) or None for NVT; parity None = round & 1.  Returns
+    (attempt, accept), (n_rungs - 1,) int64 each, accumulated into the caller's when given."""
+    e = _f64(energies).ravel()
+    R, n_rungs = e.shape[0], int(n_rungs)
+    temps = _output(temps, (R,), np.float64, "temps")
+    rung = _output(rung, (R,), np.int32, "rung")
+    v = None
+    if volumes is not None:
+        v = _f64(volumes).ravel()
+        if v.shape[0] != R:
+            raise ValueError(f"one volume per replica: {R} expected, {v.shape[0]} given")
+    if n_rungs >= 1 and R % n_rungs:
+        raise ValueError(f"{R} replicas are not whole ladders of {n_rungs} rungs")
+    res = _outputs({"attempt": ((max(n_rungs - 1, 0),), np.int64), "accept": ((max(n_rungs - 1, 0),), np.int64)},
+                   dict(attempt=attempt, accept=accept), where=None)
+    par = int(round) & 1 if parity is None else int(parity)
+    check(_lib.lib().mmc_exchange_round(R // max(n_rungs, 1), n_rungs, par, int(seed) & (2 ** 64 - 1), int(replica0),
+                                        int(round), float(pressure), _d(e), None if v is None else _d(v), _d(temps),
+                                        _ptr(rung), *_ptrs(res, "attempt", "accept")))
+    return res["attempt"], res["accept"]
+
+
 class _Handle:
     """Owns one library handle self._h, destroyed by the call self._L.<_destroy>."""
     _destroy = None
@@ -579,6 +605,64 @@ class Batch(_Handle):
         e = np.zeros(self.R) if energies is None else _f64(energies).copy()
         check(self._L.mmc_batch_run(self._h, C.byref(p), _d(e), C.byref(st)))
         return e, st.asdict()
+
+    def set_temperatures(self, temps):
+        """mmc_batch_set_temperatures: replica r's moves (run, run_chains, run_npt_replicas and its
+        volume criterion) are decided at temps[r]; the `temperature` of those calls is then ignored.
+        None switches the array off.  widom*, deletion and volume_perturb keep their own argument."""
+        if temps is None:
+            check(self._L.mmc_batch_set_temperatures(self._h, None))
+            return
+        t = _f64(temps).ravel()
+        if t.shape[0] != self.R:
+            raise ValueError(f"one temperature per replica: {self.R} expected, {t.shape[0]} given")
+        check(self._L.mmc_batch_set_temperatures(self._h, _d(t)))
+
+    def temperatures(self):
+        """mmc_batch_get_temperatures: the array as exchanges have left it; zeros when off."""
+        out = np.empty(self.R)
+        check(self._L.mmc_batch_get_temperatures(self._h, _d(out)))
+        return out
+
+    def _ladder_arrays(self, n_rungs, energies, rung, attempt, accept):
+        """The in/out arrays of an exchange: energies (R,) float64 read, rung (R,) int32 updated in
+        place, the counters (n_rungs - 1,) int64 the caller's or new."""
+        e = _f64(energies).ravel()
+        if e.shape[0] != self.R:
+            raise ValueError(f"one energy per replica: {self.R} expected, {e.shape[0]} given")
+        rung = _output(rung, (self.R,), np.int32, "rung")
+        res = _outputs({"attempt": ((max(int(n_rungs) - 1, 0),), np.int64), "accept": ((max(int(n_rungs) - 1, 0),), np.int64)},
+                       dict(attempt=attempt, accept=accept), where=None)
+        return e, rung, res
+
+    def exchange(self, n_rungs, energies, rung, seed, round, parity=None, pressure=0.0, replica0=0, attempt=None,
+                 accept=None):
+        """mmc_batch_exchange: one round of ladder exchanges (exchange_round) on the batch's own
+        temperatures; `rung` (R,) int32 is updated in place, the temperatures swap with it.  parity
+        None = round & 1.  With per-replica boxes the volumes are get_boxes() ** 3 and `pressure`
+        enters; otherwise it is ignored.  Returns (attempt, accept), accumulated."""
+        e, rung, res = self._ladder_arrays(n_rungs, energies, rung, attempt, accept)
+        par = int(round) & 1 if parity is None else int(parity)
+        check(self._L.mmc_batch_exchange(self._h, int(n_rungs), par, int(seed) & (2 ** 64 - 1), int(replica0),
+                                         int(round), float(pressure), _d(e), _ptr(rung),
+                                         *_ptrs(res, "attempt", "accept")))
+        return res["attempt"], res["accept"]
+
+    def run_exchange(self, n_rounds, steps_per_round, dr_max, dphi_max, seed, energies, rung, n_rungs, round0=0,
+                     temperature=1.0, attempt=None, accept=None, n_groups=2, n_parts=0, time_kernels=False,
+                     n_threads=1, n_streams=0, replica0=0):
+        """mmc_batch_run_exchange: n_rounds x { steps_per_round trial moves of every replica at its
+        own temperature, one exchange with round = round0 + i and parity = round & 1 }.  `rung` is
+        updated in place.  `temperature` only has to be positive: the batch's array decides.
+        Returns (energies, stats, attempt, accept)."""
+        e, rung, res = self._ladder_arrays(n_rungs, energies, rung, attempt, accept)
+        e = e.copy()
+        p = RunParams(float(temperature), float(dr_max), float(dphi_max), int(seed), int(steps_per_round),
+                      int(n_groups), int(n_parts), int(time_kernels), int(n_threads), int(n_streams), 0, int(replica0))
+        st = RunStats()
+        check(self._L.mmc_batch_run_exchange(self._h, C.byref(p), int(n_rounds), int(n_rungs), int(round0), _d(e),
+                                             _ptr(rung), *_ptrs(res, "attempt", "accept"), C.byref(st)))
+        return e, st.asdict(), res["attempt"], res["accept"]
 
     def widom(self, n_insert, temperature, seed, draw0=0, offsets=None, boltz_sum=None,
               n_overlap=None, outputs=False):

@@ -554,6 +554,84 @@ function run_npt_replicas!(b::Batch, params::MMCRunParams, npt::MMCNptParams, en
     return st[], ns
 end
 
+# ---- Parallel tempering (include/mmc_hip.h, "Parallel tempering") -----------------------------------
+"""
+    set_temperatures!(b, temps);  set_temperatures!(b, nothing);  temps = temperatures(b)
+
+Replica r's trial moves (`run!`, `run_chains!`, `run_npt_replicas!` and its volume criterion) are
+decided at `temps[r]`; `params.temperature` is then ignored.  `nothing` switches the array off.
+"""
+function set_temperatures!(b::Batch, temps::Union{Nothing,Vector{Float64}})
+    temps === nothing || length(temps) == b.n_replicas || error("one temperature per replica")
+    tp = temps === nothing ? Ptr{Float64}(C_NULL) : pointer(temps)
+    GC.@preserve temps begin
+        check(ccall((:mmc_batch_set_temperatures, libmmc), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h, tp))
+    end
+end
+function temperatures(b::Batch)
+    temps = Vector{Float64}(undef, b.n_replicas)
+    check(ccall((:mmc_batch_get_temperatures, libmmc), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h, temps))
+    return temps
+end
+
+"""
+    exchange_round!(n_rungs, parity, seed, replica0, round, pressure, energies, volumes, temps, rung, attempt, accept)
+
+One round of ladder exchanges as a pure host function (no device, no batch): ladder l is replicas
+l * n_rungs + 1 : (l + 1) * n_rungs of the arrays, `rung[r]` (0-based values) the rung replica r
+holds; `temps` and `rung` swap in place, `attempt` / `accept` (n_rungs - 1) accumulate.  `volumes`
+may be `nothing` (NVT).
+"""
+function exchange_round!(n_rungs::Integer, parity::Integer, seed::UInt64, replica0::Integer, round::Integer,
+                         pressure::Float64, energies::Vector{Float64}, volumes::Union{Nothing,Vector{Float64}},
+                         temps::Vector{Float64}, rung::Vector{Int32}, attempt::Vector{Int64}, accept::Vector{Int64})
+    length(energies) == length(temps) == length(rung) || error("one energy, temperature and rung per replica")
+    n_rungs >= 1 && length(rung) % n_rungs == 0 || error("the replicas are not whole ladders")
+    length(attempt) == length(accept) == n_rungs - 1 || error("one counter per neighbouring pair of rungs")
+    vp = volumes === nothing ? Ptr{Float64}(C_NULL) : pointer(volumes)
+    GC.@preserve volumes begin
+        check(ccall((:mmc_exchange_round, libmmc), Int32,
+                    (Int64, Int32, Int32, UInt64, UInt64, UInt64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Int32}, Ptr{Int64}, Ptr{Int64}),
+                    length(rung) ÷ n_rungs, n_rungs, parity, seed, replica0, round, pressure, energies, vp, temps, rung,
+                    attempt, accept))
+    end
+end
+
+"""
+    exchange!(b, n_rungs, parity, seed, replica0, round, pressure, energies, rung, attempt, accept)
+
+`exchange_round!` on the batch's own temperatures (volumes = box^3 with per-replica boxes, NVT
+otherwise); a swap exchanges temperatures, no replica state moves.
+"""
+function exchange!(b::Batch, n_rungs::Integer, parity::Integer, seed::UInt64, replica0::Integer, round::Integer,
+                   pressure::Float64, energies::Vector{Float64}, rung::Vector{Int32}, attempt::Vector{Int64},
+                   accept::Vector{Int64})
+    length(energies) == length(rung) == b.n_replicas || error("one energy and rung per replica")
+    length(attempt) == length(accept) == n_rungs - 1 || error("one counter per neighbouring pair of rungs")
+    check(ccall((:mmc_batch_exchange, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Int32, UInt64, UInt64, UInt64, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Int64},
+                 Ptr{Int64}), b.h, n_rungs, parity, seed, replica0, round, pressure, energies, rung, attempt, accept))
+end
+
+"""
+    stats = run_exchange!(b, params, n_rounds, n_rungs, round0, energies, rung, attempt, accept)
+
+`n_rounds` times { `params.n_steps` trial moves of every replica at its own temperature, one
+exchange with round = round0 + i and parity = round & 1 } on a one-box batch.
+"""
+function run_exchange!(b::Batch, params::MMCRunParams, n_rounds::Integer, n_rungs::Integer, round0::Integer,
+                       energies::Vector{Float64}, rung::Vector{Int32}, attempt::Vector{Int64},
+                       accept::Vector{Int64})
+    length(energies) == length(rung) == b.n_replicas || error("one energy and rung per replica")
+    length(attempt) == length(accept) == n_rungs - 1 || error("one counter per neighbouring pair of rungs")
+    p = Ref(params); st = Ref{MMCRunStats}()
+    check(ccall((:mmc_batch_run_exchange, libmmc), Int32,
+                (Ptr{Cvoid}, Ptr{MMCRunParams}, Int64, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int64},
+                 Ptr{Int64}, Ptr{MMCRunStats}), b.h, p, n_rounds, n_rungs, round0, energies, rung, attempt, accept, st))
+    return st[]
+end
+
 # ---- Widom test-particle insertion (include/mmc_hip.h, mmc_batch_widom / mmc_batch_widom_at) ------
 """
     widom!(b, n_insert, seed, draw0, offsets, temperature, boltz_sum, n_overlap)

@@ -162,3 +162,24 @@ Adjust_rot = Adjust
 # ---- Ewald/auxillary.jl:116-123 ------------------------------------------------------------------
 def Pressure(vir, rho, T, vol):
     return rho * T + vir.virial / vol
+
+
+# ---- parallel tempering (include/mmc_hip.h, "Parallel tempering") -----------------------------------
+def geometric_ladder(t_lo, t_hi, n):
+    """n temperatures from t_lo to t_hi with a constant ratio between neighbours -- the spacing that
+    keeps the exchange acceptance even along the ladder where C_v hardly changes."""
+    t_lo, t_hi, n = float(t_lo), float(t_hi), int(n)
+    if not (n >= 2 and 0.0 < t_lo < t_hi < math.inf):
+        raise ValueError("geometric_ladder: 0 < t_lo < t_hi and n >= 2")
+    t = t_lo * (t_hi / t_lo) ** (np.arange(n) / (n - 1))
+    t[0], t[-1] = t_lo, t_hi
+    return t
+
+
+def initial_rungs(R, n_rungs):
+    """rung (R,) int32 of R // n_rungs ladders at the start: replica r holds rung r % n_rungs, so
+    np.tile(ladder, R // n_rungs) is the matching array for Batch.set_temperatures."""
+    R, n_rungs = int(R), int(n_rungs)
+    if n_rungs < 2 or R < n_rungs or R % n_rungs:
+        raise ValueError(f"{R} replicas are not whole ladders of {n_rungs} rungs (n_rungs >= 2)")
+    return np.tile(np.arange(n_rungs, dtype=np.int32), R // n_rungs)

@@ -1110,3 +1110,46 @@ def quantum_correction(fsum, temperature, mass):
     return {"dA": float(trans + rot), "translational": float(trans), "rotational": float(rot),
             "per_replica": per,
             "err": float(np.std(ok, ddof=1) / np.sqrt(ok.size)) if ok.size > 1 else float("nan")}
+
+
+# ---- parallel tempering: per-rung views of per-replica results --------------------------------------
+def by_rung(values, rung, n_rungs):
+    """Regroup a per-replica array [R, ...] (energies, or the per_replica=True result of any
+    observable) by the rung each replica holds: [n_rungs, n_ladders, ...], ladder l being replicas
+    [l n_rungs, (l + 1) n_rungs) and `rung` (R,) what mmc_exchange_round maintains."""
+    v, rung, n_rungs = np.asarray(values), np.asarray(rung), int(n_rungs)
+    R = rung.shape[0]
+    if rung.ndim != 1 or n_rungs < 1 or R % n_rungs or v.shape[:1] != (R,):
+        raise ValueError("by_rung: rung (R,) with R a multiple of n_rungs, values [R, ...]")
+    per_ladder = rung.reshape(R // n_rungs, n_rungs)
+    if (np.sort(per_ladder, axis=1) != np.arange(n_rungs)).any():
+        raise ValueError("by_rung: rung is not a permutation of 0..n_rungs-1 within every ladder")
+    holder = np.argsort(per_ladder, axis=1) + n_rungs * np.arange(R // n_rungs)[:, None]  # [ladder, rung] -> replica
+    return v[holder.T]
+
+
+def exchange_acceptance(attempt, accept):
+    """Acceptance ratio of every neighbouring pair of rungs (k, k + 1) from the counters of
+    mmc_exchange_round; NaN where a pair was never attempted."""
+    at, ac = np.asarray(attempt, dtype=np.float64), np.asarray(accept, dtype=np.float64)
+    if at.shape != ac.shape:
+        raise ValueError("exchange_acceptance: attempt and accept of one shape")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(at > 0, ac / at, np.nan)
+
+
+def round_trips(rung_history, n_rungs=None):
+    """Completed bottom -> top -> bottom journeys of every replica from rung_history [n_rounds, R]
+    (a copy of `rung` after every exchange): a journey starts when the replica is on rung 0, and
+    counts when it next returns to rung 0 after having been on the top rung n_rungs - 1 (default
+    max + 1 of the history).  Returns int64 (R,)."""
+    h = np.asarray(rung_history)
+    if h.ndim != 2:
+        raise ValueError("round_trips: rung_history [n_rounds, R]")
+    top = (int(h.max()) if h.size else 0) if n_rungs is None else int(n_rungs) - 1
+    trips = np.zeros(h.shape[1], dtype=np.int64)
+    state = np.zeros(h.shape[1], dtype=np.int8)        # 0 not started, 1 left the bottom, 2 has seen the top
+    for row in h:
+        trips += (state == 2) & (row == 0)
+        state = np.where(row == 0, 1, np.where((row == top) & (state >= 1), 2, state)).astype(np.int8)
+    return trips

@@ -16,18 +16,27 @@ def env_rank():
             int(os.environ.get("WORLD_SIZE", "1")))
 
 
-def shard(replicas_per_gpu, rank):
-    """Weak scaling: every rank owns `replicas_per_gpu` chains; global index = rank*R + r."""
+def _whole_ladders(rng, n_rungs):
+    """Parallel tempering: a rank's share holds whole ladders of n_rungs replicas, so that its
+    first global index -- the `replica0` of its runs and exchanges -- is a multiple of n_rungs."""
+    if n_rungs > 1 and (rng.start % n_rungs or len(rng) % n_rungs):
+        raise ValueError(f"replicas {rng.start}..{rng.stop - 1} are not whole ladders of {n_rungs} rungs")
+    return rng
+
+
+def shard(replicas_per_gpu, rank, n_rungs=1):
+    """Weak scaling: every rank owns `replicas_per_gpu` chains; global index = rank*R + r.
+    n_rungs > 1: the shares must be whole tempering ladders (ValueError otherwise)."""
     lo = rank * replicas_per_gpu
-    return range(lo, lo + replicas_per_gpu)
+    return _whole_ladders(range(lo, lo + replicas_per_gpu), n_rungs)
 
 
-def shard_total(total_replicas, rank, world):
+def shard_total(total_replicas, rank, world, n_rungs=1):
     """Strong scaling (BASELINE configs[2]: 256 replicas over 8 GPUs): contiguous blocks, the
-    first `total % world` ranks take one extra."""
+    first `total % world` ranks take one extra.  n_rungs > 1: as shard()."""
     base, extra = divmod(total_replicas, world)
     lo = rank * base + min(rank, extra)
-    return range(lo, lo + base + (1 if rank < extra else 0))
+    return _whole_ladders(range(lo, lo + base + (1 if rank < extra else 0)), n_rungs)
 
 
 def replica_seed(global_index, phase=0):

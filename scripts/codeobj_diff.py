@@ -27,6 +27,9 @@ KEYS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_seg
 RENAMES = [
     # k_move_eval_wave<SUBST, IMG, MULTI> gained WOLF = false
     (re.compile(r"^void k_move_eval_wave<(\w+), (\w+), (\w+)>\("), r"void k_move_eval_wave<\1, \2, \3, false>("),
+    # ... and then LADDER = false
+    (re.compile(r"^void k_move_eval_wave<(\w+), (\w+), (\w+), (\w+)>\("),
+     r"void k_move_eval_wave<\1, \2, \3, \4, false>("),
     # k_move_eval_fast<PerBox...> gained a leading WOLF (false for every form that existed)
     (re.compile(r"^void k_move_eval_fast<>\("), r"void k_move_eval_fast<false>("),
     (re.compile(r"^void k_move_eval_fast<(?!false|true)([^>]+)>\("), r"void k_move_eval_fast<false, \1>("),
