@@ -1,7 +1,9 @@
 """Parallel tempering on the GPU: per-replica temperatures on every path that decides a move
-(the wave kernel deciding itself, the wave kernel and kernel 1 with the host deciding, the move
-server, Wolf style, per-replica boxes and their volume criterion), the array switched off again,
-and ladder exchanges through the batch against the pure function and its Python restatement.
+(the wave kernel deciding itself in each of its eight LADDER forms -- molecule or per-atom image,
+eight steps or one per launch, Ewald or Wolf style --, the wave kernel and kernels 0, 1 and 4 with
+the host deciding, the move server, per-replica boxes and their volume criterion), the array
+switched off again, and ladder exchanges through the batch against the pure function and its Python
+restatement.  tests/test_gpu_tempering_paths.py goes on from here.
 
 The chains are stepped by the oracle temperature by temperature: test_gpu_replay_paths.replay at
 T = temps[r], with that file's tolerances (imported, not restated)."""
@@ -60,11 +62,27 @@ def open_batch(a, R, rcut, opts, wolf=False):
 L_R, L_SEED, L_REPLICA0, L_STEPS = 8, 90210, 16, 2 * 216
 L_TEMPS = moves.geometric_ladder(250.0, 1000.0, L_R)
 L_SCALAR = 298.15                                   # p->temperature of the call: none of L_TEMPS
-PATHS = {"wave-device-8": (DEVICE8, 1, False, False),
-         "wave-host-trace": (dict(kernel=2, persistent=0, accept_on_device=0), 3, True, False),
-         "k1": (dict(kernel=1, persistent=0, accept_on_device=0), 2, True, False),
-         "server": (dict(persistent=1), 0, True, False),
-         "wolf-device-8": (DEVICE8, 1, False, True)}
+DEVICE1 = dict(DEVICE8, steps_per_launch=1)
+PER_PAIR = dict(image_by_molecule=0)                 # the per-atom minimum image: IMG = false
+HOST = dict(persistent=0, accept_on_device=0)
+# path: (options, n_parts, traced, Wolf style, launches of the call).  The kernel's own decisions run
+# k_move_eval_wave<false, IMG, MULTI, WOLF, LADDER = true>: IMG unless the path says PER_PAIR (216
+# molecules at r_cut 7 A pass the molecule-image condition), MULTI where a launch takes eight steps
+# -- one step per launch under steps_per_launch = 1, and under any trace, which asks for every step.
+PATHS = {"wave-device-8": (DEVICE8, 1, False, False, 2 * L_STEPS // 8),                             # <1, 1, 0>
+         "wave-host-trace": (dict(HOST, kernel=2), 3, True, False, 2 * L_STEPS),
+         "k1": (dict(HOST, kernel=1), 2, True, False, 2 * L_STEPS),
+         "server": (dict(persistent=1), 0, True, False, None),
+         "wolf-device-8": (DEVICE8, 1, False, True, 2 * L_STEPS // 8),                              # <1, 1, 1>
+         "wave-device-1-trace": (DEVICE1, 1, True, False, 2 * L_STEPS),                             # <1, 0, 0>
+         "wolf-device-1-trace": (DEVICE1, 1, True, True, 2 * L_STEPS),                              # <1, 0, 1>
+         "wave-device-8-perpair": (dict(DEVICE8, **PER_PAIR), 1, False, False, 2 * L_STEPS // 8),   # <0, 1, 0>
+         "wolf-device-8-perpair": (dict(DEVICE8, **PER_PAIR), 1, False, True, 2 * L_STEPS // 8),    # <0, 1, 1>
+         "wave-device-1-perpair-trace": (dict(DEVICE1, **PER_PAIR), 1, True, False, 2 * L_STEPS),   # <0, 0, 0>
+         "wolf-device-1-perpair-trace": (dict(DEVICE1, **PER_PAIR), 1, True, True, 2 * L_STEPS),    # <0, 0, 1>
+         "k0": (dict(HOST, kernel=0), 0, True, False, 2 * L_STEPS),
+         "k4": (dict(HOST, kernel=4), 0, True, False, 2 * L_STEPS),
+         "wolf-host-trace": (dict(HOST, kernel=2), 3, True, True, 2 * L_STEPS)}
 
 
 def ladder_replay(r, T, wolf):
@@ -87,8 +105,9 @@ def test_the_ladder_changes_a_decision_of_the_scalar_chain(wolf):
 def test_laddered_chains_stepped_by_the_oracle(path, orc):
     """216 molecules, two sweeps, eight replicas at 250 ... 1000 K: every replica's final centres of
     mass, coordinates and S(k), the per-step trace where the path has one, and the totals against
-    the replay at temps[r]."""
-    opts, n_parts, trace, wolf = PATHS[path]
+    the replay at temps[r]; the launch count says which launch shape ran.  One chain for every
+    path, so the replays are made once."""
+    opts, n_parts, trace, wolf, launches = PATHS[path]
     a, _, _ = rp.system("q216", False)
     with open_batch(a, L_R, Q_RCUT, opts, wolf) as b:
         total = b.potential_wolf if wolf else b.potential_ewald
@@ -103,6 +122,7 @@ def test_laddered_chains_stepped_by_the_oracle(path, orc):
         assert st["moves"] == L_R * L_STEPS
         assert st["device_decisions"] == (L_R * L_STEPS if opts.get("accept_on_device") else 0)
         assert st["server_steps"] == (L_STEPS if opts.get("persistent") == 1 else 0)
+        assert launches is None or st["launches"] == launches, st      # (which launch shape ran)
         traces = b.get_trace(L_STEPS) if trace else None
         final = {r: b.get_replica(r) + (None,) for r in range(L_R)}
         t1 = total(as_array=True).copy()
@@ -121,7 +141,10 @@ def test_laddered_chains_stepped_by_the_oracle(path, orc):
 
 
 # ---- 2. device and host decide alike under a ladder -------------------------------------------------
-def _multi_record_run(a, opts, temps):
+def _multi_record_run(a, opts, temps, style="ewald", n_steps=mr.N_STEPS, seed=mr.SEED):
+    """One call of test_gpu_multi_record.py's shape on a fresh batch under `temps`: the running
+    energies, the recomputed totals of the final state (the Wolf totals in Wolf style), the call's
+    stats and every replica's state."""
     from metropolismontecarlo_amd import structs
     from metropolismontecarlo_amd.device import Batch
     with Batch(mr.R, a["com"], a["coords"], a["atype"], a["charge"], a["eps"], a["sig"], a["box"], 5.6 / a["box"],
@@ -129,35 +152,50 @@ def _multi_record_run(a, opts, temps):
         b.set_option("device_moves", 1)
         for k, v in opts.items():
             b.set_option(k, v)
+        total = b.potential_ewald
+        if style == "wolf":
+            b.recip_long()
+            b.set_coulomb_style("wolf")
+            total = b.potential_wolf
         b.set_temperatures(temps)
-        e0 = b.potential_ewald(as_array=True)["energy"].copy()
-        e1, st = b.run(mr.N_STEPS, mr.T, mr.DR, mr.DPHI, seed=mr.SEED, energies=e0, n_groups=2, n_parts=1, n_threads=2,
+        e0 = total(as_array=True)["energy"].copy()
+        e1, st = b.run(n_steps, mr.T, mr.DR, mr.DPHI, seed=seed, energies=e0, n_groups=2, n_parts=1, n_threads=2,
                        replica0=mr.REPLICA0)
-        return e1, b.potential_ewald(as_array=True).copy(), st, state_of(b)
+        return e1, total(as_array=True).copy(), st, state_of(b)
+
+
+def check_device_against_host(dev, host, n_steps, launches, at=None):
+    """What the kernel's decisions left against what the host's left, each as _multi_record_run
+    returns it: the six counts, every replica's centre of mass, coordinates and S(k) and the
+    recomputed totals bit for bit, the running energies within test_gpu_multi_record.py's 1e-12 of
+    each other and 1e-9 of the recompute; `launches` of the deciding kernel, a launch per step and
+    group of the host's."""
+    (e_d, t_d, st_d, fin_d), (e_h, t_h, st_h, fin_h) = dev, host
+    assert st_d["launches"] == launches and st_d["device_decisions"] == mr.R * n_steps, (at, st_d)
+    assert st_h["launches"] == 2 * n_steps and st_h["device_decisions"] == 0, (at, st_h)
+    differ = [(r, what) for r in range(mr.R)
+              for x, y, what in zip(fin_d[r], fin_h[r], ("com", "coords", "S(k)")) if not same_bits(x, y)]
+    assert not differ, (at, differ)                      # (every replica that went another way, by index)
+    assert [st_d[k] for k in mr.COUNTS] == [st_h[k] for k in mr.COUNTS], (at, st_d, st_h)
+    assert 0 < st_d["trans_accept"] + st_d["rot_accept"] < mr.R * n_steps, at
+    assert t_d.tobytes() == t_h.tobytes(), at
+    print(at, "running energies, device against host:", np.max(np.abs(e_d - e_h) / np.abs(e_h)))
+    assert np.max(np.abs(e_d - e_h) / np.abs(e_h)) < 1e-12, at
+    print(at, "running energies against the recompute:", np.max(np.abs(e_d - t_d["energy"]) / np.abs(t_d["energy"])))
+    assert np.max(np.abs(e_d - t_d["energy"]) / np.abs(t_d["energy"])) < 1e-9, at
 
 
 def test_device_and_host_decide_alike_under_a_ladder():
     """NIST configuration 4, R = 24 in two groups, wave_wgs = 1, 20 steps in launches of 8 + 8 + 4
     (the shape of test_gpu_multi_record.py), twelve distinct temperatures: counts, centres of mass,
     coordinates and S(k) bit for bit between the kernel's decisions and the host's, running
-    energies within that file's 1e-12 of each other and 1e-9 of the recompute."""
+    energies within that file's 1e-12 of each other and 1e-9 of the recompute.
+    (test_gpu_tempering_paths.py: every kernel form and launch shape, a temperature per replica.)"""
     a = common.nist_arrays(4, "unwrapped")
     temps = np.tile(moves.geometric_ladder(260.0, 400.0, 12), 2)
     assert len(set(temps.tolist())) == 12
-    e_d, t_d, st_d, fin_d = _multi_record_run(a, mr.ON_DEVICE, temps)
-    e_h, t_h, st_h, fin_h = _multi_record_run(a, mr.ON_HOST, temps)
-    assert st_d["launches"] == 2 * 3 and st_d["device_decisions"] == mr.R * mr.N_STEPS, st_d
-    assert st_h["launches"] == 2 * mr.N_STEPS and st_h["device_decisions"] == 0, st_h
-    assert [st_d[k] for k in mr.COUNTS] == [st_h[k] for k in mr.COUNTS], (st_d, st_h)
-    assert 0 < st_d["trans_accept"] + st_d["rot_accept"] < mr.R * mr.N_STEPS
-    for r in range(mr.R):
-        for x, y, what in zip(fin_d[r], fin_h[r], ("com", "coords", "S(k)")):
-            assert same_bits(x, y), (r, what)
-    assert t_d.tobytes() == t_h.tobytes()
-    print("running energies, device against host:", np.max(np.abs(e_d - e_h) / np.abs(e_h)))
-    assert np.max(np.abs(e_d - e_h) / np.abs(e_h)) < 1e-12
-    print("running energies against the recompute:", np.max(np.abs(e_d - t_d["energy"]) / np.abs(t_d["energy"])))
-    assert np.max(np.abs(e_d - t_d["energy"]) / np.abs(t_d["energy"])) < 1e-9
+    check_device_against_host(_multi_record_run(a, mr.ON_DEVICE, temps), _multi_record_run(a, mr.ON_HOST, temps),
+                              mr.N_STEPS, 2 * 3)
 
 
 # ---- 3. off means off ---------------------------------------------------------------------------------
@@ -193,7 +231,7 @@ def test_off_means_off(path):
     so the Philox continuation is in it); None against a fresh batch that ran the same laddered
     call and then an array of equal values -- which the first half has shown to be the scalar
     chain.  p->temperature is 555 K wherever an array is set: it must be ignored."""
-    opts, n_parts, _, _ = PATHS[path]
+    opts, n_parts = PATHS[path][:2]
     equal = np.full(O_R, O_T)
     scalar = _two_calls(opts, n_parts, "never", "never", O_T, O_T)
     by_array = _two_calls(opts, n_parts, equal, "same", 555.0, 555.0)
@@ -212,15 +250,16 @@ X_LADDER = moves.geometric_ladder(250.0, 1000.0, X_RUNGS)
 class OracleChain:
     """test_gpu_replay_paths.replay in steps, for a chain whose temperature changes between calls:
     advance(n_steps, T) is one call of the batch (the Philox counter continues, the sweep restarts).
-    e_acc is the running sum of the accepted dU."""
+    e_acc is the running sum of the accepted dU.  `wolf`: the chain of replay(wolf=True) --
+    dU = d_lj + d_real, the S arrays left alone."""
 
-    def __init__(self, orc, a, replica, seed, dr, dphi, rcut):
+    def __init__(self, orc, a, replica, seed, dr, dphi, rcut, wolf=False):
         self.orc, self.box, self.n_mol = orc, a["box"], a["com"].shape[0]
         self.key, self.par = (seed, replica), (dr, dphi, rcut)
         self.s = common.oracle_system(a)
         self.ew = orc.Ewald(5.6 / self.box, 5, 27, self.box)
         orc.recip_long(self.ew, self.s.coords, self.s.charge, self.box)
-        self.e_acc, self.off = 0.0, 0
+        self.e_acc, self.off, self.wolf = 0.0, 0, wolf
 
     def advance(self, n_steps, T):
         s, ew, (dr, dphi, rcut) = self.s, self.ew, self.par
@@ -229,14 +268,15 @@ class OracleChain:
             _, c_new, a_new, _, u = rp.propose(0, *self.key, self.off + step, s.com[i].copy(),
                                                s.coords[3 * i:3 * i + 3].copy(), None, None, self.box, dr, dphi)
             d, ov = self.orc.trial_move(i + 1, s, ew, rcut, rcut, c_new, a_new)
-            delta = d[0] + d[1] + d[2]                                 # main.jl:593
+            delta = d[0] + d[1] if self.wolf else d[0] + d[1] + d[2]   # main.jl:593
             x = delta / T
             if (x < 0.0 or math.exp(-x) > u) and not ov:               # main.jl:598
                 self.e_acc += delta
                 s.com[i] = c_new
                 s.coords[3 * i:3 * i + 3] = a_new
-                ew.sumQExpOld = ew.sumQExpNew.copy()
-            else:
+                if not self.wolf:
+                    ew.sumQExpOld = ew.sumQExpNew.copy()
+            elif not self.wolf:
                 ew.sumQExpNew = ew.sumQExpOld.copy()
         self.off += n_steps
         return self
@@ -253,14 +293,14 @@ def replay_rounds(orc, a, replica, temps_of_round):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_ladder_run():
+def oracle_ladder_run(wolf=False, ladder=tuple(X_LADDER)):
     """The whole run of test 4 on the host: every chain stepped by the oracle, every exchange decided
     by the restatement on the oracle's energies (all replicas start from one configuration, so the
     start's energy drops out of every D).  Returns the temperature history and the counters."""
     from oracle import oracle as orc
     a, _, _ = rp.system("q216", False)
-    chains = [OracleChain(orc, a, X_REPLICA0 + r, X_SEED, Q_DR, Q_DPHI, Q_RCUT) for r in range(X_R)]
-    temps, rung = np.tile(X_LADDER, X_R // X_RUNGS).tolist(), moves.initial_rungs(X_R, X_RUNGS).tolist()
+    chains = [OracleChain(orc, a, X_REPLICA0 + r, X_SEED, Q_DR, Q_DPHI, Q_RCUT, wolf) for r in range(X_R)]
+    temps, rung = np.tile(ladder, X_R // X_RUNGS).tolist(), moves.initial_rungs(X_R, X_RUNGS).tolist()
     attempt, accept, t_hist = [0] * (X_RUNGS - 1), [0] * (X_RUNGS - 1), [list(temps)]
     for i in range(X_ROUNDS):
         e = [chains[r].advance(X_STEPS, temps[r]).e_acc for r in range(X_R)]
@@ -278,6 +318,67 @@ def test_the_ladder_spacing_accepts_and_rejects_swaps():
     assert sum(o["accept"]) >= 1 and sum(o["attempt"]) - sum(o["accept"]) >= 1, o
 
 
+X_KW = dict(n_groups=2, n_threads=2, replica0=X_REPLICA0)
+
+
+def exchange_whole(opts, n_parts=1, wolf=False):
+    """run_exchange of X_ROUNDS x X_STEPS on a fresh batch of X_R // X_RUNGS ladders: what it left
+    (energies, rung, temperatures(), state, counters), the stats, the totals before and after."""
+    a, _, _ = rp.system("q216", False)
+    with open_batch(a, X_R, Q_RCUT, opts, wolf) as b:
+        total = b.potential_wolf if wolf else b.potential_ewald
+        t0 = total(as_array=True).copy()
+        b.set_temperatures(np.tile(X_LADDER, X_R // X_RUNGS))
+        rung = moves.initial_rungs(X_R, X_RUNGS)
+        e1, st, attempt, accept = b.run_exchange(X_ROUNDS, X_STEPS, Q_DR, Q_DPHI, X_SEED, t0["energy"].copy(), rung,
+                                                 X_RUNGS, round0=X_ROUND0, temperature=555.0, n_parts=n_parts, **X_KW)
+        assert st["moves"] == X_R * X_ROUNDS * X_STEPS, st
+        whole = dict(e=e1, rung=rung, temps=b.temperatures(), state=state_of(b), attempt=attempt, accept=accept)
+        return whole, st, t0, total(as_array=True).copy()
+
+
+def exchange_by_hand(decide, opts, n_parts=1, wolf=False):
+    """The same run composed from run, set_temperatures and decide(round, energies, temps, rung,
+    attempt, accept) -> (temps, rung).  Returns what it left and the temperatures after each round."""
+    a, _, _ = rp.system("q216", False)
+    with open_batch(a, X_R, Q_RCUT, opts, wolf) as b:
+        e = (b.potential_wolf if wolf else b.potential_ewald)(as_array=True)["energy"].copy()
+        temps, rung = np.tile(X_LADDER, X_R // X_RUNGS), moves.initial_rungs(X_R, X_RUNGS)
+        att, acc = np.zeros(X_RUNGS - 1, np.int64), np.zeros(X_RUNGS - 1, np.int64)
+        t_hist = [temps.copy()]
+        for i in range(X_ROUNDS):
+            b.set_temperatures(temps)
+            e, _ = b.run(X_STEPS, 555.0, Q_DR, Q_DPHI, seed=X_SEED, energies=e, n_parts=n_parts, **X_KW)
+            temps, rung = decide(X_ROUND0 + i, e, temps, rung, att, acc)
+            t_hist.append(temps.copy())
+        b.set_temperatures(temps)
+        return dict(e=e, rung=rung, temps=b.temperatures(), state=state_of(b), attempt=att, accept=acc), t_hist
+
+
+def decide_pure(rnd, e, temps, rung, att, acc):
+    exchange_round(X_RUNGS, e, temps, rung, X_SEED, rnd, replica0=X_REPLICA0, attempt=att, accept=acc)
+    return temps, rung
+
+
+def decide_restated(rnd, e, temps, rung, att, acc):
+    t, g, at, ac = temps.tolist(), rung.tolist(), att.tolist(), acc.tolist()
+    assert tempering_ref.exchange_round(X_R // X_RUNGS, X_RUNGS, rnd & 1, X_SEED, X_REPLICA0, rnd, 0.0, e.tolist(),
+                                        None, t, g, at, ac)
+    att[:], acc[:] = at, ac
+    return np.array(t), np.array(g, dtype=np.int32)
+
+
+def check_exchange_composition(whole, hand, at):
+    """Bit for bit: energies, rung, temperatures(), the counters and every replica's state; the
+    temperatures are the ladder's at the rungs held; swaps were accepted and rejected."""
+    attempt, accept = whole["attempt"], whole["accept"]
+    assert np.array_equal(whole["temps"], X_LADDER[whole["rung"]]), at
+    assert attempt.tolist() == [9, 9, 9] and accept.sum() >= 1 and (attempt - accept).sum() >= 1, (at, attempt, accept)
+    for key in ("e", "rung", "temps", "attempt", "accept"):
+        assert same_bits(whole[key], hand[key]), (at, key, whole[key], hand[key])
+    assert same_states(whole["state"], hand["state"]), at
+
+
 def test_run_exchange_is_run_and_exchange_composed_by_hand(orc):
     """R = 12 as 3 ladders of 4 rungs: run_exchange of 6 rounds x 40 steps equals, bit for bit in
     final state, energies, rung and temperatures(), the same thing composed from run and the pure
@@ -285,50 +386,12 @@ def test_run_exchange_is_run_and_exchange_composed_by_hand(orc):
     replica whose temperature an accepted swap changed follows the oracle's replay at its new
     temperatures in the rounds after."""
     a, _, _ = rp.system("q216", False)
-    kw = dict(n_groups=2, n_parts=1, n_threads=2, replica0=X_REPLICA0)
-    temps0, rung0 = np.tile(X_LADDER, X_R // X_RUNGS), moves.initial_rungs(X_R, X_RUNGS)
-    with open_batch(a, X_R, Q_RCUT, DEVICE8) as b:
-        e0 = b.potential_ewald(as_array=True)["energy"].copy()
-        b.set_temperatures(temps0)
-        rung = rung0.copy()
-        e1, st, attempt, accept = b.run_exchange(X_ROUNDS, X_STEPS, Q_DR, Q_DPHI, X_SEED, e0, rung, X_RUNGS,
-                                                 round0=X_ROUND0, temperature=555.0, **kw)
-        assert st["moves"] == X_R * X_ROUNDS * X_STEPS and st["device_decisions"] == st["moves"]
-        whole = dict(e=e1, rung=rung, temps=b.temperatures(), state=state_of(b), attempt=attempt, accept=accept)
-        tot = b.potential_ewald(as_array=True).copy()
-    assert np.array_equal(whole["temps"], X_LADDER[whole["rung"]])
-    assert attempt.tolist() == [9, 9, 9] and accept.sum() >= 1 and (attempt - accept).sum() >= 1, (attempt, accept)
-
-    def by_hand(decide):
-        with open_batch(a, X_R, Q_RCUT, DEVICE8) as b:
-            e = b.potential_ewald(as_array=True)["energy"].copy()
-            temps, rung = temps0.copy(), rung0.copy()
-            att, acc = np.zeros(X_RUNGS - 1, np.int64), np.zeros(X_RUNGS - 1, np.int64)
-            t_hist = [temps.copy()]
-            for i in range(X_ROUNDS):
-                b.set_temperatures(temps)
-                e, _ = b.run(X_STEPS, 555.0, Q_DR, Q_DPHI, seed=X_SEED, energies=e, **kw)
-                temps, rung = decide(X_ROUND0 + i, e, temps, rung, att, acc)
-                t_hist.append(temps.copy())
-            b.set_temperatures(temps)
-            return dict(e=e, rung=rung, temps=b.temperatures(), state=state_of(b), attempt=att, accept=acc), t_hist
-
-    def pure(rnd, e, temps, rung, att, acc):
-        exchange_round(X_RUNGS, e, temps, rung, X_SEED, rnd, replica0=X_REPLICA0, attempt=att, accept=acc)
-        return temps, rung
-
-    def restated(rnd, e, temps, rung, att, acc):
-        t, g, at, ac = temps.tolist(), rung.tolist(), att.tolist(), acc.tolist()
-        assert tempering_ref.exchange_round(X_R // X_RUNGS, X_RUNGS, rnd & 1, X_SEED, X_REPLICA0, rnd, 0.0, e.tolist(),
-                                            None, t, g, at, ac)
-        att[:], acc[:] = at, ac
-        return np.array(t), np.array(g, dtype=np.int32)
-
-    for decide in (pure, restated):
-        hand, t_hist = by_hand(decide)
-        for key in ("e", "rung", "temps", "attempt", "accept"):
-            assert same_bits(whole[key], hand[key]), (decide.__name__, key, whole[key], hand[key])
-        assert same_states(whole["state"], hand["state"]), decide.__name__
+    whole, st, t0, tot = exchange_whole(DEVICE8)
+    e0 = t0["energy"]
+    assert st["device_decisions"] == st["moves"]
+    for decide in (decide_pure, decide_restated):
+        hand, t_hist = exchange_by_hand(decide, DEVICE8)
+        check_exchange_composition(whole, hand, decide.__name__)
     # a replica whose temperature changed before the last round, against the oracle at its history
     t_hist = np.array(t_hist)                                            # [round + 1, R]
     moved = [r for r in range(X_R) if (t_hist[1:X_ROUNDS, r] != t_hist[0, r]).any()]
