@@ -647,6 +647,33 @@ int32_t mmc_batch_run_chains(mmc_batch *b, const mmc_run_params *p, mmc_chain *c
 int32_t mmc_chain_block_line(const mmc_chain *chain, int64_t block, int64_t n_mol, double box,
                              double ideal_term, char *buf, int64_t len);
 
+/* ---- Candidate lists of the move kernel's COM scan ---------------------------------------------
+ * Where mmc_batch_run / mmc_batch_eval run the wave kernel with one part per move (large batches of
+ * identical molecules, one box), a trial move tests only the chosen molecule's CANDIDATES -- the
+ * molecules within gate + skin of it when the replica's lists were last built -- instead of every
+ * centre of mass, while a per-replica bound on how far any molecule has moved since then proves that
+ * no molecule outside the list can pass the prefilter; otherwise, and until stale lists have been
+ * rebuilt, the step scans in full.  The neighbours the pair loops see are the same in the same order:
+ * every result is bit for bit that of option "candidate_lists" = 0.
+ * MEMORY: 2 * 256 bytes per molecule and replica (+ 8 per molecule), allocated when the batch first runs
+ * that kernel: 23.9 GB for 61 440 replicas of 750 molecules.  If it does not fit with a sixteenth of the
+ * device (at least 1 GiB) to spare, the batch runs without lists and mmc_batch_cand_stats says so.
+ * Options (mmc_batch_set_option): "candidate_lists" 1 (default) / 0; "cand_skin", the skin in
+ * THOUSANDTHS of an Angstrom (default 2000): smaller = shorter lists that are rebuilt sooner; lists of
+ * more than 256 molecules are not used.
+ * mmc_batch_cand_stats: out[0] steps that took a list, [1] steps of the same launches that scanned in
+ * full, [2] rebuilds (replica x times), [3] bytes allocated, [4] launches of the rebuild kernel,
+ * [5] state: 0 switched off, 1 in use, 2 not allocated (memory), 3 not applicable (mixed systems,
+ * per-replica boxes, a skin too small for the gate), 4 not needed so far; [6] the budget and [7] the
+ * lists' threshold in code units (mmc_cand_thresholds).  Counts are sums over the batch's life.
+ * mmc_cand_thresholds / mmc_cand_within: the integer arithmetic of the per-step test, pure host
+ * functions (no device): out[0] the prefilter's threshold for `gate` (A) in a box, out[1] the lists'
+ * for gate + skin, out[2] the budget B; out[k] = 1 where sqrt(a2[k]) + sqrt(d2[k]) <= B is PROVEN on
+ * the squares (it may say 0 where the sum is within rounding of B, never 1 where it exceeds it). */
+int32_t mmc_batch_cand_stats(mmc_batch *b, int64_t *out /* [8] */);
+int32_t mmc_cand_thresholds(double gate, double skin, double box, uint32_t *out /* [3] */);
+int32_t mmc_cand_within(int64_t n, const uint32_t *a2, const uint32_t *d2, uint32_t budget, uint8_t *out /* [n] */);
+
 /* ---- Parallel tempering: per-replica temperatures and ladder exchanges ---------------------------
  * mmc_batch_set_temperatures gives replica r its own temperature temps[r] (K): mmc_batch_run,
  * mmc_batch_run_chains and mmc_batch_run_npt_replicas then decide replica r's trial moves with

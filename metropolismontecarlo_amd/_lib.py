@@ -180,6 +180,9 @@ SIGNATURES = {
     "mmc_batch_peek_part": [_vp, _i64, _i32, _vp, C.POINTER(C.c_uint32)],
     "mmc_batch_rdf": [_vp, _i32, _i32, _u64p],
     "mmc_batch_run": [_vp, C.POINTER(RunParams), _dp, C.POINTER(RunStats)],
+    "mmc_batch_cand_stats": [_vp, _i64p],
+    "mmc_cand_thresholds": [_d, _d, _d, C.POINTER(C.c_uint32)],
+    "mmc_cand_within": [_i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _u8p],
     "mmc_batch_set_temperatures": [_vp, _dp],
     "mmc_batch_get_temperatures": [_vp, _dp],
     "mmc_exchange_round": [_i64, _i32, _i32, C.c_uint64, C.c_uint64, C.c_uint64, _d, _dp, _dp, _dp, _i32p, _i64p,

@@ -17,8 +17,29 @@
 #define MMC_GEN_RING (MMC_GEN_MAX + 2) // + the previous step's record (pending commit) + slack
 #define MMC_QUEUE_STRIDE 32            // a 128-byte line per group's ticket counter (mmc_batch::d_queue)
 
+// Candidate lists of the move kernel's COM scan (mmc_cand.hpp): allocated when the batch first runs the
+// wave kernel with one part per move; valid per replica while its displacement bound D_r says so.
+#define MMC_CAND_EVERY 8 // launches of a range of replicas between two looks of k_cand_refresh
+struct BatchCand {
+    int enabled = 1;          // option "candidate_lists"
+    int skin_milli = 2000;    // option "cand_skin": the lists' radius beyond the gate, in 1/1000 A
+    bool tried = false;       // the allocation has been attempted (once per batch)
+    int state = 4;            // mmc_batch_cand_stats: 0 off, 1 in use, 2 no memory, 3 not applicable, 4 not needed yet
+    CandView v{};             // device arrays (idx NULL: none) and the budget they were built for
+    void *block = nullptr;    // the one allocation behind them
+    int64_t bytes = 0;
+    uint32_t t_build = 0;     // threshold of the lists (com_quant_gate of gate + skin)
+    uint32_t d_refresh = 0;   // a replica is rebuilt when D_r is above this
+    uint64_t epoch = ~0ULL;   // DeviceSystem::comq_epoch the valid lists belong to
+    bool dirty = true;        // something the lists depend on changed: every replica is stale
+    int64_t refresh_launches = 0;
+    struct Range { int64_t r0, nr; unsigned long long count; bool pending; };
+    std::vector<Range> ranges; // the groups of replicas the driver launches, each with its own cadence
+};
+
 struct mmc_batch {
     DeviceSystem sys;
+    BatchCand cand;
     double lj_rcut = 0, qq_rcut = 0;
     int n_parts = 1;
     int kernel = 3;          // 3: choose per launch between 2 and 1 (default for homogeneous
@@ -360,6 +381,14 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
         MMC_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16, MMC_ERR_ARG,
                     "steps_per_launch must be 0 (by size), 1, 2, 4, 8 or 16");
         b->steps_per_launch = (int)value;
+    } else if (!strcmp(key, "candidate_lists")) {
+        MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "candidate_lists must be 0 (scan every centre of mass) or 1");
+        b->cand.enabled = (int)value;
+        b->cand.dirty = true;
+    } else if (!strcmp(key, "cand_skin")) {
+        MMC_REQUIRE(value >= 0 && value <= 100000, MMC_ERR_ARG, "cand_skin: 0..100000 (thousandths of an Angstrom)");
+        b->cand.skin_milli = (int)value;
+        b->cand.dirty = true;
     } else if (!strcmp(key, "whole_call")) {
         MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "whole_call must be 0 (launches of steps_per_launch) or 1 (one per call)");
         b->whole_call = (int)value;
@@ -601,6 +630,122 @@ struct DevDecide {
     unsigned queue_base;    // ... tickets taken before this launch
 };
 
+// ---- candidate lists (mmc_cand.hpp) --------------------------------------------------------------
+// Before the launches of a call that runs the wave kernel with one part per move, every stream of the
+// batch idle: allocate on first use, fix the thresholds for the box and gates of the day, and mark every
+// replica stale if anything the lists depend on has changed since they were valid.
+static int32_t batch_cand_prepare(mmc_batch *b, const PairParams &pp)
+{
+    BatchCand &c = b->cand;
+    DeviceSystem &s = b->sys;
+    if (!c.enabled) {
+        c.state = 0;
+        return MMC_OK;
+    }
+    if (!s.bv.comq || s.pb.on || s.n_mol > MMC_WAVE_MAX_MOL) {
+        c.state = 3;
+        return MMC_OK;
+    }
+    if (!c.tried) {
+        c.tried = true;
+        const int64_t R = s.R, cqs = s.bv.cq_stride;
+        auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+        const int64_t b_stat = up(8 * MMC_CAND_STATS * R), b_d = up(4 * R), b_q0 = up(2 * 3 * cqs * R),
+                      b_cnt = up(2 * cqs * R), b_idx = up(2 * (int64_t)MMC_CAND_CAP * s.n_mol * R);
+        const int64_t total = b_stat + b_d + b_q0 + b_cnt + b_idx;
+        size_t free_b = 0, total_b = 0;
+        void *blk = nullptr;
+        // (leave a sixteenth of the device, at least 1 GiB, to everything that allocates later)
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess
+            && (size_t)total + std::max<size_t>(total_b / 16, (size_t)1 << 30) <= free_b
+            && hipMalloc(&blk, (size_t)total) == hipSuccess) {
+            s.allocs.push_back(blk);
+            char *p = (char *)blk;
+            c.v.stat = (unsigned long long *)p; p += b_stat;
+            c.v.D = (uint32_t *)p; p += b_d;
+            c.v.q0 = (uint16_t *)p; p += b_q0;
+            c.v.cnt = (uint16_t *)p; p += b_cnt;
+            c.v.idx = (uint16_t *)p;
+            c.block = blk;
+            c.bytes = total;
+            // (the indices need no value: nothing reads a list before k_cand_refresh has written it,
+            // and the move kernel clamps what it gathers by)
+            MMC_HIP(hipMemsetAsync(blk, 0, (size_t)(total - b_idx), s.stream));
+            c.dirty = true;
+        } else {
+            (void)hipGetLastError();
+            c.state = 2;
+        }
+    }
+    if (!c.v.idx)
+        return MMC_OK;
+    const double gate_sq = std::max(pp.lj_gate_sq, pp.qq_gate_sq), gate = std::sqrt(gate_sq);
+    const double wide = gate + 1e-3 * c.skin_milli;
+    const uint32_t t_build = com_quant_gate(wide * wide, s.box);
+    const uint32_t budget = cand_budget(t_build, com_quant_gate(gate_sq, s.box));
+    if (t_build != c.t_build || budget != c.v.budget) {
+        c.t_build = t_build;
+        c.v.budget = budget;
+        c.dirty = true;
+    }
+    // Rebuilt when the bound has used three quarters of the budget: the molecules that have themselves
+    // moved more than the last quarter scan in full until then, and a rebuild costs n_mol scans.
+    c.d_refresh = (uint32_t)(((uint64_t)budget * 3 / 4) * ((uint64_t)budget * 3 / 4));
+    c.state = budget > 0 ? 1 : 3;
+    if (c.dirty || c.epoch != s.comq_epoch) {
+        MMC_HIP(hipMemsetAsync(c.v.D, 0xff, sizeof(uint32_t) * (size_t)s.R, s.stream));
+        MMC_HIP(hipStreamSynchronize(s.stream));
+        c.dirty = false;
+        c.epoch = s.comq_epoch;
+        for (BatchCand::Range &g : c.ranges)
+            g.pending = true;
+    }
+    return MMC_OK;
+}
+
+// A launch on `stream` that commits moves of replicas [r0, r0 + nr) WITHOUT keeping their bound (any
+// kernel but the wave kernel with one part per move, or that kernel with the lists switched off): the
+// replicas are stale from there on, in stream order.
+static int32_t batch_cand_stale(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr)
+{
+    if (b->cand.v.idx) {
+        MMC_HIP(hipMemsetAsync(b->cand.v.D + r0, 0xff, sizeof(uint32_t) * (size_t)nr, stream));
+        for (BatchCand::Range &g : b->cand.ranges) // (rebuilt at their next launch with lists, not at its turn)
+            if (g.r0 < r0 + nr && r0 < g.r0 + g.nr)
+                g.pending = true;
+    }
+    return MMC_OK;
+}
+
+// The view a launch of the wave kernel with one part per move takes for replicas [r0, r0 + nr), after
+// enqueueing on the launch's own stream what keeps their lists fresh: k_cand_refresh at the range's
+// first launch after anything went stale, then every MMC_CAND_EVERY launches (a replica with nothing
+// to do costs one early exit).  Only speed depends on the cadence: a replica that is due scans in full.
+static int32_t batch_cand_for_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr, CandView *out)
+{
+    BatchCand &c = b->cand;
+    *out = CandView{};
+    if (!c.enabled || !c.v.idx || c.v.budget == 0)
+        return batch_cand_stale(b, stream, r0, nr);
+    BatchCand::Range *g = nullptr;
+    for (BatchCand::Range &x : c.ranges)
+        if (x.r0 == r0 && x.nr == nr)
+            g = &x;
+    if (!g) {
+        c.ranges.push_back(BatchCand::Range{ r0, nr, 0ULL, true });
+        g = &c.ranges.back();
+    }
+    if (g->pending || g->count % MMC_CAND_EVERY == 0) {
+        k_cand_refresh<<<(unsigned)nr, 256, 0, stream>>>(b->sys.bv, c.v, (int)r0, c.t_build, c.d_refresh);
+        MMC_HIP(hipGetLastError());
+        c.refresh_launches++;
+        g->pending = false;
+    }
+    g->count++;
+    *out = c.v;
+    return MMC_OK;
+}
+
 static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr, int P,
                             int buf, bool has_prev, const PairParams &pp,
                             hipEvent_t before_kernel = nullptr, const DevGen *dg = nullptr,
@@ -666,6 +811,8 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     // lanes, has the shorter critical path (measured crossover: 2048 .. 8192 moves per launch)
     const int kernel = batch_kernel_for(b, nr, P);
     const bool wolf = b->coulomb_style == MMC_COULOMB_WOLF; // (never with kernel 4 or per-replica boxes)
+    if (kernel != 2) // (their commits do not keep the candidate lists' bound)
+        MMC_TRY(batch_cand_stale(b, stream, r0, nr));
     MMC_REQUIRE(!wolf || (kernel != 4 && !s.pb.on), MMC_ERR_ASSERT, "Wolf style reached a kernel without a Wolf form");
     if (kernel == 4) {
         // latency form: P workgroups of four parts each per replica, one record per workgroup
@@ -699,7 +846,7 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
         s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,     \
         (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,      \
         dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,      \
-        dd ? dd->queue_base : 0u)
+        dd ? dd->queue_base : 0u, SUBST ? CandView{} : cvv)
 // the forms that decide (one part per move, SUBST = false): under per-replica temperatures their
 // LADDER twins, which read DecideConsts::temps[r]
 #define MMC_WAVE_DECIDES(IMG, MULTI)                                                             \
@@ -707,6 +854,11 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     else if (ladder) MMC_WAVE_LAUNCH5(false, IMG, MULTI, false, true);                           \
     else MMC_WAVE_LAUNCH3(false, IMG, MULTI)
         const bool ladder = dd && !b->temps.empty(); // (run_impl has put d_temps into *dd->dc)
+        CandView cvv{}; // candidate lists: the forms with one part per move keep and use them
+        if (P == 1)
+            MMC_TRY(batch_cand_for_launch(b, stream, r0, nr, &cvv));
+        else
+            MMC_TRY(batch_cand_stale(b, stream, r0, nr));
         if (P == 1 && dd && dd->n_sub > 1) {
             if (img) { MMC_WAVE_DECIDES(true, true); } else { MMC_WAVE_DECIDES(false, true); }
         } else if (P == 1) {
@@ -809,6 +961,7 @@ static int32_t batch_server_start(mmc_batch *b, hipStream_t stream, int waves, c
                                   uint64_t seed, uint64_t replica0, int64_t rng_off, int lat_wgs = 0)
 {
     DeviceSystem &s = b->sys;
+    MMC_TRY(batch_cand_stale(b, stream, 0, s.R)); // (the servers commit without the candidate lists' bound)
     if (lat_wgs > 0) {
         batch_ctrl_clear(b);
         memset(b->h_timeout, 0, 64);
@@ -864,7 +1017,8 @@ static int32_t batch_settle_range(mmc_batch *b, hipStream_t stream, int64_t r0, 
     MMC_HIP(hipMemcpyAsync(b->dev_accept + r0, b->h_accept + r0, sizeof(int32_t) * nr, hipMemcpyHostToDevice, stream));
     k_settle<<<(unsigned)((nr + 15) / 16), 256, 0, stream>>>(s.bv, prev, b->dev_accept, (int)r0, (int)nr);
     if (s.rec)
-        k_settle_rec<<<(unsigned)((nr + 15) / 16), 256, 0, stream>>>(s.bv, s.rec, prev, b->dev_accept, (int)r0, (int)nr);
+        k_settle_rec<<<(unsigned)((nr + 15) / 16), 256, 0, stream>>>(s.bv, s.rec, prev, b->dev_accept, (int)r0, (int)nr,
+                                                                     b->cand.enabled ? b->cand.v : CandView{});
     MMC_HIP(hipGetLastError());
     if (sync)
         MMC_HIP(hipStreamSynchronize(stream));
@@ -875,6 +1029,47 @@ static int32_t batch_settle_range(mmc_batch *b, hipStream_t stream, int64_t r0, 
     MMC_REQUIRE(!(b)->needs_reload, MMC_ERR_STATE,                                               \
                 "a run on this batch failed half-way: set every replica again "                   \
                 "(mmc_batch_set_replica) and recompute its energies before using it")
+
+// include/mmc_hip.h, "Candidate lists"
+extern "C" int32_t mmc_batch_cand_stats(mmc_batch *b, int64_t *out)
+{
+    BATCH_CHECK(b);
+    MMC_REQUIRE(out, MMC_ERR_ARG, "NULL argument");
+    const BatchCand &c = b->cand;
+    for (int k = 0; k < 8; k++)
+        out[k] = 0;
+    if (c.v.idx) {
+        std::vector<unsigned long long> h((size_t)b->sys.R * MMC_CAND_STATS);
+        MMC_HIP(hipDeviceSynchronize());
+        MMC_HIP(hipMemcpy(h.data(), c.v.stat, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < b->sys.R; r++)
+            for (int k = 0; k < MMC_CAND_STATS; k++)
+                out[k] += (int64_t)h[(size_t)r * MMC_CAND_STATS + k];
+    }
+    out[3] = c.bytes;
+    out[4] = c.refresh_launches;
+    out[5] = c.enabled ? c.state : 0;
+    out[6] = c.v.budget;
+    out[7] = c.t_build;
+    return MMC_OK;
+}
+
+extern "C" int32_t mmc_cand_thresholds(double gate, double skin, double box, uint32_t *out)
+{
+    MMC_REQUIRE(out && gate > 0 && skin >= 0 && box > 0, MMC_ERR_ARG, "bad gate / skin / box");
+    out[0] = com_quant_gate(gate * gate, box);
+    out[1] = com_quant_gate((gate + skin) * (gate + skin), box);
+    out[2] = cand_budget(out[1], out[0]);
+    return MMC_OK;
+}
+
+extern "C" int32_t mmc_cand_within(int64_t n, const uint32_t *a2, const uint32_t *d2, uint32_t budget, uint8_t *out)
+{
+    MMC_REQUIRE(n >= 0 && a2 && d2 && out, MMC_ERR_ARG, "NULL argument");
+    for (int64_t k = 0; k < n; k++)
+        out[k] = cand_within(a2[k], d2[k], budget) ? 1 : 0;
+    return MMC_OK;
+}
 
 extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_result *results)
 {
@@ -910,6 +1105,8 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     const unsigned stamp = ++b->stamp;
     // (kernel 4: "parts" counts waves, four to a workgroup, and a workgroup writes one record)
     const int P = b->kernel == 4 ? (b->n_parts + 3) / 4 : b->n_parts;
+    if (P == 1 && batch_kernel_for(b, R, P) == 2) // (the wave kernel, one part per move: candidate lists)
+        MMC_TRY(batch_cand_prepare(b, pp));
     MMC_TRY(batch_launch(b, s.stream, 0, R, P, b->buf, b->has_prev, pp, nullptr, nullptr, stamp));
     MMC_TRY(s.sync());
     b->eval_parts = P;

@@ -518,6 +518,7 @@ static int32_t ctx_flush_dirty(mmc_ctx *ctx)
             for (int k = 0; k < 3; k++)
                 a.at[t][k] = ma[3 * t + k];
         k_set_molecule<<<1, 64, 0, s.stream>>>(s.bv, a, s.rec);
+        s.comq_epoch++;
     }
     if (!ctx->dirty.empty())
         MMC_HIP(hipGetLastError());

@@ -1199,6 +1199,13 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         if (const char *e = getenv("MMC_LAUNCH_AT")) // (developer: percent)
             d.launch_at = std::min(1.0, std::max(0.0, atof(e) / 100.0));
     }
+    if (!d.server && d.P == 1) { // the wave kernel with one part per move: its candidate lists (mmc_cand.hpp)
+        bool wave = false;
+        for (const Group &g : d.groups)
+            wave = wave || batch_kernel_for(b, g.nr, d.P) == 2;
+        if (wave)
+            MMC_TRY(batch_cand_prepare(b, d.pp));
+    }
     if (d.server) // the one kernel runs on the first group's stream: that is the stream to watch
         for (Group &g : d.groups)
             g.stream = d.groups[0].stream;
@@ -1330,6 +1337,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         b->steps_done += p->n_steps;
     else { // accepted moves, S-buffer parity and the caller's energies may disagree now
         b->needs_reload = true;
+        b->cand.dirty = true;
         b->queue_reset = true;
         b->reloaded.assign(R, 0);
     }

@@ -31,6 +31,7 @@
 #pragma once
 #include <type_traits>
 #include "mmc_kernels.hpp"
+#include "mmc_cand.hpp"
 
 #define MMC_TILE 150      // neighbours staged per LDS tile (14 KB; doubles as reduction scratch)
 #define MMC_REC 12        // doubles per molecule record: 9 atom coordinates + 3 COM
@@ -743,15 +744,27 @@ __global__ __launch_bounds__(MMC_BLOCK) void k_move_eval_fast(
     store_part(out + (int64_t)r * n_parts + part, sm.red, tid);
 }
 
-// settle for the record layout: as k_settle, plus rec.
+// settle for the record layout: as k_settle, plus rec.  `cv`: the batch's candidate lists (mmc_cand.hpp;
+// cv.idx NULL: none) -- the commit raises the replica's displacement bound, so that a call does not end
+// by invalidating its lists.
 __global__ void k_settle_rec(BatchView bv, double *rec, const MoveRec *prev,
-                             const int32_t *accept, int r_base, int nr)
+                             const int32_t *accept, int r_base, int nr, CandView cv)
 {
     const int q = blockIdx.x * 16 + (threadIdx.x >> 4), t = threadIdx.x & 15;
     const int r = r_base + q;
-    if (q >= nr || !accept[r] || t >= 12)
+    if (q >= nr || !accept[r] || t >= 13)
         return;
     const int m = prev[r].mol - 1;
+    if (t == 12) { // (one lane per replica, the only writer of D_r while this kernel runs)
+        if (cv.idx && bv.comq) {
+            const double inv_box = 1.0 / bv.box;
+            const uint32_t xy = (uint32_t)com_quant(prev[r].com_new[0], inv_box)
+                                | (uint32_t)com_quant(prev[r].com_new[1], inv_box) << 16;
+            cand_note_commit(cv, cand_q0_xy(cv, bv.cq_stride, r, m), cand_q0_z(cv, bv.cq_stride, r, m), r, xy,
+                             (uint32_t)com_quant(prev[r].com_new[2], inv_box), cv.D[r], true);
+        }
+        return;
+    }
     const double v = (t < 9) ? prev[r].atoms_new[t] : prev[r].com_new[t - 9];
     rec[((int64_t)r * bv.n_mol + m) * MMC_RSTRIDE + t] = v;
     if (t >= 9)

@@ -79,6 +79,10 @@ struct DeviceSystem {
     std::vector<int32_t> ref_to_dev; // [nkvecs_ref] device index, or ~index of the conjugate partner
     void expand_S(const double *dev_order, double *ref_order) const;
     BatchView bv{};
+    // Bumped by every host call that rewrites bv.comq outside the move kernels' commits (upload, broadcast,
+    // volume change and restore, the per-replica-box rebuilds): what is derived from the codes and kept
+    // across calls -- the batch's candidate lists, mmc_cand.hpp -- is stale when its copy differs.
+    uint64_t comq_epoch = 0;
     std::vector<void *> allocs; // hipMalloc'ed
     std::vector<int32_t> h_first0, h_cnt;
     std::vector<double> h_charge;

@@ -126,6 +126,7 @@ extern "C" int32_t mmc_batch_volume_trial_replicas(mmc_batch *b, const double *n
     MMC_TRY(pb_upload_mask(s, moved));
     dim3 grid((unsigned)((s.n_mol + 255) / 256), (unsigned)R);
     k_rescale_pb<<<grid, 256, 0, s.stream>>>(s.bv, s.rec, s.pb.d_f, s.pb.d_new_box); // volumeChange.jl:62-80
+    s.comq_epoch++;
     MMC_HIP(hipGetLastError());
     MMC_TRY(s.pb_upload_scalars());
     MMC_TRY(s.pb_build_tables(s.pb.d_mask));            // ewalds.jl:45-103 for alpha / L_new

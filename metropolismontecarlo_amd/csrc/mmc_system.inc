@@ -318,6 +318,7 @@ int32_t DeviceSystem::set_replica(int64_t r, const double *com, const double *co
     }
     if (rec)
         k_build_rec<<<(n_mol + 255) / 256, 256, 0, stream>>>(bv, rec, (int)r);
+    comq_epoch++;
     MMC_HIP(hipGetLastError());
     note_shape(com, coords);
     return sync(); // the host arrays are borrowed for the call only
@@ -364,6 +365,7 @@ int32_t DeviceSystem::broadcast_replica0()
         const int64_t perf = 3 * bv.cq_stride / 2; // the 16-bit codes, two to a 32-bit word
         dim3 gf((unsigned)((perf + 255) / 256), (unsigned)(R - 1));
         k_broadcast_f32<<<gf, 256, 0, stream>>>(reinterpret_cast<float *>(bv.comq), perf);
+        comq_epoch++;
     }
     MMC_HIP(hipGetLastError());
     return sync();
@@ -755,6 +757,7 @@ int32_t DeviceSystem::pair_totals_enqueue(double lj_rcut, double qq_rcut,
         // kernels of the move driver write them as fractions of bv.box)
         dim3 gq((unsigned)((n_mol + 255) / 256), (unsigned)R);
         k_comq_pb<<<gq, 256, 0, stream>>>(bv, pb.d_box);
+        comq_epoch++;
         const int64_t wgs1 = (units + WV_WAVES - 1) / WV_WAVES;
         for (int64_t r = 0; r < R; r++) {
             BatchView v = bv;
@@ -824,6 +827,7 @@ int32_t DeviceSystem::volume_change(double new_box, double new_kappa)
     BatchView nbv = bv;
     nbv.box = new_box; // the fixed-point centres of mass are fractions of the NEW box
     k_rescale<<<grid, 256, 0, stream>>>(nbv, rec, f);
+    comq_epoch++; // (and the prefilter's threshold changes with the box)
     MMC_HIP(hipGetLastError());
     box = bv.box = new_box;
     return prepare_ewald(new_kappa, nk, k_sq_max, new_box, bv.factor, nullptr);
@@ -881,6 +885,7 @@ int32_t DeviceSystem::snapshot_restore()
     MMC_REQUIRE(snap.valid, MMC_ERR_STATE, "no snapshot to restore");
     MMC_HIP(hipSetDevice(device));
     k_copy_segments<<<512, 256, 0, stream>>>(snap.from_snap);
+    comq_epoch++;
     MMC_HIP(hipGetLastError());
     box = bv.box = snap.box;
     bv.kappa = snap.kappa;
@@ -958,6 +963,8 @@ int32_t DeviceSystem::pb_snapshot(const int32_t *d_mask, bool take)
     }
     dim3 grid(64, (unsigned)R);
     k_copy_replicas<<<grid, 256, 0, stream>>>(take ? pb.to_snap : pb.from_snap, d_mask);
+    if (!take)
+        comq_epoch++;
     MMC_HIP(hipGetLastError());
     return MMC_OK;
 }

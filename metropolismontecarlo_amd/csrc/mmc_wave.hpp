@@ -315,9 +315,12 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
     const int32_t *__restrict__ kpack, FastConsts fc, const MoveRec *__restrict__ cur,
     const MoveRec *__restrict__ prev, PartOut *out, int n_parts, PairParams pp, int r_base,
     int n_units, const uint8_t *flagv, unsigned stamp, const DecideConsts *__restrict__ dc, long long dec_step,
-    int n_sub_arg, int slot0, unsigned *queue, unsigned queue_base)
+    int n_sub_arg, int slot0, unsigned *queue, unsigned queue_base, CandView cv)
 {
     const int n_sub = MULTI ? n_sub_arg : 1;
+    // candidate lists of the COM scan (mmc_cand.hpp, WV_CAND in mmc_wave_unit.inc): the forms with one part
+    // per move, where this wave is the replica's only reader and writer in the launch; cv.idx NULL: none
+    const bool cand_on = !SUBST && cv.idx != nullptr;
     __shared__ __align__(16) WaveSharedT<WV_MWAVES, !WOLF> sm;
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -376,6 +379,10 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
         int flags_carry = -1;            // accept | S-buffer bit << 1 after the step before
         double e_sum = 0.0;              // dU of the accepted steps, in step order
         unsigned acc_mask = 0, ovl_mask = 0, kind_mask = 0;
+        uint32_t d_cur = MMC_CAND_STALE; // the replica's displacement bound D_r, carried through the unit's steps
+        unsigned n_cand = 0;             // steps of this unit that took a candidate list
+        if (!SUBST && cand_on)
+            d_cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)cv.D[r]);
       for (int sub = 0; sub < n_sub; sub++) {
         if (MULTI) { // (opaque once per STEP here: see above; the steps are a loop inside the unit's)
             lane = lane0;
@@ -405,6 +412,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
         // pending commit of the previous accepted move (main.jl:598-621): written by part 0;
         // every reader of this launch substitutes the pending words for that molecule
         int pend = -1;
+        uint32_t pcxy = 0, pcz = 0; // (candidate lists: the codes of the commit's centre of mass, x | y << 16 and z)
         if (commit) {
             const double *pvp = reinterpret_cast<const double *>(prev_s + r);
             double pw = 0.0;
@@ -425,6 +433,11 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
                     (d == 0 ? bv.comx : d == 1 ? bv.comy : bv.comz)[r * bv.mol_stride + pend] = pw;
                     comq_store(bv, r, pend, d, pw, inv_box);
                 }
+            }
+            if (!SUBST && cand_on) {
+                const int cq = (lane >= 9 && lane < 12) ? (int)com_quant(pw, inv_box) : 0;
+                pcxy = (uint32_t)lane_i32(cq, 9) | (uint32_t)lane_i32(cq, 10) << 16;
+                pcz = (uint32_t)lane_i32(cq, 11);
             }
             if (bv.quat) { // totProps.quat[i] = ei (main.jl:619)
                 const double q0 = wave_pick(pw, 13), q1 = wave_pick(pw, 14),
@@ -488,6 +501,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #define WV_ONE_CALL_MOVE 1
 #endif
 #define WV_ONE_CALL WV_ONE_CALL_MOVE
+#define WV_CAND (!SUBST)
     // (n_parts == 1: every unit has the reciprocal part, and the commit's stores, issued before the
     // phase tables were computed, have mostly landed when those are done)
 #define WV_AFTER_PHASE_TABLES                                                                    \
@@ -500,6 +514,7 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
 #undef WV_VIRIAL
 #undef WV_PASSES
 #undef WV_ONE_CALL
+#undef WV_CAND
 #undef WV_XY
 #undef WV_SUBST
 #undef WV_ZERO
@@ -512,6 +527,10 @@ __attribute__((amdgpu_waves_per_eu(WOLF ? WV_OCC_WOLF : WV_OCC, WOLF ? WV_OCC_WO
         if (n_sub > 1) // what this step stored (S_new, soon the commit) is read by the next
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } // sub
+        if (!SUBST && cand_on && lane == 0) { // (counters of mmc_batch_cand_stats; nothing waits for them)
+            atomicAdd(cv.stat + (int64_t)r * MMC_CAND_STATS, (unsigned long long)n_cand);
+            atomicAdd(cv.stat + (int64_t)r * MMC_CAND_STATS + 1, (unsigned long long)((unsigned)n_sub - n_cand));
+        }
     }
 }
 

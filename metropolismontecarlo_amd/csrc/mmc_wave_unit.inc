@@ -54,6 +54,9 @@
 #define WV_ONE_CALL 0
 #define WV_ONE_CALL_DEFAULTED
 #endif
+// WV_CAND (defined by k_move_eval_wave alone, a constant expression: true in its SUBST = false instantiations;
+// not defined = 0): a step may fill the list from the chosen molecule's candidate list instead of scanning
+// every centre of mass (see the COM scan).  Every other includer compiles exactly as without it.
 #ifndef WV_XY // 1: the (kx, ky) products of the moved atoms once per column of k-vectors (see the k loop)
 #define WV_XY 0
 #define WV_XY_DEFAULTED
@@ -586,6 +589,67 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                 pqz = (uint32_t)__builtin_amdgcn_readfirstlane((int)com_quant(pvw[11], inv_box));
             }
             int base = j_begin, cnt = 0;
+#ifdef WV_CAND
+            // CANDIDATE LIST (mmc_cand.hpp; the includer provides cv, cand_on, d_cur, pcxy, pcz, n_cand; one part
+            // per move: j_begin = 0, j_end = n_mol).  The chosen molecule's list names, in ascending j, every
+            // molecule that can pass the prefilter while a + sqrt(D_r) stays inside the lists' budget: the SAME
+            // test on the molecules' CURRENT codes is then made for those only -- at most MMC_CAND_CAP / 64
+            // blocks instead of n_mol / 64 -- and list[0 .. cnt) is what the scan would have made.
+            // Everything is requested at once, outside any branch (see below): the snapshot's codes of the
+            // chosen molecule and of the one just committed, the list's length and its four blocks of
+            // indices (scalar base + lane offset + immediate), then the codes gathered by index.  A step
+            // that may not use them (bound run out, list overflowed, replica stale) has loaded 14 words
+            // for nothing and scans.
+#if WV_NS != 2 || !WV_ONE_CALL
+#error "the candidate path: trial moves (WV_NS 2) and one call site of process() (WV_ONE_CALL)"
+#endif
+            bool cand_pre = false;
+            if constexpr (WV_CAND) {
+            if (cand_on) { // (uniform over the launch: the batch has lists)
+                const int64_t cqs = bv.cq_stride;
+                const uint16_t *ip = cv.idx + ((int64_t)r * n_mol + i0) * MMC_CAND_CAP;
+                uint32_t cix[MMC_CAND_CAP / 64], gxy[MMC_CAND_CAP / 64], gz[MMC_CAND_CAP / 64];
+#pragma unroll
+                for (int b = 0; b < MMC_CAND_CAP / 64; b++)
+                    cix[b] = ip[64 * b + lane];
+                const int pm = pend >= 0 ? pend : i0; // (no branch around a load)
+                const uint32_t qixy = cand_q0_xy(cv, cqs, r, i0), qiz = cand_q0_z(cv, cqs, r, i0);
+                const uint32_t qpxy = cand_q0_xy(cv, cqs, r, pm), qpz = cand_q0_z(cv, cqs, r, pm);
+                const uint32_t ccnt = cv.cnt[(int64_t)r * cqs + i0];
+                const uint32_t *gpxy = reinterpret_cast<const uint32_t *>(WV_CQ_BASE);
+                const uint16_t *gpz = WV_CQ_BASE + 2 * cqs;
+#pragma unroll
+                for (int b = 0; b < MMC_CAND_CAP / 64; b++) {
+                    cix[b] = min(cix[b], (uint32_t)(n_mol - 1)); // (slots past the count: whatever they hold is readable)
+                    gxy[b] = gpxy[cix[b]];
+                    gz[b] = gpz[cix[b]];
+                }
+                // the commit this step wrote (its codes: pcxy, pcz) raises the replica's bound ...
+                if (pend >= 0)
+                    d_cur = (uint32_t)__builtin_amdgcn_readfirstlane(
+                        (int)cand_note_commit(cv, qpxy, qpz, r, pcxy, pcz, d_cur, lane == 0));
+                // ... and the one wave-uniform test, on the squares (cand_within)
+                const uint32_t a2 = (uint32_t)__builtin_amdgcn_readfirstlane(
+                    (int)max(com_quant_dist2(qixy, qiz, cqxy[0], cqz[0]), com_quant_dist2(qixy, qiz, cqxy[1], cqz[1])));
+                const int ncand = __builtin_amdgcn_readfirstlane((int)ccnt);
+                cand_pre = ncand <= MMC_CAND_CAP && cand_within(a2, d_cur, cv.budget);
+                if (cand_pre) {
+#pragma unroll
+                    for (int b = 0; b < MMC_CAND_CAP / 64; b++) {
+                        const bool keep = (64 * b + lane < ncand)
+                                          && ((com_quant_dist2(gxy[b], gz[b], cqxy[0], cqz[0]) < gate_q)
+                                              | (com_quant_dist2(gxy[b], gz[b], cqxy[1], cqz[1]) < gate_q));
+                        const unsigned long long m = wave_ballot(keep);
+                        if (keep)
+                            list[cnt + lanes_below(m)] = (wv_list_t)cix[b];
+                        cnt += __popcll(m);
+                    }
+                    base = j_end;
+                    n_cand++;
+                }
+            }
+            }
+#endif
             uint32_t fxy[WV_PF], fz[WV_PF];
 #if WV_ONE_CALL
             // ONE call site of process(): scan until the list has no room for another WV_PF blocks or
@@ -594,8 +658,14 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
             // and one behind it, one copy of the pair loops instead of two).  The prefetch starts anew
             // with every list -- the blocks it re-reads were requested by the trip before -- so its
             // registers are not live across the pair loops.
+#ifdef WV_CAND // (a list filled from the candidates goes through the same call of process(), once)
+            while (cand_pre || base < j_end) {
+            if (!cand_pre) {
+            cnt = 0;
+#else
             while (base < j_end) {
             cnt = 0;
+#endif
 #endif
 #pragma unroll
             for (int b = 0; b < WV_PF; b++) {
@@ -633,6 +703,10 @@ static_assert(WV_VIRIAL, "the one-state body always delivers the virial");
                 pz += 128 * WV_PF;
 #if WV_ONE_CALL
             }
+#ifdef WV_CAND
+            }
+            cand_pre = false;
+#endif
             WV_STAMP(4); // scan done (the last list's, where there are several)
             if (cnt)
                 process(cnt);

@@ -490,6 +490,13 @@ class Batch(_Handle):
     def set_option(self, key, value):
         check(self._L.mmc_batch_set_option(self._h, key.encode(), int(value)))
 
+    def cand_stats(self):
+        """mmc_batch_cand_stats: what the candidate lists of the move kernel's COM scan did so far."""
+        out = (C.c_int64 * 8)()
+        check(self._L.mmc_batch_cand_stats(self._h, out))
+        keys = ("list_steps", "scan_steps", "refreshes", "bytes", "refresh_launches", "state", "budget", "t_build")
+        return dict(zip(keys, (int(v) for v in out)))
+
     def volume_change(self, new_box, new_kappa):
         check(self._L.mmc_batch_volume_change(self._h, float(new_box), float(new_kappa)))
         self.box, self.kappa = float(new_box), float(new_kappa)

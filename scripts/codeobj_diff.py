@@ -6,7 +6,7 @@
 For every kernel symbol: .vgpr_count, .sgpr_count, .private_segment_fixed_size and
 .group_segment_fixed_size from the code object's metadata note, and the size of the symbol's
 .text.  A kernel of BASE is looked up in NEW by its demangled name; where a function template has
-gained trailing parameters with defaults, the BASE name is matched with those defaults appended
+gained trailing parameters with defaults, or a kernel a trailing argument, the BASE name is matched with those appended
 (RENAMES below: the only difference is the mangled name).  Prints every kernel of BASE that
 differs or is missing, lists the kernels only NEW has, and exits 1 if a BASE kernel differs.
 
@@ -33,6 +33,9 @@ RENAMES = [
     # k_move_eval_fast<PerBox...> gained a leading WOLF (false for every form that existed)
     (re.compile(r"^void k_move_eval_fast<>\("), r"void k_move_eval_fast<false>("),
     (re.compile(r"^void k_move_eval_fast<(?!false|true)([^>]+)>\("), r"void k_move_eval_fast<false, \1>("),
+    # k_move_eval_wave and k_settle_rec gained a trailing CandView argument (the candidate lists, mmc_cand.hpp)
+    (re.compile(r"^(void k_move_eval_wave<\w+, \w+, \w+, \w+, \w+>\(.*unsigned int\*, unsigned int)\)$"), r"\1, CandView)"),
+    (re.compile(r"^(k_settle_rec\(.*int, int)\)$"), r"\1, CandView)"),
     # k_move_eval became a template <bool WOLF = false>
     (re.compile(r"^k_move_eval\("), r"void k_move_eval<false>("),
 ]
