@@ -87,7 +87,7 @@ struct mmc_batch {
                                             // memory instead of reading host memory over PCIe
     int32_t *h_timeout = nullptr, *hd_timeout = nullptr;      // pinned: a workgroup gave up waiting
     hipStream_t run_streams[MMC_MAX_GROUPS] = {}; // the native driver's streams and timing events,
-    hipEvent_t run_events[MMC_MAX_GROUPS][4] = {}; // created on first use, kept until destroy ([2], [3]: the second launch in flight)
+    hipEvent_t run_events[MMC_MAX_GROUPS][2] = {}; // created on first use, kept until destroy
     void *pool = nullptr;              // the native driver's worker threads (WorkerPool, mmc_engine.inc), kept
     void (*pool_destroy)(void *) = nullptr; // between calls; joined by mmc_batch_destroy through this
     int steps_per_launch = 0;          // option "steps_per_launch": 0 = by size, 1, 2, 4, 8, 16
@@ -267,7 +267,7 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         (void)hipHostFree(b->h_steps);
     for (int g = 0; g < MMC_MAX_GROUPS; g++) {
         if (b->run_streams[g]) (void)hipStreamDestroy(b->run_streams[g]);
-        for (int k = 0; k < 4; k++)
+        for (int k = 0; k < 2; k++)
             if (b->run_events[g][k]) (void)hipEventDestroy(b->run_events[g][k]);
     }
     if (b->h_ctrl)
@@ -607,11 +607,10 @@ static inline const MoveRec *batch_ring_slot(const mmc_batch *b, int64_t step)
     return b->d_ring + (step % b->ring_slots) * b->sys.R;
 }
 
-// Enqueue one step for replicas [r0, r0 + nr): proposals h_moves[buf] -> device (or generated
-// there when `dg` is given), then the fused move kernel.  `has_prev`: the previous proposals of
-// these replicas are outstanding (moves[buf ^ 1], or the ring slot of step - 1).
-// `before_kernel`: optional event recorded in front of the move kernel (kernel timing).
 // Which move kernel a launch of nr replicas x P parts runs (option "kernel"; 3 = by size).
+// kernel 3: a wave per unit pays once a launch has a wave for every slot of the machine
+// (4 per SIMD); below that the workgroup-per-move kernel, which spreads one move over 256
+// lanes, has the shorter critical path (measured crossover: 2048 .. 8192 moves per launch)
 static int batch_kernel_for(const mmc_batch *b, int64_t nr, int P)
 {
     if (b->sys.pb.on) // per-replica boxes: the workgroup-per-move kernel is the one with a box per replica
@@ -746,7 +745,17 @@ static int32_t batch_cand_for_launch(mmc_batch *b, hipStream_t stream, int64_t r
     return MMC_OK;
 }
 
-static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr, int P,
+// The form of a k_move_eval_wave launch: its five template arguments.  subst = several parts per move,
+// which the host adds up and decides on: never with multi or ladder, which belong to the kernel's own
+// decision.  20 of the 32 combinations exist.
+struct WaveForm { bool subst, img, multi, wolf, ladder; };
+
+// Enqueue one step for replicas [r0, r0 + nr): proposals h_moves[buf] -> device (or generated
+// there when `dg` is given), then the fused move kernel.  `has_prev`: the previous proposals of
+// these replicas are outstanding (moves[buf ^ 1], or the ring slot of step - 1).
+// `before_kernel`: optional event recorded in front of the move kernel (kernel timing).
+// `kernel`: batch_kernel_for of this launch's replicas and parts, from the caller.
+static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_t nr, int P, int kernel,
                             int buf, bool has_prev, const PairParams &pp,
                             hipEvent_t before_kernel = nullptr, const DevGen *dg = nullptr,
                             unsigned stamp = 0, const DevDecide *dd = nullptr)
@@ -804,16 +813,14 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     if (before_kernel)
         MMC_HIP(hipEventRecord(before_kernel, stream));
     dim3 grid((unsigned)P, (unsigned)nr);
-    MMC_REQUIRE(!dd || (dg && P == 1 && !b->zero_copy_moves && batch_kernel_for(b, nr, P) == 2), MMC_ERR_ASSERT,
+    MMC_REQUIRE(!dd || (dg && P == 1 && !b->zero_copy_moves && kernel == 2), MMC_ERR_ASSERT,
                 "the kernel's own accept decision needs device-side proposals, one part per move and the wave kernel");
-    // kernel 3: a wave per unit pays once a launch has a wave for every slot of the machine
-    // (4 per SIMD); below that the workgroup-per-move kernel, which spreads one move over 256
-    // lanes, has the shorter critical path (measured crossover: 2048 .. 8192 moves per launch)
-    const int kernel = batch_kernel_for(b, nr, P);
     const bool wolf = b->coulomb_style == MMC_COULOMB_WOLF; // (never with kernel 4 or per-replica boxes)
     if (kernel != 2) // (their commits do not keep the candidate lists' bound)
         MMC_TRY(batch_cand_stale(b, stream, r0, nr));
     MMC_REQUIRE(!wolf || (kernel != 4 && !s.pb.on), MMC_ERR_ASSERT, "Wolf style reached a kernel without a Wolf form");
+    using Yes = std::true_type;
+    using No = std::false_type;
     if (kernel == 4) {
         // latency form: P workgroups of four parts each per replica, one record per workgroup
         MMC_REQUIRE(lat_applies(4 * P, (int)s.n_mol, (int)s.nkvecs), MMC_ERR_UNSUPPORTED,
@@ -837,58 +844,55 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
                          s.image_by_molecule(std::max(pp.lj_gate_sq, pp.qq_gate_sq)) &&
                          s.pairs_inside_slack(pp.qq_gate_sq, pp.qq_slack_sq) &&
                          s.pairs_inside_slack(pp.lj_gate_sq, pp.lj_slack_sq);
-#define MMC_WAVE_LAUNCH(SUBST, IMG) MMC_WAVE_LAUNCH3(SUBST, IMG, false)
-#define MMC_WAVE_LAUNCH3(SUBST, IMG, MULTI)                                                      \
-    if (wolf) MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, true); else MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, false)
-#define MMC_WAVE_LAUNCH4(SUBST, IMG, MULTI, WOLF) MMC_WAVE_LAUNCH5(SUBST, IMG, MULTI, WOLF, false)
-#define MMC_WAVE_LAUNCH5(SUBST, IMG, MULTI, WOLF, LADDER)                                        \
-    k_move_eval_wave<SUBST, IMG, MULTI, WOLF, LADDER><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>( \
-        s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,     \
-        (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,      \
-        dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,      \
-        dd ? dd->queue_base : 0u, SUBST ? CandView{} : cvv)
-// the forms that decide (one part per move, SUBST = false): under per-replica temperatures their
-// LADDER twins, which read DecideConsts::temps[r]
-#define MMC_WAVE_DECIDES(IMG, MULTI)                                                             \
-    if (ladder && wolf) MMC_WAVE_LAUNCH5(false, IMG, MULTI, true, true);                         \
-    else if (ladder) MMC_WAVE_LAUNCH5(false, IMG, MULTI, false, true);                           \
-    else MMC_WAVE_LAUNCH3(false, IMG, MULTI)
-        const bool ladder = dd && !b->temps.empty(); // (run_impl has put d_temps into *dd->dc)
+        // the forms that decide (dd: one part per move, above): several steps in one record, and under
+        // per-replica temperatures the LADDER twins, which read DecideConsts::temps[r] (the driver has
+        // put d_temps into *dd->dc)
+        const WaveForm f{ P != 1, img, dd && dd->n_sub > 1, wolf, dd && !b->temps.empty() };
         CandView cvv{}; // candidate lists: the forms with one part per move keep and use them
         if (P == 1)
             MMC_TRY(batch_cand_for_launch(b, stream, r0, nr, &cvv));
         else
             MMC_TRY(batch_cand_stale(b, stream, r0, nr));
-        if (P == 1 && dd && dd->n_sub > 1) {
-            if (img) { MMC_WAVE_DECIDES(true, true); } else { MMC_WAVE_DECIDES(false, true); }
-        } else if (P == 1) {
-            if (img) { MMC_WAVE_DECIDES(true, false); } else { MMC_WAVE_DECIDES(false, false); }
+        auto launch = [&](auto subst, auto img_, auto multi, auto wolf_, auto ladder) {
+            k_move_eval_wave<subst(), img_(), multi(), wolf_(), ladder()><<<(unsigned)wgs, WV_MWAVES * 64, 0, stream>>>(
+                s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur, prev, dd ? dd->parts : b->d_parts, P, pp,
+                (int)r0, (int)n_units, flagv, stamp, dd ? dd->dc : nullptr, dd ? (long long)dd->step : 0LL,
+                dd ? dd->n_sub : 1, (int)(dg ? dg->step % b->ring_slots : 0), dd ? dd->queue : nullptr,
+                dd ? dd->queue_base : 0u, cvv);
+        };
+        // (only what is named here exists: 4 x 4 forms with one part per move, 2 x 2 with several)
+        auto pick = [&](auto subst, auto img_, auto multi) {
+            if (f.ladder) {
+                if constexpr (!subst()) {
+                    if (f.wolf) launch(subst, img_, multi, Yes{}, Yes{});
+                    else launch(subst, img_, multi, No{}, Yes{});
+                }
+            } else if (f.wolf) launch(subst, img_, multi, Yes{}, No{});
+            else launch(subst, img_, multi, No{}, No{});
+        };
+        if (f.multi) {
+            if (f.img) pick(No{}, Yes{}, Yes{}); else pick(No{}, No{}, Yes{});
+        } else if (!f.subst) {
+            if (f.img) pick(No{}, Yes{}, No{}); else pick(No{}, No{}, No{});
         } else {
-            if (img) { MMC_WAVE_LAUNCH(true, true); } else { MMC_WAVE_LAUNCH(true, false); }
+            if (f.img) pick(Yes{}, Yes{}, No{}); else pick(Yes{}, No{}, No{});
         }
-#undef MMC_WAVE_DECIDES
-#undef MMC_WAVE_LAUNCH
-#undef MMC_WAVE_LAUNCH3
-#undef MMC_WAVE_LAUNCH5
-#undef MMC_WAVE_LAUNCH4
-    } else if (kernel == 1 && s.pb.on)
-        k_move_eval_fast<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, nullptr, s.kpack, s.fc, cur, prev,
-                                                                b->d_parts, P, pp, (int)r0, flagv, stamp,
-                                                                s.pb_view());
-    else if (kernel == 1 && wolf)
-        k_move_eval_fast<true><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
-                                                               prev, b->d_parts, P, pp, (int)r0, flagv,
-                                                               stamp);
-    else if (kernel == 1)
-        k_move_eval_fast<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, s.qq_tab, s.kpack, s.fc, cur,
-                                                                prev, b->d_parts, P, pp, (int)r0, flagv,
-                                                                stamp);
-    else if (wolf)
-        k_move_eval<true><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
-                                                          s.rec, flagv, stamp);
-    else
-        k_move_eval<false><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
-                                                           s.rec, flagv, stamp);
+    } else if (kernel == 1) {
+        auto launch = [&](auto wolf_, const double *qq_tab, auto... per_box) {
+            k_move_eval_fast<wolf_()><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, s.rec, qq_tab, s.kpack, s.fc, cur, prev,
+                                                                     b->d_parts, P, pp, (int)r0, flagv, stamp,
+                                                                     per_box...);
+        };
+        if (s.pb.on) launch(No{}, nullptr, s.pb_view());
+        else if (wolf) launch(Yes{}, s.qq_tab);
+        else launch(No{}, s.qq_tab);
+    } else {
+        auto launch = [&](auto wolf_) {
+            k_move_eval<wolf_()><<<grid, MMC_BLOCK, 0, stream>>>(s.bv, cur, prev, b->d_parts, P, pp, (int)r0,
+                                                                 s.rec, flagv, stamp);
+        };
+        if (wolf) launch(Yes{}); else launch(No{});
+    }
     MMC_HIP(hipGetLastError());
     return MMC_OK;
 }
@@ -1105,9 +1109,10 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     const unsigned stamp = ++b->stamp;
     // (kernel 4: "parts" counts waves, four to a workgroup, and a workgroup writes one record)
     const int P = b->kernel == 4 ? (b->n_parts + 3) / 4 : b->n_parts;
-    if (P == 1 && batch_kernel_for(b, R, P) == 2) // (the wave kernel, one part per move: candidate lists)
+    const int kernel = batch_kernel_for(b, R, P);
+    if (P == 1 && kernel == 2) // (the wave kernel, one part per move: candidate lists)
         MMC_TRY(batch_cand_prepare(b, pp));
-    MMC_TRY(batch_launch(b, s.stream, 0, R, P, b->buf, b->has_prev, pp, nullptr, nullptr, stamp));
+    MMC_TRY(batch_launch(b, s.stream, 0, R, P, kernel, b->buf, b->has_prev, pp, nullptr, nullptr, stamp));
     MMC_TRY(s.sync());
     b->eval_parts = P;
     for (int64_t r = 0; r < R; r++) {

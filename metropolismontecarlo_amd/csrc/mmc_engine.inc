@@ -121,21 +121,36 @@ struct SpinBarrier { // sense-reversing; the driver's threads are never oversubs
     }
 };
 
+// What a call will do, decided by run_plan from the batch's options and the call's parameters before
+// anything is touched: the Driver only reads it.
+struct RunPlan {
+    int G = 0;                   // groups of replicas, each with its own launches
+    struct { int64_t r0, nr; int kernel; } group[MMC_MAX_GROUPS]; // replicas [r0, r0 + nr) and their move kernel (batch_kernel_for)
+    int n_streams = 1;           // group g launches on stream g % n_streams
+    int T = 1;                   // host threads
+    int P = 1;                   // result records per move the host reads
+    bool devgen = false;         // proposals generated on the device (mmc_propose.hpp)
+    bool server = false;         // the persistent move server does the launches' work
+    int server_waves = 0;        // ... with this many parts (waves of a replica's workgroup)
+    int server_lat_wgs = 0;      // > 0: the latency server, this many workgroups per replica
+    bool devacc = false;         // the accept decision made by the move kernel itself (thread_main_devacc)
+    int K = 1;                   // ... which then takes every replica through K steps per launch (DecideConsts)
+    int gen_max = MMC_GEN_MAX;   // steps one k_propose launch draws (a whole call's: K, run_plan)
+    bool cand = false;           // some group runs the wave kernel with one part per move: its candidate lists (mmc_cand.hpp)
+    bool no_tail_share = true;   // Driver::share: every thread one contiguous slice
+};
+
 struct Group {
     int64_t r0 = 0, nr = 0;
+    int kernel = 0;        // the move kernel of its launches (RunPlan)
     hipStream_t stream = nullptr;
     hipStream_t launched_on = nullptr; // the stream of its launch in flight (the first may ride on another group's: prelaunch)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int buf = 0;           // h_moves[buf] holds the proposals in flight (after the first launch)
-    bool has_prev = false; // a launch of this group has completed before
     int64_t gen_end = 0;   // device proposals: records of steps < gen_end exist in the ring
     unsigned long long n_launch = 0; // launches enqueued in this run
     unsigned stamp = 0;    // stamp of the launch in flight (PartOut::ovl[1], see store_part)
     bool timed = false;    // the launch in flight is bracketed by ev0 / ev1
-    // device-side decisions: two launches of a group are in flight, steps of either parity
-    hipEvent_t evs[2][2] = {};
-    unsigned stamp_of[2] = { 0, 0 };
-    bool timed_of[2] = { false, false };
     std::chrono::steady_clock::time_point t_post; // move server: when the step's words were posted
 };
 
@@ -162,6 +177,8 @@ inline void adjust_step(int64_t &naccepp, int64_t &attempp, int64_t naccept, int
 }
 
 struct Driver {
+    const RunPlan plan;
+    explicit Driver(const RunPlan &pl) : plan(pl) {}
     mmc_batch *b;
     const mmc_run_params *p;
     double *energies;          // mmc_batch_run
@@ -170,18 +187,10 @@ struct Driver {
     int adjust = 0;
     uint8_t s_flip = 1;          // an accepted move hands the S buffers over (main.jl:621); 0 in Wolf style,
                                  // whose moves leave both where they were
-    bool devgen = false;         // proposals generated on the device (mmc_propose.hpp)
-    bool devacc = false;         // ... and the accept decision made by the move kernel itself (thread_main_devacc)
-    int K = 1;                   // ... which then takes every replica through K steps per launch (DecideConsts)
-    int gen_max = MMC_GEN_MAX;   // steps one k_propose launch draws (a whole call's: K, run_impl)
-    bool server = false;         // the persistent move server does the launches' work
-    int server_waves = 0;        // ... with this many parts (waves of a replica's workgroup)
-    int server_lat_wgs = 0;      // > 0: the latency server, this many workgroups per replica
     std::vector<Group> groups;
     std::vector<Rng> rng;
     std::vector<uint8_t> acc_prev, kind;
     PairParams pp;
-    int P = 1, T = 1;
     SpinBarrier bar;
     std::atomic<int32_t> status{ MMC_OK };
     std::atomic<int> drained_polls{ 0 };
@@ -206,10 +215,11 @@ struct Driver {
     // the checksum of the bytes copied out of it matches (store_part: the four 16-byte pieces of
     // the device's store may land separately; a torn record fails the checksum and is read again).
     // Returns 1 = collected, 0 = not yet, -1 = the run has failed (test hook, see below).
+    // slot: the half of h_parts the launch wrote (1: the kernel's own decisions only, P == 1).
     int collect(int64_t r, unsigned want, PartOut *parts, int &q_done, mmc_run_stats &st, int slot = 0)
     {
-        for (; q_done < P; q_done++) {
-            const PartOut *src = &b->h_parts[(size_t)slot * b->sys.R + r * P + q_done]; // (slot 1: P == 1 only)
+        for (; q_done < plan.P; q_done++) {
+            const PartOut *src = &b->h_parts[(size_t)slot * b->sys.R + r * plan.P + q_done];
             if (part_stamp_of(*(const volatile int32_t *)&src->ovl[1]) != want)
                 return 0;
             std::atomic_thread_fence(std::memory_order_acquire);
@@ -261,7 +271,7 @@ struct Driver {
         const double T_ = temps ? temps[r] : p->temperature, factor = b->sys.bv.factor;
         const bool sweep_end = (step_done % b->sys.n_mol) == b->sys.n_mol - 1;
         mmc_move_result res;
-        mmc_combine_parts(parts, P, factor, &res);
+        mmc_combine_parts(parts, plan.P, factor, &res);
         const double delta = res.d_lj + res.d_real + res.d_recip; // main.jl:593
         if (res.overlap)
             st.overlaps++; // main.jl:595-597
@@ -270,9 +280,8 @@ struct Driver {
         bool met;
         if (dev_accept >= 0) met = dev_accept != 0;
         else if (x < 0.0) met = true;
-        else met = std::exp(-x) > (devgen ? mmc_metropolis_uniform(chain_key(r),
-                                                                    (uint64_t)(rng_off + step_done))
-                                          : rng[r].uniform());
+        else met = std::exp(-x) > (plan.devgen ? mmc_metropolis_uniform(chain_key(r), (uint64_t)(rng_off + step_done))
+                                               : rng[r].uniform());
         const bool accept = met && !res.overlap;
         if (step_done < b->trace_steps) { // test hook "trace_steps"
             b->trace_delta[(size_t)r * b->trace_steps + step_done] = delta;
@@ -307,7 +316,7 @@ struct Driver {
                         c.trans_set_value, b->sys.box, c.dr_max);
             adjust_step(c.rot_naccepp, c.rot_attempp, c.rot_naccept, c.rot_attempt,
                         c.rot_set_value, b->sys.box, c.dphi_max);
-            if (devgen)
+            if (plan.devgen)
                 b->h_steps[r] = make_double2(c.dr_max, c.dphi_max);
         }
     }
@@ -318,15 +327,14 @@ struct Driver {
     // that to every record it takes (all threads working through interleaved chunks of 128 from the
     // start: the launch ran 15 % longer, round 4).  Gated it happens to one line of the chunk, and
     // the rest -- written in the same round of the kernel -- is almost always there in its turn.
-    // slot >= 0: device-side decisions -- the records of the launch of that parity, which carry the
-    // decision; the host adds the step's bookkeeping (and the kind of the move, for the counts).
+    // Device-side decisions: the records carry the decision; the host adds the step's bookkeeping (and
+    // the kind of the move, for the counts).  slot: the half of h_parts the launch wrote (collect).
     void metropolis(const Group &g, int64_t lo, int64_t hi, int64_t step_done, mmc_run_stats &st,
-                    bool gated = false, int slot = -1)
+                    bool gated = false, int slot = 0)
     {
-        const unsigned want = (slot >= 0 ? g.stamp_of[slot] : g.stamp) & MMC_STAMP_MASK;
-        const int sl = slot >= 0 ? slot : 0;
+        const unsigned want = g.stamp & MMC_STAMP_MASK;
         if (gated && hi > lo) {
-            const PartOut *gate = &b->h_parts[(size_t)sl * b->sys.R + (hi - 1) * P + (P - 1)];
+            const PartOut *gate = &b->h_parts[(size_t)slot * b->sys.R + (hi - 1) * plan.P + (plan.P - 1)];
             for (unsigned spins = 1; part_stamp_of(*(const volatile int32_t *)&gate->ovl[1]) != want; spins++) {
                 if (((spins & 0xffff) == 0 && !still_running(g)) || status.load(std::memory_order_relaxed) != MMC_OK)
                     return;
@@ -338,14 +346,14 @@ struct Driver {
             PartOut parts[MMC_MAX_PARTS];
             int q_done = 0;
             for (unsigned spins = 1;; spins++) {
-                const int c = collect(r, want, parts, q_done, st, sl);
+                const int c = collect(r, want, parts, q_done, st, slot);
                 if (c > 0)
                     break;
                 if (c < 0 || ((spins & 0xfffff) == 0 && !still_running(g)))
                     return;
                 mmc_cpu_relax(); // (a polling core that hammers the line the GPU is about to write slows that write)
             }
-            const int64_t n_sub = slot >= 0 ? std::min<int64_t>(K, p->n_steps - step_done) : 1;
+            const int64_t n_sub = plan.devacc ? std::min<int64_t>(plan.K, p->n_steps - step_done) : 1;
             if (n_sub > 1) { // one record for the launch's steps [step_done, step_done + n_sub)
                 unsigned long long bits, kbits;
                 memcpy(&bits, &parts[0].lj_pot[1], 8);
@@ -367,7 +375,7 @@ struct Driver {
                     }
                 }
                 st.moves += n_sub;
-            } else if (slot >= 0) {
+            } else if (plan.devacc) {
                 kind[r] = (uint8_t)mmc_move_kind(chain_key(r), (uint64_t)(rng_off + step_done));
                 decide(r, parts, step_done, st, part_accept_of(parts[0].ovl[1]));
                 if (acc_prev[r] && step_done + 1 < p->n_steps)
@@ -384,18 +392,19 @@ struct Driver {
     // every other split tried in round 4 was no better: chunks of 64-512 dealt out in turn from the
     // start ran the LAUNCH 5-25 % longer (threads that keep pace with the kernel read lines the GPU
     // is about to write: see metropolis), and a contiguous 7/8 + a dealt-out last eighth measured
-    // the same as this (MMC_TAIL_DIV=8) -- a thread's 200 us per launch is the cost, not its order.
-    // Device-side decisions: the last eighth dealt out in chunks of MMC_HOST_CHUNK (the bookkeeping
-    // is light, and nothing waits for it but the end of the call).
+    // the same as this -- a thread's 200 us per launch is the cost, not its order.
+    // Device-side decisions: the last eighth (tail_div) dealt out in chunks of MMC_HOST_CHUNK (the
+    // bookkeeping is light, and nothing waits for it but the end of the call).
     // fn(lo, hi, gated): gated = a chunk of the tail (see metropolis).
+    static constexpr int tail_div = 8;
     template <class F> void share(const Group &g, int t, F &&fn) const
     {
-        const int64_t tail = g.nr >= 16 * (int64_t)MMC_HOST_CHUNK * T && !no_tail_share ? g.nr / tail_div : 0;
+        const int64_t tail = g.nr >= 16 * (int64_t)MMC_HOST_CHUNK * plan.T && !plan.no_tail_share ? g.nr / tail_div : 0;
         const int64_t bulk = g.nr - tail;
-        if (bulk * t / T < bulk * (t + 1) / T)
-            fn(g.r0 + bulk * t / T, g.r0 + bulk * (t + 1) / T, false);
+        if (bulk * t / plan.T < bulk * (t + 1) / plan.T)
+            fn(g.r0 + bulk * t / plan.T, g.r0 + bulk * (t + 1) / plan.T, false);
         const int64_t n_chunks = (tail + MMC_HOST_CHUNK - 1) / MMC_HOST_CHUNK;
-        for (int64_t c = t; c < n_chunks; c += T) {
+        for (int64_t c = t; c < n_chunks; c += plan.T) {
             const int64_t lo = g.r0 + bulk + c * MMC_HOST_CHUNK;
             fn(lo, std::min(lo + (int64_t)MMC_HOST_CHUNK, g.r0 + g.nr), true);
         }
@@ -407,14 +416,14 @@ struct Driver {
         MoveRec *cur = b->h_moves[buf];
         const MoveRec *prev = b->h_moves[buf ^ 1];
         const int mol = (int)(step % s.n_mol) + 1; // main.jl:490: `for i = 1:numbers.molecules`
-        if (devgen) { // the device draws the move; the host only says what became of the last one
+        if (plan.devgen) { // the device draws the move; the host only says what became of the last one
             for (int64_t r = lo; r < hi; r++) {
                 if (acc_prev[r])
                     b->s_cur[r] ^= s_flip; // main.jl:621
                 b->h_flags[r] = (uint8_t)((acc_prev[r] ? 1 : 0) | (b->s_cur[r] << 1));
                 kind[r] = (uint8_t)mmc_move_kind(chain_key(r), (uint64_t)(rng_off + step));
             }
-            if (b->bar_flags && !server && hi > lo) { // this thread's slice, straight into device memory
+            if (b->bar_flags && !plan.server && hi > lo) { // this thread's slice, straight into device memory
                 memcpy(b->bar_flags + lo, b->h_flags + lo, (size_t)(hi - lo));
                 mmc_bar_flush();
             }
@@ -449,12 +458,12 @@ struct Driver {
     {
         if (status.load() != MMC_OK)
             return false;
-        if (server && __atomic_load_n(b->h_timeout, __ATOMIC_ACQUIRE)) {
+        if (plan.server && __atomic_load_n(b->h_timeout, __ATOMIC_ACQUIRE)) {
             server_timeout_error();
             fail(MMC_ERR_HIP);
             return false;
         }
-        if (server && !server_async && std::chrono::steady_clock::now() - g.t_post > std::chrono::seconds(30)) {
+        if (plan.server && !server_async && std::chrono::steady_clock::now() - g.t_post > std::chrono::seconds(30)) {
             // e.g. a workgroup that never became resident because something else holds its
             // compute unit: give up; the epilogue posts "quit", which every workgroup honours
             // whenever it does start
@@ -466,7 +475,7 @@ struct Driver {
         const hipError_t q = hipStreamQuery(g.launched_on ? g.launched_on : g.stream); // (any thread: hipStreamQuery is thread-safe)
         if (q == hipErrorNotReady)
             return true;
-        if (q == hipSuccess && server) { // the server has ended before its run: it gave up or failed
+        if (q == hipSuccess && plan.server) { // the server has ended before its run: it gave up or failed
             mmc_set_error("the persistent move server ended before the run did");
             fail(MMC_ERR_HIP);
             return false;
@@ -485,17 +494,15 @@ struct Driver {
     }
 
     // ---- thread 0 only: the calls that enqueue or wait on streams ---------------------------
-    int32_t read_timing(Group &g, mmc_run_stats &st, int slot = -1)
+    int32_t read_timing(Group &g, mmc_run_stats &st)
     {
-        bool &timed = slot >= 0 ? g.timed_of[slot] : g.timed;
-        if (timed) {
+        if (g.timed) {
             float ms = 0.f;
-            hipEvent_t e0 = slot >= 0 ? g.evs[slot][0] : g.ev0, e1 = slot >= 0 ? g.evs[slot][1] : g.ev1;
-            MMC_HIP(hipEventSynchronize(e1));
-            MMC_HIP(hipEventElapsedTime(&ms, e0, e1));
+            MMC_HIP(hipEventSynchronize(g.ev1));
+            MMC_HIP(hipEventElapsedTime(&ms, g.ev0, g.ev1));
             st.kernel_ms += ms;
             st.timed_launches++;
-            timed = false;
+            g.timed = false;
         }
         return MMC_OK;
     }
@@ -503,7 +510,7 @@ struct Driver {
     int32_t launch(Group &g, int64_t step, mmc_run_stats &st, hipStream_t on = nullptr)
     {
         g.launched_on = on ? on : g.stream;
-        if (server) { // no launch: one control word per replica of the group
+        if (plan.server) { // no launch: one control word per replica of the group
             const bool new_steps = step == 0 || (adjust && step % b->sys.n_mol == 0);
             g.n_launch++;
             g.timed = false;
@@ -520,7 +527,7 @@ struct Driver {
         }
         // ev0 is recorded between the H2D copy and the kernel: ev0..ev1 brackets the kernel only
         DevGen dg{};
-        if (devgen) {
+        if (plan.devgen) {
             const int64_t n_mol = b->sys.n_mol, i0 = step % n_mol;
             dg.seed = p->seed;
             dg.replica0 = p->replica0;
@@ -529,7 +536,7 @@ struct Driver {
             dg.upload_steps = step == 0 || (adjust && i0 == 0);
             if (step >= g.gen_end) { // generate the next run of records (see k_propose)
                 int64_t k = n_mol - 1 < 1 ? 1 : n_mol - 1;
-                if (k > gen_max) k = gen_max;
+                if (k > plan.gen_max) k = plan.gen_max;
                 if (k > p->n_steps - step) k = p->n_steps - step;
                 if (adjust && k > n_mol - i0) k = n_mol - i0; // step sizes change between sweeps
                 dg.n_gen = (int)k;
@@ -544,26 +551,19 @@ struct Driver {
         g.timed = p->time_kernels > 0
                   && (g.n_launch - 1) % (unsigned)p->time_kernels == (unsigned)p->time_kernels / 2;
         g.stamp = ++b->stamp;
-        if (devacc) { // the launch of this parity: its own stamp, events and result slot
-            const int64_t n_sub = std::min<int64_t>(K, p->n_steps - step); // (K == 1: a step per launch)
-            const int slot = (int)((step / K) & 1);
-            g.stamp_of[slot] = g.stamp;
-            g.timed_of[slot] = g.timed;
+        DevDecide dd{};
+        if (plan.devacc) { // the launch's records go to the half of d_parts of its parity
+            const int64_t n_sub = std::min<int64_t>(plan.K, p->n_steps - step); // (K == 1: a step per launch)
+            const int slot = (int)((step / plan.K) & 1);
             const size_t gi = (size_t)(&g - groups.data());
-            DevDecide dd{ b->d_decide, rng_off + step, b->d_parts + (size_t)slot * b->sys.R, step == 0, (int)n_sub,
-                          n_sub > 1 ? b->d_queue + MMC_QUEUE_STRIDE * gi : nullptr, b->queue_base[gi] };
+            dd = DevDecide{ b->d_decide, rng_off + step, b->d_parts + (size_t)slot * b->sys.R, step == 0, (int)n_sub,
+                            n_sub > 1 ? b->d_queue + MMC_QUEUE_STRIDE * gi : nullptr, b->queue_base[gi] };
             if (n_sub > 1)
-                b->queue_base[gi] += (unsigned)(g.nr * P); // (what the launch takes: wave_ticket)
-            MMC_TRY(batch_launch(b, g.launched_on, g.r0, g.nr, P, g.buf, step > 0, pp,
-                                 g.timed ? g.evs[slot][0] : nullptr, &dg, g.stamp, &dd));
-            if (g.timed)
-                MMC_HIP(hipEventRecord(g.evs[slot][1], g.launched_on));
-            g.timed = false;
-            st.launches++;
-            return MMC_OK;
+                b->queue_base[gi] += (unsigned)(g.nr * plan.P); // (what the launch takes: wave_ticket)
         }
-        MMC_TRY(batch_launch(b, g.launched_on, g.r0, g.nr, P, g.buf, g.has_prev, pp,
-                             g.timed ? g.ev0 : nullptr, devgen ? &dg : nullptr, g.stamp));
+        // (step > 0: a launch of this group has completed before, its proposals are outstanding)
+        MMC_TRY(batch_launch(b, g.launched_on, g.r0, g.nr, plan.P, g.kernel, g.buf, step > 0, pp,
+                             g.timed ? g.ev0 : nullptr, plan.devgen ? &dg : nullptr, g.stamp, plan.devacc ? &dd : nullptr));
         if (g.timed)
             MMC_HIP(hipEventRecord(g.ev1, g.launched_on));
         st.launches++;
@@ -583,7 +583,7 @@ struct Driver {
             b->h_accept[r] = acc_prev[r];
             if (acc_prev[r]) {
                 b->s_cur[r] ^= s_flip;
-                if (!devgen)
+                if (!plan.devgen)
                     batch_mirror_commit(b, r, prev[r]);
             }
         }
@@ -592,7 +592,7 @@ struct Driver {
     {
         // (not waited for here: run_impl synchronises every group's stream once, after the last)
         return batch_settle_range(b, g.stream, g.r0, g.nr,
-                                  devgen ? batch_ring_slot(b, p->n_steps - 1) : b->dev_moves(g.buf), false);
+                                  plan.devgen ? batch_ring_slot(b, p->n_steps - 1) : b->dev_moves(g.buf), false);
     }
     // the move server applied the last accepted moves itself when it was told to quit
     void settle_server(Group &g)
@@ -636,13 +636,13 @@ struct Driver {
     {
         mmc_run_stats st{}; // (a copy: the threads' entries of tstats share cache lines)
         const int64_t R = b->sys.R, n_steps = p->n_steps;
-        const int64_t lo = R * t / T, hi = R * (t + 1) / T;
+        const int64_t lo = R * t / plan.T, hi = R * (t + 1) / plan.T;
         if (hi <= lo)
             return;
         const size_t n = (size_t)(hi - lo);
         std::vector<int64_t> step(n, 0);
         std::vector<int> q_done(n, 0);
-        std::vector<PartOut> parts(n * P);
+        std::vector<PartOut> parts(n * plan.P);
         // this thread's slice of the per-replica arrays (see RepView); written back when it is done
         std::vector<uint8_t> l_acc(n, 0), l_kind(n, 0), l_scur(b->s_cur.begin() + lo, b->s_cur.begin() + hi),
             l_flags(n, 0);
@@ -675,12 +675,12 @@ struct Driver {
                 if (sr >= n_steps)
                     continue;
                 const unsigned want = (server_stamp0 + (unsigned)sr + 1u) & MMC_STAMP_MASK;
-                const int c = collect(r, want, &parts[(size_t)(r - lo) * P], q_done[r - lo], st);
+                const int c = collect(r, want, &parts[(size_t)(r - lo) * plan.P], q_done[r - lo], st);
                 if (c < 0)
                     return;
                 if (c == 0)
                     continue;
-                decide(r, &parts[(size_t)(r - lo) * P], sr, st, v);
+                decide(r, &parts[(size_t)(r - lo) * plan.P], sr, st, v);
                 q_done[r - lo] = 0;
                 sr++;
                 any = true;
@@ -725,15 +725,12 @@ struct Driver {
     // cost the second launch 6 ms of host time).  Device-side decisions: see below.
     // thread_main skips the launch of step 0 for the groups launched here.
     int prelaunched = 0; // groups whose step 0 is already in flight
-    bool no_tail_share = true; int tail_div = 8; // (developer: MMC_TAIL_DIV = 0 / n)
-    double launch_at = 0.5;     // device-side decisions: share of the other group's launch that has come back when a group's next is enqueued
-    int run_ahead = 0;          // device-side decisions: launches of a group enqueued beyond the one whose records are being read
     mmc_run_stats pre_st{};
     void prelaunch()
     {
-        if (!devgen || server || p->n_steps < 1 || (!devacc && getenv("MMC_NO_PRELAUNCH")))
+        if (!plan.devgen || plan.server || p->n_steps < 1)
             return;
-        const int G = devacc ? (int)groups.size() : 1;
+        const int G = plan.devacc ? (int)groups.size() : 1;
         for (int gi = 0; gi < G; gi++) { // (the flag bytes of every group the kernel will decide for)
             const Group &g = groups[gi];
             for (int64_t r = g.r0; r < g.r0 + g.nr; r++)
@@ -744,10 +741,8 @@ struct Driver {
         if (b->bar_flags)
             mmc_bar_flush();
         Group &g = groups[0];
-        int32_t rc = launch(g, 0, pre_st); // (the first group's; where the kernel decides the others
-                                           // follow when this one is under way: thread_main_devacc)
-        if (rc == MMC_OK && devacc && p->n_steps > K && run_ahead)
-            rc = launch(g, K, pre_st);
+        const int32_t rc = launch(g, 0, pre_st); // (the first group's; where the kernel decides the others
+                                                 // follow when this one is under way: thread_main_devacc)
         if (rc != MMC_OK) {
             fail(rc);
             return;
@@ -759,13 +754,29 @@ struct Driver {
 
     // ---- device-side decisions ------------------------------------------------------------------
     // The move kernel decides (DecideConsts): a chain's next step needs nothing from the host, and
-    // the host is not between two launches any more.  Every group has TWO launches enqueued on its
-    // stream, steps s and s + 1 (stream order is the chain's order); their result records go to two
-    // slots.  Iteration (s, group): the threads do the bookkeeping of step s - 1 from its records --
-    // energies, counts, the S-buffer bit; the decision is the record's -- and thread 0 enqueues
-    // step s + 1, into the slot just read.  The GPU waits for the host only if the host falls a
-    // whole launch behind.  (With the decision on the host, a group's next launch waited for the
-    // host's pass over 32768 records: ~220 of the 235 us a launch takes, eight threads.)
+    // the host is not between two launches any more.  Every group has ONE launch in flight, K steps
+    // of its chains; launches of even and odd number write the two halves of the result records in
+    // turn.  Iteration (l, group): the threads do the bookkeeping of launch l - 1 from its records --
+    // energies, counts, the S-buffer bit; the decisions are the record's -- and thread 0 enqueues
+    // launch l, at once (one group) or when the next group's launch is half back (launch_held).
+    // (With the decision on the host, a group's next launch waited for the host's pass over 32768
+    // records: ~220 of the 235 us a launch takes, eight threads.)
+    //
+    // One stamp, one `timed` and one pair of events per group are enough, because every read of them
+    // is ordered after the write it means and before the next.  Thread 0 alone writes them, in
+    // launch(); all threads read g.stamp in metropolis, thread 0 reads the rest in read_timing.
+    //  - Launch 0 of group 0 is written by prelaunch() before the pool starts the threads; launch 0 of
+    //    the other groups by thread 0 before its first bar.wait.  Every read is behind that barrier.
+    //  - Group g's stamp is read only between the two barriers of an iteration (l, g), and launch l of
+    //    g is enqueued only after the second of them, where read_timing has taken launch l - 1's
+    //    events.  One group: thread 0 enqueues it right there, before it reaches the first barrier of
+    //    iteration (l + 1, g), behind which the next reads are.  Several groups: it is held and
+    //    enqueued by launch_held() between the barriers of the NEXT group's iteration, in which the
+    //    threads read that other group's stamp and nobody g's; thread 0 again arrives at the first
+    //    barrier of (l + 1, g) only afterwards.  (The held launch is never the group's whose
+    //    iteration it is enqueued in: it is set after one group's iteration and gone after the next.)
+    //  - What a wrong stamp would do is not a hang: still_running ends every spin on a stream that
+    //    has drained without the awaited stamp.
     void thread_main_devacc(int t, mmc_run_stats &st)
     {
         int sense = 0;
@@ -779,6 +790,7 @@ struct Driver {
         // set that timing by accident).  So the launch waits, on the host, until `launch_at` of
         // the other group's launch in flight has come back: thread 0 looks at one record of it
         // before it starts on its own share.  (`held`: the launch that waits, -1 = none.)
+        constexpr double launch_at = 0.5;
         int64_t held_step = -1;
         int held_group = -1;
         auto launch_held = [&]() {
@@ -792,7 +804,7 @@ struct Driver {
             }
             held_group = -1;
         };
-        const int64_t n_l = (n_steps + K - 1) / K; // launches per group: launch l takes steps [l K, (l + 1) K)
+        const int64_t n_l = (n_steps + plan.K - 1) / plan.K; // launches per group: launch l takes steps [l K, (l + 1) K)
         // The other groups' first launches: when the first group's is under way -- its first record
         // is back, so all its workgroups are resident and working (a launch that starts while another
         // is still being dispatched shares the compute units with it for its whole length, and two
@@ -801,7 +813,7 @@ struct Driver {
         // on the GPU for the first one's workgroups to leave.
         if (t == 0 && G > 1) {
             const Group &g0 = groups[0];
-            const unsigned want = g0.stamp_of[0] & MMC_STAMP_MASK;
+            const unsigned want = g0.stamp & MMC_STAMP_MASK;
             const PartOut *rec = &b->h_parts[g0.r0];
             for (unsigned spins = 1; part_stamp_of(*(const volatile int32_t *)&rec->ovl[1]) != want; spins++) {
                 if (((spins & 0xffff) == 0 && !still_running(g0)) || status.load(std::memory_order_relaxed) != MMC_OK)
@@ -810,9 +822,7 @@ struct Driver {
                     mmc_cpu_relax();
             }
             for (int gi = 1; gi < G && status.load() == MMC_OK; gi++) {
-                int32_t rc = launch(groups[gi], 0, st);
-                if (rc == MMC_OK && n_steps > K && run_ahead)
-                    rc = launch(groups[gi], K, st);
+                const int32_t rc = launch(groups[gi], 0, st);
                 if (rc != MMC_OK) fail(rc);
                 if (trace_t.capacity() > trace_t.size())
                     trace_t.push_back(now_us());
@@ -821,12 +831,12 @@ struct Driver {
         for (int64_t l = 1; l <= n_l; l++) {
             for (int gi = 0; gi < G; gi++) {
                 Group &g = groups[gi];
-                bar.wait(sense); // thread 0 has enqueued launch l - 1 of this group long ago
-                const int slot = (int)((l - 1) & 1);
-                const int64_t s0 = (l - 1) * K;
+                bar.wait(sense); // thread 0 has enqueued launch l - 1 of this group (g.stamp is set)
+                const int slot = (int)((l - 1) & 1); // (the half of the records it wrote: launch())
+                const int64_t s0 = (l - 1) * plan.K;
                 if (t == 0 && held_group >= 0) { // (thread 0 only knows `held`)
                     const int64_t probe = g.r0 + (int64_t)(launch_at * (double)(g.nr - 1));
-                    const unsigned want = g.stamp_of[slot] & MMC_STAMP_MASK;
+                    const unsigned want = g.stamp & MMC_STAMP_MASK;
                     const PartOut *rec = &b->h_parts[(size_t)slot * b->sys.R + probe];
                     for (unsigned spins = 1; part_stamp_of(*(const volatile int32_t *)&rec->ovl[1]) != want; spins++) {
                         if (((spins & 0xffff) == 0 && !still_running(g)) || status.load(std::memory_order_relaxed) != MMC_OK)
@@ -842,18 +852,16 @@ struct Driver {
                         if (l == n_l)
                             settle_slice(g, lo, hi);
                     });
-                bar.wait(sense); // launch l - 1's records are consumed: their slot is free
+                bar.wait(sense); // launch l - 1's records are consumed: the group's next may be enqueued
                 if (t == 0) {
                     if (status.load() == MMC_OK) {
-                        int32_t rc = read_timing(g, st, slot);
+                        int32_t rc = read_timing(g, st);
                         if (rc != MMC_OK) fail(rc);
                     }
-                    g.has_prev = true;
-                    if (l + run_ahead < n_l) {
-                        launch_held(); // (one group: nothing to wait for)
+                    if (l < n_l) { // (nothing is held here: what was has been enqueued in this iteration)
                         held_group = gi;
-                        held_step = (l + run_ahead) * K;
-                        if (G < 2 || launch_at <= 0.0)
+                        held_step = l * plan.K;
+                        if (G < 2) // one group: nothing to wait for
                             launch_held();
                     }
                     if (l == n_l && status.load() == MMC_OK) {
@@ -873,7 +881,7 @@ struct Driver {
             fail(MMC_ERR_HIP);
         if (!entry_t.empty())
             entry_t[t] = now_us();
-        if (server) {
+        if (plan.server) {
             server_thread_main(t);
             return;
         }
@@ -883,7 +891,7 @@ struct Driver {
         };
         mmc_run_stats st{}; // (a copy, written back on the way out: the threads' entries of tstats share cache lines)
         struct Back { mmc_run_stats &dst, &src; ~Back() { dst = src; } } back{ tstats[t], st };
-        if (devacc) {
+        if (plan.devacc) {
             thread_main_devacc(t, st);
             return;
         }
@@ -913,10 +921,8 @@ struct Driver {
                         int32_t rc = read_timing(g, st);
                         if (rc != MMC_OK) fail(rc);
                     }
-                    if (s > 0) {
+                    if (s > 0)
                         g.buf ^= 1 * (s < n_steps ? 1 : 0); // the new proposals' buffer
-                        g.has_prev = true;
-                    }
                     if (s == n_steps && status.load() == MMC_OK) {
                         int32_t rc = settle_enqueue(g);
                         if (rc != MMC_OK) fail(rc);
@@ -1015,165 +1021,167 @@ struct WorkerPool {
 
 } // namespace
 
-static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
-                        mmc_chain *chains, int32_t adjust, mmc_run_stats *stats)
+// What the call will do (RunPlan), from the batch's options and the call's parameters alone: no HIP
+// call, no allocation, nothing written into *b.  Every requirement on the shape of a call is here.
+static int32_t run_plan(const mmc_batch *b, const mmc_run_params *p, bool chains, int adjust, RunPlan *out)
 {
-    BATCH_CHECK(b);
-    BATCH_USABLE(b);
-    BATCH_NO_VOLUME_TRIAL(b);
-    MMC_REQUIRE(p && (energies || chains) && stats, MMC_ERR_ARG, "NULL argument");
-    MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
-    MMC_REQUIRE(p->temperature > 0 && p->n_steps >= 0, MMC_ERR_ARG, "bad run parameters");
-    BATCH_S_FRESH(b, "mmc_batch_run");
+    const DeviceSystem &s = b->sys;
+    const int64_t R = s.R;
     const bool wolf = b->coulomb_style == MMC_COULOMB_WOLF;
+    RunPlan pl;
     MMC_REQUIRE(!b->quat_mode || b->device_moves, MMC_ERR_UNSUPPORTED,
                 "orientations are set (mmc_batch_set_orientations): the quaternion move generation "
                 "runs on the device only, set option device_moves = 1");
-    DeviceSystem &s = b->sys;
-    const int64_t R = s.R;
-    int G = p->n_groups < 1 ? 1 : p->n_groups;
-    if (G > R) G = (int)R;
-    if (G > MMC_MAX_GROUPS) G = MMC_MAX_GROUPS;
-    memset(stats, 0, sizeof(*stats));
-    if (p->n_steps == 0)
+    pl.G = p->n_groups < 1 ? 1 : p->n_groups;
+    if (pl.G > R) pl.G = (int)R;
+    if (pl.G > MMC_MAX_GROUPS) pl.G = MMC_MAX_GROUPS;
+    if (p->n_steps == 0) { // (nothing will run: nothing more is asked of the call)
+        *out = pl;
         return MMC_OK;
-
-    Driver d;
-    d.b = b; d.p = p; d.energies = energies; d.chains = chains; d.adjust = adjust;
-    d.devgen = b->device_moves != 0;
-    d.temps = b->temps.empty() ? nullptr : b->temps.data();
-    d.s_flip = wolf ? 0 : 1;
-    d.rng_off = b->steps_done;
-    d.inject_left.store(b->inject_torn);
-    if (d.devgen) {
-        for (int64_t r = 0; r < R; r++)
-            b->h_steps[r] = chains ? make_double2(chains[r].dr_max, chains[r].dphi_max)
-                                   : make_double2(p->dr_max, p->dphi_max);
-        b->mirror_valid = false; // the host copy of the coordinates is not maintained
-        MMC_TRY(batch_ensure_ring(b));
-    } else
-        MMC_TRY(batch_refresh_mirror(b));
-    d.P = p->n_parts > 0 ? p->n_parts : b->n_parts;
+    }
+    pl.devgen = b->device_moves != 0;
+    pl.P = p->n_parts > 0 ? p->n_parts : b->n_parts;
     if (b->kernel == 4) { // parts are waves, four to a workgroup; the host sees one record per workgroup
         if (p->n_parts <= 0) { // sixteen, or as many as the system's size asks for
-            d.P = 16;
-            while (d.P < LAT_MAX_PARTS && !lat_applies(d.P, (int)s.n_mol, (int)s.nkvecs))
-                d.P += LAT_WAVES;
+            pl.P = 16;
+            while (pl.P < LAT_MAX_PARTS && !lat_applies(pl.P, (int)s.n_mol, (int)s.nkvecs))
+                pl.P += LAT_WAVES;
         }
-        MMC_REQUIRE(lat_applies(d.P, (int)s.n_mol, (int)s.nkvecs), MMC_ERR_UNSUPPORTED,
+        MMC_REQUIRE(lat_applies(pl.P, (int)s.n_mol, (int)s.nkvecs), MMC_ERR_UNSUPPORTED,
                     "kernel 4 needs n_parts = 4, 8, ... %d with at most %d molecules per pair part",
                     LAT_MAX_PARTS, LAT_MAXMOL);
-        d.P /= LAT_WAVES;
-    } else if (d.P > MMC_MAX_PARTS) {
-        d.P = MMC_MAX_PARTS;
+        pl.P /= LAT_WAVES;
+    } else if (pl.P > MMC_MAX_PARTS) {
+        pl.P = MMC_MAX_PARTS;
     }
-    MMC_REQUIRE(!s.pb.on || d.devgen, MMC_ERR_UNSUPPORTED,
+    MMC_REQUIRE(!s.pb.on || pl.devgen, MMC_ERR_UNSUPPORTED,
                 "per-replica boxes: the trial moves are drawn on the device (device_moves = 1)");
     if (b->persistent != 0 && !s.pb.on && !wolf) { // small batches: the persistent move server (one box, Ewald style)
-        d.server = batch_server_applies(b) && (b->persistent == 1 || R <= MMC_SERVER_AUTO_MAX);
-        MMC_REQUIRE(d.server || b->persistent != 1, MMC_ERR_UNSUPPORTED,
+        pl.server = batch_server_applies(b) && (b->persistent == 1 || R <= MMC_SERVER_AUTO_MAX);
+        MMC_REQUIRE(pl.server || b->persistent != 1, MMC_ERR_UNSUPPORTED,
                     "the persistent move server needs device_moves = 1, the table kernel, no "
                     "orientations and at most one replica per compute unit");
-        if (d.server) { // the parts are waves of one workgroup: the host sees one record
-            d.server_waves = p->n_parts > 1 ? (p->n_parts > SRV_WAVES ? SRV_WAVES : p->n_parts)
-                                            : batch_server_parts(s.n_mol, R);
-            d.P = 1;
+        if (pl.server) { // the parts are waves of one workgroup: the host sees one record
+            pl.server_waves = p->n_parts > 1 ? (p->n_parts > SRV_WAVES ? SRV_WAVES : p->n_parts)
+                                             : batch_server_parts(s.n_mol, R);
+            pl.P = 1;
             // few replicas: the latency server, several workgroups per replica, one record each
-            int G = batch_lat_shape(b);
+            int wgs = batch_lat_shape(b);
             if (p->n_parts > 1 && b->server_wgs != 0) { // an explicit part count picks the shape
-                G = (p->n_parts % LAT_WAVES == 0 && lat_applies(p->n_parts, (int)s.n_mol, (int)s.nkvecs)
-                     && R * (p->n_parts / LAT_WAVES) <= (int64_t)b->n_cus && b->kernel == 4)
-                        ? p->n_parts / LAT_WAVES : (b->kernel == 4 ? -1 : 0);
-                MMC_REQUIRE(G >= 0, MMC_ERR_UNSUPPORTED,
+                wgs = (p->n_parts % LAT_WAVES == 0 && lat_applies(p->n_parts, (int)s.n_mol, (int)s.nkvecs)
+                       && R * (p->n_parts / LAT_WAVES) <= (int64_t)b->n_cus && b->kernel == 4)
+                          ? p->n_parts / LAT_WAVES : (b->kernel == 4 ? -1 : 0);
+                MMC_REQUIRE(wgs >= 0, MMC_ERR_UNSUPPORTED,
                             "kernel 4 with the move server needs n_parts = 8, 12, ... %d (a multiple of 4 whose "
                             "pair parts hold at most %d molecules each)", LAT_MAX_PARTS, LAT_MAXMOL);
             }
-            if (G >= 2) {
-                d.server_lat_wgs = G;
-                d.server_waves = LAT_WAVES * G;
-                d.P = G;
+            if (wgs >= 2) {
+                pl.server_lat_wgs = wgs;
+                pl.server_waves = LAT_WAVES * wgs;
+                pl.P = wgs;
             }
         }
     }
-    d.T = p->n_threads > 0 ? p->n_threads : 1;
-    if (d.T > 64) d.T = 64;
-    d.bar.n = d.T;
-    d.pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
-    d.groups.resize(G);
-    for (int g = 0; g < G; g++) {
-        d.groups[g].r0 = R * g / G;
-        d.groups[g].nr = R * (g + 1) / G - d.groups[g].r0;
-        // Streams.  Host proposals: one stream per group, so that a group's H2D copy of its move
-        // records overlaps the other group's kernel.  Device proposals: nothing but a flag byte
-        // per replica is copied; the groups alternate between TWO streams, so that the start of
-        // one launch -- 5120 waves that all load their move record, then all build phase tables,
-        // ... in step -- overlaps the end of the other, whose waves have long drifted apart:
-        // 1.30e8 moves/s against 1.22e8 with every launch alone on the GPU (65536 chains of 750
-        // molecules, round 4).  A launch's own span then says less than its cost: see
-        // mmc_run_stats.kernel_ms.  (p->n_streams overrides.)
-        const int n_streams = p->n_streams > 0 ? p->n_streams : (b->device_moves ? (G < 2 ? G : 2) : G);
-        // streams and events live as long as the batch: creating and destroying them costs ~3 ms
-        // per call, a fifth of a 20-step run
-        if (g >= n_streams) {
-            d.groups[g].stream = d.groups[g % n_streams].stream;
-        } else {
-            if (!b->run_streams[g])
-                MMC_HIP(hipStreamCreateWithFlags(&b->run_streams[g], hipStreamNonBlocking));
-            d.groups[g].stream = b->run_streams[g];
-        }
-        if (p->time_kernels) {
-            for (int k = 0; k < 4; k++)
-                if (!b->run_events[g][k])
-                    MMC_HIP(hipEventCreate(&b->run_events[g][k]));
-            d.groups[g].ev0 = b->run_events[g][0];
-            d.groups[g].ev1 = b->run_events[g][1];
-            for (int k = 0; k < 4; k++)
-                d.groups[g].evs[k / 2][k % 2] = b->run_events[g][k];
-        }
-    }
+    pl.T = p->n_threads > 0 ? p->n_threads : 1;
+    if (pl.T > 64) pl.T = 64;
+    // Streams.  Host proposals: one stream per group, so that a group's H2D copy of its move
+    // records overlaps the other group's kernel.  Device proposals: nothing but a flag byte
+    // per replica is copied; the groups alternate between TWO streams, so that the start of
+    // one launch -- 5120 waves that all load their move record, then all build phase tables,
+    // ... in step -- overlaps the end of the other, whose waves have long drifted apart:
+    // 1.30e8 moves/s against 1.22e8 with every launch alone on the GPU (65536 chains of 750
+    // molecules, round 4).  A launch's own span then says less than its cost: see
+    // mmc_run_stats.kernel_ms.  (p->n_streams overrides.)
+    pl.n_streams = p->n_streams > 0 ? p->n_streams : (pl.devgen ? (pl.G < 2 ? pl.G : 2) : pl.G);
     // Who decides: the move kernel itself where it holds the whole move (one part, the wave kernel)
     // and draws it (device-side proposals); the host otherwise -- parts that only the host adds up,
     // the caller's proposals, the move server, and chains whose step sizes the host adapts between
     // sweeps (the launches are enqueued a step ahead of the host's bookkeeping).
-    d.devacc = d.devgen && !d.server && d.P == 1 && !b->zero_copy_moves && !(chains && adjust);
+    pl.devacc = pl.devgen && !pl.server && pl.P == 1 && !b->zero_copy_moves && !(chains && adjust);
     int64_t nr_max = 0;
-    for (const Group &g : d.groups) {
-        d.devacc = d.devacc && batch_kernel_for(b, g.nr, d.P) == 2;
-        nr_max = std::max(nr_max, g.nr);
-    }
-    {   // (developer: MMC_DEVICE_ACCEPT / MMC_HOST_ACCEPT override the option)
-        int want = b->accept_on_device;
-        if (getenv("MMC_DEVICE_ACCEPT")) want = 1;
-        if (getenv("MMC_HOST_ACCEPT")) want = 0;
-        // by size: where a launch can take several steps (below) the kernel decides; for one step
-        // per launch only where a thread's pass over more than 4096 records would outlast the launch
-        const bool multi_ok = !chains && b->trace_steps == 0 && s.n_mol > MMC_GEN_MAX && b->steps_per_launch != 1;
-        if (want < 0)
-            want = (multi_ok || nr_max > (int64_t)4096 * d.T) ? 1 : 0;
-        d.devacc = d.devacc && want == 1;
+    for (int g = 0; g < pl.G; g++) {
+        auto &pg = pl.group[g];
+        pg.r0 = R * g / pl.G;
+        pg.nr = R * (g + 1) / pl.G - pg.r0;
+        pg.kernel = batch_kernel_for(b, pg.nr, pl.P);
+        pl.devacc = pl.devacc && pg.kernel == 2;
+        pl.cand = pl.cand || (!pl.server && pl.P == 1 && pg.kernel == 2);
+        nr_max = std::max(nr_max, pg.nr);
     }
     // ... and how many steps a launch takes: one record per replica and launch then, so only where
     // the caller asked for energies and counts (no per-chain averages, no trace of single steps),
     // and where a burst of device-made proposals covers them (n_mol > MMC_GEN_MAX).
-    d.K = 1;
-    if (d.devacc && !chains && b->trace_steps == 0 && s.n_mol > MMC_GEN_MAX) {
-        d.K = b->steps_per_launch > 0 ? b->steps_per_launch : 8;
-        if (const char *e = getenv("MMC_STEPS_PER_LAUNCH"))
-            d.K = atoi(e);
-        if (d.K != 1 && d.K != 2 && d.K != 4 && d.K != 8 && d.K != 16)
-            d.K = 1;
+    const bool multi_ok = !chains && b->trace_steps == 0 && s.n_mol > MMC_GEN_MAX;
+    // by size (option "accept_on_device" < 0): where a launch can take several steps the kernel
+    // decides; for one step per launch only where a thread's pass over more than 4096 records would
+    // outlast the launch
+    const int want = b->accept_on_device >= 0 ? b->accept_on_device
+                                              : ((multi_ok && b->steps_per_launch != 1) || nr_max > (int64_t)4096 * pl.T);
+    pl.devacc = pl.devacc && want == 1;
+    if (pl.devacc && multi_ok) {
+        pl.K = b->steps_per_launch > 0 ? b->steps_per_launch : 8;
+        if (pl.K != 1 && pl.K != 2 && pl.K != 4 && pl.K != 8 && pl.K != 16)
+            pl.K = 1;
         // A whole call in ONE launch per group (option "whole_call" = 1): K = the call's steps, as
         // many as a record carries and a burst of proposals may draw (n_mol - 1; the ring grows to
         // hold them).  Not taken by default: at the bench's 20-step call it ran 1.34 x 10^8 moves/s
         // against 1.40 for launches of eight, both with the queue of units (profiles/README.md,
         // "The 20-step call") -- one launch's tail is a whole 20-step unit long, and nothing covers it.
         if (b->whole_call == 1) {
-            d.K = (int)std::min<int64_t>(std::min<int64_t>(p->n_steps, MMC_STEPS_PER_LAUNCH_MAX), s.n_mol - 1);
-            d.gen_max = std::max(d.K, (int)MMC_GEN_MAX);
+            pl.K = (int)std::min<int64_t>(std::min<int64_t>(p->n_steps, MMC_STEPS_PER_LAUNCH_MAX), s.n_mol - 1);
+            pl.gen_max = std::max(pl.K, (int)MMC_GEN_MAX);
         }
     }
-    if (d.devacc) {
-        MMC_TRY(batch_ensure_ring(b, d.gen_max + 2));
+    pl.no_tail_share = !pl.devacc;
+    *out = pl;
+    return MMC_OK;
+}
+
+// Everything of a call that touches the device before its first launch, in this order: the step sizes
+// and the ring (or the host mirror), streams and events, what the kernel's own decision reads, the
+// candidate lists, the move server; then the driver's own arrays and the worker pool.
+static int32_t run_prepare(Driver &d)
+{
+    mmc_batch *b = d.b;
+    const mmc_run_params *p = d.p;
+    const RunPlan &pl = d.plan;
+    DeviceSystem &s = b->sys;
+    const int64_t R = s.R;
+    if (pl.devgen) {
+        for (int64_t r = 0; r < R; r++)
+            b->h_steps[r] = d.chains ? make_double2(d.chains[r].dr_max, d.chains[r].dphi_max)
+                                     : make_double2(p->dr_max, p->dphi_max);
+        b->mirror_valid = false; // the host copy of the coordinates is not maintained
+        MMC_TRY(batch_ensure_ring(b));
+    } else
+        MMC_TRY(batch_refresh_mirror(b));
+    d.bar.n = pl.T;
+    d.pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
+    d.groups.resize(pl.G);
+    for (int g = 0; g < pl.G; g++) {
+        Group &dg = d.groups[g];
+        dg.r0 = pl.group[g].r0;
+        dg.nr = pl.group[g].nr;
+        dg.kernel = pl.group[g].kernel;
+        // streams and events live as long as the batch: creating and destroying them costs ~3 ms
+        // per call, a fifth of a 20-step run
+        if (g >= pl.n_streams) {
+            dg.stream = d.groups[g % pl.n_streams].stream;
+        } else {
+            if (!b->run_streams[g])
+                MMC_HIP(hipStreamCreateWithFlags(&b->run_streams[g], hipStreamNonBlocking));
+            dg.stream = b->run_streams[g];
+        }
+        if (p->time_kernels) {
+            for (int k = 0; k < 2; k++)
+                if (!b->run_events[g][k])
+                    MMC_HIP(hipEventCreate(&b->run_events[g][k]));
+            dg.ev0 = b->run_events[g][0];
+            dg.ev1 = b->run_events[g][1];
+        }
+    }
+    if (pl.devacc) {
+        MMC_TRY(batch_ensure_ring(b, pl.gen_max + 2));
         DecideConsts dc{};
         dc.temperature = p->temperature; dc.factor = s.bv.factor;
         dc.seed = p->seed; dc.replica0 = (uint32_t)p->replica0;
@@ -1194,26 +1202,17 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
             MMC_HIP(hipMemcpy(b->d_decide, &dc, sizeof(dc), hipMemcpyHostToDevice));
             b->decide_host = dc;
         }
-        if (const char *e = getenv("MMC_RUN_AHEAD"))
-            d.run_ahead = atoi(e) ? 1 : 0;
-        if (const char *e = getenv("MMC_LAUNCH_AT")) // (developer: percent)
-            d.launch_at = std::min(1.0, std::max(0.0, atof(e) / 100.0));
     }
-    if (!d.server && d.P == 1) { // the wave kernel with one part per move: its candidate lists (mmc_cand.hpp)
-        bool wave = false;
-        for (const Group &g : d.groups)
-            wave = wave || batch_kernel_for(b, g.nr, d.P) == 2;
-        if (wave)
-            MMC_TRY(batch_cand_prepare(b, d.pp));
-    }
-    if (d.server) // the one kernel runs on the first group's stream: that is the stream to watch
+    if (pl.cand)
+        MMC_TRY(batch_cand_prepare(b, d.pp));
+    if (pl.server) { // the one kernel runs on the first group's stream: that is the stream to watch
         for (Group &g : d.groups)
             g.stream = d.groups[0].stream;
-    if (d.server)
-        MMC_TRY(batch_server_start(b, d.groups[0].stream, d.server_waves, d.pp, p->seed, p->replica0,
-                                   b->steps_done, d.server_lat_wgs));
-    d.rng.resize(d.devgen ? 0 : R); // (device-side proposals draw everything from Philox counters)
-    for (int64_t r = 0; r < (d.devgen ? 0 : R); r++) { // hash of (seed, global replica index, steps already run)
+        MMC_TRY(batch_server_start(b, d.groups[0].stream, pl.server_waves, d.pp, p->seed, p->replica0,
+                                   b->steps_done, pl.server_lat_wgs));
+    }
+    d.rng.resize(pl.devgen ? 0 : R); // (device-side proposals draw everything from Philox counters)
+    for (int64_t r = 0; r < (pl.devgen ? 0 : R); r++) { // hash of (seed, global replica index, steps already run)
         uint64_t h = p->seed;
         h = Rng::splitmix(h) ^ (p->replica0 + (uint64_t)r);
         h = Rng::splitmix(h) ^ (uint64_t)b->steps_done;
@@ -1223,27 +1222,12 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     d.kind.assign(R, 0);
     b->trace_delta.assign((size_t)(b->trace_steps * R), 0.0);
     b->trace_flags.assign((size_t)(b->trace_steps * R), 0);
-    d.tstats.assign(d.T, mmc_run_stats{});
-    if (d.server) { // one stamp per step, the same sequence for every replica (Driver::server_post_step)
+    d.tstats.assign(pl.T, mmc_run_stats{});
+    if (pl.server) { // one stamp per step, the same sequence for every replica (Driver::server_post_step)
         d.server_stamp0 = b->stamp;
         b->stamp += (unsigned)p->n_steps;
     }
-
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool run_trace = getenv("MMC_RUN_TRACE") != nullptr; // (developer: where a call's fixed cost goes)
-    const auto t_enter = t0;
-    if (run_trace) {
-        d.trace_t.reserve(64);
-        d.trace_t0 = t0;
-        d.entry_t.assign(d.T, 0.0);
-        d.mark_t.reserve(4 * 12);
-    }
-    d.no_tail_share = !d.devacc;
-    if (const char *e = getenv("MMC_TAIL_DIV")) {
-        d.no_tail_share = atoi(e) <= 0;
-        d.tail_div = atoi(e) > 0 ? atoi(e) : 8;
-    }
-    if (!b->pool) { // (before the clock of this call's statistics starts?  no: the first call pays for it)
+    if (!b->pool) { // (the first call pays for it)
         WorkerPool *w = new WorkerPool();
         w->device = s.device;
         if (const char *e = getenv("MMC_POOL_BLOCKTIME_US"))
@@ -1251,10 +1235,51 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         b->pool = w;
         b->pool_destroy = &WorkerPool::destroy;
     }
+    return MMC_OK;
+}
+
+static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
+                        mmc_chain *chains, int32_t adjust, mmc_run_stats *stats)
+{
+    BATCH_CHECK(b);
+    BATCH_USABLE(b);
+    BATCH_NO_VOLUME_TRIAL(b);
+    MMC_REQUIRE(p && (energies || chains) && stats, MMC_ERR_ARG, "NULL argument");
+    MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
+    MMC_REQUIRE(p->temperature > 0 && p->n_steps >= 0, MMC_ERR_ARG, "bad run parameters");
+    BATCH_S_FRESH(b, "mmc_batch_run");
+    memset(stats, 0, sizeof(*stats));
+    // ---- 1. what the call will do ----
+    RunPlan plan;
+    MMC_TRY(run_plan(b, p, chains != nullptr, adjust, &plan));
+    if (p->n_steps == 0)
+        return MMC_OK;
+    const int64_t R = b->sys.R;
+
+    // ---- 2. everything it needs on the device and the host, before the first launch ----
+    Driver d(plan);
+    d.b = b; d.p = p; d.energies = energies; d.chains = chains; d.adjust = adjust;
+    d.temps = b->temps.empty() ? nullptr : b->temps.data();
+    d.s_flip = b->coulomb_style == MMC_COULOMB_WOLF ? 0 : 1;
+    d.rng_off = b->steps_done;
+    d.inject_left.store(b->inject_torn);
+    MMC_TRY(run_prepare(d));
+
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool run_trace = getenv("MMC_RUN_TRACE") != nullptr; // (developer: where a call's fixed cost goes)
+    const auto t_enter = t0;
+    if (run_trace) {
+        d.trace_t.reserve(64);
+        d.trace_t0 = t0;
+        d.entry_t.assign(plan.T, 0.0);
+        d.mark_t.reserve(4 * 12);
+    }
+    // ---- 3. the run: the first launch from this thread, then the threads ----
     d.prelaunch();
-    static_cast<WorkerPool *>(b->pool)->run(&d, d.T);
+    static_cast<WorkerPool *>(b->pool)->run(&d, plan.T);
+    // ---- 4. finish: release the server, wait for the last commits, add up, leave the batch's state right ----
     const auto t_join = std::chrono::steady_clock::now();
-    if (d.server) { // release the server whatever happened: last accept decisions + quit
+    if (plan.server) { // release the server whatever happened: last accept decisions + quit
         for (int64_t r = 0; r < R; r++)
             batch_server_post(b, r, p->n_steps + 1, 0u,
                               SRV_QUIT | (d.status.load() == MMC_OK && d.acc_prev[r] ? SRV_ACCEPT : 0u));
@@ -1280,7 +1305,7 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
     int32_t status = d.status.load();
     auto t_enq = t_join;
     if (status == MMC_OK) { // (the commit of the last proposals is already enqueued: Driver::settle_enqueue)
-        if (d.server)
+        if (plan.server)
             for (Group &g : d.groups)
                 d.settle_server(g);
         t_enq = std::chrono::steady_clock::now();
@@ -1305,9 +1330,9 @@ static int32_t run_impl(mmc_batch *b, const mmc_run_params *p, double *energies,
         stats->timed_launches += w.timed_launches;
         stats->torn_records += w.torn_records;
     }
-    stats->server_steps = d.server ? p->n_steps : 0;
-    stats->device_decisions = d.devacc ? stats->moves : 0;
-    if (d.server) // control words are posted per replica as it goes: count what a lock-step driver would
+    stats->server_steps = plan.server ? p->n_steps : 0;
+    stats->device_decisions = plan.devacc ? stats->moves : 0;
+    if (plan.server) // control words are posted per replica as it goes: count what a lock-step driver would
         stats->launches = p->n_steps * (int64_t)d.groups.size();
     stats->wall_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     for (int64_t r = 0; r < R; r++)

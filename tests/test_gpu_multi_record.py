@@ -124,3 +124,52 @@ def test_overlaps_travel_through_the_record():
     assert sum(n_ovl) >= 1, n_ovl
     (_, _, st_d, _), (_, _, st_h, _) = runs("ewald-unwrapped-overlaps")
     assert st_d["overlaps"] == sum(n_ovl) and st_h["overlaps"] == sum(n_ovl), (st_d["overlaps"], n_ovl)
+
+
+# ---- kernel timing and launch counts -----------------------------------------------------------------
+# time_kernels = 1 brackets every launch of a group with the group's pair of events, on both driver
+# paths.  (n_groups, n_steps): launches of 8 + 8 + 4 per group, one group alone (its next launch is
+# enqueued at once, nothing is held back), exactly one launch per group (the last is the first) and a
+# single step.  Timing must change nothing but the timing fields.
+TIMING_SHAPES = [(2, 20), (1, 20), (2, 8), (2, 1)]
+TIMING_MODES = {"device": ON_DEVICE, "host": ON_HOST}
+
+
+def _run_timed(opts, n_groups, n_steps, time_kernels):
+    """One call on a fresh batch of the "ewald-unwrapped" case: energies, stats, final states."""
+    from metropolismontecarlo_amd import structs
+    from metropolismontecarlo_amd.device import Batch
+    a = common.nist_arrays(4, "unwrapped")
+    with Batch(R, a["com"], a["coords"], a["atype"], a["charge"], a["eps"], a["sig"], a["box"],
+               5.6 / a["box"], structs.factor, RCUT, RCUT) as b:
+        b.set_option("device_moves", 1)
+        for k, v in opts.items():
+            b.set_option(k, v)
+        e0 = b.potential_ewald(as_array=True)["energy"].copy()
+        e1, st = b.run(n_steps, T, DR, DPHI, seed=SEED, energies=e0, n_groups=n_groups, n_parts=1, n_threads=2,
+                       replica0=REPLICA0, time_kernels=time_kernels)
+        final = [b.get_replica(r) for r in range(R)]
+    return e1, st, final
+
+
+@pytest.mark.parametrize("n_groups,n_steps", TIMING_SHAPES)
+@pytest.mark.parametrize("mode", list(TIMING_MODES))
+def test_every_launch_is_timed_and_timing_changes_nothing(mode, n_groups, n_steps):
+    opts = TIMING_MODES[mode]
+    e_t, st_t, fin_t = _run_timed(opts, n_groups, n_steps, 1)
+    e_0, st_0, fin_0 = _run_timed(opts, n_groups, n_steps, 0)
+    # the kernel decides: launches of up to eight steps; the host decides: a launch per step
+    want = n_groups * ((n_steps + 7) // 8 if mode == "device" else n_steps)
+    print(mode, n_groups, n_steps, "launches", st_t["launches"], "timed", st_t["timed_launches"], "kernel_ms",
+          st_t["kernel_ms"])
+    assert st_t["launches"] == want and st_0["launches"] == want, (st_t, st_0)
+    assert st_t["device_decisions"] == (R * n_steps if mode == "device" else 0), st_t
+    assert st_t["timed_launches"] == st_t["launches"], st_t
+    assert st_t["kernel_ms"] > 0, st_t
+    assert st_0["timed_launches"] == 0 and st_0["kernel_ms"] == 0, st_0
+    assert [st_t[k] for k in COUNTS] == [st_0[k] for k in COUNTS], (st_t, st_0)
+    assert st_t["moves"] == R * n_steps, st_t
+    for r in range(R):
+        for x, y, what in zip(fin_t[r], fin_0[r], ("com", "coords", "S(k)")):
+            assert _same_bits(x, y), (mode, n_groups, n_steps, r, what)
+    assert _same_bits(e_t, e_0), (mode, n_groups, n_steps)   # timing changes no sum
