@@ -1872,6 +1872,108 @@ int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *sc
                                  double *du_out     /* [R][K][4] may be NULL */,
                                  double *base_out   /* [R][4]    may be NULL */);
 
+/* ---- Save and resume: bulk state records ------------------------------------------------------------
+ * Everything of a replica that the chains carry from one call to the next, as one fixed-size
+ * RECORD per replica, moved in bulk; and one mmc_state_info that describes the batch the records
+ * belong to.  The library moves records and checks that the receiving batch is ALREADY configured
+ * for them; configuring a fresh batch (mmc_batch_set_coulomb_style, _set_boxes, _set_temperatures,
+ * _set_orientations, _volume_change) and the file are the caller's (checkpoint.py, Batch.save /
+ * Batch.load).  No entry point here decides, proposes or evaluates a move.
+ *
+ * Guarantee: after mmc_batch_set_state of all R replicas into a batch of the same system, created
+ * from ANY coordinates and brought into the saved mode, every chain continues bit for bit (same
+ * energies, decisions, coordinates and S(k)) provided the resuming batch uses the same options
+ * `kernel`, parts, `persistent` / `server_wgs`, `steps_per_launch` and `half_k` -- the condition
+ * mmc_run_params::replica0 documents for shardings.  Options are not part of the state: the caller
+ * sets them, as at creation.  The caller also keeps what the batch never held: the running
+ * energies, the mmc_chain array, rung / attempt / accept and the exchange round, NPT statistics.
+ *
+ * mmc_state_info: 8-byte fields only, 42 of them (336 bytes).
+ *   identity (a mismatch is MMC_ERR_ARG: these records are not of this batch's system)
+ *     magic        MMC_STATE_MAGIC
+ *     version      MMC_STATE_VERSION
+ *     R            replicas of the batch that wrote the info
+ *     n_mol        molecules per replica (3 atoms each)
+ *     nkvecs       k-vectors the device holds: 293 with half_k, else 337
+ *     half_k       1 / 0
+ *     lj_rcut, qq_rcut
+ *     topology     FNV-1a (64 bit) over n_types, atype, charge, eps, sig as given to mmc_batch_create
+ *     nk, k_sq_max, factor
+ *   mode (a difference from how the batch is configured NOW is MMC_ERR_STATE)
+ *     coulomb_style, s_stale      mmc_batch_set_coulomb_style and whether S(k) awaits a rebuild
+ *     per_box      1: per-replica boxes (mmc_batch_set_boxes); alpha is compared only then
+ *     alpha
+ *     temps_on     1: per-replica temperatures are set
+ *     quat_mode    0 / 1 / 2 (mmc_batch_set_orientations); db[9] is compared only when not 0
+ *     db[9]
+ *     box, kappa   the shared box and kappa; compared only when per_box == 0
+ *   batch-level scalars (applied by mmc_batch_set_state)
+ *     steps_done   position of the random streams ("Random streams")
+ *     r_mol_max    bound on an atom's distance from its centre of mass (+inf: unknown)
+ *     rigid_only   1: every committed move was drawn on the device
+ *     reserved[10] zero
+ * Of the receiving batch, R may differ from info->R (a record range of another batch); everything
+ * else of the identity must agree. */
+#define MMC_STATE_MAGIC 0x31544154534d434dULL /* "MCMSTAT1" */
+#define MMC_STATE_VERSION 1
+typedef struct {
+    uint64_t magic;
+    int64_t version;
+    int64_t R, n_mol, nkvecs, half_k;
+    double lj_rcut, qq_rcut;
+    uint64_t topology;
+    int64_t nk, k_sq_max;
+    double factor;
+    int64_t coulomb_style, s_stale, per_box;
+    double alpha;
+    int64_t temps_on, quat_mode;
+    double db[9];
+    double box, kappa;
+    int64_t steps_done;
+    double r_mol_max;
+    int64_t rigid_only;
+    int64_t reserved[10];
+} mmc_state_info;
+
+/* The record of one replica, the single definition of the format (a pure host function: no device,
+ * no batch; it reads n_mol, nkvecs and quat_mode of `info`).  offsets[0..7], in bytes from the
+ * start of the record, every one a multiple of 8 and [3] .. [7] of 16:
+ *   [0] box          double: the replica's box (the shared box when per_box == 0)
+ *   [1] temperature  double: 0.0 when temps_on == 0
+ *   [2] flags        uint64: bit 0 per_box, bit 1 temps_on, bit 2 quat_mode != 0 (then 8 zero bytes)
+ *   [3] com          double [n_mol][3]      as mmc_batch_get_replica returns it
+ *   [4] coords       double [3 n_mol][3]    as mmc_batch_get_replica returns it
+ *   [5] S            double [nkvecs][2]     the buffer that is sumQExpOld, in DEVICE order (the
+ *                    order of mmc_get_kvectors of a batch with this half_k), bit for bit: the
+ *                    incrementally updated S(k), not a fresh sum
+ *   [6] quat         double [n_mol][4]      only when quat_mode != 0 (else [6] == [7])
+ *   [7] end of the data
+ * Sections are padded to 16 bytes and the record to *record_bytes, a multiple of 64; padding is 0.
+ * `info` points to an mmc_state_info (void * here and below: the Julia binding passes a Ref). */
+int32_t mmc_state_record_layout(const void *info, int64_t *offsets /* [8] */, int64_t *record_bytes);
+/* The info of the batch as it is configured now. */
+int32_t mmc_batch_state_info(mmc_batch *b, void *info /* mmc_state_info, out */);
+/* Pack replicas [r0, r0 + nr) on the device (k_state_pack) and deliver them to `records`, host
+ * memory of nr * record_bytes.  Changes nothing.  MMC_ERR_STATE while proposals are outstanding
+ * (mmc_batch_eval without mmc_batch_settle) or a volume trial is open.  Works in chunks of option
+ * "state_chunk" replicas (0: by a budget of 256 MiB of staging) through two pinned buffers: the
+ * pack of one chunk runs while the other is copied out.  Option "state_delivery": 1 = the kernels
+ * write and read the mapped pinned buffers themselves, 0 = device memory and a copy, -1 (default) =
+ * what measured faster for each call: 1 for mmc_batch_get_state, 0 for mmc_batch_set_state. */
+int32_t mmc_batch_get_state(mmc_batch *b, int64_t r0, int64_t nr, void *records);
+/* Validate `info` against the batch (identity: MMC_ERR_ARG; mode: MMC_ERR_STATE; a record whose
+ * box or temperature the batch's setters would refuse: MMC_ERR_ARG) -- nothing is changed on any
+ * refusal -- then unpack the records into replicas [r0, r0 + nr) (k_state_unpack): the SoA arrays,
+ * the per-molecule records and fixed-point centres of mass of homogeneous systems (with the
+ * replica's own box), the orientations; S(k) into BOTH buffers with buffer 0 current, the state
+ * mmc_batch_recip_long leaves; with per-replica boxes the box, kappa = alpha / box and the cfac row
+ * and erfc table of exactly these replicas; the temperature.  Applies the batch-level scalars
+ * (r_mol_max and rigid_only exactly when the range is the whole batch, else their weaker
+ * combination), marks the candidate lists and the host mirror stale, and after a failed run makes
+ * the batch usable again once every replica has been set.  Other replicas keep every bit. */
+int32_t mmc_batch_set_state(mmc_batch *b, const void *info /* mmc_state_info */, int64_t r0, int64_t nr,
+                            const void *records);
+
 /* ---- the one collective of a sharded run: RCCL over xGMI ---------------------
  * Replicas shard over GPUs with no data-path collective; what is reduced, once per block, is a
  * handful of observables (sums of energies and acceptance counters, the maximum of the elapsed

@@ -82,6 +82,17 @@ class NptStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class StateInfo(C.Structure):
+    """mmc_state_info: 8-byte fields only"""
+    _fields_ = [("magic", C.c_uint64), ("version", C.c_int64), ("R", C.c_int64), ("n_mol", C.c_int64),
+                ("nkvecs", C.c_int64), ("half_k", C.c_int64), ("lj_rcut", C.c_double), ("qq_rcut", C.c_double),
+                ("topology", C.c_uint64), ("nk", C.c_int64), ("k_sq_max", C.c_int64), ("factor", C.c_double),
+                ("coulomb_style", C.c_int64), ("s_stale", C.c_int64), ("per_box", C.c_int64), ("alpha", C.c_double),
+                ("temps_on", C.c_int64), ("quat_mode", C.c_int64), ("db", C.c_double * 9), ("box", C.c_double),
+                ("kappa", C.c_double), ("steps_done", C.c_int64), ("r_mol_max", C.c_double),
+                ("rigid_only", C.c_int64), ("reserved", C.c_int64 * 10)]
+
+
 # mmc_totals as a numpy record (Batch.potential_ewald(as_array=True): no per-replica Python objects)
 TOTALS_DTYPE = np.dtype([("energy", "f8"), ("virial", "f8"), ("coulomb", "f8"), ("lj", "f8"),
                          ("real", "f8"), ("recip", "f8"), ("self", "f8"), ("n_overlap", "i4"),
@@ -224,6 +235,10 @@ SIGNATURES = {
     "mmc_batch_cavity_at": [_vp, _i64, _dp, _i32, _i32, _dp, _i32, _i32, _d, _i32, _u64p, _u64p, _u64p, _i32p, _dp,
                             _i32p],
     "mmc_batch_volume_perturb": [_vp, _i32, _dp, _d, _dp, _i64p, _dp, _dp],
+    "mmc_state_record_layout": [_vp, _i64p, _i64p],
+    "mmc_batch_state_info": [_vp, _vp],
+    "mmc_batch_get_state": [_vp, _i64, _i64, _vp],
+    "mmc_batch_set_state": [_vp, _vp, _i64, _i64, _vp],
     "mmc_batch_run_chains": [_vp, C.POINTER(RunParams), _vp, _i32, C.POINTER(RunStats)],
     "mmc_chain_block_line": [_vp, _i64, _i64, _d, _d, C.c_char_p, _i64],
     "mmc_dist_unique_id": [C.c_char_p],                      # uint8_t[128]

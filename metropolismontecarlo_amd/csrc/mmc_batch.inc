@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cmath>
 #include <thread>
+#include "mmc_state.hpp"
 
 #define MMC_MAX_GROUPS 64
 // option persistent = -1: replicas up to which the move server is used: up to one replica per
@@ -131,6 +132,17 @@ struct mmc_batch {
     int bond_chunk = 0;         // mmc_batch_bond_order: replicas per chunk of scratch records (0: by its budget)
     int ring_chunk = 0;         // mmc_batch_hbond_rings: replicas per launch with count_out or ring_out (0: by its budget)
     int voronoi_prune = 1;      // mmc_batch_voronoi: a face stops at the first plane that cannot reach it (0: walks them all; same bits)
+    // save and resume (mmc_state.inc)
+    uint64_t topology = 0;      // fingerprint of the topology the batch was created with (mmc_state_info::topology)
+    int state_chunk = 0;        // mmc_batch_get_state / _set_state: replicas per chunk of staging (0: by its budget)
+    int state_delivery = -1;    // ... 1: the kernels read and write the mapped pinned buffers themselves, 0: device
+                                // staging and a copy, -1: what measured faster for each call (pack 1, unpack 0;
+                                // profiles/checkpoint_bench.json -- the host's copy bounds both, so by a few per cent)
+    void *st_h[2] = { nullptr, nullptr }, *st_hd[2] = { nullptr, nullptr }; // pinned + mapped staging, device aliases
+    void *st_d[2] = { nullptr, nullptr };                                   // device staging
+    size_t st_bytes = 0;        // of each of the four
+    hipEvent_t st_ev[2] = {};   // buffer k's chunk has been packed and copied / unpacked
+    uint8_t *d_state_cur = nullptr; // [R] device copy of s_cur for k_state_pack
 
     const MoveRec *dev_moves(int which) const
     {
@@ -228,6 +240,7 @@ extern "C" int32_t mmc_batch_create(int32_t device, void *hip_stream, int64_t n_
     }
     b->lj_rcut = lj_rcut;
     b->qq_rcut = qq_rcut;
+    b->topology = state_topology(n_mol, atype, charge, n_types, eps, sig);
     b->n_parts = batch_default_parts(R, n_mol);
     // identical molecules and a cutoff the erfc table covers -> fast kernel, else the generic one
     b->fast_ok = b->sys.fast_table_ok(qq_rcut) && b->sys.n_mol <= MMC_WAVE_MAX_MOL;
@@ -282,6 +295,11 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         (void)hipFree(b->obs_buf);
     if (b->obs_host)
         (void)hipHostFree(b->obs_host);
+    for (int k = 0; k < 2; k++) {
+        if (b->st_h[k]) (void)hipHostFree(b->st_h[k]);
+        if (b->st_d[k]) (void)hipFree(b->st_d[k]);
+        if (b->st_ev[k]) (void)hipEventDestroy(b->st_ev[k]);
+    }
     b->sys.release();
     delete b;
     return MMC_OK;
@@ -365,6 +383,12 @@ extern "C" int32_t mmc_batch_set_option(mmc_batch *b, const char *key, int64_t v
     } else if (!strcmp(key, "ring_chunk")) {
         MMC_REQUIRE(value >= 0 && value <= (1 << 30), MMC_ERR_ARG, "ring_chunk must be 0 (by the staging budget) or the replicas per launch");
         b->ring_chunk = (int)value;
+    } else if (!strcmp(key, "state_chunk")) {
+        MMC_REQUIRE(value >= 0 && value <= (1 << 30), MMC_ERR_ARG, "state_chunk must be 0 (by the staging budget) or the replicas per chunk");
+        b->state_chunk = (int)value;
+    } else if (!strcmp(key, "state_delivery")) {
+        MMC_REQUIRE(value >= -1 && value <= 1, MMC_ERR_ARG, "state_delivery must be -1 (by call), 0 (device staging and a copy) or 1 (mapped pinned memory)");
+        b->state_delivery = (int)value;
     } else if (!strcmp(key, "voronoi_prune")) {
         MMC_REQUIRE(value == 0 || value == 1, MMC_ERR_ARG, "voronoi_prune must be 1 (stop at the first plane out of reach) or 0 (never)");
         b->voronoi_prune = (int)value;

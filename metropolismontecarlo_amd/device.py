@@ -1234,6 +1234,104 @@ class Batch(_Handle):
                                                *_ptrs(res, "boltz_sum", "n_overlap", "du", "base")))
         return tuple(res.values())
 
+    # ---- save and resume (include/mmc_hip.h, "Save and resume"; checkpoint.py) ----
+    def state_info(self):
+        """mmc_batch_state_info: the _lib.StateInfo of the batch as it is configured now."""
+        info = _lib.StateInfo()
+        check(self._L.mmc_batch_state_info(self._h, C.byref(info)))
+        return info
+
+    def get_state(self, r0=0, nr=None, out=None):
+        """mmc_batch_get_state: the records of replicas [r0, r0 + nr) (nr None: to the last) as a uint8
+        array [nr, record_bytes], the caller's `out` or a new one.  Changes nothing."""
+        from . import checkpoint
+        r0 = int(r0)
+        nr = self.R - r0 if nr is None else int(nr)
+        if not (0 <= r0 <= self.R and 0 <= nr <= self.R - r0):
+            raise ValueError(f"replicas [{r0}, {r0 + nr}) outside 0..{self.R}")
+        rb = checkpoint.record_layout(self.state_info())[1]
+        out = _output(out, (nr, rb), np.uint8)
+        check(self._L.mmc_batch_get_state(self._h, r0, nr, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_state(self, info, records, r0=0):
+        """mmc_batch_set_state: `records` (uint8 [nr, record_bytes], as get_state returns them) into
+        replicas [r0, r0 + nr).  `info` (state_info() of the batch that wrote them, or the dict of a
+        checkpoint's header) must agree with this batch's system and with how it is configured now."""
+        from . import checkpoint
+        sinfo = info if isinstance(info, _lib.StateInfo) else checkpoint.info_from_dict(info)
+        rb = checkpoint.record_layout(sinfo)[1]
+        if not (isinstance(records, np.ndarray) and records.dtype == np.uint8 and records.ndim == 2
+                and records.shape[1] == rb and records.flags.c_contiguous):
+            raise ValueError(f"records: a C-contiguous uint8 array of shape (nr, {rb})")
+        r0, nr = int(r0), records.shape[0]
+        if not (0 <= r0 <= self.R and nr <= self.R - r0):
+            raise ValueError(f"replicas [{r0}, {r0 + nr}) outside 0..{self.R}")
+        check(self._L.mmc_batch_set_state(self._h, C.byref(sinfo), r0, nr, records.ctypes.data_as(C.c_void_p)))
+
+    def save(self, path, extra=None, replica0=0):
+        """Write the batch's state to the checkpoint file `path` (checkpoint.py), atomically.  `extra`:
+        a dict of the numpy arrays the caller holds and the batch does not -- running energies, the
+        chains array of run_chains, rung / attempt / accept and the exchange round, NPT statistics.
+        `replica0`: the global index of this batch's first replica (a rank saves its own shard).
+        Options are not saved: the resuming batch sets them, as at creation."""
+        from . import checkpoint
+        info = self.state_info()
+        rb = checkpoint.record_layout(info)[1]
+        per = max(1, min(self.R, checkpoint.CHUNK_BYTES // rb))
+        buf = np.zeros((per, rb), dtype=np.uint8)
+        checkpoint.write(path, info, self.R, lambda r0, n: self.get_state(r0, n, out=buf[:n]), extra=extra,
+                         replica0=replica0, chunk_records=per)
+
+    def load(self, path):
+        """Resume from the checkpoint `path`, written by save() of a batch of the same system and
+        size; this batch may have been created from any coordinates.  Refuses, before anything reaches
+        the library's state, a wrong magic or version, a truncated file, a CRC mismatch and a state of
+        another system.  Then brings the batch into the saved mode through its own setters
+        (set_coulomb_style, set_boxes, volume_change, set_temperatures, set_orientations) and streams
+        the records in with set_state.  Returns the file's `extra` arrays.  Chains continue bit for
+        bit when this batch has the options (kernel, parts, persistent / server_wgs,
+        steps_per_launch, half_k) of the one that saved."""
+        from . import checkpoint
+        head = checkpoint.read_header(path)
+        saved = head["info"]
+        if saved["n_mol"] != self.n_mol:
+            raise checkpoint.CheckpointError(f"identity mismatch: the checkpoint's n_mol is {saved['n_mol']}, the "
+                                             f"batch has {self.n_mol}")
+        if head["n_records"] != self.R:
+            raise checkpoint.CheckpointError(f"identity mismatch: the checkpoint holds {head['n_records']} replicas, "
+                                             f"the batch has {self.R}")
+        boxes, temps = checkpoint.verify(path, head)        # every CRC, before the batch is touched
+        mine = checkpoint.info_to_dict(self.state_info())
+        checkpoint.check_identity(saved, mine)
+        style = self.COULOMB_STYLES[saved["coulomb_style"]]
+        if style == "wolf":
+            self.set_coulomb_style("wolf")
+        elif saved["s_stale"] and not (mine["coulomb_style"] == 0 and mine["s_stale"]):
+            self.set_coulomb_style("wolf")                   # (back from Wolf: S(k) awaits its rebuild, as saved)
+            self.set_coulomb_style("ewald")
+        else:
+            self.set_coulomb_style("ewald")
+            if mine["s_stale"] or mine["coulomb_style"] != 0:
+                self.recip_long()
+        if saved["per_box"]:
+            self.set_boxes(boxes, saved["alpha"])
+        elif mine["per_box"]:
+            raise checkpoint.CheckpointError("the checkpoint has one box, the batch per-replica boxes, which cannot be "
+                                             "switched off: create a new batch")
+        elif saved["box"] != mine["box"] or saved["kappa"] != mine["kappa"]:
+            self.volume_change(saved["box"], saved["kappa"])
+        self.set_temperatures(temps if saved["temps_on"] else None)
+        if saved["quat_mode"]:   # (any unit quaternions: the records bring the saved ones)
+            self.set_orientations(np.tile([1.0, 0.0, 0.0, 0.0], (self.n_mol, 1)), saved["db"],
+                                  faithful=saved["quat_mode"] == 1)
+        elif mine["quat_mode"]:
+            self.set_orientations(None, None)
+        sinfo = checkpoint.info_from_dict(saved)
+        for r0, rec in checkpoint.iter_chunks(path, head):
+            self.set_state(sinfo, rec, r0)
+        return checkpoint.read_extra(path, head)
+
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the
         bookkeeping Loop() keeps in total / averages / trans_moves / rot_moves / totProps."""

@@ -142,6 +142,25 @@ struct MMCChain
     trans_set_value::Float64; rot_set_value::Float64
 end
 
+# mmc_state_info ("Save and resume"): 8-byte fields only; passed as a Ref where the C prototypes say void *
+struct MMCStateInfo
+    magic::UInt64; version::Int64
+    R::Int64; n_mol::Int64; nkvecs::Int64; half_k::Int64
+    lj_rcut::Float64; qq_rcut::Float64
+    topology::UInt64
+    nk::Int64; k_sq_max::Int64
+    factor::Float64
+    coulomb_style::Int64; s_stale::Int64; per_box::Int64
+    alpha::Float64
+    temps_on::Int64; quat_mode::Int64
+    db::NTuple{9, Float64}
+    box::Float64; kappa::Float64
+    steps_done::Int64
+    r_mol_max::Float64
+    rigid_only::Int64
+    reserved::NTuple{10, Int64}
+end
+
 "Address of the first Float64 of a Vector of bits types (SVector{3,Float64}, ComplexF64, Float64)."
 fptr(x) = Ptr{Float64}(pointer(x))
 
@@ -1238,6 +1257,46 @@ function volume_perturb!(b::Batch, scales::Vector{Float64}, temperature::Float64
                 (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
                 b.h, K, scales, temperature, boltz_sum, n_overlap, C_NULL, C_NULL))
     return boltz_sum, n_overlap
+end
+
+# ---- save and resume: bulk state records (include/mmc_hip.h, "Save and resume") ----
+"""
+    info = state_info(b)                        # the batch as it is configured now
+    offsets, record_bytes = state_record_layout(info)
+    records = get_state(b, r0, nr)              # Matrix{UInt8} (record_bytes, nr): column k = replica r0 + k
+    set_state!(b, info, r0, records)            # into a batch of the same system, configured the same way
+
+The records carry what the chains keep from call to call (box, temperature, centres of mass,
+coordinates, S(k) in device order bit for bit, orientations), `info` the batch-level rest (the
+position of the random streams among it).  `set_state!` configures nothing: bring a fresh batch into
+the saved mode first (`set_coulomb_style!`, `set_boxes!`, `set_temperatures!`), then chains resume
+bit for bit under the same options.  The file format of the Python side (checkpoint.py) is a prefix,
+a JSON header with these fields and the raw records: `write(io, records)` gives the same bytes.
+"""
+function state_info(b::Batch)
+    info = Ref{MMCStateInfo}()
+    check(ccall((:mmc_batch_state_info, libmmc), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), b.h, info))
+    return info[]
+end
+function state_record_layout(info::MMCStateInfo)
+    offsets = Vector{Int64}(undef, 8)
+    bytes = Ref{Int64}(0)
+    check(ccall((:mmc_state_record_layout, libmmc), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}),
+                Ref(info), offsets, bytes))
+    return offsets, bytes[]
+end
+function get_state(b::Batch, r0::Integer, nr::Integer)
+    _, bytes = state_record_layout(state_info(b))
+    records = Matrix{UInt8}(undef, bytes, nr)
+    check(ccall((:mmc_batch_get_state, libmmc), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}),
+                b.h, r0, nr, records))
+    return records
+end
+function set_state!(b::Batch, info::MMCStateInfo, r0::Integer, records::Matrix{UInt8})
+    _, bytes = state_record_layout(info)
+    size(records, 1) == bytes || error("a record of this state has $bytes bytes")
+    check(ccall((:mmc_batch_set_state, libmmc), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}),
+                b.h, Ref(info), r0, size(records, 2), records))
 end
 
 # ---- the one collective of a sharded run: RCCL behind the C ABI (include/mmc_hip.h, mmc_dist_*) ----
