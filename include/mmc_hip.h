@@ -845,6 +845,72 @@ int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *c
                                   double temperature, double *boltz_sum, int64_t *n_overlap,
                                   double *du_out, uint8_t *ovl_out);
 
+/* ---- A fixed solute: chains around a solute, hydration shells of every replica --------------------
+ * The calls above insert a solute as a test particle; no chain feels it.  mmc_batch_set_solute holds
+ * ONE rigid solute of 1..MMC_SOLUTE_MAX_SITES sites fixed at the same place in every replica: from
+ * then on every trial move (mmc_batch_eval, mmc_batch_run, _run_chains, _run_exchange), every total
+ * (mmc_batch_recip_long, mmc_batch_potential_ewald) and the saved state see it as molecule N + 1 of
+ * the reference's potential(..., "ewald").  A solute that is held fixed is all one solute needs, by
+ * translation invariance; it is never moved and needs no commit.  Definitions, gates, the overlap rule,
+ * "no neutralising background" and "no intramolecular term" are those stated for
+ * mmc_batch_widom_solute: per trial move of a water the solute adds LJ_poly_dU's and EwaldReal's terms
+ * of that water against the S sites (COM gate on the solute's reference point c, per-pair vector1D,
+ * r^2 < r_cut^2 + 100, eps > 0.001, the batch's erfc table, overlap = r^2 < 0.5 and q_a q_b < 0), and
+ * S(k) carries the constant S_sol(k) = sum_a q_a exp(2 pi i k . r_a / L).  Nothing changes while no
+ * solute is set.
+ *   mmc_batch_set_solute(b, n_sites, mol, charge, eps, sig)
+ *     mol [S + 1][3]: the sites, then the reference point c, as mol_in of mmc_batch_widom_solute_at;
+ *     charge [S]; eps, sig [S][3] against the three atom slots of the batch's molecule.  n_sites == 0
+ *     removes the solute (the arrays are not read).  MMC_ERR_ARG, in mmc_batch_widom_solute_at's order
+ *     and without a batch: n_sites outside 0..MMC_SOLUTE_MAX_SITES, a NULL array, a non-finite charge,
+ *     eps or sig, eps < 0 or sig < 0, a non-finite coordinate.  MMC_ERR_STATE while proposals or a
+ *     volume trial are outstanding.  MMC_ERR_UNSUPPORTED, with nothing changed, on a batch with
+ *     per-replica boxes or in Wolf style and on a system the table kernels do not take.  If the new or
+ *     the previous solute carries a charge, S(k) is stale until mmc_batch_recip_long (or
+ *     mmc_batch_potential_ewald) -- the flag of the change from Wolf to Ewald style, and MMC_ERR_STATE
+ *     from the same calls until then.  An uncharged solute neither reads nor stales S(k).
+ *   mmc_batch_get_solute: *n_sites and the arrays as they were set; every pointer may be NULL.
+ *   With a solute set
+ *     - the host decides every move from the move kernel's records and one more, k_solute_move's, a
+ *       launch per step: options "accept_on_device", "steps_per_launch" and "whole_call" fall back
+ *       silently as they do wherever they do not apply, and mmc_run_stats::device_decisions is 0.
+ *       Candidate lists, host or device proposals, parts, per-replica temperatures, chains with their
+ *       virial (the solute's part included) and option "trace_steps" work as without one.  An explicit
+ *       option persistent = 1 or kernel = 4 is MMC_ERR_UNSUPPORTED from the run (kernel = 4 from
+ *       mmc_batch_eval too, which never takes the move server); chosen by size, the move server is
+ *       not taken.
+ *     - mmc_batch_recip_long adds S_sol(k) to both buffers before the energy is formed;
+ *       mmc_batch_get_replica and the state record then carry S(k) of the N + 1 system.
+ *     - mmc_batch_potential_ewald returns every field of mmc_totals as potential() of the N + 1 system:
+ *       each water-solute pair twice in the halved double-counted sums, EwaldSelf over the solute's
+ *       charges too.  A replica in which the solute overlaps a water has energy +inf and n_overlap
+ *       one higher, as a replica with per-replica boxes reports an overlap.
+ *     - MMC_ERR_UNSUPPORTED, nothing computed or changed (the energies would be another system's):
+ *       mmc_batch_set_boxes, mmc_batch_set_coulomb_style(Wolf), mmc_batch_potential_wolf,
+ *       mmc_batch_volume_change / _trial / _accept / _reject, mmc_batch_run_npt (and _npt_replicas,
+ *       which needs the boxes), mmc_batch_widom*, mmc_batch_deletion, mmc_batch_forces,
+ *       mmc_batch_volume_perturb, mmc_batch_pair_energy.  The observables that read coordinates only
+ *       stay open and see the water.
+ *   mmc_batch_solute_energy: u_lj[r], u_real[r] = the water-solute pair energy of replica r -- d_lj
+ *     and d_real of mmc_batch_widom_solute_at at the solute's place, the summand of <u_sw> -- and
+ *     ovl[r] = 1 where a pair overlaps (u_real = 0 then).  Lane l of the replica's wave adds the
+ *     waters l, l + 64, ... in that order, the sites in order, and the 64 lane sums are added in a
+ *     fixed order: bitwise independent of the launch.  MMC_ERR_STATE without a solute.  Read-only.
+ *   mmc_batch_rdf_solute: uint64 counts hist[1 + S][3][numbins] (per_replica == 0, summed over the
+ *     replicas) or hist[R][1 + S][3][numbins]: row 0 measured from c, row 1 + a from site a, each
+ *     against the three water slots.  d = (the solute's point) - (the water's site); image, r, bin =
+ *     ceil(r / dr), dr and the r_max rule exactly mmc_batch_rdf_sites'; a distance with 1 <= bin <=
+ *     numbins is counted at [bin - 1] (a site exactly on the point is not counted).  hist is
+ *     overwritten.  Arguments and preconditions as mmc_batch_rdf_sites; MMC_ERR_STATE without a
+ *     solute.  Read-only. */
+int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const double *mol, const double *charge,
+                             const double *eps, const double *sig);
+int32_t mmc_batch_get_solute(mmc_batch *b, int32_t *n_sites, double *mol, double *charge, double *eps,
+                             double *sig);
+int32_t mmc_batch_solute_energy(mmc_batch *b, double *u_lj, double *u_real, uint8_t *ovl);
+int32_t mmc_batch_rdf_solute(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica,
+                             uint64_t *hist);
+
 /* ---- Solute pairs: potentials of mean force at infinite dilution ------------------------------------
  * How two foreign solutes A and B interact through the solvent -- the methane-methane contact and
  * solvent-separated minima, an ion pair -- from test particles (potential distribution theorem):
@@ -1877,8 +1943,8 @@ int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *sc
  * RECORD per replica, moved in bulk; and one mmc_state_info that describes the batch the records
  * belong to.  The library moves records and checks that the receiving batch is ALREADY configured
  * for them; configuring a fresh batch (mmc_batch_set_coulomb_style, _set_boxes, _set_temperatures,
- * _set_orientations, _volume_change) and the file are the caller's (checkpoint.py, Batch.save /
- * Batch.load).  No entry point here decides, proposes or evaluates a move.
+ * _set_orientations, _volume_change, _set_solute) and the file are the caller's (checkpoint.py,
+ * Batch.save / Batch.load).  No entry point here decides, proposes or evaluates a move.
  *
  * Guarantee: after mmc_batch_set_state of all R replicas into a batch of the same system, created
  * from ANY coordinates and brought into the saved mode, every chain continues bit for bit (same
@@ -1911,7 +1977,11 @@ int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *sc
  *     steps_done   position of the random streams ("Random streams")
  *     r_mol_max    bound on an atom's distance from its centre of mass (+inf: unknown)
  *     rigid_only   1: every committed move was drawn on the device
- *     reserved[10] zero
+ *   the fixed solute (mode: a difference is MMC_ERR_STATE)
+ *     solute_on    1: a solute is set (mmc_batch_set_solute); 0: none
+ *     solute_hash  FNV-1a (64 bit) over n_sites (8 bytes) and mol, charge, eps, sig as given to
+ *                  mmc_batch_set_solute; 0 without a solute
+ *     reserved[8]  zero
  * Of the receiving batch, R may differ from info->R (a record range of another batch); everything
  * else of the identity must agree. */
 #define MMC_STATE_MAGIC 0x31544154534d434dULL /* "MCMSTAT1" */
@@ -1932,7 +2002,9 @@ typedef struct {
     int64_t steps_done;
     double r_mol_max;
     int64_t rigid_only;
-    int64_t reserved[10];
+    int64_t solute_on;
+    uint64_t solute_hash;
+    int64_t reserved[8];
 } mmc_state_info;
 
 /* The record of one replica, the single definition of the format (a pure host function: no device,

@@ -90,7 +90,8 @@ class StateInfo(C.Structure):
                 ("coulomb_style", C.c_int64), ("s_stale", C.c_int64), ("per_box", C.c_int64), ("alpha", C.c_double),
                 ("temps_on", C.c_int64), ("quat_mode", C.c_int64), ("db", C.c_double * 9), ("box", C.c_double),
                 ("kappa", C.c_double), ("steps_done", C.c_int64), ("r_mol_max", C.c_double),
-                ("rigid_only", C.c_int64), ("reserved", C.c_int64 * 10)]
+                ("rigid_only", C.c_int64), ("solute_on", C.c_int64), ("solute_hash", C.c_uint64),
+                ("reserved", C.c_int64 * 8)]
 
 
 # mmc_totals as a numpy record (Batch.potential_ewald(as_array=True): no per-replica Python objects)
@@ -209,6 +210,10 @@ SIGNATURES = {
     "mmc_batch_widom_solute": [_vp, _i32, _dp, _dp, _dp, _dp, _i64, C.c_uint64, _i64, _d, _dp, _i64p, _dp, _dp,
                                _u8p],
     "mmc_batch_widom_solute_at": [_vp, _i32, _dp, _dp, _dp, _i64, _dp, _d, _dp, _i64p, _dp, _u8p],
+    "mmc_batch_set_solute": [_vp, _i32, _dp, _dp, _dp, _dp],
+    "mmc_batch_get_solute": [_vp, _i32p, _dp, _dp, _dp, _dp],
+    "mmc_batch_solute_energy": [_vp, _dp, _dp, _u8p],
+    "mmc_batch_rdf_solute": [_vp, _i32, _d, _i32, _u64p],
     "mmc_batch_widom_pair": [_vp, _i32, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _i32, _dp, _i64,
                              C.c_uint64, _i64, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _dp, _dp, _u8p],
     "mmc_batch_widom_pair_at": [_vp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _i32, _i64, _dp, _dp, _d,

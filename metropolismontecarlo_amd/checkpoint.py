@@ -31,6 +31,8 @@ STATE_VERSION = 1
 IDENTITY = ("magic", "version", "n_mol", "nkvecs", "half_k", "lj_rcut", "qq_rcut", "topology", "nk", "k_sq_max",
             "factor")   # (R is the file's own: a shard may be loaded into a batch only of its size, Batch.load checks)
 _INFO_FIELDS = [n for n, _ in StateInfo._fields_ if n != "reserved"]
+_SOLUTE_FIELDS = ("solute_on", "solute_hash")   # both 0 without a solute, and then not in the dict: the
+#                                                 header of a file written before there were solutes has neither
 
 
 class CheckpointError(ValueError):
@@ -41,7 +43,8 @@ def info_to_dict(info):
     """mmc_state_info (a _lib.StateInfo or already a dict) as a dict of ints, floats and the list db."""
     if isinstance(info, dict):
         return dict(info)
-    return {n: (list(info.db) if n == "db" else getattr(info, n)) for n in _INFO_FIELDS}
+    return {n: (list(info.db) if n == "db" else getattr(info, n)) for n in _INFO_FIELDS
+            if n not in _SOLUTE_FIELDS or info.solute_on}
 
 
 def info_from_dict(d):
@@ -49,7 +52,7 @@ def info_from_dict(d):
     for n in _INFO_FIELDS:
         if n == "db":
             info.db[:] = [float(x) for x in d["db"]]
-        else:
+        elif n not in _SOLUTE_FIELDS or n in d:
             setattr(info, n, d[n])
     return info
 

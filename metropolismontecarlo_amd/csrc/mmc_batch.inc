@@ -7,6 +7,7 @@
 #include <cmath>
 #include <thread>
 #include "mmc_state.hpp"
+#include "mmc_solute_chain.hpp"
 
 #define MMC_MAX_GROUPS 64
 // option persistent = -1: replicas up to which the move server is used: up to one replica per
@@ -38,9 +39,23 @@ struct BatchCand {
     std::vector<Range> ranges; // the groups of replicas the driver launches, each with its own cadence
 };
 
+// The fixed solute of the batch (mmc_batch_set_solute, mmc_solute_chain.inc): n == 0 = none.
+struct BatchSolute {
+    int n = 0;                 // sites
+    bool charged = false;      // some charge is not zero
+    double mol[3 * (SOL_MAX_SITES + 1)] = { 0 }; // [n + 1][3]: sites, then the reference point c
+    double charge[SOL_MAX_SITES] = { 0 }, eps[3 * SOL_MAX_SITES] = { 0 }, sig[3 * SOL_MAX_SITES] = { 0 };
+    double q2 = 0.0;           // sum_a q_a^2 in site order (EwaldSelf)
+    uint64_t hash = 0;         // mmc_state_info::solute_hash
+    double *d_par = nullptr;   // [SOLC_PAR_DOUBLES] the device block of SoluteView, allocated on first use
+    PartOut *h_parts = nullptr, *d_parts = nullptr; // [R] pinned + mapped: k_solute_move's record of every replica
+    SoluteView view() const { return SoluteView{ d_par, n, charged ? 1 : 0 }; }
+};
+
 struct mmc_batch {
     DeviceSystem sys;
     BatchCand cand;
+    BatchSolute sol;
     double lj_rcut = 0, qq_rcut = 0;
     int n_parts = 1;
     int kernel = 3;          // 3: choose per launch between 2 and 1 (default for homogeneous
@@ -300,6 +315,7 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
         if (b->st_d[k]) (void)hipFree(b->st_d[k]);
         if (b->st_ev[k]) (void)hipEventDestroy(b->st_ev[k]);
     }
+    if (b->sol.h_parts) (void)hipHostFree(b->sol.h_parts);
     b->sys.release();
     delete b;
     return MMC_OK;
@@ -309,6 +325,11 @@ extern "C" int32_t mmc_batch_destroy(mmc_batch *b)
 #define BATCH_NO_VOLUME_TRIAL(b)                                                                 \
     MMC_REQUIRE(!(b)->vol_outstanding, MMC_ERR_STATE,                                            \
                 "volume move not settled: call mmc_batch_volume_accept or mmc_batch_volume_reject first")
+
+// what a fixed solute fences (include/mmc_hip.h, "A fixed solute"): the energies would be another system's
+#define BATCH_NO_SOLUTE(b, what)                                                                 \
+    MMC_REQUIRE((b)->sol.n == 0, MMC_ERR_UNSUPPORTED,                                            \
+                "%s: not available while a solute is set (mmc_batch_set_solute)", what)
 
 #define BATCH_CHECK(b)                                                                           \
     MMC_REQUIRE((b) != nullptr, MMC_ERR_ARG, "batch is NULL");                                   \
@@ -475,12 +496,17 @@ extern "C" int32_t mmc_batch_get_replica(mmc_batch *b, int64_t r, double *com, d
     return MMC_OK;
 }
 
+static int32_t batch_solute_recip(mmc_batch *b, double *energies);  // mmc_solute_chain.inc
+static int32_t batch_solute_totals(mmc_batch *b, mmc_totals *tot);
+
 extern "C" int32_t mmc_batch_recip_long(mmc_batch *b, double *energies)
 {
     BATCH_CHECK(b);
     MMC_REQUIRE(energies, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     MMC_TRY(b->sys.recip_long_all(energies));
+    if (b->sol.charged) // + S_sol(k): the energies and both buffers are those of the N + 1 system
+        MMC_TRY(batch_solute_recip(b, energies));
     b->s_stale = false; // both buffers of every replica hold S(k) of its coordinates
     return MMC_OK;
 }
@@ -490,7 +516,10 @@ extern "C" int32_t mmc_batch_potential_ewald(mmc_batch *b, mmc_totals *tot)
     BATCH_CHECK(b);
     MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
-    MMC_TRY(b->sys.totals_ewald(b->lj_rcut, b->qq_rcut, tot));
+    if (b->sol.n)
+        MMC_TRY(batch_solute_totals(b, tot));
+    else
+        MMC_TRY(b->sys.totals_ewald(b->lj_rcut, b->qq_rcut, tot));
     b->s_stale = false; // RecipLong inside wrote both arrays (energy.jl:1008)
     return MMC_OK;
 }
@@ -506,6 +535,7 @@ extern "C" int32_t mmc_batch_set_coulomb_style(mmc_batch *b, int32_t style)
     if (style == b->coulomb_style)
         return MMC_OK;
     if (style == MMC_COULOMB_WOLF) {
+        BATCH_NO_SOLUTE(b, "Wolf style");
         MMC_REQUIRE(!b->sys.pb.on, MMC_ERR_UNSUPPORTED,
                     "Wolf style: the batch has per-replica boxes (mmc_batch_set_boxes)");
         MMC_REQUIRE(b->kernel != 4, MMC_ERR_UNSUPPORTED,
@@ -535,6 +565,7 @@ extern "C" int32_t mmc_batch_potential_wolf(mmc_batch *b, mmc_totals *tot)
     MMC_REQUIRE(tot, MMC_ERR_ARG, "NULL out pointer");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     BATCH_ONE_BOX(b, "mmc_batch_potential_wolf");
+    BATCH_NO_SOLUTE(b, "mmc_batch_potential_wolf");
     DeviceSystem &s = b->sys;
     MMC_REQUIRE(s.uploaded && s.ewald_ready, MMC_ERR_STATE,
                 "potential needs an uploaded system and an EWALD (kappa, factor)");
@@ -836,6 +867,15 @@ static int32_t batch_launch(mmc_batch *b, hipStream_t stream, int64_t r0, int64_
     }
     if (before_kernel)
         MMC_HIP(hipEventRecord(before_kernel, stream));
+    // A fixed solute: its record of every replica of the launch, IN FRONT of the move kernel on its stream.
+    // It needs the step's move records only, and it is over in microseconds: its records are in host
+    // memory when the move kernel's first ones arrive, so the host still works through a launch's
+    // records while the launch runs.  (Behind the move kernel the host could not complete one replica
+    // before the whole launch had ended, and its pass over the records ran after the launch instead of
+    // beside it; DESIGN.md, "A fixed solute".)
+    if (b->sol.n)
+        k_solute_move<<<(unsigned)((nr + SOLC_BLOCK / 16 - 1) / (SOLC_BLOCK / 16)), SOLC_BLOCK, 0, stream>>>(
+            b->sol.view(), cur, s.qq_tab, s.fc, pp, s.box, b->sol.d_parts, (int)r0, (int)nr, stamp);
     dim3 grid((unsigned)P, (unsigned)nr);
     MMC_REQUIRE(!dd || (dg && P == 1 && !b->zero_copy_moves && kernel == 2), MMC_ERR_ASSERT,
                 "the kernel's own accept decision needs device-side proposals, one part per move and the wave kernel");
@@ -1107,6 +1147,8 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     BATCH_NO_VOLUME_TRIAL(b);
     BATCH_S_FRESH(b, "mmc_batch_eval");
     MMC_REQUIRE(moves && results, MMC_ERR_ARG, "NULL argument");
+    MMC_REQUIRE(!(b->sol.n && b->kernel == 4), MMC_ERR_UNSUPPORTED,
+                "a solute is set (mmc_batch_set_solute): kernel 4 does not evaluate it"); // (as the runs: run_plan)
     MMC_TRY(batch_refresh_mirror(b));
     DeviceSystem &s = b->sys;
     const int64_t R = s.R;
@@ -1139,13 +1181,14 @@ extern "C" int32_t mmc_batch_eval(mmc_batch *b, const mmc_move *moves, mmc_move_
     MMC_TRY(batch_launch(b, s.stream, 0, R, P, kernel, b->buf, b->has_prev, pp, nullptr, nullptr, stamp));
     MMC_TRY(s.sync());
     b->eval_parts = P;
+    const int PS = P + (b->sol.n ? 1 : 0); // (a fixed solute: one more record, k_solute_move's)
     for (int64_t r = 0; r < R; r++) {
-        PartOut parts[MMC_MAX_PARTS];
-        for (int q = 0; q < P; q++)
-            MMC_REQUIRE(part_copy_checked(b->h_parts + r * P + q, stamp, &parts[q]),
+        PartOut parts[MMC_MAX_PARTS + 1];
+        for (int q = 0; q < PS; q++)
+            MMC_REQUIRE(part_copy_checked(q < P ? b->h_parts + r * P + q : b->sol.h_parts + r, stamp, &parts[q]),
                         MMC_ERR_HIP, "replica %lld part %d: result record incomplete after the "
                         "stream was synchronised (stamp/checksum mismatch)", (long long)r, q);
-        mmc_combine_parts(parts, P, s.bv.factor, &results[r]);
+        mmc_combine_parts(parts, PS, s.bv.factor, &results[r]);
     }
     b->buf ^= 1;
     b->has_prev = true;
@@ -1273,6 +1316,7 @@ extern "C" int32_t mmc_batch_settle(mmc_batch *b, const int32_t *accept)
 extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double new_kappa)
 {
     BATCH_CHECK(b);
+    BATCH_NO_SOLUTE(b, "mmc_batch_volume_change");
     BATCH_NOT_WOLF(b, "mmc_batch_volume_change");
     BATCH_ONE_BOX(b, "mmc_batch_volume_change");
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
@@ -1307,6 +1351,7 @@ extern "C" int32_t mmc_batch_volume_change(mmc_batch *b, double new_box, double 
 extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double new_kappa, mmc_totals *tot)
 {
     BATCH_CHECK(b);
+    BATCH_NO_SOLUTE(b, "mmc_batch_volume_trial");
     BATCH_NOT_WOLF(b, "mmc_batch_volume_trial");
     BATCH_ONE_BOX(b, "mmc_batch_volume_trial");
     BATCH_USABLE(b);
@@ -1345,6 +1390,7 @@ extern "C" int32_t mmc_batch_volume_trial(mmc_batch *b, double new_box, double n
 extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_NO_SOLUTE(b, "mmc_batch_volume_accept");
     BATCH_NOT_WOLF(b, "mmc_batch_volume_accept");
     BATCH_ONE_BOX(b, "mmc_batch_volume_accept");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");
@@ -1356,6 +1402,7 @@ extern "C" int32_t mmc_batch_volume_accept(mmc_batch *b)
 extern "C" int32_t mmc_batch_volume_reject(mmc_batch *b)
 {
     BATCH_CHECK(b);
+    BATCH_NO_SOLUTE(b, "mmc_batch_volume_reject");
     BATCH_NOT_WOLF(b, "mmc_batch_volume_reject");
     BATCH_ONE_BOX(b, "mmc_batch_volume_reject");
     MMC_REQUIRE(b->vol_outstanding, MMC_ERR_STATE, "no volume move outstanding");

@@ -128,7 +128,9 @@ struct RunPlan {
     struct { int64_t r0, nr; int kernel; } group[MMC_MAX_GROUPS]; // replicas [r0, r0 + nr) and their move kernel (batch_kernel_for)
     int n_streams = 1;           // group g launches on stream g % n_streams
     int T = 1;                   // host threads
-    int P = 1;                   // result records per move the host reads
+    int P = 1;                   // result records per move the move kernel writes
+    bool solute = false;         // a fixed solute (mmc_batch_set_solute): one more record per move, k_solute_move's
+    int records() const { return P + (solute ? 1 : 0); } // ... and what the host reads and adds up
     bool devgen = false;         // proposals generated on the device (mmc_propose.hpp)
     bool server = false;         // the persistent move server does the launches' work
     int server_waves = 0;        // ... with this many parts (waves of a replica's workgroup)
@@ -218,8 +220,9 @@ struct Driver {
     // slot: the half of h_parts the launch wrote (1: the kernel's own decisions only, P == 1).
     int collect(int64_t r, unsigned want, PartOut *parts, int &q_done, mmc_run_stats &st, int slot = 0)
     {
-        for (; q_done < plan.P; q_done++) {
-            const PartOut *src = &b->h_parts[(size_t)slot * b->sys.R + r * plan.P + q_done];
+        for (; q_done < plan.records(); q_done++) {
+            const PartOut *src = q_done < plan.P ? &b->h_parts[(size_t)slot * b->sys.R + r * plan.P + q_done]
+                                                 : &b->sol.h_parts[r]; // (the host decides: slot 0)
             if (part_stamp_of(*(const volatile int32_t *)&src->ovl[1]) != want)
                 return 0;
             std::atomic_thread_fence(std::memory_order_acquire);
@@ -271,7 +274,7 @@ struct Driver {
         const double T_ = temps ? temps[r] : p->temperature, factor = b->sys.bv.factor;
         const bool sweep_end = (step_done % b->sys.n_mol) == b->sys.n_mol - 1;
         mmc_move_result res;
-        mmc_combine_parts(parts, plan.P, factor, &res);
+        mmc_combine_parts(parts, plan.records(), factor, &res);
         const double delta = res.d_lj + res.d_real + res.d_recip; // main.jl:593
         if (res.overlap)
             st.overlaps++; // main.jl:595-597
@@ -343,7 +346,7 @@ struct Driver {
             }
         }
         for (int64_t r = lo; r < hi; r++) {
-            PartOut parts[MMC_MAX_PARTS];
+            PartOut parts[MMC_MAX_PARTS + 1];
             int q_done = 0;
             for (unsigned spins = 1;; spins++) {
                 const int c = collect(r, want, parts, q_done, st, slot);
@@ -642,7 +645,7 @@ struct Driver {
         const size_t n = (size_t)(hi - lo);
         std::vector<int64_t> step(n, 0);
         std::vector<int> q_done(n, 0);
-        std::vector<PartOut> parts(n * plan.P);
+        std::vector<PartOut> parts(n * plan.records());
         // this thread's slice of the per-replica arrays (see RepView); written back when it is done
         std::vector<uint8_t> l_acc(n, 0), l_kind(n, 0), l_scur(b->s_cur.begin() + lo, b->s_cur.begin() + hi),
             l_flags(n, 0);
@@ -675,12 +678,12 @@ struct Driver {
                 if (sr >= n_steps)
                     continue;
                 const unsigned want = (server_stamp0 + (unsigned)sr + 1u) & MMC_STAMP_MASK;
-                const int c = collect(r, want, &parts[(size_t)(r - lo) * plan.P], q_done[r - lo], st);
+                const int c = collect(r, want, &parts[(size_t)(r - lo) * plan.records()], q_done[r - lo], st);
                 if (c < 0)
                     return;
                 if (c == 0)
                     continue;
-                decide(r, &parts[(size_t)(r - lo) * plan.P], sr, st, v);
+                decide(r, &parts[(size_t)(r - lo) * plan.records()], sr, st, v);
                 q_done[r - lo] = 0;
                 sr++;
                 any = true;
@@ -1040,6 +1043,14 @@ static int32_t run_plan(const mmc_batch *b, const mmc_run_params *p, bool chains
         return MMC_OK;
     }
     pl.devgen = b->device_moves != 0;
+    // A fixed solute: its record is k_solute_move's, beside a launch per step whose decision the host
+    // makes.  The move server and the latency form have no such launch: refused where asked for by
+    // name, not taken where the size would choose them; "accept_on_device", "steps_per_launch" and
+    // "whole_call" fall back as they do wherever they do not apply.
+    pl.solute = b->sol.n > 0;
+    MMC_REQUIRE(!pl.solute || (b->persistent != 1 && b->kernel != 4), MMC_ERR_UNSUPPORTED,
+                "a solute is set (mmc_batch_set_solute): the persistent move server (option persistent = 1) and "
+                "kernel 4 do not evaluate it");
     pl.P = p->n_parts > 0 ? p->n_parts : b->n_parts;
     if (b->kernel == 4) { // parts are waves, four to a workgroup; the host sees one record per workgroup
         if (p->n_parts <= 0) { // sixteen, or as many as the system's size asks for
@@ -1056,7 +1067,7 @@ static int32_t run_plan(const mmc_batch *b, const mmc_run_params *p, bool chains
     }
     MMC_REQUIRE(!s.pb.on || pl.devgen, MMC_ERR_UNSUPPORTED,
                 "per-replica boxes: the trial moves are drawn on the device (device_moves = 1)");
-    if (b->persistent != 0 && !s.pb.on && !wolf) { // small batches: the persistent move server (one box, Ewald style)
+    if (b->persistent != 0 && !s.pb.on && !wolf && !pl.solute) { // small batches: the persistent move server (one box, Ewald style)
         pl.server = batch_server_applies(b) && (b->persistent == 1 || R <= MMC_SERVER_AUTO_MAX);
         MMC_REQUIRE(pl.server || b->persistent != 1, MMC_ERR_UNSUPPORTED,
                     "the persistent move server needs device_moves = 1, the table kernel, no "
@@ -1097,7 +1108,7 @@ static int32_t run_plan(const mmc_batch *b, const mmc_run_params *p, bool chains
     // and draws it (device-side proposals); the host otherwise -- parts that only the host adds up,
     // the caller's proposals, the move server, and chains whose step sizes the host adapts between
     // sweeps (the launches are enqueued a step ahead of the host's bookkeeping).
-    pl.devacc = pl.devgen && !pl.server && pl.P == 1 && !b->zero_copy_moves && !(chains && adjust);
+    pl.devacc = pl.devgen && !pl.server && pl.P == 1 && !b->zero_copy_moves && !(chains && adjust) && !pl.solute;
     int64_t nr_max = 0;
     for (int g = 0; g < pl.G; g++) {
         auto &pg = pl.group[g];
@@ -1398,6 +1409,7 @@ extern "C" int32_t mmc_batch_run_npt(mmc_batch *b, const mmc_run_params *p, cons
 {
     BATCH_CHECK(b);
     BATCH_NOT_WOLF(b, "mmc_batch_run_npt");
+    BATCH_NO_SOLUTE(b, "mmc_batch_run_npt");
     BATCH_ONE_BOX(b, "mmc_batch_run_npt (per-replica boxes: mmc_batch_run_npt_replicas)");
     MMC_REQUIRE(p && q && energy && stats && ns, MMC_ERR_ARG, "NULL argument");
     MMC_REQUIRE(b->sys.R == 1, MMC_ERR_UNSUPPORTED,

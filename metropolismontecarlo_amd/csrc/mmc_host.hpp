@@ -38,6 +38,14 @@ void mmc_set_error(const char *fmt, ...);
 #define MMC_MAX_PARTS 32 // result records (units) per trial move
 static_assert(LAT_MAX_PARTS / LAT_WAVES <= MMC_MAX_PARTS, "one record per workgroup of the latency kernels");
 
+// What a caller of DeviceSystem::totals_ewald adds to the sums the totals are formed from, once the
+// pair kernels and RecipLong are back: the double-counted pair sums, RecipLong's energies and sum q^2
+// (the batch's fixed solute, mmc_solute_chain.inc).
+struct TotalsHook {
+    int32_t (*fn)(void *ctx, std::vector<TotalsRaw> &ht, std::vector<double> &erec, double *sq2);
+    void *ctx;
+};
+
 // Device state of R replicas of one system + Ewald tables.  R = 1 for a context.
 struct DeviceSystem {
     int device = 0;
@@ -114,7 +122,7 @@ struct DeviceSystem {
     int32_t recip_long_enqueue(double *energies_host /* [R] */);
     int32_t pair_totals_enqueue(double lj_rcut, double qq_rcut, std::vector<TotalsRaw> &ht, bool *fast);
     int32_t pair_totals_finish(double lj_rcut, double qq_rcut, std::vector<TotalsRaw> &ht, bool fast);
-    int32_t totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *tot /* [R] */);
+    int32_t totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *tot /* [R] */, const TotalsHook *hook = nullptr);
     // one system, one launch (mmc_potential.hpp): pair totals and / or structure factor + energy
     TotalPart *d_tparts1 = nullptr; // [units] of the one-system launch
     double *d_spart1 = nullptr;   // [POT_MAX_CHUNKS][2 * MMC_NK_STRIDE] chunk partials of S(k)

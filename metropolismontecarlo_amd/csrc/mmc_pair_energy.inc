@@ -30,6 +30,7 @@ extern "C" int32_t mmc_batch_pair_energy(mmc_batch *b, int32_t numbins, double r
     std::vector<double> thr;
     MMC_TRY(tile_plan(b, numbins, r_max, "mmc_batch_pair_energy", &pa.ta, &thr));
     MMC_REQUIRE(s.uniform3, MMC_ERR_UNSUPPORTED, "mmc_batch_pair_energy: three-site molecules only");
+    BATCH_NO_SOLUTE(b, "mmc_batch_pair_energy");
     pa.ta.per_replica = per_replica ? 1 : 0;
 
     const size_t rs = (size_t)numbins + 2, e_slots = uhist ? (size_t)n_ebins + 2 : 0, ws = 3 * rs + e_slots + 1;

@@ -37,6 +37,7 @@ extern "C" int32_t mmc_batch_set_boxes(mmc_batch *b, const double *boxes, double
 {
     BATCH_CHECK(b);
     BATCH_NOT_WOLF(b, "mmc_batch_set_boxes");
+    BATCH_NO_SOLUTE(b, "mmc_batch_set_boxes");
     BATCH_USABLE(b);
     BATCH_NO_VOLUME_TRIAL(b);
     MMC_REQUIRE(boxes, MMC_ERR_ARG, "NULL argument");

@@ -47,6 +47,19 @@ static inline uint64_t state_topology(int64_t n_mol, const int64_t *atype, const
     return state_fnv(h, sig, sizeof(double) * n_types * n_types);
 }
 
+// The fixed solute as mmc_batch_set_solute was given it (mmc_state_info::solute_hash): FNV-1a over
+// n_sites (8 bytes) and the five arrays mol [S + 1][3], charge [S], eps [S][3], sig [S][3].
+static inline uint64_t state_solute_hash(int64_t n_sites, const double *mol, const double *charge, const double *eps,
+                                         const double *sig)
+{
+    uint64_t h = 0xcbf29ce484222325ULL;
+    h = state_fnv(h, &n_sites, sizeof(n_sites));
+    h = state_fnv(h, mol, sizeof(double) * 3 * (n_sites + 1));
+    h = state_fnv(h, charge, sizeof(double) * n_sites);
+    h = state_fnv(h, eps, sizeof(double) * 3 * n_sites);
+    return state_fnv(h, sig, sizeof(double) * 3 * n_sites);
+}
+
 #define ST_FLAG_PER_BOX 1u
 #define ST_FLAG_TEMPS 2u
 #define ST_FLAG_QUAT 4u

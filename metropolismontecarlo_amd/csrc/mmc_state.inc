@@ -43,6 +43,8 @@ static void state_fill_info(const mmc_batch *b, mmc_state_info *o)
     o->steps_done = b->steps_done;
     o->r_mol_max = s.r_mol_max;
     o->rigid_only = b->rigid_only ? 1 : 0;
+    o->solute_on = b->sol.n > 0 ? 1 : 0;
+    o->solute_hash = b->sol.n > 0 ? b->sol.hash : 0;
 }
 
 extern "C" int32_t mmc_batch_state_info(mmc_batch *b, void *info)
@@ -185,6 +187,9 @@ static int32_t state_check_info(const mmc_batch *b, const mmc_state_info *in)
     ST_MODE(in->per_box || (in->box == me.box && in->kappa == me.kappa),
             "box %.17g and kappa %.17g, the batch has %.17g and %.17g (mmc_batch_volume_change)", in->box, in->kappa,
             me.box, me.kappa);
+    ST_MODE(in->solute_on == me.solute_on && in->solute_hash == me.solute_hash,
+            "solute %s (hash %016llx), the batch has %s (hash %016llx) (mmc_batch_set_solute)", in->solute_on ? "set" : "not set",
+            (unsigned long long)in->solute_hash, me.solute_on ? "one" : "none", (unsigned long long)me.solute_hash);
 #undef ST_MODE
     return MMC_OK;
 }

@@ -970,7 +970,7 @@ int32_t DeviceSystem::pb_snapshot(const int32_t *d_mask, bool take)
 }
 
 // potential(..., "ewald") for every replica (energy.jl:946-1032)
-int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *tot)
+int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *tot, const TotalsHook *hook)
 {
     MMC_REQUIRE(uploaded && ewald_ready, MMC_ERR_STATE,
                 "potential needs an uploaded system and PrepareEwaldVariables");
@@ -994,6 +994,8 @@ int32_t DeviceSystem::totals_ewald(double lj_rcut, double qq_rcut, mmc_totals *t
         MMC_TRY(sync());
     }
     MMC_TRY(pair_totals_finish(lj_rcut, qq_rcut, ht, fast));
+    if (hook)
+        MMC_TRY(hook->fn(hook->ctx, ht, erec, &sq2));
     const double factor = bv.factor;
     for (int64_t r = 0; r < R; r++) {
         const double kappa = pb.on ? pb.kappa[r] : bv.kappa;

@@ -67,6 +67,7 @@ static int32_t units_state_scope(const mmc_batch *b, const char *what)
     BATCH_S_FRESH(b, what);
     BATCH_ONE_BOX(b, what);
     BATCH_NOT_WOLF(b, what);
+    BATCH_NO_SOLUTE(b, what);
     MMC_REQUIRE(b->fast_ok, MMC_ERR_UNSUPPORTED,
                 "%s: needs identical 3-atom molecules and a cutoff / kappa the erfc table covers", what);
     return MMC_OK;

@@ -25,6 +25,7 @@ extern "C" int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const
     BATCH_USABLE(b);
     BATCH_NOT_WOLF(b, "mmc_batch_volume_perturb");
     BATCH_ONE_BOX(b, "mmc_batch_volume_perturb");
+    BATCH_NO_SOLUTE(b, "mmc_batch_volume_perturb");
     DeviceSystem &s = b->sys;
     MMC_REQUIRE(s.uploaded && s.ewald_ready, MMC_ERR_STATE,
                 "mmc_batch_volume_perturb needs an uploaded system and PrepareEwaldVariables");

@@ -728,6 +728,55 @@ class Batch(_Handle):
                                                 *_ptrs(res, "boltz_sum", "n_overlap", "du", "ovl")))
         return tuple(res.values())
 
+    # ---- a fixed solute (include/mmc_hip.h, "A fixed solute") ----
+    def set_solute(self, solute, mol=None):
+        """mmc_batch_set_solute: hold the rigid solute (structs.Solute) fixed in every replica at mol
+        (S + 1, 3) = its S sites, then its reference point; every trial move, total and saved state
+        then sees it as molecule N + 1.  solute None removes it.  A charged solute (set or removed)
+        leaves S(k) stale: call recip_long() or potential_ewald() before the next run."""
+        if solute is None:
+            check(self._L.mmc_batch_set_solute(self._h, 0, None, None, None, None))
+            return
+        S = solute.n_sites
+        mol = _f64(mol)
+        if mol.shape != (S + 1, 3):
+            raise ValueError("mol must be (n_sites + 1, 3): the sites, then the reference point")
+        check(self._L.mmc_batch_set_solute(self._h, S, _d(mol), _d(solute.charge), _d(solute.eps), _d(solute.sig)))
+
+    def get_solute(self):
+        """mmc_batch_get_solute: (structs.Solute, mol (S + 1, 3)) as set -- the Solute's offsets are the
+        sites minus the reference point -- or None while no solute is set."""
+        from .structs import Solute
+        n = C.c_int32(0)
+        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), None, None, None, None))
+        S = n.value
+        if S == 0:
+            return None
+        res = _outputs({"mol": ((S + 1, 3), np.float64), "charge": ((S,), np.float64), "eps": ((S, 3), np.float64),
+                        "sig": ((S, 3), np.float64)}, None)
+        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), *_ptrs(res, "mol", "charge", "eps", "sig")))
+        return Solute("solute", res["mol"][:S] - res["mol"][S], res["charge"], res["eps"], res["sig"]), res["mol"]
+
+    def solute_energy(self, out=None):
+        """mmc_batch_solute_energy: the water-solute pair energy of every replica, the summand of
+        <u_sw>: (u_lj (R,), u_real (R,), ovl (R,) uint8) in K; `out`: a dict of such arrays to write."""
+        res = _outputs({"u_lj": ((self.R,), np.float64), "u_real": ((self.R,), np.float64),
+                        "ovl": ((self.R,), np.uint8)}, out, known_only=True)
+        check(self._L.mmc_batch_solute_energy(self._h, *_ptrs(res, "u_lj", "u_real", "ovl")))
+        return res["u_lj"], res["u_real"], res["ovl"]
+
+    def rdf_solute(self, numbins, r_max=0.0, per_replica=False, out=None):
+        """mmc_batch_rdf_solute: solute-water pair histograms, uint64 [1 + S, 3, numbins] summed over
+        the replicas or [R, 1 + S, 3, numbins] with per_replica: row 0 from the reference point, row
+        1 + a from site a, against the three water slots; bin k holds k dr < r <= (k + 1) dr, dr as
+        rdf_sites'.  `out` (that shape, uint64, contiguous) is overwritten and returned."""
+        n = C.c_int32(0)
+        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), None, None, None, None))
+        shape = (1 + n.value, 3, max(int(numbins), 1))
+        out = _output(out, (self.R,) + shape if per_replica else shape, np.uint64)
+        check(self._L.mmc_batch_rdf_solute(self._h, int(numbins), float(r_max), int(bool(per_replica)), _ptr(out)))
+        return out
+
     def pair_sums(self, sums, K):
         """The six accumulators of widom_pair: a dict (or None = new zero arrays) with boltz_a (R,),
         n_zero_a (R,), boltz_b, boltz_ab (R, K), n_zero_b, n_zero_ab (R, K)."""
@@ -1269,6 +1318,8 @@ class Batch(_Handle):
             raise ValueError(f"replicas [{r0}, {r0 + nr}) outside 0..{self.R}")
         check(self._L.mmc_batch_set_state(self._h, C.byref(sinfo), r0, nr, records.ctypes.data_as(C.c_void_p)))
 
+    _SOLUTE_EXTRA = ("solute_mol", "solute_charge", "solute_eps", "solute_sig")   # save()'s own names among `extra`
+
     def save(self, path, extra=None, replica0=0):
         """Write the batch's state to the checkpoint file `path` (checkpoint.py), atomically.  `extra`:
         a dict of the numpy arrays the caller holds and the batch does not -- running energies, the
@@ -1277,6 +1328,13 @@ class Batch(_Handle):
         Options are not saved: the resuming batch sets them, as at creation."""
         from . import checkpoint
         info = self.state_info()
+        sol = self.get_solute()
+        taken = sorted(set(extra or {}) & set(self._SOLUTE_EXTRA))
+        if taken:
+            raise ValueError(f"extra: the names {taken} are the file's own (the batch's solute); choose others")
+        if sol is not None:   # (the arrays mmc_state_info::solute_hash is the fingerprint of: load() sets them again)
+            extra = dict(extra or {}, solute_mol=sol[1], solute_charge=sol[0].charge, solute_eps=sol[0].eps,
+                         solute_sig=sol[0].sig)
         rb = checkpoint.record_layout(info)[1]
         per = max(1, min(self.R, checkpoint.CHUNK_BYTES // rb))
         buf = np.zeros((per, rb), dtype=np.uint8)
@@ -1288,8 +1346,8 @@ class Batch(_Handle):
         size; this batch may have been created from any coordinates.  Refuses, before anything reaches
         the library's state, a wrong magic or version, a truncated file, a CRC mismatch and a state of
         another system.  Then brings the batch into the saved mode through its own setters
-        (set_coulomb_style, set_boxes, volume_change, set_temperatures, set_orientations) and streams
-        the records in with set_state.  Returns the file's `extra` arrays.  Chains continue bit for
+        (set_coulomb_style, set_boxes, volume_change, set_temperatures, set_orientations, set_solute)
+        and streams the records in with set_state.  Returns the file's `extra` arrays.  Chains continue bit for
         bit when this batch has the options (kernel, parts, persistent / server_wgs,
         steps_per_launch, half_k) of the one that saved."""
         from . import checkpoint
@@ -1304,6 +1362,18 @@ class Batch(_Handle):
         boxes, temps = checkpoint.verify(path, head)        # every CRC, before the batch is touched
         mine = checkpoint.info_to_dict(self.state_info())
         checkpoint.check_identity(saved, mine)
+        same_solute = (saved.get("solute_on", 0), saved.get("solute_hash", 0)) == (mine.get("solute_on", 0),
+                                                                                   mine.get("solute_hash", 0))
+        # (first: a solute fences the setters below -- also the detour through Wolf style that marks a fresh
+        # S(k) stale as saved; the solute is then set again at the end)
+        stale_by_wolf = (saved["coulomb_style"] == 0 and saved["s_stale"]
+                         and not (mine["coulomb_style"] == 0 and mine["s_stale"]))
+        if mine.get("solute_on", 0) and (not same_solute or stale_by_wolf or saved["coulomb_style"] != 0
+                                           or saved["per_box"] or saved["box"] != mine["box"]
+                                           or saved["kappa"] != mine["kappa"]):
+            self.set_solute(None)
+            same_solute = not saved.get("solute_on", 0)
+            mine = checkpoint.info_to_dict(self.state_info())
         style = self.COULOMB_STYLES[saved["coulomb_style"]]
         if style == "wolf":
             self.set_coulomb_style("wolf")
@@ -1327,10 +1397,19 @@ class Batch(_Handle):
                                   faithful=saved["quat_mode"] == 1)
         elif mine["quat_mode"]:
             self.set_orientations(None, None)
+        extra = checkpoint.read_extra(path, head)
+        if saved.get("solute_on", 0) and not same_solute:
+            from .structs import Solute
+            mol = extra["solute_mol"]
+            self.set_solute(Solute("solute", mol[:-1] - mol[-1], extra["solute_charge"], extra["solute_eps"],
+                                   extra["solute_sig"]), mol)
+            if not saved["s_stale"] and self.state_info().s_stale:
+                self.recip_long()                            # (a charged solute: S(k) awaits no rebuild, as saved)
+        extra = {k: v for k, v in extra.items() if k not in self._SOLUTE_EXTRA}
         sinfo = checkpoint.info_from_dict(saved)
         for r0, rec in checkpoint.iter_chunks(path, head):
             self.set_state(sinfo, rec, r0)
-        return checkpoint.read_extra(path, head)
+        return extra
 
     def new_chains(self, energies, virials=None, dr_max=0.15, dphi_max=0.05, set_value=0.5):
         """One mmc_chain record per replica (numpy structured array, _lib.CHAIN_DTYPE): the

@@ -158,7 +158,9 @@ struct MMCStateInfo
     steps_done::Int64
     r_mol_max::Float64
     rigid_only::Int64
-    reserved::NTuple{10, Int64}
+    solute_on::Int64
+    solute_hash::UInt64
+    reserved::NTuple{8, Int64}
 end
 
 "Address of the first Float64 of a Vector of bits types (SVector{3,Float64}, ComplexF64, Float64)."
@@ -726,6 +728,61 @@ function widom_solute_at!(b::Batch, charge::Vector{Float64}, eps::Vector{Float64
                  Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}),
                 b.h, S, charge, eps, sig, n_insert, mol_in, temperature, boltz_sum, n_overlap, C_NULL, C_NULL))
     return boltz_sum, n_overlap
+end
+
+# ---- a fixed solute (include/mmc_hip.h, "A fixed solute") ---------------------------------------------
+"""
+    set_solute!(b, mol, charge, eps, sig)      remove_solute!(b)
+    get_solute(b) -> (n_sites, mol, charge, eps, sig)
+    solute_energy(b) -> (u_lj, u_real, ovl)
+    rdf_solute(b, numbins, r_max, per_replica) -> hist
+
+One rigid solute of S = `length(charge)` sites (1..16) held fixed at the same place in every replica:
+`mol` = 3 (S + 1) Float64, the sites, then the reference point; `eps` / `sig` 3 S Float64 against the
+three atom slots of the batch's molecule.  Every trial move, total and saved state then sees it as
+molecule N + 1 of potential(..., "ewald"); the host decides every move.  A charged solute (set or
+removed) leaves S(k) stale until `recip_long!` / `potential_ewald`.  `solute_energy`: the water-solute
+pair energy of every replica (K) and its overlap flag.  `rdf_solute`: UInt64 counts
+[numbins, 3, 1 + S] (column-major: C's [1 + S][3][numbins]), with `per_replica` one such block per
+replica: row 1 from the reference point, row 1 + a from site a, against the three water slots.
+"""
+function set_solute!(b::Batch, mol::Vector{Float64}, charge::Vector{Float64}, eps::Vector{Float64},
+                     sig::Vector{Float64})
+    S = length(charge)
+    1 <= S <= 16 || error("a solute has 1..16 sites")
+    length(mol) == 3 * (S + 1) && length(eps) == 3S && length(sig) == 3S || error("mol: (S + 1) x 3; eps, sig: S x 3")
+    check(ccall((:mmc_batch_set_solute, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, S, mol, charge, eps, sig))
+    return b
+end
+function remove_solute!(b::Batch)
+    check(ccall((:mmc_batch_set_solute, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, 0, C_NULL, C_NULL, C_NULL, C_NULL))
+    return b
+end
+function get_solute(b::Batch)
+    n = Ref{Int32}(0)
+    mol, charge, eps, sig = zeros(51), zeros(16), zeros(48), zeros(48)
+    check(ccall((:mmc_batch_get_solute, libmmc), Int32,
+                (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, n, mol, charge, eps, sig))
+    S = Int(n[])
+    return S, mol[1:(S > 0 ? 3 * (S + 1) : 0)], charge[1:S], eps[1:3S], sig[1:3S]
+end
+function solute_energy(b::Batch)
+    u_lj, u_real, ovl = zeros(b.n_replicas), zeros(b.n_replicas), zeros(UInt8, b.n_replicas)
+    check(ccall((:mmc_batch_solute_energy, libmmc), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}), b.h, u_lj, u_real, ovl))
+    return u_lj, u_real, ovl
+end
+function rdf_solute(b::Batch, numbins::Integer, r_max::Float64 = 0.0, per_replica::Bool = false)
+    S = get_solute(b)[1]
+    hist = per_replica ? zeros(UInt64, numbins, 3, 1 + S, b.n_replicas) : zeros(UInt64, numbins, 3, 1 + S)
+    check(ccall((:mmc_batch_rdf_solute, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{UInt64}), b.h, numbins, r_max, per_replica ? 1 : 0, hist))
+    return hist
 end
 
 # ---- solute pairs (include/mmc_hip.h, mmc_batch_widom_pair / mmc_batch_widom_pair_at) -----------------

@@ -54,6 +54,34 @@ def normalize_rdf_pairs(row, n_site_pairs, dr, inv_volume_sum):
     return rrr, row[..., 1:] / (float(n_site_pairs) * float(inv_volume_sum) * shell)
 
 
+def normalize_rdf_solute(row, n_sites, dr, inv_volume_sum):
+    """g(r) of one row of solute-water counts (Batch.rdf_solute: row[k] counts k dr < r <= (k + 1) dr):
+    g(r_k) = row[k] / (n_sites inv_volume_sum 4 pi (r_k^2 + dr^2/12) dr) at r_k = (k + 1/2) dr.
+    n_sites: the water sites a frame counts into the row (N for one slot; 2 N for the two hydrogen
+    slots added up); inv_volume_sum: sum of 1 / V over the frames (replicas x samples).
+    4 pi (r_k^2 + dr^2/12) dr is gr.jl:100-103's shell volume, which is the exact volume of the
+    shell: an ideal gas gives 1 in every bin.  Returns (r, g)."""
+    row = np.asarray(row, dtype=float)
+    k = np.arange(row.shape[-1])
+    rrr = (k + 0.5) * dr
+    shell = 4.0 * np.pi * (rrr * rrr + dr * dr / 12.0) * dr
+    return rrr, row / (float(n_sites) * float(inv_volume_sum) * shell)
+
+
+def coordination_number(row, n_frames, dr, r_shell=None):
+    """Running coordination number of one row of solute-water counts (Batch.rdf_solute): n(r) at the
+    upper bin edges r = dr, 2 dr, ..., the mean number of counted water sites within r of the solute's
+    point per frame.  With r_shell: the value at the last edge not beyond r_shell (the first-shell
+    coordination number for r_shell = the first minimum of g) as a float; else (edges, n)."""
+    row = np.asarray(row, dtype=float)
+    edges = (np.arange(row.shape[-1]) + 1.0) * dr
+    n = np.cumsum(row, axis=-1) / float(n_frames)
+    if r_shell is None:
+        return edges, n
+    k = int(np.searchsorted(edges, float(r_shell) * (1.0 + 1e-12), side="right"))
+    return n[..., k - 1] if k > 0 else np.zeros(row.shape[:-1])
+
+
 def dielectric_constant(M, temperature, volume, factor):
     """Static dielectric constant from the fluctuation of the total dipole moment under the
     conducting (tinfoil) boundary of the Ewald sum:
