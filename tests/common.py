@@ -6,6 +6,7 @@ import re
 
 import numpy as np
 
+from boundary import header_define  # noqa: F401  (tests import it from here)
 from metropolismontecarlo_amd import io as mio
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -363,14 +364,6 @@ def widom_host_sums(du, ovl, boltz0, novl0, temperature):
         bs = np.where(flagged[:, j], bs, bs + w[:, j])
     no += flagged.sum(1)
     return bs, no
-
-
-def header_define(name):
-    """The value of `#define name value` in include/mmc_hip.h, as text."""
-    from test_abi import HEADER
-    m = re.search(r"^#define\s+%s\s+(\S+)" % name, open(HEADER).read(), flags=re.M)
-    assert m, f"{name} is not defined in mmc_hip.h"
-    return m.group(1)
 
 
 class _UnreachableLibrary:

@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_bond_order"
@@ -14,35 +15,17 @@ PROTOTYPE = ("int32_t mmc_batch_bond_order(mmc_batch *b, int32_t l, double r_nb,
              "int32_t per_replica, uint64_t *q_hist, uint64_t *qbar_hist, uint64_t *c_hist, uint64_t *ab_hist, "
              "uint64_t *size_hist, int64_t *stats, double *sums, double *q_out, double *qbar_out, "
              "int32_t *nbr_out, uint8_t *ab_out, int32_t *label_out);")
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32,
-          "uint64_t *": C.POINTER(C.c_uint64), "double *": C.POINTER(C.c_double),
-          "int32_t *": C.POINTER(C.c_int32), "int64_t *": C.POINTER(C.c_int64), "uint8_t *": C.POINTER(C.c_uint8)}
 INF, NAN = float("inf"), float("nan")
 
 
-def header_prototype():
-    from test_abi import HEADER
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
-
-
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert len(want) == 25 and _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
+    assert len(boundary.header_prototypes()[NAME][1]) == 25
 
 
 def test_the_header_fixes_the_limits_and_the_definitions():
-    from test_abi import HEADER
-    text = open(HEADER).read()
+    text = boundary.header_text()
     for macro, value in (("MMC_BO_MAX_NB", 16), ("MMC_BO_MAX_BINS", 4096), ("MMC_BO_STATS", 8), ("MMC_BO_MAX_MOL", 8000)):
         assert re.search(r"#define\s+%s\s+%d\b" % (macro, value), text), macro
     sec = text[text.index("---- Bond order"):text.index("int32_t mmc_batch_bond_order")]
@@ -53,10 +36,9 @@ def test_the_header_fixes_the_limits_and_the_definitions():
 
 def test_the_julia_binding_and_the_python_method_carry_it():
     import inspect
-    import os
     from metropolismontecarlo_amd import observables as obs
     from metropolismontecarlo_amd.device import Batch
-    jl = open(os.path.join(os.path.dirname(_lib.__file__), "julia", "MMCHip.jl"), encoding="utf-8").read()
+    jl = boundary.julia_text()
     assert ":mmc_batch_bond_order" in jl and "function bond_order(" in jl
     sig = inspect.signature(Batch.bond_order)
     assert [(k, p.default) for k, p in sig.parameters.items()][1:] == [

@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 PROTOTYPES = {
@@ -20,38 +21,16 @@ PROTOTYPES = {
         "uint64_t *occ_hist, uint64_t *occ_mom, uint64_t *nn_hist, int32_t *count_out, double *nn_r2_out, "
         "int32_t *nn_idx_out);"),
 }
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32, "int64_t": C.c_int64,
-          "uint64_t": C.c_uint64, "uint64_t *": C.POINTER(C.c_uint64), "double *": C.POINTER(C.c_double),
-          "const double *": C.POINTER(C.c_double), "int32_t *": C.POINTER(C.c_int32)}
-
-
-def header_code():
-    from test_abi import HEADER
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def header_prototype(name):
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % name, header_code())
-    assert m, f"{name} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
 def test_symbols_are_declared_exported_and_bound_with_the_header_prototype(name):
-    from test_abi import header_functions
-    proto = PROTOTYPES[name]
-    assert name in header_functions()
-    assert header_prototype(name) == proto
-    assert hasattr(C.CDLL(_lib.LIB_PATH), name)
-    params = proto[proto.index("(") + 1:proto.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[name] == want
-    fn = getattr(_lib.lib(), name)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(name) == PROTOTYPES[name]
 
 
 def test_the_constants_of_the_header():
-    code = header_code()
+    code = boundary.header_code()
     assert re.search(r"#define\s+MMC_SLOT_CAVITY\s+MMC_SLOT_WIDOM\b", code)
     for name, value in (("MMC_CAVITY_MAX_RADII", 8), ("MMC_CAVITY_MAX_CAP", 255), ("MMC_CAVITY_MAX_BINS", 4096)):
         assert re.search(r"#define\s+%s\s+%d\b" % (name, value), code), name

@@ -51,7 +51,7 @@ def test_the_library_refuses_an_info_that_is_not_one():
 def test_state_info_mirror_has_the_headers_layout(tmp_path):
     import ctypes as C
     import subprocess
-    from test_abi import HEADER
+    from boundary import HEADER
     prog = tmp_path / "layout.c"
     prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mmc_hip.h"\nint main(void){\n'
                     'printf("%zu %zu %zu %zu %zu\\n", sizeof(mmc_state_info), offsetof(mmc_state_info, topology), '

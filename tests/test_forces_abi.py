@@ -2,46 +2,27 @@
 matching ctypes, loud on a NULL batch and on every argument that can be refused without a device,
 and the Python wrapper's own argument checks."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
-from metropolismontecarlo_amd import _lib
+import boundary
 from common import fake_batch
+from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_forces"
-PROTOTYPE = ("int32_t mmc_batch_forces(mmc_batch *b, int32_t n_sel, const int32_t *sel, const double *mass , "
-             "double *force_out , double *torque_out , double *vir_out , double *atom_out , double *fsum , "
-             "int64_t *n_flagged , uint8_t *ovl_out );")
-CTYPES = {"mmc_batch *": C.c_void_p, "int32_t": C.c_int32, "const int32_t *": C.POINTER(C.c_int32),
-          "const double *": C.POINTER(C.c_double), "double *": C.POINTER(C.c_double),
-          "int64_t *": C.POINTER(C.c_int64), "uint8_t *": C.POINTER(C.c_uint8)}
-
-
-def header_prototype():
-    from test_abi import HEADER
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
+PROTOTYPE = ("int32_t mmc_batch_forces(mmc_batch *b, int32_t n_sel, const int32_t *sel, const double *mass, "
+             "double *force_out, double *torque_out, double *vir_out, double *atom_out, double *fsum, "
+             "int64_t *n_flagged, uint8_t *ovl_out);")
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE          # (the blanks are where the header's comments were)
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+\s*$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
 
 
 def test_the_header_states_the_definition_with_its_reference_lines():
-    from test_abi import HEADER
-    src = open(HEADER).read()
+    src = boundary.header_text()
     sec = src[src.index("Forces and torques on every molecule"):src.index("int32_t mmc_batch_forces")]
     for cite in ("Ewald/energy.jl:946-1032", "energy.jl:254", "ewalds.jl:340", "boundaries.jl:8-14",
                  "energy.jl:270-281", "ewalds.jl:359-367", ":359-360", "ewalds.jl:538-604", ":829-833",
@@ -53,10 +34,7 @@ def test_the_header_states_the_definition_with_its_reference_lines():
 
 
 def test_the_julia_binding_calls_it():
-    from test_julia_binding import JL, julia_ccalls, ccall_mismatches
-    text = open(JL, encoding="utf-8").read()
-    assert NAME in {c[0] for c in julia_ccalls(text)}
-    assert not ccall_mismatches(text)
+    assert NAME in boundary.julia_bound()
 
 
 def call(b=None, sel=None, n_sel=0, mass=None, outputs=(True,) * 7):

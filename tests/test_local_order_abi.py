@@ -3,39 +3,21 @@ bound with matching ctypes, and loud on a NULL batch and on every argument that 
 without a device."""
 import ctypes as C
 import math
-import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_local_order"
 PROTOTYPE = ("int32_t mmc_batch_local_order(mmc_batch *b, double r_hb, double cos_hb, int32_t q_bins, "
              "int32_t per_replica, uint64_t *hb_hist, uint64_t *q_hist, double *q_sum, int32_t *nbr_out, "
              "double *q_out, uint8_t *hb_out);")
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32,
-          "uint64_t *": C.POINTER(C.c_uint64), "double *": C.POINTER(C.c_double),
-          "int32_t *": C.POINTER(C.c_int32), "uint8_t *": C.POINTER(C.c_uint8)}
-
-
-def header_prototype():
-    from test_abi import HEADER
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
 
 
 def call(b=None, r_hb=3.5, cos_hb=math.cos(math.radians(30.0)), q_bins=400, outputs=(True, True, True)):

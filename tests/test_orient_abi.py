@@ -2,42 +2,28 @@
 with matching ctypes, loud on a NULL batch and on every argument that can be refused without a
 device, and the Python wrapper's own check of `out`."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
+import boundary
+from boundary import header_define
+from common import fake_batch
 from metropolismontecarlo_amd import _lib
-from common import fake_batch, header_define
 
 NAME = "mmc_batch_orient_corr"
 PROTOTYPE = ("int32_t mmc_batch_orient_corr(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica, "
-             "int64_t *hist );")
-CTYPES = {"mmc_batch *": C.c_void_p, "int32_t": C.c_int32, "double": C.c_double, "int64_t *": C.POINTER(C.c_int64)}
+             "int64_t *hist);")
 SENTINEL = -0x0123456789abcdef
 
 
-def header_text():
-    from test_abi import HEADER
-    return open(HEADER).read()
-
-
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m and re.sub(r"\s+", " ", m.group(0)) == PROTOTYPE    # (the blank is where the header's comment was)
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+\s*$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
 
 
 def test_the_header_states_the_definition_and_its_constants():
-    src = header_text()
+    src = boundary.header_text()
     sec = src[src.index("Orientational pair correlations"):src.index("int32_t mmc_batch_orient_corr")]
     assert src.index("Structure observables") < src.index("Orientational pair correlations") < src.index("Local order")
     for cite in ("row (0,0) of mmc_batch_rdf_sites", "gr.jl:75-80", "mmc_batch_dipoles", "u = mu / sqrt(n^2)",
@@ -52,10 +38,7 @@ def test_the_header_states_the_definition_and_its_constants():
 
 
 def test_the_julia_binding_calls_it():
-    from test_julia_binding import JL, julia_ccalls, ccall_mismatches
-    text = open(JL, encoding="utf-8").read()
-    assert NAME in {c[0] for c in julia_ccalls(text)}
-    assert not ccall_mismatches(text)
+    assert NAME in boundary.julia_bound()
 
 
 def call(b=None, numbins=10, r_max=0.0, per_replica=0, hist=True):

@@ -1,25 +1,10 @@
 """CPU tests of the per-replica-box entry points (mmc_batch_set_boxes and the batched NPT move):
-declared, exported, bound, and loud on a bad handle without touching a device."""
+loud on a bad handle without touching a device.  (Declared, exported and bound: tests/test_abi.py.)"""
 import ctypes as C
 
 import pytest
 
 from metropolismontecarlo_amd import _lib
-
-NEW = ("mmc_batch_set_boxes", "mmc_batch_get_boxes", "mmc_batch_volume_trial_replicas",
-       "mmc_batch_volume_settle", "mmc_batch_run_npt_replicas", "mmc_batch_qq_table_replica")
-
-
-def test_per_box_symbols_are_declared_exported_and_bound():
-    from test_abi import header_functions
-    names = header_functions()
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in NEW:
-        assert n in names, n
-        assert hasattr(L, n), n
-        assert n in _lib.SIGNATURES, n
-        assert getattr(_lib.lib(), n).argtypes is not None, n
-
 
 def test_per_box_entry_points_fail_loudly_on_a_null_batch():
     L = _lib.lib()

@@ -7,45 +7,24 @@ import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_hbond_rings"
 PROTOTYPE = ("int32_t mmc_batch_hbond_rings(mmc_batch *b, double r_hb, double cos_hb, int32_t n_max, "
              "int32_t per_replica, uint64_t *ring_hist, uint64_t *member_hist, int64_t *stats, "
              "uint16_t *count_out, int64_t max_rings, int32_t *ring_out);")
-CTYPES = {"mmc_batch *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double,
-          "uint64_t *": C.POINTER(C.c_uint64), "int64_t *": C.POINTER(C.c_int64), "uint16_t *": C.POINTER(C.c_uint16),
-          "int32_t *": C.POINTER(C.c_int32)}
 COS30 = math.cos(math.radians(30.0))
 N = 40   # the size the untouched outputs are laid out for
 
 
-def header_text():
-    from test_abi import HEADER
-    return open(HEADER).read()
-
-
-def header_prototype():
-    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
-
-
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
 
 
 def test_the_header_states_the_limits_and_the_definitions():
-    text = header_text()
+    text = boundary.header_text()
     for name, value in (("MMC_RING_MAX_SIZE", 8), ("MMC_RING_MAX_DEG", 8), ("MMC_RING_STATS", 8),
                         ("MMC_RING_MEMBER_BINS", 33)):
         assert re.search(r"#define\s+%s\s+%d\b" % (name, value), text), name
@@ -99,15 +78,12 @@ def test_arguments_refused_without_a_device(kw, word):
 
 
 def test_the_julia_method_passes_the_prototypes_types():
-    """tests/test_julia_binding.py reads the ccall(...) form and knows no 16-bit pointer; this method is
-    written with the @ccall macro, so its argument types are held against the prototype here."""
-    from test_julia_binding import JL
-    text = re.sub(r"(?m)#[^\n]*$", "", open(JL, encoding="utf-8").read())
+    """boundary.julia_ccalls reads the ccall(...) form and boundary.C2J knows no 16-bit pointer; this
+    method is written with the @ccall macro, so its argument types are held against the prototype here."""
+    text = re.sub(r"(?m)#[^\n]*$", "", boundary.julia_text())
     m = re.search(r"@ccall libmmc\.%s\((.*?)\)::Int32\)" % NAME, text, flags=re.S)
     assert m, "MMCHip.jl does not call " + NAME
     types = re.findall(r"::((?:Ptr\{\w+\})|\w+)\s*(?:,|$)", re.sub(r"\s+", " ", m.group(1)))
-    julia = {"mmc_batch *": "Ptr{Cvoid}", "int32_t": "Int32", "int64_t": "Int64", "double": "Float64",
-             "uint64_t *": "Ptr{UInt64}", "int64_t *": "Ptr{Int64}", "uint16_t *": "Ptr{UInt16}", "int32_t *": "Ptr{Int32}"}
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    assert types == [julia[re.sub(r"\w+$", "", p).strip()] for p in params]
+    julia = dict(boundary.C2J, **{"uint16_t*": "Ptr{UInt16}"})
+    assert types == [julia[c] for c in boundary.header_prototypes()[NAME][1]]
     assert re.search(r"(?m)^function hbond_rings\(b::Batch;", text)

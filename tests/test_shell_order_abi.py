@@ -3,10 +3,10 @@ bound with matching ctypes, and loud on a NULL batch and on every argument that 
 without a device."""
 import ctypes as C
 import math
-import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_shell_order"
@@ -15,37 +15,19 @@ PROTOTYPE = ("int32_t mmc_batch_shell_order(mmc_batch *b, double r_list, double 
              "int32_t zeta_bins, double zeta_lo, double zeta_hi, int32_t per_replica, "
              "uint64_t *rank_hist, uint64_t *lsi_hist, uint64_t *ang_hist, uint64_t *zeta_hist, uint64_t *flagged, "
              "double *sums, int32_t *count_out, int32_t *nbr_out, double *lsi_out, double *zeta_out);")
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32,
-          "uint64_t *": C.POINTER(C.c_uint64), "double *": C.POINTER(C.c_double),
-          "int32_t *": C.POINTER(C.c_int32)}
 INF, NAN = float("inf"), float("nan")
 
 
-def header_prototype():
-    from test_abi import HEADER
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
-
-
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert len(want) == 25 and _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
+    assert len(boundary.header_prototypes()[NAME][1]) == 25
 
 
 def test_the_julia_binding_and_the_python_method_carry_it():
     import inspect
-    import os
     from metropolismontecarlo_amd.device import Batch
-    jl = open(os.path.join(os.path.dirname(_lib.__file__), "julia", "MMCHip.jl"), encoding="utf-8").read()
+    jl = boundary.julia_text()
     assert ":mmc_batch_shell_order" in jl and "function shell_order(" in jl
     sig = inspect.signature(Batch.shell_order)
     assert [(k, p.default) for k, p in sig.parameters.items()][1:] == [

@@ -2,10 +2,10 @@
 declared with the agreed prototypes, exported, bound with matching ctypes, and loud on a NULL batch
 and on every argument that can be refused without a device, in the documented order."""
 import ctypes as C
-import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 PROTOTYPES = {
@@ -21,40 +21,21 @@ PROTOTYPES = {
         "int32_t mmc_batch_rdf_solute(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica, "
         "uint64_t *hist);"),
 }
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32, "double *": C.POINTER(C.c_double),
-          "const double *": C.POINTER(C.c_double), "int32_t *": C.POINTER(C.c_int32), "uint8_t *": C.POINTER(C.c_uint8),
-          "uint64_t *": C.POINTER(C.c_uint64)}
-
-
-def header_prototype(name):
-    from test_solute_abi import header_code
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % name, header_code())
-    assert m, f"{name} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
 def test_symbols_are_declared_exported_and_bound_with_the_header_prototype(name):
-    from test_abi import header_functions
-    proto = PROTOTYPES[name]
-    assert name in header_functions()
-    assert header_prototype(name) == proto
-    assert hasattr(C.CDLL(_lib.LIB_PATH), name)
-    params = proto[proto.index("(") + 1:proto.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[name] == want
-    fn = getattr(_lib.lib(), name)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(name) == PROTOTYPES[name]
 
 
 def test_the_binding_and_the_julia_module_name_every_entry():
-    import os
     from metropolismontecarlo_amd import device
     for method in ("set_solute", "get_solute", "solute_energy", "rdf_solute"):
         assert callable(getattr(device.Batch, method))
-    jl = open(os.path.join(os.path.dirname(_lib.__file__), "julia", "MMCHip.jl"), encoding="utf-8").read()
+    bound = boundary.julia_bound()
     for name in PROTOTYPES:
-        assert f"(:{name}, libmmc)" in jl, name
+        assert name in bound, name
 
 
 def set_solute(b=None, S=2, n_sites=None, mol=1.0, charge=(0.4, -0.4), eps=50.0, sig=3.0):

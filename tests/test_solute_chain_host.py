@@ -16,7 +16,7 @@ from metropolismontecarlo_amd import _lib, checkpoint, observables, structs
 
 
 def test_solute_fields_sit_in_the_reserved_words_and_the_size_is_unchanged(tmp_path):
-    from test_abi import HEADER
+    from boundary import HEADER
     prog = tmp_path / "layout.c"
     prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mmc_hip.h"\nint main(void){\n'
                     'printf("%zu %zu %zu %zu %zu\\n", sizeof(mmc_state_info), offsetof(mmc_state_info, rigid_only), '

@@ -5,6 +5,7 @@ import ctypes as C
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAMES = ("mmc_batch_rdf_sites", "mmc_batch_dipoles")
@@ -33,10 +34,7 @@ def dipoles(b=None, dip=True):
 
 
 def test_the_julia_binding_calls_them():
-    from test_julia_binding import JL, julia_ccalls, ccall_mismatches
-    text = open(JL, encoding="utf-8").read()
-    assert set(NAMES) <= {c[0] for c in julia_ccalls(text)}
-    assert not ccall_mismatches(text)
+    assert set(NAMES) <= boundary.julia_bound()
 
 
 def test_a_null_batch_fails_loudly():

@@ -7,42 +7,24 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NEW = ("mmc_batch_set_temperatures", "mmc_batch_get_temperatures", "mmc_exchange_round", "mmc_batch_exchange",
        "mmc_batch_run_exchange")
 
 
-def test_tempering_symbols_are_declared_exported_and_bound():
-    from test_abi import header_functions
-    names = header_functions()
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in NEW:
-        assert n in names, n
-        assert hasattr(L, n), n
-        assert n in _lib.SIGNATURES, n
-        assert getattr(_lib.lib(), n).argtypes is not None, n
-
-
 def test_tempering_symbols_are_bound_in_julia_with_the_headers_arity():
-    from test_julia_binding import JL, ccall_mismatches, header_prototypes, julia_ccalls
-    text = open(JL, encoding="utf-8").read()
-    calls = {c[0]: c for c in julia_ccalls(text)}
-    protos = header_prototypes()
-    for n in NEW:
-        assert n in calls, f"{n} is not bound in MMCHip.jl"
-        _, ret, types, n_values = calls[n]
-        assert ret == "Int32" and len(types) == len(protos[n][1]) == n_values == len(_lib.SIGNATURES[n]), \
-            (n, types, protos[n])
-    assert not [m for m in ccall_mismatches(text) if any(n in m for n in NEW)]
+    """(With the header's arity and types: tests/test_julia_binding.py, for every ccall.)"""
+    assert set(NEW) <= boundary.julia_bound()
+    text = boundary.julia_text()
     for fn in ("set_temperatures!", "exchange!(b::Batch", "run_exchange!(b::Batch"):
         assert fn in text, fn
 
 
 def test_the_exchange_slot_is_the_headers_and_the_restatements():
-    from test_julia_binding import HEADER
     import tempering_ref
-    assert "#define MMC_SLOT_EXCHANGE 0x60000000u" in open(HEADER).read()
+    assert "#define MMC_SLOT_EXCHANGE 0x60000000u" in boundary.header_text()
     assert tempering_ref.SLOT_EXCHANGE == 0x60000000
 
 

@@ -2,44 +2,25 @@
 bound with matching ctypes, and loud on a NULL batch and on every argument that can be refused
 without a device."""
 import ctypes as C
-import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_volume_perturb"
-PROTOTYPE = ("int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *scale , "
-             "double temperature, double *boltz_sum , int64_t *n_overlap , double *du_out , "
-             "double *base_out );")
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32,
-          "const double *": C.POINTER(C.c_double), "double *": C.POINTER(C.c_double),
-          "int64_t *": C.POINTER(C.c_int64)}
-
-
-def header_prototype():
-    from test_abi import HEADER
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
+PROTOTYPE = ("int32_t mmc_batch_volume_perturb(mmc_batch *b, int32_t n_scale, const double *scale, "
+             "double temperature, double *boltz_sum, int64_t *n_overlap, double *du_out, "
+             "double *base_out);")
 
 
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE          # (the blanks are where the header's comments were)
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+\s*$", "", p).strip()] for p in params]
-    assert _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
 
 
 def test_the_header_states_the_definition_with_its_reference_lines():
-    from test_abi import HEADER
-    src = open(HEADER).read()
+    src = boundary.header_text()
     sec = src[src.index("Virtual volume moves"):src.index("int32_t mmc_batch_volume_perturb")]
     for cite in ("volumeChange.jl:62-80", "volumeChange.jl:129-130", "main.jl:290-291",
                  "Ewald/energy.jl:946-1032", "Ewald/ewalds.jl:45-103", "Ewald/ewalds.jl:829-833",

@@ -2,11 +2,10 @@
 with matching ctypes, carried by the Julia module and the Python class, and loud on a NULL batch
 and on every argument that can be refused without a device -- with the outputs untouched."""
 import ctypes as C
-import math
-import re
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NAME = "mmc_batch_voronoi"
@@ -15,38 +14,17 @@ PROTOTYPE = ("int32_t mmc_batch_voronoi(mmc_batch *b, double r_list, double area
              "uint64_t *vol_hist, uint64_t *eta_hist, uint64_t *face_hist, uint64_t *side_hist, uint64_t *nbr_hist, "
              "uint64_t *flagged, double *sums, "
              "double *vol_out, double *area_out, int32_t *faces_out, int32_t *nbr_out, double *face_area_out);")
-CTYPES = {"mmc_batch *": C.c_void_p, "double": C.c_double, "int32_t": C.c_int32,
-          "uint64_t *": C.POINTER(C.c_uint64), "double *": C.POINTER(C.c_double),
-          "int32_t *": C.POINTER(C.c_int32)}
 INF, NAN = float("inf"), float("nan")
 
 
-def header_text():
-    from test_abi import HEADER
-    return open(HEADER).read()
-
-
-def header_prototype():
-    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
-    m = re.search(r"int32_t\s+%s\s*\([^;]*;" % NAME, code)
-    assert m, f"{NAME} is not declared in mmc_hip.h"
-    return re.sub(r"\s+", " ", m.group(0))
-
-
 def test_symbol_is_declared_exported_and_bound_with_the_header_prototype():
-    from test_abi import header_functions
-    assert NAME in header_functions()
-    assert header_prototype() == PROTOTYPE
-    assert hasattr(C.CDLL(_lib.LIB_PATH), NAME)
-    params = PROTOTYPE[PROTOTYPE.index("(") + 1:PROTOTYPE.rindex(")")].split(", ")
-    want = [CTYPES[re.sub(r"\w+$", "", p).strip()] for p in params]
-    assert len(want) == 21 and _lib.SIGNATURES[NAME] == want
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == want and fn.restype is C.c_int32
+    """(Exported and bound with these types: tests/test_abi.py, for every function of the header.)"""
+    assert boundary.prototype_text(NAME) == PROTOTYPE
+    assert len(boundary.header_prototypes()[NAME][1]) == 21
 
 
 def test_the_header_states_the_constants_the_rule_and_the_limits():
-    text = header_text()
+    text = boundary.header_text()
     for word in ("#define MMC_VORONOI_CAP      64", "#define MMC_VORONOI_MAXV     16", "MMC_VORONOI_PRUNE, PRUNE = 1 + 2^-20",
                  "w = e(p_j) / (e(p_j) - e(q))", "K = 36.0 x 3.141592653589793", "biased low", "voronoi_prune"):
         assert word in text, word
@@ -54,10 +32,9 @@ def test_the_header_states_the_constants_the_rule_and_the_limits():
 
 def test_the_julia_binding_and_the_python_method_carry_it():
     import inspect
-    import os
     from metropolismontecarlo_amd import observables as obs
     from metropolismontecarlo_amd.device import Batch
-    jl = open(os.path.join(os.path.dirname(_lib.__file__), "julia", "MMCHip.jl"), encoding="utf-8").read()
+    jl = boundary.julia_text()
     assert ":mmc_batch_voronoi" in jl and "function voronoi(" in jl
     sig = inspect.signature(Batch.voronoi)
     assert [(k, p.default) for k, p in sig.parameters.items()][1:] == [

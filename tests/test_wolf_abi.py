@@ -5,39 +5,22 @@ import ctypes as C
 
 import pytest
 
+import boundary
 from metropolismontecarlo_amd import _lib
 
 NEW = ("mmc_batch_set_coulomb_style", "mmc_batch_get_coulomb_style", "mmc_batch_potential_wolf")
 
 
-def test_wolf_symbols_are_declared_exported_and_bound():
-    from test_abi import header_functions
-    names = header_functions()
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in NEW:
-        assert n in names, n
-        assert hasattr(L, n), n
-        assert n in _lib.SIGNATURES, n
-        assert getattr(_lib.lib(), n).argtypes is not None, n
-
-
 def test_wolf_symbols_are_bound_in_julia_with_the_headers_arity():
-    from test_julia_binding import JL, ccall_mismatches, header_prototypes, julia_ccalls
-    text = open(JL, encoding="utf-8").read()
-    calls = {c[0]: c for c in julia_ccalls(text)}
-    protos = header_prototypes()
-    for n in NEW:
-        assert n in calls, f"{n} is not bound in MMCHip.jl"
-        _, ret, types, n_values = calls[n]
-        assert ret == "Int32" and len(types) == len(protos[n][1]) == n_values, (n, types, protos[n])
-    assert not [m for m in ccall_mismatches(text) if any(n in m for n in NEW)]
+    """(With the header's arity and types: tests/test_julia_binding.py, for every ccall.)"""
+    assert set(NEW) <= boundary.julia_bound()
+    text = boundary.julia_text()
     for fn in ("set_coulomb_style!", "coulomb_style", "potential_wolf(b::Batch)"):
         assert fn in text, fn
 
 
 def test_the_style_constants_are_the_headers():
-    from test_julia_binding import HEADER
-    src = open(HEADER).read()
+    src = boundary.header_text()
     assert "enum { MMC_COULOMB_EWALD = 0, MMC_COULOMB_WOLF = 1 };" in src
     from metropolismontecarlo_amd.device import Batch
     assert Batch.COULOMB_STYLES == ("ewald", "wolf")      # index == the enum's value
