@@ -902,7 +902,55 @@ int32_t mmc_batch_widom_solute_at(mmc_batch *b, int32_t n_sites, const double *c
  *     ceil(r / dr), dr and the r_max rule exactly mmc_batch_rdf_sites'; a distance with 1 <= bin <=
  *     numbins is counted at [bin - 1] (a site exactly on the point is not counted).  hist is
  *     overwritten.  Arguments and preconditions as mmc_batch_rdf_sites; MMC_ERR_STATE without a
- *     solute.  Read-only. */
+ *     solute.  Read-only.
+ *   mmc_batch_hydration_map: the solute-centred maps, the first-order terms of grid inhomogeneous
+ *     solvation theory.  The solute is fixed and the same in every replica, so the laboratory frame is
+ *     its frame and one grid takes the waters of all replicas; nothing is aligned.  int64 maps
+ *     [n_ch][cells + 2] (per_replica == 0, summed over the replicas) or [R][n_ch][cells + 2], n_ch =
+ *     popcount(channel_mask), the channels in rising bit order, cells = (2 n_half)^3.  maps is
+ *     overwritten, not accumulated, and untouched on any error.  Everything below is unfused fp64 in the
+ *     order written, with IEEE sqrt and divide, dot(a,b) = (a.x b.x + a.y b.y) + a.z b.z
+ *     (tests/hydration_map_ref.py restates it).
+ *     Grid: a cube on the laboratory axes centred on the solute's reference point c (mol[S]).  Edges
+ *       e_k = (double)k * cell, k = -n_half .. n_half; a coordinate p lies in cell k when
+ *       e_k <= p < e_k+1, stored at index k + n_half; flat index (ix g + iy) g + iz with g = 2 n_half:
+ *       mmc_batch_sdf's cell rule without folding.  A deposit with any coordinate in no cell is
+ *       `outside`; a NaN counts as outside.
+ *     Position of a water site w: x = w - c per component (water minus solute), then the image of
+ *       mmc_batch_rdf_solute with the batch's box L: |x| > L / 2 (strict) moves x by one box.
+ *     Channels.  Bits 0, 1, 2 (counts): every water deposits 1 at the cell of its slot-a site, a = 0, 1,
+ *       2, each site with its own image.  Bits 3, 4, 5 (orientation): every water deposits Q30(e_z.x),
+ *       Q30(e_z.y), Q30(e_z.z) at the cell of its slot-0 site; e_z is the unit bisector exactly as
+ *       mmc_batch_sdf defines it: o_a = vector1D(s0, s_a), b = o1 + o2, nb2 = dot(b,b), e_z = b /
+ *       sqrt(nb2); Q30(v) = v * 2^30 rounded to nearest, ties to even.  A water with nb2 zero or not
+ *       finite has no frame: it deposits nothing and is counted in the channel's last slot.  Bit 6 is
+ *       Q20(u_lj), bit 7 Q20(u_real), Q20(u) = u * 2^20 rounded likewise, deposited at the cell of the
+ *       slot-0 site: the water's own pair energy with the solute in K by the definitions above (the COM
+ *       gates on c, the slack cutoffs, eps > 0.001, the batch's erfc table), a fresh accumulator per
+ *       water over the sites 0 .. S - 1 in order, u_lj = (0.0 + sum_lj) * 4 and u_real = factor * (0.0 +
+ *       sum_qq): the summands of mmc_batch_solute_energy.  A water is `flagged` if it overlaps the
+ *       solute, if u_lj or u_real is not finite, or if either has magnitude >= 2^20 K; a flagged water
+ *       deposits into neither energy channel and is counted in the last slot of both.  With an
+ *       uncharged solute u_real = 0 for every water and the erfc table is not read.
+ *     Tail slots of every channel: slot `cells` holds the same quantity summed over the deposits that
+ *       fell outside the cube; slot cells + 1 the number of waters left out (no frame for channels 3-5,
+ *       flagged for 6-7, always 0 for 0-2).  So per replica a count channel sums to N exactly.  All sums
+ *       are 64-bit integers added modulo 2^64: the result does not depend on the grid of the launch,
+ *       on option "wave_wgs", on which channels are requested together or on the order of atomics.
+ *     Checks, in this order.  MMC_ERR_ARG without looking at the batch: NULL maps; n_half < 1; cell not
+ *       finite or <= 0; channel_mask outside 1..255; (2 n_half)^3 > MMC_HMAP_MAX_CELLS (n_half <= 12).
+ *       Then the batch (NULL: MMC_ERR_ARG); MMC_ERR_STATE while proposals or a volume trial are
+ *       outstanding; MMC_ERR_STATE without a solute; MMC_ERR_ARG when (double)n_half * cell > L / 2 (the
+ *       cube would reach a second image).  Read-only: S(k), the streams and mmc_state_info are not
+ *       touched.  The per-replica output is one device allocation of R n_ch (cells + 2) words; a
+ *       device that cannot make it fails the call with the allocation's status (the call is not cut
+ *       into chunks of replicas).
+ *     observables.hydration_density, _polarisation, _energy, _radial_average turn the maps into g(x, y,
+ *     z), <e_z>, the mean u_sw per water and per volume, and shell averages. */
+#define MMC_HMAP_CHANNELS 8
+#define MMC_HMAP_MAX_CELLS 16384      /* 64-bit cells in 128 KB of a workgroup's LDS */
+#define MMC_HMAP_VEC_SCALE 1073741824.0 /* 2^30 */
+#define MMC_HMAP_E_SCALE   1048576.0    /* 2^20, = MMC_PAIRE_SCALE */
 int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const double *mol, const double *charge,
                              const double *eps, const double *sig);
 int32_t mmc_batch_get_solute(mmc_batch *b, int32_t *n_sites, double *mol, double *charge, double *eps,
@@ -910,6 +958,8 @@ int32_t mmc_batch_get_solute(mmc_batch *b, int32_t *n_sites, double *mol, double
 int32_t mmc_batch_solute_energy(mmc_batch *b, double *u_lj, double *u_real, uint8_t *ovl);
 int32_t mmc_batch_rdf_solute(mmc_batch *b, int32_t numbins, double r_max, int32_t per_replica,
                              uint64_t *hist);
+int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double cell, int32_t channel_mask,
+                                int32_t per_replica, int64_t *maps);
 
 /* ---- Solute pairs: potentials of mean force at infinite dilution ------------------------------------
  * How two foreign solutes A and B interact through the solvent -- the methane-methane contact and

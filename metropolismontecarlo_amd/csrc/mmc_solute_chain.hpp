@@ -15,6 +15,9 @@
 //   k_solute_total  per replica: the water-solute LJ, virial and real-space sums and the overlap flag.
 //   k_rdf_solute    solute-water pair histograms, from c and from every site, against the three water
 //                   slots, in mmc_batch_rdf_sites' arithmetic.
+//   k_hydration_map the solute-centred 3-D maps: where the waters' sites sit around the solute, which
+//                   way the waters point there and what each place adds to the water-solute energy
+//                   (at the end of this file).
 // One site against one water is solute_site_water(), the same for the moves and the totals.
 //
 // Lane layout of k_solute_move: a row of 16 lanes per replica, lane a of the row = site a, four
@@ -25,6 +28,7 @@
 #pragma once
 #include "mmc_solute.hpp"
 #include "mmc_struct.hpp"
+#include "mmc_sdf.hpp"
 
 #define SOLC_BLOCK 256                     // threads per workgroup of k_solute_move: 16 replicas
 #define SOLC_PAR_DOUBLES (SOL_MAX_SITES * SOL_PAR + 4) // device block: [S][SOL_PAR], then c at [16 * SOL_PAR]
@@ -248,5 +252,142 @@ __global__ __launch_bounds__(SOLC_WAVES * 64) void k_rdf_solute(BatchView bv, co
             }
             __syncthreads();
         }
+    }
+}
+
+// ---- k_hydration_map: the solute-centred maps of mmc_batch_hydration_map -------------------------------
+// The solute is fixed and the same in every replica, so the laboratory frame is its frame: one cube of
+// (2 n_half)^3 cells on the laboratory axes, centred on the reference point c, takes the deposits of all
+// replicas.  A workgroup of HMAP_THREADS threads takes the replicas g, g + gridDim.x, ... and runs one
+// PASS per requested channel over them: thread t the waters t, t + HMAP_THREADS, ..., each water one
+// deposit -- 1, Q30 of a component of e_z, or Q20 of its pair energy with the solute -- at the cell of
+// one of its sites.  x = st_image(site - c) per component; the cell is sd_cell's (mmc_sdf.hpp: a float
+// estimate corrected by two compares against the host's edges in LDS, -1 or n beyond the cube and for a
+// NaN, no branch on the cell).  The grid is ONE array of 64-bit words per workgroup in LDS (128 KB at
+// MMC_HMAP_MAX_CELLS), added to with workgroup-scope LDS atomics; summed output keeps it across all the
+// workgroup's replicas of a pass and flushes its non-zero cells once with 64-bit global atomics,
+// per-replica output flushes after every replica.  The two tail slots (the deposits outside the cube;
+// the waters left out) are kept per thread, added over the wave at the flush, one global atomic a wave.
+// Every sum is of 64-bit integers modulo 2^64: no grid, "wave_wgs", set of channels or order of atomics
+// changes a bit.  Dynamic LDS: 8 (2 n_half + 1) + 8 n_cells bytes.
+#define HMAP_THREADS 1024       // the largest workgroup: 16 waves, 4 per SIMD, at most 128 VGPRs a lane
+#define HMAP_U_MAX 1048576.0    // a water's energy of this magnitude (2^20 K) or beyond is flagged
+static_assert(8 * MMC_HMAP_MAX_CELLS == 131072, "MMC_HMAP_MAX_CELLS is what 128 KB of LDS hold");
+static_assert(MMC_HMAP_CHANNELS == 8, "channels: three counts, three components of e_z, two energies");
+
+struct HmapArgs {
+    const double *edge;        // [2 n_half + 1]: e_k = (double)k * cell, built by the host
+    unsigned long long *maps;  // [n_ch][n_cells + 2] or [R][n_ch][n_cells + 2], zeroed by the host
+    int32_t n_half, n_cells, channel_mask, per_replica;
+    float inv_cell;
+    int32_t R;
+};
+
+// the sum over the 64 lanes, in every lane (integers: any order)
+__device__ __forceinline__ long long hm_wave_sum(long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays.
+// grid: at most R workgroups of HMAP_THREADS threads.
+template <bool REC>
+__global__ __launch_bounds__(HMAP_THREADS) void k_hydration_map(BatchView bv, const double *__restrict__ rec, SoluteView sv,
+                                                                const double *__restrict__ qq_tab, FastConsts fc,
+                                                                PairParams pp, HmapArgs ha)
+{
+    extern __shared__ __align__(16) unsigned char hm_lds[];
+    const int n_edge = 2 * ha.n_half + 1, n_cells = ha.n_cells, tid = threadIdx.x;
+    double *const edge = reinterpret_cast<double *>(hm_lds);
+    unsigned long long *const cells = reinterpret_cast<unsigned long long *>(hm_lds + 8 * n_edge);
+    tile_prologue(edge, ha.edge, n_edge, cells, n_cells);
+
+    const SdfAxis ax = sd_axis(ha.n_half, false);
+    const int S = sv.n_sites, n_mol = bv.n_mol;
+    const double cx = sv.par[SOLC_C], cy = sv.par[SOLC_C + 1], cz = sv.par[SOLC_C + 2];
+    const BoxConsts bc = box_consts(bv.box);
+    const double half = bv.box / 2.0, neg_box = -bv.box;
+    const int64_t row_len = (int64_t)n_cells + 2;
+    const int n_ch = __popc((unsigned)ha.channel_mask);
+    long long t_out = 0, t_left = 0; // of this thread since the last flush
+
+    // the grid and the threads' tails added to one row of the output, and cleared
+    auto flush = [&](unsigned long long *dst) {
+        __syncthreads();
+        for (int q = tid; q < n_cells; q += HMAP_THREADS) {
+            const unsigned long long v = cells[q];
+            if (v != 0ull) {
+                atomicAdd(&dst[q], v);
+                cells[q] = 0ull;
+            }
+        }
+        const long long s_out = hm_wave_sum(t_out), s_left = hm_wave_sum(t_left);
+        if ((tid & 63) == 0) {
+            if (s_out != 0)
+                atomicAdd(&dst[n_cells], (unsigned long long)s_out);
+            if (s_left != 0)
+                atomicAdd(&dst[n_cells + 1], (unsigned long long)s_left);
+        }
+        t_out = 0;
+        t_left = 0;
+        __syncthreads();
+    };
+
+    int ci = 0; // the channel's row among those requested
+    for (int ch = 0; ch < MMC_HMAP_CHANNELS; ch++) { // (ch, r and the branches on them are uniform over the workgroup)
+        if (!((ha.channel_mask >> ch) & 1))
+            continue;
+        for (int r = blockIdx.x; r < ha.R; r += gridDim.x) {
+            for (int j = tid; j < n_mol; j += HMAP_THREADS) {
+                double sx, sy, sz; // the site whose cell takes the deposit
+                long long val = 1;
+                bool on = true;    // false: the water is left out and counted in the last slot
+                if (ch < 6) {
+                    double w[9];
+                    load_sites9<REC>(bv, rec, r, j, w);
+                    sx = ch == 1 ? w[3] : ch == 2 ? w[6] : w[0];
+                    sy = ch == 1 ? w[4] : ch == 2 ? w[7] : w[1];
+                    sz = ch == 1 ? w[5] : ch == 2 ? w[8] : w[2];
+                    if (ch >= 3) { // e_z as sd_molecule (mmc_sdf.hpp) forms it
+                        double bb[3];
+#pragma unroll
+                        for (int d = 0; d < 3; d++)
+                            bb[d] = vector1D(w[d], w[3 + d], bc) + vector1D(w[d], w[6 + d], bc);
+                        const double nb2 = sd_dot(bb[0], bb[1], bb[2], bb[0], bb[1], bb[2]);
+                        const double nb = sqrt(nb2);
+                        const double ez = (ch == 3 ? bb[0] : ch == 4 ? bb[1] : bb[2]) / nb;
+                        on = nb2 > 0.0 && nb2 < INFINITY; // (false for a NaN)
+                        val = (long long)rint(on ? ez * MMC_HMAP_VEC_SCALE : 0.0);
+                    }
+                } else {
+                    double w[12];
+                    load_sites12<REC>(bv, rec, r, j, w);
+                    sx = w[0]; sy = w[1]; sz = w[2];
+                    SolAcc acc = { 0.0, 0.0, 0.0, false };
+                    for (int a = 0; a < S; a++)
+                        solute_site_water(sv.par + SOL_PAR * a, cx, cy, cz, w, qq_tab, fc, pp, sv.charged != 0, bc, acc);
+                    const double u_lj = (0.0 + acc.lj) * 4, u_real = bv.factor * (0.0 + acc.qq); // mmc_batch_solute_energy's
+                    on = !acc.ov && fabs(u_lj) < HMAP_U_MAX && fabs(u_real) < HMAP_U_MAX; // (false for a NaN)
+                    val = (long long)rint(on ? (ch == 6 ? u_lj : u_real) * MMC_HMAP_E_SCALE : 0.0);
+                }
+                const int ix = sd_cell(edge, ax, st_image(sx - cx, half, neg_box), ha.inv_cell);
+                const int iy = sd_cell(edge, ax, st_image(sy - cy, half, neg_box), ha.inv_cell);
+                const int iz = sd_cell(edge, ax, st_image(sz - cz, half, neg_box), ha.inv_cell);
+                const bool in = (unsigned)ix < (unsigned)ax.n && (unsigned)iy < (unsigned)ax.n && (unsigned)iz < (unsigned)ax.n;
+                if (on && in)
+                    __hip_atomic_fetch_add(&cells[(ix * ax.n + iy) * ax.n + iz], (unsigned long long)val, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                t_out += (on && !in) ? val : 0;
+                t_left += on ? 0 : 1;
+            }
+            if (ha.per_replica)
+                flush(ha.maps + ((int64_t)r * n_ch + ci) * row_len);
+        }
+        if (!ha.per_replica)
+            flush(ha.maps + (int64_t)ci * row_len);
+        ci++;
     }
 }

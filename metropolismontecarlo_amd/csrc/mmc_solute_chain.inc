@@ -1,8 +1,9 @@
 // mmc_solute_chain.inc -- host side of the batch's fixed solute (include/mmc_hip.h, "A fixed solute";
 // the kernels are in mmc_solute_chain.hpp): setting and reading it, its part of RecipLong and of the
-// totals, and the two observables that need it.  What the move driver does with it is three lines of
-// mmc_batch.inc / mmc_engine.inc: batch_launch enqueues k_solute_move in front of the move kernel, and
-// collect / mmc_batch_eval read one more record per move.  Included by mmc_hip.hip after mmc_units.inc.
+// totals, and the three observables that need it (the pair energy, the radial histograms, the 3-D
+// maps).  What the move driver does with it is three lines of mmc_batch.inc / mmc_engine.inc:
+// batch_launch enqueues k_solute_move in front of the move kernel, and collect / mmc_batch_eval read one
+// more record per move.  Included by mmc_hip.hip after mmc_units.inc.
 
 // S >= 1: the arguments of a solute, in mmc_batch_widom_solute_at's order; none of it needs a batch
 static int32_t solute_chain_args(int32_t S, const double *mol, const double *charge, const double *eps, const double *sig,
@@ -234,5 +235,71 @@ extern "C" int32_t mmc_batch_rdf_solute(mmc_batch *b, int32_t numbins, double r_
             s.bv, s.rec, b->sol.view(), ra); // (a workgroup per replica; 12 numbins <= 24 KiB of LDS)
     oc.launched();
     oc.fetch(hist, ra.hist, hist_bytes);
+    return oc.finish(what);
+}
+
+extern "C" int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double cell, int32_t channel_mask,
+                                           int32_t per_replica, int64_t *maps)
+{
+    const char *what = "mmc_batch_hydration_map";
+    // what can be refused without the batch comes first
+    MMC_REQUIRE(maps, MMC_ERR_ARG, "%s: NULL out pointer", what);
+    MMC_REQUIRE(n_half >= 1, MMC_ERR_ARG, "%s: n_half must be >= 1", what);
+    MMC_REQUIRE(std::isfinite(cell) && cell > 0.0, MMC_ERR_ARG, "%s: cell must be finite and > 0", what);
+    MMC_REQUIRE(channel_mask >= 1 && channel_mask < (1 << MMC_HMAP_CHANNELS), MMC_ERR_ARG, "%s: channel_mask outside 1..%d",
+                what, (1 << MMC_HMAP_CHANNELS) - 1);
+    MMC_REQUIRE(n_half <= 12 && 8 * (int64_t)n_half * n_half * n_half <= MMC_HMAP_MAX_CELLS, MMC_ERR_ARG,
+                "%s: the grid has more than %d cells", what, MMC_HMAP_MAX_CELLS);
+    BATCH_CHECK(b);
+    DeviceSystem &s = b->sys;
+    STRUCT_STATE(b);
+    MMC_REQUIRE(b->sol.n > 0, MMC_ERR_STATE, "%s: no solute is set (mmc_batch_set_solute)", what);
+    // (one box and Ewald style: mmc_batch_set_solute fences the rest)
+    MMC_REQUIRE(!((double)n_half * cell > s.bv.box / 2.0), MMC_ERR_ARG,
+                "%s: n_half cell = %g exceeds half of the box %g: the cube would reach a second image", what,
+                (double)n_half * cell, s.bv.box);
+    const int n_edge = 2 * n_half + 1;
+    const int64_t n_cells = 8 * (int64_t)n_half * n_half * n_half;
+    const size_t lds = 8 * (size_t)n_edge + 8 * (size_t)n_cells;
+    MMC_REQUIRE((int64_t)lds + 64 <= s.lds_per_block, MMC_ERR_UNSUPPORTED,
+                "%s: the device grants %lld bytes of LDS per workgroup, %lld cells need %zu", what,
+                (long long)s.lds_per_block, (long long)n_cells, lds + 64);
+    std::vector<double> edge((size_t)n_edge);
+    for (int k = -n_half; k <= n_half; k++)
+        edge[(size_t)(k + n_half)] = (double)k * cell;
+
+    const size_t R = (size_t)s.R;
+    const size_t n_ch = (size_t)__builtin_popcount((unsigned)channel_mask);
+    const size_t map_bytes = sizeof(unsigned long long) * (per_replica ? R : 1) * n_ch * (size_t)(n_cells + 2);
+    ObsCall oc(b);
+    const size_t o_maps = oc.take(map_bytes), o_edge = oc.take(sizeof(double) * edge.size());
+    MMC_TRY(oc.alloc()); // (the per-replica output in one piece: the allocation's status if the device has no room)
+    HmapArgs ha{};
+    ha.edge = oc.at<double>(o_edge);
+    ha.maps = oc.at<unsigned long long>(o_maps);
+    ha.n_half = n_half;
+    ha.n_cells = (int32_t)n_cells;
+    ha.channel_mask = channel_mask;
+    ha.per_replica = per_replica ? 1 : 0;
+    ha.inv_cell = (float)(1.0 / cell);
+    ha.R = (int32_t)R;
+    const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
+    const bool use_rec = struct_use_rec(b);
+    if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_sdf_wave
+        oc.e = hipFuncSetAttribute(use_rec ? reinterpret_cast<const void *>(k_hydration_map<true>)
+                                           : reinterpret_cast<const void *>(k_hydration_map<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
+    oc.zero(map_bytes);
+    oc.to_device(oc.at<double>(o_edge), edge.data(), sizeof(double) * edge.size());
+    // one workgroup of sixteen waves per compute unit (its grid may take 128 KB of the unit's LDS), a replica at a time
+    const unsigned wgs = obs_grid(b, HMAP_THREADS / 64, (int64_t)R * (HMAP_THREADS / 64));
+    if (oc.e == hipSuccess) {
+        if (use_rec)
+            k_hydration_map<true><<<wgs, HMAP_THREADS, lds, oc.st>>>(s.bv, s.rec, b->sol.view(), s.qq_tab, s.fc, pp, ha);
+        else
+            k_hydration_map<false><<<wgs, HMAP_THREADS, lds, oc.st>>>(s.bv, nullptr, b->sol.view(), s.qq_tab, s.fc, pp, ha);
+    }
+    oc.launched();
+    oc.fetch(maps, ha.maps, map_bytes);
     return oc.finish(what);
 }

@@ -777,6 +777,38 @@ class Batch(_Handle):
         check(self._L.mmc_batch_rdf_solute(self._h, int(numbins), float(r_max), int(bool(per_replica)), _ptr(out)))
         return out
 
+    HYDRATION_CHANNELS = ("O", "H1", "H2", "px", "py", "pz", "u_lj", "u_real")
+
+    def hydration_map(self, n_half, cell, channels=255, per_replica=False, out=None):
+        """mmc_batch_hydration_map: the maps of the water around the fixed solute on a cube of
+        (2 n_half)^3 cells of edge `cell` on the laboratory axes, centred on the solute's reference
+        point.  `channels`: a mask (bit k = channel k) or an iterable of names among "O", "H1", "H2"
+        (counts of the three water slots), "px", "py", "pz" (sums of the unit bisector's components
+        in units of 2^-30, at the O's cell), "u_lj", "u_real" (sums of the water's pair energy with
+        the solute in units of 2^-20 K, at the O's cell).  Returns int64 [n_ch, cells + 2], summed over
+        the replicas, or [R, n_ch, cells + 2] with per_replica: the requested channels in rising bit
+        order; slot `cells` holds the deposits outside the cube, slot cells + 1 the number of waters
+        left out (no bisector; an overlap or an energy beyond 2^20 K).  observables.hydration_density,
+        hydration_polarisation, hydration_energy and hydration_radial_average take its rows.  `out`
+        (that shape, int64, contiguous) is overwritten and returned."""
+        if isinstance(channels, (int, np.integer)):
+            mask = int(channels)
+        else:
+            names = [channels] if isinstance(channels, str) else list(channels)
+            unknown = [c for c in names if c not in self.HYDRATION_CHANNELS]
+            if unknown:
+                raise ValueError(f"channels: {unknown} are not among {self.HYDRATION_CHANNELS}")
+            mask = sum({1 << self.HYDRATION_CHANNELS.index(c) for c in names})
+        n = max(int(n_half), 0)
+        cells = (2 * n) ** 3
+        n_ch = bin(mask & 255).count("1")   # (arguments the library refuses still get an array to leave alone)
+        shape = (n_ch, cells + 2)
+        if out is None and cells > 16384:   # (a grid the library refuses: two slots a channel, not cells + 2)
+            shape = (n_ch, 2)
+        out = _output(out, (self.R,) + shape if per_replica else shape, np.int64)
+        check(self._L.mmc_batch_hydration_map(self._h, int(n_half), float(cell), mask, int(bool(per_replica)), _ptr(out)))
+        return out
+
     def pair_sums(self, sums, K):
         """The six accumulators of widom_pair: a dict (or None = new zero arrays) with boltz_a (R,),
         n_zero_a (R,), boltz_b, boltz_ab (R, K), n_zero_b, n_zero_ab (R, K)."""

@@ -785,6 +785,27 @@ function rdf_solute(b::Batch, numbins::Integer, r_max::Float64 = 0.0, per_replic
     return hist
 end
 
+"""
+    hydration_map(b, n_half, cell, channel_mask, per_replica) -> maps
+
+The solute-centred maps of the water around the fixed solute (`mmc_batch_hydration_map`): Int64
+[cells + 2, n_ch] (column-major: C's [n_ch][cells + 2]) with cells = (2 n_half)^3 and n_ch =
+count_ones(channel_mask), with `per_replica` one such block per replica.  Bits 0..2 of the mask: counts
+of the three water slots; 3..5: sums of the unit bisector's components in units of 2^-30; 6, 7: sums of
+the water-solute LJ and real-space energy in units of 2^-20 K.  The last two entries of a channel: the
+deposits outside the cube, and the waters left out.
+"""
+function hydration_map(b::Batch, n_half::Integer, cell::Float64, channel_mask::Integer = 255,
+                       per_replica::Bool = false)
+    1 <= n_half <= 12 && 1 <= channel_mask <= 255 || error("n_half: 1..12, channel_mask: 1..255")
+    n_ch, len = count_ones(channel_mask), (2 * n_half)^3 + 2
+    maps = per_replica ? zeros(Int64, len, n_ch, b.n_replicas) : zeros(Int64, len, n_ch)
+    check(ccall((:mmc_batch_hydration_map, libmmc), Int32,
+                (Ptr{Cvoid}, Int32, Float64, Int32, Int32, Ptr{Int64}),
+                b.h, n_half, cell, channel_mask, per_replica ? 1 : 0, maps))
+    return maps
+end
+
 # ---- solute pairs (include/mmc_hip.h, mmc_batch_widom_pair / mmc_batch_widom_pair_at) -----------------
 """
     widom_pair!(b, A, B, eps_ab, sig_ab, d, n_insert, seed, draw0, temperature, sums)

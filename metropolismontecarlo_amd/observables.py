@@ -82,6 +82,91 @@ def coordination_number(row, n_frames, dr, r_shell=None):
     return n[..., k - 1] if k > 0 else np.zeros(row.shape[:-1])
 
 
+# ---- maps around a fixed solute (include/mmc_hip.h, mmc_batch_hydration_map) -----------------------
+HMAP_VEC_SCALE = 2.0 ** 30  # MMC_HMAP_VEC_SCALE: one unit of the orientation channels
+HMAP_E_SCALE = 2.0 ** 20    # MMC_HMAP_E_SCALE: one unit of the energy channels, in K
+
+
+def _hmap_cube(row):
+    """The cells of rows [..., cells + 2] of Batch.hydration_map as [..., g, g, g] floats (the two
+    tail slots dropped)."""
+    row = np.asarray(row)
+    cells = row.shape[-1] - 2
+    g = int(round(max(cells, 0) ** (1.0 / 3.0)))
+    if cells < 8 or g * g * g != cells or g % 2:
+        raise ValueError("a row of Batch.hydration_map has (2 n_half)^3 + 2 entries")
+    return row[..., :cells].astype(float).reshape(row.shape[:-1] + (g, g, g))
+
+
+def hydration_map_centres(n_half, cell):
+    """The centres of the cells of Batch.hydration_map's cube relative to the solute's reference
+    point, [g, g, g, 3] with g = 2 n_half: cell (ix, iy, iz) spans (i - n_half) cell <= p <
+    (i - n_half + 1) cell along each axis."""
+    ax = (np.arange(-int(n_half), int(n_half)) + 0.5) * float(cell)
+    return np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), axis=-1)
+
+
+def hydration_density(count_row, frames, n_mol, volume, cell):
+    """g(x, y, z) of one count row [..., cells + 2] of Batch.hydration_map ("O", "H1" or "H2"):
+    count / (frames n_mol / volume cell^3), the local density of that site over its bulk density;
+    frames = replicas x samples accumulated into the row.  An ideal gas gives 1 in every cell.
+    Returns [..., g, g, g]."""
+    ideal = float(frames) * float(n_mol) / float(volume) * float(cell) ** 3
+    return _hmap_cube(count_row) / ideal
+
+
+def hydration_polarisation(vec_rows, count_O):
+    """<e_z> per cell from the rows "px", "py", "pz" ([3, cells + 2]) and the "O" row of
+    Batch.hydration_map: the mean unit bisector (it points from the O towards the hydrogens) of the
+    waters whose O lies in the cell, [g, g, g, 3]; NaN exactly where the cell is empty.  (A water
+    without a bisector is in count_O and in no orientation sum; the map's last slot counts them.)"""
+    v = _hmap_cube(vec_rows)
+    if v.shape[0] != 3 or v.ndim != 4:
+        raise ValueError("vec_rows must be the three orientation rows [3, cells + 2]")
+    n = _hmap_cube(count_O)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = np.moveaxis(v, 0, -1) / HMAP_VEC_SCALE / n[..., None]
+    p[n == 0] = np.nan
+    return p
+
+
+def hydration_energy(u_rows, count_O, cell, frames):
+    """The water-solute energy per cell from the rows "u_lj" and / or "u_real" ([k, cells + 2] or one
+    row; several are added) and the "O" row of Batch.hydration_map.  Returns (per_water, per_volume):
+    the mean u_sw in K of a water whose O lies in the cell (NaN where the cell is empty) and the
+    energy density <u_sw> in K per A^3 of the cell; per_volume.sum() cell^3 is the share of <u_sw> per
+    frame that the cube holds.  frames = replicas x samples accumulated into the rows."""
+    u = _hmap_cube(np.atleast_2d(np.asarray(u_rows))).sum(0) / HMAP_E_SCALE
+    n = _hmap_cube(count_O)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_water = u / n
+    per_water[n == 0] = np.nan
+    return per_water, u / (float(frames) * float(cell) ** 3)
+
+
+def hydration_radial_average(row, n_half, cell, dr):
+    """The average of a map over shells of cell centres: `row` [cells + 2] of Batch.hydration_map or a
+    cube [g, g, g] (a density, say), shell k = the cells whose centre lies at k dr <= r < (k + 1) dr
+    from the reference point, out to the inscribed sphere n_half cell.  Returns (r, mean, n_cells): the
+    shell mid-points, the mean over each shell's cells (NaN for a shell without a centre; NaN cells
+    are skipped) and the number of cells averaged."""
+    a = np.asarray(row)
+    g = 2 * int(n_half)
+    cube = _hmap_cube(a) if a.ndim == 1 else a.astype(float)
+    if cube.shape != (g, g, g):
+        raise ValueError("row does not belong to a cube of (2 n_half)^3 cells")
+    c = hydration_map_centres(n_half, cell)
+    r = np.sqrt((c * c).sum(-1))
+    nb = max(int(np.floor(int(n_half) * float(cell) / float(dr) * (1.0 + 1e-12))), 1)
+    k = np.floor(r / float(dr)).astype(np.int64)
+    ok = (k < nb) & np.isfinite(cube)
+    tot = np.bincount(k[ok], weights=cube[ok], minlength=nb)
+    cnt = np.bincount(k[ok], minlength=nb)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(cnt > 0, tot / cnt, np.nan)
+    return (np.arange(nb) + 0.5) * float(dr), mean, cnt
+
+
 def dielectric_constant(M, temperature, volume, factor):
     """Static dielectric constant from the fluctuation of the total dipole moment under the
     conducting (tinfoil) boundary of the Ewald sum:
