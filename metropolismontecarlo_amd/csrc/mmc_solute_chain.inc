@@ -284,6 +284,9 @@ extern "C" int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double 
     ha.inv_cell = (float)(1.0 / cell);
     ha.R = (int32_t)R;
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
+    // (always true here: mmc_batch_set_solute requires fast_ok, which implies the records of a homogeneous
+    // batch, and everything that could clear it -- a volume change, per-replica boxes, Wolf style -- is fenced
+    // while a solute is set.  k_hydration_map<false> is kept for the scaffold's shape, not reached, and has no test.)
     const bool use_rec = struct_use_rec(b);
     if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_sdf_wave
         oc.e = hipFuncSetAttribute(use_rec ? reinterpret_cast<const void *>(k_hydration_map<true>)

@@ -4,7 +4,9 @@ of 2^-20 K per deposit, planted waters on the cube's edges and ends, independenc
 the refusals that need a batch.
 
 The systems are test_gpu_solute_chain.py's: NIST configuration 3 (a 20 A box, a dyadic number) reduced
-to 257 waters -- 4 x 64 + 1, so the 1024-thread stride and the last wave both have a remainder -- three
+to 257 waters -- 4 x 64 + 1, so the fifth wave holds one water and eleven waves none; the 1024 threads
+make ONE pass of their stride here (a second pass, and a thread whose tails take more than one deposit
+before a flush, are test_gpu_solute_chain_shapes.py's, at 1090 waters) -- three
 replicas diversified by 600 device-proposed steps and doubled to six, so that under wave_wgs = 1 one
 workgroup strides over replicas; cutoffs LJ 8.5 and real space 9.5 A; the solute at corner(box), so that
 the cube crosses a face, an edge and the corner of the box."""

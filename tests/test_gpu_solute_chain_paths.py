@@ -96,9 +96,34 @@ def check_final(final, n1, r, at):
     return com, coords
 
 
+def check_kernel_and_lists(b, opts, n_parts, n_moves, at):
+    """A row that names the wave kernel (option "kernel" = 2; batch_kernel_for then takes it whatever the
+    size) shows by mmc_batch_cand_stats which scan its steps made.  The counters are the wave kernel's own,
+    kept only where a launch has lists to count against (k_move_eval_wave: one part per move and a
+    CandView): with the lists on and one part every step is counted once, on its list or on the full scan;
+    with the lists off, or with several parts per move, no list is ever allocated and nothing is counted --
+    the state word says which of the two it was (0: switched off; 4: never asked for, as the several-parts
+    form marks the lists stale and does not prepare them)."""
+    if opts.get("kernel") != 2:
+        return
+    c = b.cand_stats()
+    print(f"  {at}: cand_stats {c}")
+    if opts.get("candidate_lists", 1) and n_parts == 1:
+        assert c["state"] == 1 and c["list_steps"] > 0 and c["list_steps"] + c["scan_steps"] == n_moves, (at, c)
+    else:
+        assert c["list_steps"] == 0 and c["scan_steps"] == 0 and c["bytes"] == 0, (at, c)
+        assert c["state"] == (0 if n_parts == 1 else 4), (at, c)
+
+
+# The rows of kernel 2 run k_move_eval_wave at R = 3, where the size alone (kernel 3) picks the
+# workgroup-per-move kernel: ("cation", {"candidate_lists": 0}, 1) above them is therefore a row of kernel 1.
+# At this box (20 A, gate 9.5 A) the image-by-molecule form does not apply (gate + 2 r_mol > L / 2), so the
+# row with "image_by_molecule" = 0 runs the same form as the one without and holds the option's handling.
 @pytest.mark.parametrize("name,opts,n_parts", [
     ("cation", {}, 1), ("cation", {"candidate_lists": 0}, 1), ("dipole", {}, 3), ("methane", {"kernel": 1}, 1),
     ("synthetic16", {"accept_on_device": 1, "steps_per_launch": 8}, 1), ("dipole", {"kernel": 0}, 3),
+    ("cation", {"kernel": 2}, 1), ("dipole", {"kernel": 2, "candidate_lists": 0}, 1),
+    ("synthetic16", {"kernel": 2, "image_by_molecule": 0}, 1), ("dipole", {"kernel": 2}, 3),
 ])
 def test_device_made_chains_stepped_by_the_oracle(orc, water, name, opts, n_parts):
     a, R, seed = water, 3, 4321
@@ -116,6 +141,7 @@ def test_device_made_chains_stepped_by_the_oracle(orc, water, name, opts, n_part
         d_gpu, f_gpu = b.get_trace(STEPS)
         finals = [b.get_replica(r) for r in range(R)]
         assert st["moves"] == R * STEPS and st["device_decisions"] == 0 and st["server_steps"] == 0
+        check_kernel_and_lists(b, opts, n_parts, R * STEPS, (name, opts, n_parts))
         fresh = b.potential_ewald(as_array=True)
         assert np.abs(e1 - fresh["energy"]).max() < 1e-9 * np.abs(fresh["energy"]).max(), (e1, fresh["energy"])
         worst = 0.0
@@ -132,7 +158,8 @@ def test_device_made_chains_stepped_by_the_oracle(orc, water, name, opts, n_part
     print(f"chain {name} {opts} parts={n_parts}: largest |dU - oracle| over {R * STEPS} steps {worst:.3e}")
 
 
-@pytest.mark.parametrize("name,n_parts,opts", [("cation", 1, {}), ("dipole", 3, {}), ("synthetic16", 1, {"zero_copy_moves": 1})])
+@pytest.mark.parametrize("name,n_parts,opts", [("cation", 1, {}), ("dipole", 3, {}), ("synthetic16", 1, {"zero_copy_moves": 1}),
+                                               ("dipole", 1, {"kernel": 2})])
 def test_chains_of_host_proposals_stepped_by_the_oracle(orc, water, name, n_parts, opts):
     """The driver proposes on the host: k_solute_move reads the step's records from the host-proposal
     buffer (copied to the device, or with zero_copy_moves in place) instead of a ring slot.  The
@@ -153,6 +180,7 @@ def test_chains_of_host_proposals_stepped_by_the_oracle(orc, water, name, n_part
         d_gpu, f_gpu = b.get_trace(STEPS)
         finals = [b.get_replica(r) for r in range(R)]
         assert st["moves"] == R * STEPS and st["device_decisions"] == 0 and st["server_steps"] == 0
+        check_kernel_and_lists(b, opts, n_parts, R * STEPS, (name, "host", opts, n_parts))
         fresh = b.potential_ewald(as_array=True)
         assert np.abs(e1 - fresh["energy"]).max() < 1e-9 * np.abs(fresh["energy"]).max(), (e1, fresh["energy"])
         worst = 0.0
@@ -238,8 +266,10 @@ def chain_state(b, seed, n_parts=1, opts=None):
     return dict(e0=e0.tobytes(), e1=e1.tobytes(), d=d.tobytes(), f=f.tobytes(), rec=b.get_state().tobytes()), st
 
 
-@pytest.mark.parametrize("device_moves,n_parts", [(1, 1), (1, 3), (0, 1)])
-def test_a_null_solute_changes_no_bit(water, device_moves, n_parts):
+@pytest.mark.parametrize("device_moves,n_parts,kernel", [
+    pytest.param(1, 1, 3, id="1-1"), pytest.param(1, 3, 3, id="1-3"), pytest.param(0, 1, 3, id="0-1"),   # (3: by size, the default)
+    pytest.param(1, 1, 2, id="1-1-wave")])
+def test_a_null_solute_changes_no_bit(water, device_moves, n_parts, kernel):
     a = water
     null = structs.Solute("null", [[0.0, 0.0, 0.0], [0.7, 0.1, 0.0]], [0.0, 0.0], np.zeros((2, 3)), np.zeros((2, 3)))
     out = []
@@ -249,7 +279,10 @@ def test_a_null_solute_changes_no_bit(water, device_moves, n_parts):
             if with_solute:
                 b.set_solute(null, placed_in_the_water(a, null))
             # (the path a solute takes: the host decides, a launch per step -- not the move server)
-            out.append(chain_state(b, 55, n_parts, {"accept_on_device": 0, "persistent": 0})[0])
+            out.append(chain_state(b, 55, n_parts, {"accept_on_device": 0, "persistent": 0, "kernel": kernel})[0])
+            if kernel == 2:      # the wave kernel on its candidate lists, with the solute's record and without
+                c = b.cand_stats()
+                assert c["state"] == 1 and c["list_steps"] > 0 and c["list_steps"] + c["scan_steps"] == 3 * STEPS, c
     for k in out[0]:
         assert out[0][k] == out[1][k] or k == "rec", k
     # the state records differ in nothing either: the info carries the solute, the records do not
