@@ -15,8 +15,7 @@ extern "C" int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t
     // ---- arguments (MMC_ERR_ARG; those that need no batch first, so that they are refused without a
     // device), then state (MMC_ERR_STATE), then scope (MMC_ERR_UNSUPPORTED); nothing is written
     // before every check has passed ----
-    MMC_REQUIRE(std::isfinite(temperature) && temperature > 0.0, MMC_ERR_ARG,
-                "%s: temperature must be positive and finite", what);
+    MMC_TRY(temperature_arg(temperature, what));
     MMC_REQUIRE(hist || esum || boltz_sum || n_flagged || du_out || ovl_out, MMC_ERR_ARG,
                 "%s: every output is NULL", what);
     if (hist) {
@@ -57,12 +56,7 @@ extern "C" int32_t mmc_batch_deletion(mmc_batch *b, int32_t n_sel, const int32_t
     da.flags = uc.d_flags();
     da.scur = uc.d_scur();
     da.n = (int32_t)n;
-    {   // EwaldSelf(N) - EwaldSelf(N \ i) in orc_ewald_self's arithmetic (ewalds.jl:829-833)
-        double q2 = 0.0;
-        for (int a = 0; a < 3; a++)
-            q2 += s.fc.q[a] * s.fc.q[a];
-        da.self_d = -s.bv.kappa * q2 / std::sqrt(M_PI) * s.bv.factor;
-    }
+    da.self_d = ewald_self_term(s.fc.q, 3, s.bv.kappa, s.bv.factor); // EwaldSelf(N) - EwaldSelf(N \ i)
 
     DeletionReduceArgs ra{};
     ra.terms = uc.d_rows();

@@ -292,9 +292,8 @@ __device__ __forceinline__ long long hm_wave_sum(long long v)
     return v;
 }
 
-// REC: molecules are the 128-byte records of homogeneous batches; else the SoA arrays.
-// grid: at most R workgroups of HMAP_THREADS threads.
-template <bool REC>
+// The molecules are read from the 128-byte records `rec`, which a batch with a solute always keeps in
+// step (mmc_batch_set_solute).  grid: at most R workgroups of HMAP_THREADS threads.
 __global__ __launch_bounds__(HMAP_THREADS) void k_hydration_map(BatchView bv, const double *__restrict__ rec, SoluteView sv,
                                                                 const double *__restrict__ qq_tab, FastConsts fc,
                                                                 PairParams pp, HmapArgs ha)
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(HMAP_THREADS) void k_hydration_map(BatchView bv, co
                 bool on = true;    // false: the water is left out and counted in the last slot
                 if (ch < 6) {
                     double w[9];
-                    load_sites9<REC>(bv, rec, r, j, w);
+                    load_sites9<true>(bv, rec, r, j, w);
                     sx = ch == 1 ? w[3] : ch == 2 ? w[6] : w[0];
                     sy = ch == 1 ? w[4] : ch == 2 ? w[7] : w[1];
                     sz = ch == 1 ? w[5] : ch == 2 ? w[8] : w[2];
@@ -364,7 +363,7 @@ __global__ __launch_bounds__(HMAP_THREADS) void k_hydration_map(BatchView bv, co
                     }
                 } else {
                     double w[12];
-                    load_sites12<REC>(bv, rec, r, j, w);
+                    load_sites12<true>(bv, rec, r, j, w);
                     sx = w[0]; sy = w[1]; sz = w[2];
                     SolAcc acc = { 0.0, 0.0, 0.0, false };
                     for (int a = 0; a < S; a++)

@@ -3,26 +3,8 @@
 // totals, and the three observables that need it (the pair energy, the radial histograms, the 3-D
 // maps).  What the move driver does with it is three lines of mmc_batch.inc / mmc_engine.inc:
 // batch_launch enqueues k_solute_move in front of the move kernel, and collect / mmc_batch_eval read one
-// more record per move.  Included by mmc_hip.hip after mmc_units.inc.
-
-// S >= 1: the arguments of a solute, in mmc_batch_widom_solute_at's order; none of it needs a batch
-static int32_t solute_chain_args(int32_t S, const double *mol, const double *charge, const double *eps, const double *sig,
-                                 const char *what)
-{
-    MMC_REQUIRE(charge, MMC_ERR_ARG, "%s: NULL charge", what);
-    MMC_REQUIRE(eps, MMC_ERR_ARG, "%s: NULL eps", what);
-    MMC_REQUIRE(sig, MMC_ERR_ARG, "%s: NULL sig", what);
-    MMC_REQUIRE(mol, MMC_ERR_ARG, "%s: NULL mol", what);
-    for (int a = 0; a < S; a++)
-        MMC_REQUIRE(std::isfinite(charge[a]), MMC_ERR_ARG, "%s: non-finite charge", what);
-    for (int q = 0; q < 3 * S; q++) {
-        MMC_REQUIRE(std::isfinite(eps[q]) && eps[q] >= 0.0, MMC_ERR_ARG, "%s: eps must be finite and >= 0", what);
-        MMC_REQUIRE(std::isfinite(sig[q]) && sig[q] >= 0.0, MMC_ERR_ARG, "%s: sig must be finite and >= 0", what);
-    }
-    for (int q = 0; q < 3 * (S + 1); q++)
-        MMC_REQUIRE(std::isfinite(mol[q]), MMC_ERR_ARG, "%s: non-finite mol", what);
-    return MMC_OK;
-}
+// more record per move.  Included by mmc_hip.hip after mmc_units.inc, which holds the solute's record,
+// refusals and parameter rows.
 
 extern "C" int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const double *mol, const double *charge,
                                         const double *eps, const double *sig)
@@ -31,8 +13,16 @@ extern "C" int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const dou
     const int32_t S = n_sites;
     MMC_REQUIRE(S >= 0 && S <= SOL_MAX_SITES, MMC_ERR_ARG, "%s: n_sites must be 0..%d (0 removes the solute)", what,
                 SOL_MAX_SITES);
-    if (S > 0)
-        MMC_TRY(solute_chain_args(S, mol, charge, eps, sig, what));
+    const SoluteIn in{ S, nullptr, charge, eps, sig, "" };
+    bool charged = false;
+    double q2 = 0.0;
+    if (S > 0) { // the arguments of a solute, in mmc_batch_widom_solute_at's order; none of it needs a batch
+        MMC_TRY(solute_null_args(in, what));
+        MMC_REQUIRE(mol, MMC_ERR_ARG, "%s: NULL mol", what);
+        MMC_TRY(solute_value_args(in, what, &charged, &q2));
+        for (int q = 0; q < 3 * (S + 1); q++)
+            MMC_REQUIRE(std::isfinite(mol[q]), MMC_ERR_ARG, "%s: non-finite mol", what);
+    }
     BATCH_CHECK(b);
     MMC_REQUIRE(!b->has_prev, MMC_ERR_STATE, "proposals outstanding: call mmc_batch_settle first");
     BATCH_NO_VOLUME_TRIAL(b);
@@ -48,15 +38,7 @@ extern "C" int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const dou
         if (!sol.h_parts)
             MMC_TRY(batch_pinned((void **)&sol.h_parts, (void **)&sol.d_parts, sizeof(PartOut) * (size_t)s.R));
         double h_par[SOLC_PAR_DOUBLES] = { 0 };
-        for (int a = 0; a < S; a++) {
-            double *p = h_par + SOL_PAR * a;
-            for (int d = 0; d < 3; d++) {
-                p[d] = mol[3 * a + d];
-                p[4 + d] = eps[3 * a + d];
-                p[7 + d] = sig[3 * a + d];
-            }
-            p[3] = charge[a];
-        }
+        solute_pack(h_par, in, mol);
         for (int d = 0; d < 3; d++)
             h_par[SOLC_C + d] = mol[3 * S + d];
         MMC_TRY(s.sync());
@@ -65,14 +47,10 @@ extern "C" int32_t mmc_batch_set_solute(mmc_batch *b, int32_t n_sites, const dou
     // ---- nothing fails from here ----
     const bool was_charged = sol.charged;
     sol.n = S;
-    sol.charged = false;
-    sol.q2 = 0.0;
-    for (int a = 0; a < S; a++) {
-        sol.charge[a] = charge[a];
-        sol.charged = sol.charged || charge[a] != 0.0;
-        sol.q2 += charge[a] * charge[a];
-    }
+    sol.charged = charged;
+    sol.q2 = q2;
     if (S > 0) {
+        memcpy(sol.charge, charge, sizeof(double) * S);
         memcpy(sol.mol, mol, sizeof(double) * 3 * (S + 1));
         memcpy(sol.eps, eps, sizeof(double) * 3 * S);
         memcpy(sol.sig, sig, sizeof(double) * 3 * S);
@@ -264,6 +242,9 @@ extern "C" int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double 
     MMC_REQUIRE((int64_t)lds + 64 <= s.lds_per_block, MMC_ERR_UNSUPPORTED,
                 "%s: the device grants %lld bytes of LDS per workgroup, %lld cells need %zu", what,
                 (long long)s.lds_per_block, (long long)n_cells, lds + 64);
+    // (holds while a solute is set: mmc_batch_set_solute requires fast_ok of a homogeneous batch, and what
+    // could clear it -- a volume change, per-replica boxes, Wolf style -- is fenced)
+    MMC_REQUIRE(struct_use_rec(b), MMC_ERR_UNSUPPORTED, "%s: the batch does not keep its molecules' records in step", what);
     std::vector<double> edge((size_t)n_edge);
     for (int k = -n_half; k <= n_half; k++)
         edge[(size_t)(k + n_half)] = (double)k * cell;
@@ -284,24 +265,15 @@ extern "C" int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double 
     ha.inv_cell = (float)(1.0 / cell);
     ha.R = (int32_t)R;
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
-    // (always true here: mmc_batch_set_solute requires fast_ok, which implies the records of a homogeneous
-    // batch, and everything that could clear it -- a volume change, per-replica boxes, Wolf style -- is fenced
-    // while a solute is set.  k_hydration_map<false> is kept for the scaffold's shape, not reached, and has no test.)
-    const bool use_rec = struct_use_rec(b);
     if (lds > TILE_LDS_BYTES) // beyond what a workgroup may ask for without opting in: as k_sdf_wave
-        oc.e = hipFuncSetAttribute(use_rec ? reinterpret_cast<const void *>(k_hydration_map<true>)
-                                           : reinterpret_cast<const void *>(k_hydration_map<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds_per_block - 64));
+        oc.e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_hydration_map), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(s.lds_per_block - 64));
     oc.zero(map_bytes);
     oc.to_device(oc.at<double>(o_edge), edge.data(), sizeof(double) * edge.size());
     // one workgroup of sixteen waves per compute unit (its grid may take 128 KB of the unit's LDS), a replica at a time
     const unsigned wgs = obs_grid(b, HMAP_THREADS / 64, (int64_t)R * (HMAP_THREADS / 64));
-    if (oc.e == hipSuccess) {
-        if (use_rec)
-            k_hydration_map<true><<<wgs, HMAP_THREADS, lds, oc.st>>>(s.bv, s.rec, b->sol.view(), s.qq_tab, s.fc, pp, ha);
-        else
-            k_hydration_map<false><<<wgs, HMAP_THREADS, lds, oc.st>>>(s.bv, nullptr, b->sol.view(), s.qq_tab, s.fc, pp, ha);
-    }
+    if (oc.e == hipSuccess)
+        k_hydration_map<<<wgs, HMAP_THREADS, lds, oc.st>>>(s.bv, s.rec, b->sol.view(), s.qq_tab, s.fc, pp, ha);
     oc.launched();
     oc.fetch(maps, ha.maps, map_bytes);
     return oc.finish(what);

@@ -84,7 +84,7 @@ template <int SMAX> __device__ __forceinline__ double *pair_tile(PairShared<SMAX
 
 // B's frame from slots MMC_SLOT_WIDOM + 3, 4, 5: the ray's direction nh = (s cos phi, s sin phi, z),
 // z = 1 - 2 u, s = sqrt(1 - z^2), phi = 2 pi v of slot +3; Shoemake's rotation of (u1, u2) = slot +4
-// and u3 = the first uniform of slot +5, in widom_draw's expressions.  Host mirror:
+// and u3 = the first uniform of slot +5 (shoemake_matrix, mmc_widom.hpp).  Host mirror:
 // observables.pair_molecules.
 __device__ __forceinline__ void pair_draw(uint64_t seed, uint64_t ctr, uint32_t replica, double nh[3], double Rm[3][3])
 {
@@ -97,21 +97,7 @@ __device__ __forceinline__ void pair_draw(uint64_t seed, uint64_t ctr, uint32_t 
     nh[0] = s * cp;
     nh[1] = s * sp;
     nh[2] = z;
-    const double u1 = d4.a, u2 = d4.b, u3 = d5.a;
-    const double s1 = sqrt(1.0 - u1), s2 = sqrt(u1);
-    double sa, ca, sb, cb;
-    sincos(MMC_TWOPI * u2, &sa, &ca);
-    sincos(MMC_TWOPI * u3, &sb, &cb);
-    const double qw = s2 * cb, qx = s1 * sa, qy = s1 * ca, qz = s2 * sb;
-    Rm[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz);
-    Rm[0][1] = 2.0 * (qx * qy - qw * qz);
-    Rm[0][2] = 2.0 * (qx * qz + qw * qy);
-    Rm[1][0] = 2.0 * (qx * qy + qw * qz);
-    Rm[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz);
-    Rm[1][2] = 2.0 * (qy * qz - qw * qx);
-    Rm[2][0] = 2.0 * (qx * qz - qw * qy);
-    Rm[2][1] = 2.0 * (qy * qz + qw * qx);
-    Rm[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    shoemake_matrix(d4.a, d4.b, d5.a, Rm);
 }
 
 // grid: any number of workgroups of WV_WAVES waves; wave w of workgroup g takes units

@@ -1,15 +1,10 @@
 // mmc_solute_pair.inc -- host side of Widom insertion of solute pairs (include/mmc_hip.h, "Solute
-// pairs"; the kernels are in mmc_solute_pair.hpp).  Included by mmc_hip.hip after mmc_solute.inc; the
-// state checks, the device scratch, the pinned staging, the launch and the drain of the stream are
-// mmc_units.inc's.
+// pairs"; the kernels are in mmc_solute_pair.hpp).  Included by mmc_hip.hip after mmc_solute.inc; each
+// solute's record, refusals and parameter rows, the state checks, the device scratch, the pinned
+// staging, the launch and the drain of the stream are mmc_units.inc's.
 #include "mmc_solute_pair.hpp"
 
-struct PairSoluteIn { // one solute of the pair, as mmc_batch_widom_solute takes it
-    int32_t S;
-    const double *offsets, *charge, *eps, *sig;
-};
-
-static int32_t solute_pair_run(mmc_batch *b, const PairSoluteIn &A, const PairSoluteIn &B, const double *eps_ab,
+static int32_t solute_pair_run(mmc_batch *b, const SoluteIn &A, const SoluteIn &B, const double *eps_ab,
                                const double *sig_ab, int32_t K, const double *d, int64_t M, uint64_t seed, int64_t draw0,
                                const double *mol_a_in, const double *mol_b_in, bool at, double temperature,
                                double *boltz_a, int64_t *n_zero_a, double *boltz_b, int64_t *n_zero_b, double *boltz_ab,
@@ -23,12 +18,8 @@ static int32_t solute_pair_run(mmc_batch *b, const PairSoluteIn &A, const PairSo
     MMC_REQUIRE(B.S >= 1 && B.S <= SOL_MAX_SITES - 1, MMC_ERR_ARG, "%s: n_sites_b must be 1..%d", what, SOL_MAX_SITES - 1);
     MMC_REQUIRE(A.S + B.S <= SOL_MAX_SITES, MMC_ERR_ARG, "%s: n_sites_a + n_sites_b must be <= %d", what, SOL_MAX_SITES);
     MMC_REQUIRE(K >= 1 && K <= PAIR_MAX_SEP, MMC_ERR_ARG, "%s: n_sep must be 1..%d", what, PAIR_MAX_SEP);
-    MMC_REQUIRE(A.charge, MMC_ERR_ARG, "%s: NULL charge_a", what);
-    MMC_REQUIRE(A.eps, MMC_ERR_ARG, "%s: NULL eps_a", what);
-    MMC_REQUIRE(A.sig, MMC_ERR_ARG, "%s: NULL sig_a", what);
-    MMC_REQUIRE(B.charge, MMC_ERR_ARG, "%s: NULL charge_b", what);
-    MMC_REQUIRE(B.eps, MMC_ERR_ARG, "%s: NULL eps_b", what);
-    MMC_REQUIRE(B.sig, MMC_ERR_ARG, "%s: NULL sig_b", what);
+    MMC_TRY(solute_null_args(A, what));
+    MMC_TRY(solute_null_args(B, what));
     MMC_REQUIRE(eps_ab, MMC_ERR_ARG, "%s: NULL eps_ab", what);
     MMC_REQUIRE(sig_ab, MMC_ERR_ARG, "%s: NULL sig_ab", what);
     if (at) {
@@ -43,22 +34,11 @@ static int32_t solute_pair_run(mmc_batch *b, const PairSoluteIn &A, const PairSo
     MMC_REQUIRE(boltz_b && n_zero_b, MMC_ERR_ARG, "%s: boltz_b and n_zero_b are required", what);
     MMC_REQUIRE(boltz_ab && n_zero_ab, MMC_ERR_ARG, "%s: boltz_ab and n_zero_ab are required", what);
     MMC_REQUIRE(M >= 1, MMC_ERR_ARG, "%s: n_insert must be >= 1", what);
-    MMC_REQUIRE(std::isfinite(temperature) && temperature > 0.0, MMC_ERR_ARG,
-                "%s: temperature must be positive and finite", what);
-    bool charged = false;
-    for (const PairSoluteIn *s : { &A, &B }) {
-        const char *tag = s == &A ? "a" : "b";
-        for (int a = 0; a < s->S; a++) {
-            MMC_REQUIRE(std::isfinite(s->charge[a]), MMC_ERR_ARG, "%s: non-finite charge_%s", what, tag);
-            charged = charged || s->charge[a] != 0.0;
-        }
-        for (int q = 0; q < 3 * s->S; q++) {
-            MMC_REQUIRE(std::isfinite(s->eps[q]) && s->eps[q] >= 0.0, MMC_ERR_ARG, "%s: eps_%s must be finite and >= 0", what, tag);
-            MMC_REQUIRE(std::isfinite(s->sig[q]) && s->sig[q] >= 0.0, MMC_ERR_ARG, "%s: sig_%s must be finite and >= 0", what, tag);
-            if (!at)
-                MMC_REQUIRE(std::isfinite(s->offsets[q]), MMC_ERR_ARG, "%s: non-finite offsets_%s", what, tag);
-        }
-    }
+    MMC_TRY(temperature_arg(temperature, what));
+    bool charged = false; // one of the two
+    double q2;
+    MMC_TRY(solute_value_args(A, what, &charged, &q2));
+    MMC_TRY(solute_value_args(B, what, &charged, &q2));
     for (int q = 0; q < A.S * B.S; q++) {
         MMC_REQUIRE(std::isfinite(eps_ab[q]) && eps_ab[q] >= 0.0, MMC_ERR_ARG, "%s: eps_ab must be finite and >= 0", what);
         MMC_REQUIRE(std::isfinite(sig_ab[q]) && sig_ab[q] >= 0.0, MMC_ERR_ARG, "%s: sig_ab must be finite and >= 0", what);
@@ -113,17 +93,8 @@ static int32_t solute_pair_run(mmc_batch *b, const PairSoluteIn &A, const PairSo
         }
     }
     std::vector<double> h_par((size_t)SOL_PAR * S2, 0.0), h_x((size_t)3 * A.S * B.S), h_d((size_t)K, 0.0);
-    for (int i = 0; i < S2; i++) {
-        const PairSoluteIn &u = i < A.S ? A : B;
-        const int a = i < A.S ? i : i - A.S;
-        double *p = h_par.data() + SOL_PAR * i;
-        for (int c = 0; c < 3; c++) {
-            p[c] = at ? 0.0 : u.offsets[3 * a + c];
-            p[4 + c] = u.eps[3 * a + c];
-            p[7 + c] = u.sig[3 * a + c];
-        }
-        p[3] = u.charge[a];
-    }
+    solute_pack(h_par.data(), A, A.offsets);
+    solute_pack(h_par.data() + SOL_PAR * A.S, B, B.offsets);
     for (int q = 0; q < A.S * B.S; q++) {
         h_x[3 * q] = eps_ab[q];
         h_x[3 * q + 1] = sig_ab[q];
@@ -150,15 +121,8 @@ static int32_t solute_pair_run(mmc_batch *b, const PairSoluteIn &A, const PairSo
     sa.n_a = A.S;
     sa.n_b = B.S;
     sa.n_sep = K;
-    {   // EwaldSelf in orc_ewald_self's arithmetic (ewalds.jl:829-833), of each solute
-        double qa = 0.0, qb = 0.0;
-        for (int a = 0; a < A.S; a++)
-            qa += A.charge[a] * A.charge[a];
-        for (int a = 0; a < B.S; a++)
-            qb += B.charge[a] * B.charge[a];
-        sa.self_a = -s.bv.kappa * qa / std::sqrt(M_PI) * s.bv.factor;
-        sa.self_b = -s.bv.kappa * qb / std::sqrt(M_PI) * s.bv.factor;
-    }
+    sa.self_a = ewald_self_term(A.charge, A.S, s.bv.kappa, s.bv.factor); // EwaldSelf of each solute
+    sa.self_b = ewald_self_term(B.charge, B.S, s.bv.kappa, s.bv.factor);
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
     // the instantiation: no reciprocal part and no tables when neither solute carries a charge
     const units_kernel_t<SolutePairArgs> kern = charged ? k_solute_pair_wave<16> : k_solute_pair_wave<0>;
@@ -223,7 +187,8 @@ extern "C" int32_t mmc_batch_widom_pair(mmc_batch *b, int32_t n_sites_a, const d
                                         int64_t *n_zero_b, double *boltz_ab, int64_t *n_zero_ab, double *mol_a_out,
                                         double *mol_b_out, double *du_out, uint8_t *flags_out)
 {
-    const PairSoluteIn A{ n_sites_a, offsets_a, charge_a, eps_a, sig_a }, B{ n_sites_b, offsets_b, charge_b, eps_b, sig_b };
+    const SoluteIn A{ n_sites_a, offsets_a, charge_a, eps_a, sig_a, "_a" },
+                   B{ n_sites_b, offsets_b, charge_b, eps_b, sig_b, "_b" };
     return solute_pair_run(b, A, B, eps_ab, sig_ab, n_sep, d, n_insert, seed, draw0, nullptr, nullptr, false, temperature,
                            boltz_a, n_zero_a, boltz_b, n_zero_b, boltz_ab, n_zero_ab, mol_a_out, mol_b_out, du_out,
                            flags_out, "mmc_batch_widom_pair");
@@ -237,7 +202,8 @@ extern "C" int32_t mmc_batch_widom_pair_at(mmc_batch *b, int32_t n_sites_a, cons
                                            int64_t *n_zero_a, double *boltz_b, int64_t *n_zero_b, double *boltz_ab,
                                            int64_t *n_zero_ab, double *du_out, uint8_t *flags_out)
 {
-    const PairSoluteIn A{ n_sites_a, nullptr, charge_a, eps_a, sig_a }, B{ n_sites_b, nullptr, charge_b, eps_b, sig_b };
+    const SoluteIn A{ n_sites_a, nullptr, charge_a, eps_a, sig_a, "_a" },
+                   B{ n_sites_b, nullptr, charge_b, eps_b, sig_b, "_b" };
     return solute_pair_run(b, A, B, eps_ab, sig_ab, n_sep, nullptr, n_insert, 0, 0, mol_a_in, mol_b_in, true, temperature,
                            boltz_a, n_zero_a, boltz_b, n_zero_b, boltz_ab, n_zero_ab, nullptr, nullptr, du_out, flags_out,
                            "mmc_batch_widom_pair_at");

@@ -10,6 +10,8 @@
 //   _hbond_rings and _cavity / _cavity_at (min_box, stage_fits, nbr_launch; the kernels' shared part is
 //   mmc_nbr.hpp);
 //   and mmc_batch_dipoles, _structure_factor, _volume_perturb.
+// At the end: what the insertion and solute calls share on the host (the temperature check, the Ewald
+// self term, one solute's record, its refusals and the packer of its SOL_PAR rows).
 // Included by mmc_hip.hip after mmc_batch.inc and before all of them.  DESIGN.md, "Unit kernels",
 // "Tile passes" and "Neighbour scans".
 #include "mmc_unit.hpp"
@@ -386,3 +388,76 @@ struct UnitsCall : ObsCall {
         return ObsCall::finish(what);
     }
 };
+
+// ---- what the insertion and solute calls share (mmc_widom.inc, mmc_solute.inc, mmc_solute_pair.inc,
+// mmc_solute_chain.inc, mmc_deletion.inc); none of it needs a batch
+
+static int32_t temperature_arg(double temperature, const char *what)
+{
+    MMC_REQUIRE(std::isfinite(temperature) && temperature > 0.0, MMC_ERR_ARG,
+                "%s: temperature must be positive and finite", what);
+    return MMC_OK;
+}
+
+// EwaldSelf of the charges q[n] alone, in orc_ewald_self's arithmetic (ewalds.jl:829-833): what a
+// molecule's insertion adds to EwaldSelf(N) and its deletion takes away.
+static double ewald_self_term(const double *q, int n, double kappa, double factor)
+{
+    double q2 = 0.0;
+    for (int a = 0; a < n; a++)
+        q2 += q[a] * q[a];
+    return -kappa * q2 / std::sqrt(M_PI) * factor;
+}
+
+// One rigid solute as the calls take it: S sites, charge [S], eps and sig [S][3] against the three
+// water slots, the body offsets [S][3] where the call draws the placements (else NULL), and the
+// suffix of its arguments' names in messages ("", "_a", "_b").
+struct SoluteIn {
+    int32_t S;
+    const double *offsets, *charge, *eps, *sig;
+    const char *tag;
+};
+
+// The refusals of a solute, S in range: its NULL arrays (a caller checks the offsets or placements
+// itself, in its own order) ...
+static int32_t solute_null_args(const SoluteIn &u, const char *what)
+{
+    MMC_REQUIRE(u.charge, MMC_ERR_ARG, "%s: NULL charge%s", what, u.tag);
+    MMC_REQUIRE(u.eps, MMC_ERR_ARG, "%s: NULL eps%s", what, u.tag);
+    MMC_REQUIRE(u.sig, MMC_ERR_ARG, "%s: NULL sig%s", what, u.tag);
+    return MMC_OK;
+}
+// ... and its values, the offsets where there are any.  *charged |= some charge is not zero,
+// *q2 = sum q^2 in site order.
+static int32_t solute_value_args(const SoluteIn &u, const char *what, bool *charged, double *q2)
+{
+    *q2 = 0.0;
+    for (int a = 0; a < u.S; a++) {
+        MMC_REQUIRE(std::isfinite(u.charge[a]), MMC_ERR_ARG, "%s: non-finite charge%s", what, u.tag);
+        *charged = *charged || u.charge[a] != 0.0;
+        *q2 += u.charge[a] * u.charge[a];
+    }
+    for (int q = 0; q < 3 * u.S; q++) {
+        MMC_REQUIRE(std::isfinite(u.eps[q]) && u.eps[q] >= 0.0, MMC_ERR_ARG, "%s: eps%s must be finite and >= 0", what, u.tag);
+        MMC_REQUIRE(std::isfinite(u.sig[q]) && u.sig[q] >= 0.0, MMC_ERR_ARG, "%s: sig%s must be finite and >= 0", what, u.tag);
+        if (u.offsets)
+            MMC_REQUIRE(std::isfinite(u.offsets[q]), MMC_ERR_ARG, "%s: non-finite offsets%s", what, u.tag);
+    }
+    return MMC_OK;
+}
+
+// The solute's rows of the parameter block the kernels read, par [S][SOL_PAR]: xyz [S][3] (the body
+// offsets, or the sites of a fixed solute; NULL = zeros, the placements are the caller's), charge,
+// eps (3), sig (3).
+static void solute_pack(double *par, const SoluteIn &u, const double *xyz)
+{
+    for (int a = 0; a < u.S; a++) {
+        double *p = par + SOL_PAR * a;
+        for (int d = 0; d < 3; d++) {
+            p[d] = xyz ? xyz[3 * a + d] : 0.0;
+            p[4 + d] = u.eps[3 * a + d];
+            p[7 + d] = u.sig[3 * a + d];
+        }
+        p[3] = u.charge[a];
+    }
+}

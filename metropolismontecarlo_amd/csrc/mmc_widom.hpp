@@ -46,19 +46,9 @@ struct WidomArgs {
     double self_d;       // -factor kappa / sqrt(pi) sum_a q_a^2 (the host's arithmetic)
 };
 
-// Shoemake's uniform unit quaternion from three uniforms, as a rotation matrix; the COM is u L
-// per axis (boundaries.jl:16-26: [0, L)).  Host mirror: metropolismontecarlo_amd/observables.py
-// widom_molecules.
-__device__ __forceinline__ void widom_draw(uint64_t seed, uint64_t ctr, uint32_t replica, double box,
-                                           double com[3], double Rm[3][3])
+// Shoemake's uniform unit quaternion from three uniforms, as a rotation matrix
+__device__ __forceinline__ void shoemake_matrix(double u1, double u2, double u3, double Rm[3][3])
 {
-    const ChainKey ck{ seed, replica };
-    const Uniform2 d0 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT), d1 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT + 1),
-                   d2 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT + 2);
-    com[0] = d0.a * box;
-    com[1] = d0.b * box;
-    com[2] = d1.a * box;
-    const double u1 = d1.b, u2 = d2.a, u3 = d2.b;
     const double s1 = sqrt(1.0 - u1), s2 = sqrt(u1);
     double sa, ca, sb, cb;
     sincos(MMC_TWOPI * u2, &sa, &ca);
@@ -73,6 +63,20 @@ __device__ __forceinline__ void widom_draw(uint64_t seed, uint64_t ctr, uint32_t
     Rm[2][0] = 2.0 * (qx * qz - qw * qy);
     Rm[2][1] = 2.0 * (qy * qz + qw * qx);
     Rm[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+}
+
+// The COM, u L per axis (boundaries.jl:16-26: [0, L)), and the orientation, Shoemake's of the next three
+// uniforms.  Host mirror: metropolismontecarlo_amd/observables.py widom_molecules.
+__device__ __forceinline__ void widom_draw(uint64_t seed, uint64_t ctr, uint32_t replica, double box,
+                                           double com[3], double Rm[3][3])
+{
+    const ChainKey ck{ seed, replica };
+    const Uniform2 d0 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT), d1 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT + 1),
+                   d2 = mmc_draw(ck, ctr, MMC_WIDOM_SLOT + 2);
+    com[0] = d0.a * box;
+    com[1] = d0.b * box;
+    com[2] = d1.a * box;
+    shoemake_matrix(d1.b, d2.a, d2.b, Rm);
 }
 
 // grid: any number of workgroups of WV_WAVES waves; wave w of workgroup g takes units

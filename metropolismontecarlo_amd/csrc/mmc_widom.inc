@@ -1,7 +1,8 @@
 // mmc_widom.inc -- host side of Widom test-particle insertion (include/mmc_hip.h, "Widom
 // test-particle insertion"; the kernels are in mmc_widom.hpp).  Included by mmc_hip.hip after
 // mmc_units.inc, which holds what the call shares with mmc_deletion.inc and mmc_forces.inc: the state
-// checks, the device scratch and pinned staging, the launch and the drain of the stream.
+// checks, the device scratch and pinned staging, the launch and the drain of the stream.  InsertionCall,
+// here, is what the call shares with mmc_solute.inc from the staging of the sums to the caller's arrays.
 #include "mmc_widom.hpp"
 
 // Largest distance of an atom from its COM over the caller's molecules [n][12] (atoms, COM), or
@@ -22,6 +23,61 @@ static double widom_extent(const double *mol, int64_t n, double box)
     return std::sqrt(m2);
 }
 
+// An insertion call (mmc_batch_widom / _widom_at here, mmc_batch_widom_solute / _solute_at in
+// mmc_solute.inc): a unit call with terms [R M][4], flags [R M], one sum and one count per replica,
+// then the inserted species' parameters and, where the caller gives or wants them, the placements
+// [R M][words].  begin(), the caller's launch() of its unit kernel, finish().
+struct InsertionCall : UnitsCall {
+    size_t par_bytes, mol_bytes, o_par, o_mol;
+
+    InsertionCall(mmc_batch *b_, size_t n_units, size_t par_bytes_, size_t mol_bytes_)
+        : UnitsCall(b_, n_units, 4, 1), par_bytes(par_bytes_), mol_bytes(mol_bytes_)
+    {
+        o_par = take(par_bytes);
+        o_mol = take(mol_bytes);
+    }
+    double *d_par() const { return at<double>(o_par); }
+    double *d_mol() const { return mol_bytes ? at<double>(o_mol) : nullptr; }
+
+    // after alloc(): the caller's sums into the staged block, and what the unit kernel reads to the
+    // device (h_par, mol_in: NULL = the kernel does not read them).  From here to finish() nothing returns.
+    void begin(const double *boltz_sum, const int64_t *n_overlap, const double *h_par, const double *mol_in)
+    {
+        memcpy(h_sums(), boltz_sum, sizeof(double) * R);
+        memcpy(h_counts(), n_overlap, sizeof(long long) * R);
+        upload_block();
+        if (h_par)
+            to_device(d_par(), h_par, par_bytes);
+        if (mol_in)
+            to_device(d_mol(), mol_in, mol_bytes);
+    }
+    // after launch(): k_widom_reduce adds every replica's M terms to its sums, the stream is drained,
+    // and the caller's arrays are written only once the whole call has succeeded
+    int32_t finish(int64_t M, double temperature, double *boltz_sum, int64_t *n_overlap, double *mol_out, double *du_out,
+                   uint8_t *ovl_out, const char *what)
+    {
+        if (e == hipSuccess)
+            k_widom_reduce<<<(unsigned)R, 64, 0, st>>>(d_rows(), d_flags(), (int)M, 1.0 / temperature, d_sums(), d_counts());
+        launched();
+        std::vector<double> h_terms, h_mol(mol_out ? mol_bytes / sizeof(double) : 0);
+        std::vector<uint8_t> h_flags;
+        if (mol_out)
+            to_host(h_mol.data(), d_mol(), mol_bytes);
+        MMC_TRY(UnitsCall::finish(du_out ? &h_terms : nullptr, ovl_out ? &h_flags : nullptr, what));
+        memcpy(boltz_sum, h_sums(), sizeof(double) * R);
+        memcpy(n_overlap, h_counts(), sizeof(long long) * R);
+        if (du_out)
+            for (size_t i = 0; i < nu; i++)
+                for (int c = 0; c < 3; c++)
+                    du_out[3 * i + c] = h_terms[4 * i + c];
+        if (ovl_out)
+            memcpy(ovl_out, h_flags.data(), nu);
+        if (mol_out)
+            memcpy(mol_out, h_mol.data(), mol_bytes);
+        return MMC_OK;
+    }
+};
+
 static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, const double *offsets,
                          const double *mol_in, double temperature, double *boltz_sum, int64_t *n_overlap,
                          double *mol_out, double *du_out, uint8_t *ovl_out, const char *what)
@@ -35,8 +91,7 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     MMC_REQUIRE(R * M <= (int64_t)INT32_MAX, MMC_ERR_ARG, "%s: replicas x n_insert exceeds 2^31 - 1", what);
     MMC_REQUIRE(boltz_sum && n_overlap, MMC_ERR_ARG, "%s: boltz_sum and n_overlap are required", what);
     MMC_REQUIRE(offsets || mol_in, MMC_ERR_ARG, "%s: NULL %s", what, mol_in ? "mol_in" : "offsets");
-    MMC_REQUIRE(std::isfinite(temperature) && temperature > 0.0, MMC_ERR_ARG,
-                "%s: temperature must be positive and finite", what);
+    MMC_TRY(temperature_arg(temperature, what));
     double r_test = 0.0; // the test molecule's extent about its COM
     if (offsets) {
         for (int q = 0; q < 9; q++)
@@ -51,33 +106,22 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     }
     MMC_TRY(units_state_scope(b, what));
 
-    // ---- device scratch: terms [R M][4], flags [R M], the per-replica block (sums [R], counts [R]),
-    // offsets [9], molecules [R M][12] ----
+    // ---- device scratch: the parameters are the offsets [9], a placement the molecule [12] ----
     const size_t n = (size_t)(R * M);
-    const bool need_mol = mol_in || mol_out;
-    UnitsCall uc(b, n, 4, 1);
-    const size_t o_off = uc.take(sizeof(double) * 9), o_mol = uc.take(need_mol ? sizeof(double) * 12 * n : 0);
+    InsertionCall uc(b, n, sizeof(double) * 9, (mol_in || mol_out) ? sizeof(double) * 12 * n : 0);
     MMC_TRY(uc.alloc());
-    double *d_off = uc.at<double>(o_off), *d_mol = need_mol ? uc.at<double>(o_mol) : nullptr;
-    memcpy(uc.h_sums(), boltz_sum, sizeof(double) * R);
-    memcpy(uc.h_counts(), n_overlap, sizeof(long long) * R);
 
     WidomArgs wa{};
     wa.seed = seed;
     wa.draw0 = draw0;
-    wa.off = d_off;
-    wa.mol_in = mol_in ? d_mol : nullptr;
-    wa.mol_out = (!mol_in && mol_out) ? d_mol : nullptr;
+    wa.off = uc.d_par();
+    wa.mol_in = mol_in ? uc.d_mol() : nullptr;
+    wa.mol_out = (!mol_in && mol_out) ? uc.d_mol() : nullptr;
     wa.terms = uc.d_rows();
     wa.flags = uc.d_flags();
     wa.scur = uc.d_scur();
     wa.n_insert = (int32_t)M;
-    {   // EwaldSelf(N+1) - EwaldSelf(N) in orc_ewald_self's arithmetic (ewalds.jl:829-833)
-        double q2 = 0.0;
-        for (int a = 0; a < 3; a++)
-            q2 += s.fc.q[a] * s.fc.q[a];
-        wa.self_d = -s.bv.kappa * q2 / std::sqrt(M_PI) * s.bv.factor;
-    }
+    wa.self_d = ewald_self_term(s.fc.q, 3, s.bv.kappa, s.bv.factor); // EwaldSelf(N+1) - EwaldSelf(N)
 
     const PairParams pp = mmc_pair_params(b->lj_rcut, b->qq_rcut, 0.0, 0.5, s.bv.kappa, false);
     // the minimum image of an atom pair from its molecules' (WV_IMG): k_move_eval_wave's condition with
@@ -88,34 +132,9 @@ static int32_t widom_run(mmc_batch *b, int64_t M, uint64_t seed, int64_t draw0, 
     const bool img = b->rigid_only && b->image_by_molecule != 0 && std::isfinite(far) && far < 0.5 * s.box &&
                      far * far < pp.qq_slack_sq && far * far < pp.lj_slack_sq;
 
-    // ---- from here to finish() nothing returns ----
-    uc.upload_block();
-    if (offsets)
-        uc.to_device(d_off, offsets, sizeof(double) * 9);
-    if (mol_in)
-        uc.to_device(d_mol, mol_in, sizeof(double) * 12 * n);
+    uc.begin(boltz_sum, n_overlap, offsets, mol_in);
     uc.launch(img, k_widom_wave<true>, k_widom_wave<false>, WIDOM_OCC, pp, wa);
-    if (uc.e == hipSuccess)
-        k_widom_reduce<<<(unsigned)R, 64, 0, uc.st>>>(uc.d_rows(), uc.d_flags(), (int)M, 1.0 / temperature, uc.d_sums(),
-                                                     uc.d_counts());
-    uc.launched();
-    std::vector<double> h_terms, h_mol(mol_out ? 12 * n : 0);
-    std::vector<uint8_t> h_flags;
-    if (mol_out)
-        uc.to_host(h_mol.data(), d_mol, sizeof(double) * 12 * n);
-    MMC_TRY(uc.finish(du_out ? &h_terms : nullptr, ovl_out ? &h_flags : nullptr, what));
-    // (the caller's arrays are written only once the whole call has succeeded)
-    memcpy(boltz_sum, uc.h_sums(), sizeof(double) * R);
-    memcpy(n_overlap, uc.h_counts(), sizeof(long long) * R);
-    if (du_out)
-        for (size_t i = 0; i < n; i++)
-            for (int c = 0; c < 3; c++)
-                du_out[3 * i + c] = h_terms[4 * i + c];
-    if (ovl_out)
-        memcpy(ovl_out, h_flags.data(), n);
-    if (mol_out)
-        memcpy(mol_out, h_mol.data(), sizeof(double) * 12 * n);
-    return MMC_OK;
+    return uc.finish(M, temperature, boltz_sum, n_overlap, mol_out, du_out, ovl_out, what);
 }
 
 extern "C" int32_t mmc_batch_widom(mmc_batch *b, int64_t n_insert, uint64_t seed, int64_t draw0,

@@ -743,18 +743,22 @@ class Batch(_Handle):
             raise ValueError("mol must be (n_sites + 1, 3): the sites, then the reference point")
         check(self._L.mmc_batch_set_solute(self._h, S, _d(mol), _d(solute.charge), _d(solute.eps), _d(solute.sig)))
 
+    def _solute_sites(self):
+        """The number of sites of the fixed solute, 0 while none is set."""
+        n = C.c_int32(0)
+        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), None, None, None, None))
+        return n.value
+
     def get_solute(self):
         """mmc_batch_get_solute: (structs.Solute, mol (S + 1, 3)) as set -- the Solute's offsets are the
         sites minus the reference point -- or None while no solute is set."""
         from .structs import Solute
-        n = C.c_int32(0)
-        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), None, None, None, None))
-        S = n.value
+        S = self._solute_sites()
         if S == 0:
             return None
         res = _outputs({"mol": ((S + 1, 3), np.float64), "charge": ((S,), np.float64), "eps": ((S, 3), np.float64),
                         "sig": ((S, 3), np.float64)}, None)
-        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), *_ptrs(res, "mol", "charge", "eps", "sig")))
+        check(self._L.mmc_batch_get_solute(self._h, None, *_ptrs(res, "mol", "charge", "eps", "sig")))
         return Solute("solute", res["mol"][:S] - res["mol"][S], res["charge"], res["eps"], res["sig"]), res["mol"]
 
     def solute_energy(self, out=None):
@@ -770,9 +774,7 @@ class Batch(_Handle):
         the replicas or [R, 1 + S, 3, numbins] with per_replica: row 0 from the reference point, row
         1 + a from site a, against the three water slots; bin k holds k dr < r <= (k + 1) dr, dr as
         rdf_sites'.  `out` (that shape, uint64, contiguous) is overwritten and returned."""
-        n = C.c_int32(0)
-        check(self._L.mmc_batch_get_solute(self._h, C.byref(n), None, None, None, None))
-        shape = (1 + n.value, 3, max(int(numbins), 1))
+        shape = (1 + self._solute_sites(), 3, max(int(numbins), 1))
         out = _output(out, (self.R,) + shape if per_replica else shape, np.uint64)
         check(self._L.mmc_batch_rdf_solute(self._h, int(numbins), float(r_max), int(bool(per_replica)), _ptr(out)))
         return out
@@ -854,13 +856,12 @@ class Batch(_Handle):
             raise ValueError("mol_b must be (R, n_insert, n_sep, n_sites_b + 1, 3)")
         K = mol_b.shape[2]
         sm = self.pair_sums(sums, K)
-        du = np.zeros((self.R, M, 1 + 2 * K, 3))
-        fl = np.zeros((self.R, M, 1 + K), dtype=np.uint8)
+        new = _outputs({"du": ((self.R, M, 1 + 2 * K, 3), np.float64), "flags": ((self.R, M, 1 + K), np.uint8)}, None)
         check(self._L.mmc_batch_widom_pair_at(
             self._h, a.n_sites, _d(a.charge), _d(a.eps), _d(a.sig), b.n_sites, _d(b.charge), _d(b.eps), _d(b.sig),
             _d(pair.eps_ab), _d(pair.sig_ab), K, M, _d(mol_a), _d(mol_b), float(temperature), *_ptrs(sm, *sm),
-            _ptr(du), _ptr(fl)))
-        return sm, du, fl
+            *_ptrs(new, "du", "flags")))
+        return sm, new["du"], new["flags"]
 
     def deletion(self, temperature, sel=None, bins=None, per_replica=False, boltz_sum=None,
                  n_flagged=None, details=False):
