@@ -41,6 +41,27 @@ def test_record_layout_of_the_library_and_its_python_mirror(n_mol, nkvecs, quat_
     assert off[7] - off[6] == (32 * n_mol if quat_mode else 0)
 
 
+@pytest.mark.parametrize("quat_mode", (0, 1, 2))
+@pytest.mark.parametrize("nkvecs", NKVECS)
+def test_record_layout_at_every_size_up_to_three_slabs(nkvecs, quat_mode):
+    """Every n_mol of 1..260 (odd and even, both sides of the slab edges 128 and 256 of the state
+    kernels): the two implementations agree and the offsets obey the rules of state_layout --
+    sections start on 16 bytes, a section of an odd number of doubles (com 3 n, coords 9 n: odd
+    exactly when n is) is followed by a pad of exactly 8 bytes and every other by none, the record
+    ends on the next multiple of 64."""
+    for n in range(1, 261):
+        info = make_info(n, nkvecs, quat_mode)
+        off, rb = checkpoint.record_layout(info)
+        assert (off, rb) == checkpoint.library_layout(info), n
+        assert off[:4] == [0, 8, 16, 32], n                              # box, temperature, flags and 8 zero bytes
+        assert all(o % 16 == 0 for o in off[3:]), (n, off)
+        pad = 8 * (n % 2)
+        assert off[4] - (off[3] + 24 * n) == pad and off[5] - (off[4] + 72 * n) == pad, (n, off)
+        assert off[6] == off[5] + 16 * nkvecs, (n, off)                  # (16 bytes an entry: never padded)
+        assert off[7] == off[6] + (32 * n if quat_mode else 0), (n, off)
+        assert rb % 64 == 0 and off[7] <= rb < off[7] + 64, (n, off, rb)
+
+
 def test_the_library_refuses_an_info_that_is_not_one():
     with pytest.raises(_lib.MMCError, match="MMC_ERR_ARG.*version"):
         checkpoint.library_layout(make_info(version=2))

@@ -51,6 +51,20 @@ def counts(st):
     return [int(st[k]) for k in COUNTS]
 
 
+def device_order(s_ref, info):
+    """get_replica's S(k) (the reference's k-vector walk, ewalds.jl:57-89: kx = 0..nk, ky and kz =
+    -nk..nk, 0 < k^2 < k_sq_max) in the order a record holds it (include/mmc_hip.h, "Save and
+    resume"): the same walk with, on a half_k batch, the later member of each kx = 0 conjugate pair
+    left out.  The entries that stay are copies, so the comparison with a record is bitwise."""
+    d = checkpoint.info_to_dict(info)
+    nk, k_sq_max, half_k = min(int(d["nk"]), 5), int(d["k_sq_max"]), bool(d["half_k"])
+    keep = [not (half_k and kx == 0 and (ky > 0 or (ky == 0 and kz > 0)))
+            for kx in range(nk + 1) for ky in range(-nk, nk + 1) for kz in range(-nk, nk + 1)
+            if 0 < kx * kx + ky * ky + kz * kz < k_sq_max]
+    assert len(keep) == s_ref.shape[0] and sum(keep) == int(d["nkvecs"]), (len(keep), sum(keep), s_ref.shape)
+    return s_ref[np.array(keep)]
+
+
 # ---- the run paths ------------------------------------------------------------------------------------
 class Path:
     """One way of driving a batch.  configure(): the modes a fresh batch is put into (arm A; load does
@@ -242,10 +256,54 @@ class CandidateLists(Path):
         return dict(cand_state=np.array(b.cand_stats()["state"]))
 
 
+class Mixture(Path):
+    """An SPC/E + TIP3P mixture: no record lines, so get_state and set_state take the array forms
+    k_state_pack<false> / k_state_unpack<false>, and the generic move kernel, the only one a
+    mixture runs on, reads what they wrote."""
+    options = dict(kernel=0)
+
+    def arrays(self):
+        return common.spce_tip3p_mixture(1, "interleaved")[0]
+
+
+class Generic(Path):
+    """The generic kernel on a homogeneous system: set_state writes the record lines too, the move
+    kernel reads the arrays."""
+    options = dict(kernel=0)
+
+
+class LatencyServer(Path):
+    """What a one-replica batch gets from kernel 3 with the server on: the latency server, several
+    workgroups a replica, each with its own copy of its molecules, which set_state has to
+    invalidate.  (The run statistics tell a server from launches; that the server of one replica
+    of 100 molecules is the latency form is run_plan's rule, batch_lat_shape.)"""
+    n_rep = 1
+    options = dict(device_moves=1, kernel=3, persistent=1)
+    n1, n2 = 60, 37
+    kw = dict(n_groups=1, n_threads=1, replica0=REPLICA0)
+
+    def check_stats(self, st, n):
+        assert st["server_steps"] == n and st["device_decisions"] == 0, st
+
+
+class LatencySteps(Path):
+    """k_move_eval_lat launched per step: kernel 4 with sixteen parts (four workgroups a replica),
+    the host adding up and deciding."""
+    options = dict(device_moves=1, kernel=4, persistent=0)
+    n1, n2 = 60, 37
+    kw = dict(Path.kw, n_parts=16)
+
+    def check_stats(self, st, n):
+        assert st["server_steps"] == 0 and st["device_decisions"] == 0 and st["launches"] == 2 * n, st
+        assert st["moves"] == self.n_rep * n, st
+
+
 PATHS = {"default": Path(), "headline": Headline(), "whole_call": WholeCall(), "headline_traced": HeadlineTraced(),
          "server": Server(), "chains": Chains(),
          "exchange": Exchange(), "per_box": PerBox(), "wolf": Wolf(), "quat_faithful": Quaternions(True),
-         "quat_at": Quaternions(False), "npt": Npt(), "cand_lists": CandidateLists()}
+         "quat_at": Quaternions(False), "npt": Npt(), "cand_lists": CandidateLists(),
+         "mixture": Mixture(), "generic": Generic(), "latency_server": LatencyServer(),
+         "latency_steps": LatencySteps()}
 
 
 def arm(path, interrupted, ckpt):
@@ -352,9 +410,9 @@ def test_the_file_reads_back_without_a_device(saved):
         com, coords, s_ref = saved["b"].get_replica(r)
         assert bits(rec["com"]) == bits(com) and bits(rec["coords"]) == bits(coords)
         assert rec["box"] == 20.0 and rec["temperature"] == 0.0 and rec["quat"] is None and rec["flags"] == 0
-        # S in device order: every entry is an entry of get_replica's 337 (or the conjugate of one)
-        have = set(bits(v) for v in s_ref) | set(bits(np.conj(v)) for v in s_ref)
-        assert rec["S"].shape == (head["info"]["nkvecs"],) and all(bits(v) in have for v in rec["S"])
+        # S in device order, entry for entry: get_replica's 337 through the walk the library documents
+        assert rec["S"].shape == (head["info"]["nkvecs"],)
+        assert bits(rec["S"]) == bits(device_order(s_ref, head["info"]))
 
 
 # ---- ranges ---------------------------------------------------------------------------------------------
