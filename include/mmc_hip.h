@@ -961,6 +961,61 @@ int32_t mmc_batch_rdf_solute(mmc_batch *b, int32_t numbins, double r_max, int32_
 int32_t mmc_batch_hydration_map(mmc_batch *b, int32_t n_half, double cell, int32_t channel_mask,
                                 int32_t per_replica, int64_t *maps);
 
+/* ---- A fixed solute: the mean force, field and potential on it ---------------------------------------
+ * What the water does to the solute of mmc_batch_set_solute, in every replica, in one read-only pass
+ * over the coordinates and the committed S(k): the solvent's force and torque on the held solute (the
+ * integrand of a potential of mean force by constrained integration), the electrostatic potential at
+ * its sites (dU/dq_a, the integrand of a charging free energy) and the electric field there.  The
+ * reference has no forces; as for mmc_batch_forces they are DEFINED as gradients of its own total.  The
+ * differenced energy U is every term of potential(..., "ewald") (energy.jl:946-1032) of the N + 1 system
+ * that depends on the solute, each pair once, with the reference point c and all COMs frozen:
+ *   U = LJ_poly_dU(N + 1) (energy.jl:209-290) + EwaldShort(N + 1) (ewalds.jl:892-906, EwaldReal :293-376)
+ *       + factor RecipLong(all N + 1 molecules) (ewalds.jl:538-602) + EwaldSelf(the solute's charges)
+ *       (ewalds.jl:829-833),
+ * at fixed neighbour sets: the COM gates and the atom slack decide which pairs count and are not
+ * differentiated.  Site a is at r_a with charge q_a.  A water j is gated by its COM against c exactly as
+ * in the moves: rij = vector1D(com_j, c), |rij|^2 < r_cut^2 (strict; energy.jl:248-254 for LJ,
+ * ewalds.jl:334-340 for qq); the qq gate is applied WHETHER OR NOT the solute is charged, because phi
+ * and the field of an uncharged site are outputs too.  For water atom b: rab = vector1D(atom b, site a)
+ * (site minus atom, one box moved where |.| >= L / 2), u = (rab.x^2 + rab.y^2) + rab.z^2 unfused.
+ *   Lennard-Jones site force (LJ gate, u < lj_rcut^2 + 100, eps_ab > 0.001; energy.jl:270-281), with
+ *   s2 = sig_ab^2 / u, s6 = s2^3, s12 = s6^2:
+ *     site_lj[a] += 24 eps_ab (2 s12 - s6) / u * rab
+ *   Real-space field and potential (qq gate, u < qq_rcut^2 + 100; ewalds.jl:359-367), r = sqrt(u):
+ *     field[a] += factor q_b (erfc(kappa r) / r + 2 kappa / sqrt(pi) exp(-kappa^2 u)) / u * rab
+ *     phi[a]   += factor q_b erfc(kappa r) / r
+ *   erfc(kappa r) / r from the batch's table where it covers u (u >= 0.25), from the series below it.
+ *   Reciprocal part, over the batch's half-space list with weights cfac_k and integer vectors n_k, the
+ *   replica's committed S_k (it includes the solute's constant S_sol) and e_{a,k} = exp(2 pi i n_k . r_a
+ *   / L) by the reference's phase recurrence (ewalds.jl:564-585):
+ *     field[a] += factor (4 pi / L) sum_k cfac_k n_k Im(conj(S_k) e_{a,k})
+ *     phi[a]   += 2 factor sum_k cfac_k Re(conj(S_k) e_{a,k})
+ *     phi[a]   -= 2 factor kappa / sqrt(pi) q_a                        (EwaldSelf)
+ *   So phi[a] = dU/dq_a exactly (U is quadratic in the charges; the term of S_sol against itself holds
+ *   the solute's own periodic images and its intramolecular reciprocal part, as U does), and the site
+ *   force is f_a = site_lj[a] + q_a field[a] = -dU/dr_a.  recip_out[r][a] = the three reciprocal field
+ *   components and the reciprocal potential (without the self term) alone.
+ *   Per replica, with d_a = vector1D(c, r_a) as mmc_batch_forces:
+ *     F = sum_a f_a,  tau = sum_a d_a x f_a   (sites in index order, from zero)
+ *   No intramolecular term, as everywhere for a solute: for a two-body "solute" the caller adds the
+ *   direct interaction of its two parts.
+ * Units: K / A (forces), K (torque), K / (e A) (field), K / e (phi).
+ * flags_out[r]: bit 0 (MMC_WIDOM_OVERLAP's value 1) a site and a water atom of opposite charges with
+ *   u < 0.5 inside the qq gate (the moves' rule, ewalds.jl:359); bit 1 (value 2) some output not finite
+ *   (an atom exactly on a site).  A flagged replica has zeros in every row.
+ * Order of summation: for each site, lane l of the replica's wave adds the waters l, l + 64, ... in that
+ *   order, atoms b = 0, 1, 2, then the k-vectors l, l + 64, ...; the 64 lane sums are added in a fixed
+ *   order.  No grid, option "wave_wgs", shard or set of requested outputs changes a bit.
+ * Every output may be NULL; those given are overwritten: force_out, torque_out [R][3]; site_lj_out,
+ *   field_out [R][S][3]; phi_out [R][S]; recip_out [R][S][4]; flags_out [R].
+ * Read-only: coordinates, S(k), streams and counters are untouched.  On any error every output is
+ *   untouched.  MMC_ERR_ARG: every output NULL (without looking at the batch), a NULL batch.
+ *   MMC_ERR_STATE: proposals or a volume trial outstanding, no solute set, a run that failed half-way,
+ *   S(k) stale (a charged solute set or removed before mmc_batch_recip_long; an uncharged solute does
+ *   not stale S(k) and the call works).  tests/solute_force_ref.py restates every output. */
+int32_t mmc_batch_solute_forces(mmc_batch *b, double *force_out, double *torque_out, double *site_lj_out,
+                                double *field_out, double *phi_out, double *recip_out, uint8_t *flags_out);
+
 /* ---- Solute pairs: potentials of mean force at infinite dilution ------------------------------------
  * How two foreign solutes A and B interact through the solvent -- the methane-methane contact and
  * solvent-separated minima, an ion pair -- from test particles (potential distribution theorem):

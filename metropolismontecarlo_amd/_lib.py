@@ -215,6 +215,7 @@ SIGNATURES = {
     "mmc_batch_solute_energy": [_vp, _dp, _dp, _u8p],
     "mmc_batch_rdf_solute": [_vp, _i32, _d, _i32, _u64p],
     "mmc_batch_hydration_map": [_vp, _i32, _d, _i32, _i32, _i64p],
+    "mmc_batch_solute_forces": [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _u8p],
     "mmc_batch_widom_pair": [_vp, _i32, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _i32, _dp, _i64,
                              C.c_uint64, _i64, _d, _dp, _i64p, _dp, _i64p, _dp, _i64p, _dp, _dp, _dp, _u8p],
     "mmc_batch_widom_pair_at": [_vp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _dp, _i32, _i64, _dp, _dp, _d,

@@ -811,6 +811,25 @@ class Batch(_Handle):
         check(self._L.mmc_batch_hydration_map(self._h, int(n_half), float(cell), mask, int(bool(per_replica)), _ptr(out)))
         return out
 
+    def solute_forces(self, details=False, out=None):
+        """mmc_batch_solute_forces: what the water does to the fixed solute in every replica.  Returns a
+        dict: force (R, 3) in K / A and torque (R, 3) in K about the reference point, flags (R,) uint8
+        (bit 0: an overlap; bit 1: a non-finite output; a flagged replica's rows are zeros); with
+        details also site_lj (R, S, 3), the Lennard-Jones force on every site, field (R, S, 3) in
+        K / (e A) and phi (R, S) in K / e, the field and the potential at every site (phi = dU/dq_a; the
+        force on site a is site_lj[a] + q_a field[a]), and recip (R, S, 4), the reciprocal part of
+        (field, phi) alone.  `out`: a dict of such arrays to write.  Read-only."""
+        R, S = self.R, self._solute_sites()
+        spec = {"force": ((R, 3), np.float64), "torque": ((R, 3), np.float64)}
+        if details:
+            spec.update(site_lj=((R, S, 3), np.float64), field=((R, S, 3), np.float64), phi=((R, S), np.float64),
+                        recip=((R, S, 4), np.float64))
+        spec["flags"] = ((R,), np.uint8)
+        res = _outputs(spec, out, known_only=True)
+        check(self._L.mmc_batch_solute_forces(self._h, *_ptrs(res, "force", "torque", "site_lj", "field", "phi", "recip",
+                                                               "flags")))
+        return res
+
     def pair_sums(self, sums, K):
         """The six accumulators of widom_pair: a dict (or None = new zero arrays) with boltz_a (R,),
         n_zero_a (R,), boltz_b, boltz_ab (R, K), n_zero_b, n_zero_ab (R, K)."""

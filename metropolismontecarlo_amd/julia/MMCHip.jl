@@ -806,6 +806,27 @@ function hydration_map(b::Batch, n_half::Integer, cell::Float64, channel_mask::I
     return maps
 end
 
+"""
+    solute_forces(b; details = false) -> (force, torque, flags[, site_lj, field, phi, recip])
+
+What the water does to the fixed solute in every replica (`mmc_batch_solute_forces`): `force`, `torque`
+[3, R] (column-major: C's [R][3]) in K / A and K about the reference point, `flags` [R] (bit 0 an overlap,
+bit 1 a non-finite output; a flagged replica's rows are zeros).  With `details` also `site_lj`, `field`
+[3, S, R], `phi` [S, R] and `recip` [4, S, R]: the Lennard-Jones force on every site, the electric field
+and the electrostatic potential there (phi = dU/dq_a), and the reciprocal part of (field, phi) alone.
+"""
+function solute_forces(b::Batch; details::Bool = false)
+    R, S = b.n_replicas, get_solute(b)[1]
+    force, torque, flags = zeros(3, R), zeros(3, R), zeros(UInt8, R)
+    site_lj, field, phi, recip = zeros(3, S, R), zeros(3, S, R), zeros(S, R), zeros(4, S, R)
+    check(ccall((:mmc_batch_solute_forces, libmmc), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{UInt8}),
+                b.h, force, torque, details ? site_lj : C_NULL, details ? field : C_NULL, details ? phi : C_NULL,
+                details ? recip : C_NULL, flags))
+    return details ? (force, torque, flags, site_lj, field, phi, recip) : (force, torque, flags)
+end
+
 # ---- solute pairs (include/mmc_hip.h, mmc_batch_widom_pair / mmc_batch_widom_pair_at) -----------------
 """
     widom_pair!(b, A, B, eps_ab, sig_ab, d, n_insert, seed, draw0, temperature, sums)

@@ -1225,6 +1225,82 @@ def quantum_correction(fsum, temperature, mass):
             "err": float(np.std(ok, ddof=1) / np.sqrt(ok.size)) if ok.size > 1 else float("nan")}
 
 
+# ---- the mean force, field and potential on a fixed solute (include/mmc_hip.h, mmc_batch_solute_forces) ----
+def solute_mean_force(force, flags):
+    """The mean over the unflagged replicas of a per-replica row of Batch.solute_forces -- force or
+    torque (R, 3), or any (R, ...) -- and its standard error, the replicas being independent chains.
+    Returns (mean, err, n): err is NaN for fewer than two replicas."""
+    force, flags = np.asarray(force, dtype=float), np.asarray(flags)
+    if flags.ndim != 1 or force.shape[:1] != flags.shape:
+        raise ValueError("force (R, ...) and flags (R,) of the same replicas")
+    ok = force[flags == 0]
+    n = ok.shape[0]
+    mean = ok.mean(axis=0) if n else np.full(force.shape[1:], np.nan)
+    err = np.std(ok, axis=0, ddof=1) / np.sqrt(n) if n > 1 else np.full(force.shape[1:], np.nan)
+    return mean, err, n
+
+
+def pair_mean_force(site_force, mol, a, b):
+    """The solvent's force along the axis of a two-body solute, per replica: (f_b - f_a) / 2 projected on
+    the unit vector from site a to site b of mol (S + 1, 3) as given to Batch.set_solute (the two sites
+    lie within half a box of each other).  site_force (R, S, 3) = site_lj + charge[:, None] * field of
+    Batch.solute_forces(details=True).  Positive pushes the two apart."""
+    sf, mol = np.asarray(site_force, dtype=float), np.asarray(mol, dtype=float)
+    if a == b or sf.ndim != 3 or sf.shape[1] != mol.shape[0] - 1:
+        raise ValueError("site_force (R, S, 3), mol (S + 1, 3) and two different sites")
+    e = mol[b] - mol[a]
+    e = e / np.sqrt(e @ e)
+    return 0.5 * ((sf[:, b] - sf[:, a]) @ e)
+
+
+def pmf_from_mean_force(d, f, f_err):
+    """The potential of mean force W(d) = integral from d to d_max of <f>(s) ds by the cumulative
+    trapezoid from the largest separation, where W = 0, with the errors of the independent points
+    propagated: (W, W_err) in the order of d.  f: the mean of pair_mean_force at each separation d.
+    The reference has no intramolecular term, so <f> holds the solvent's part (and the periodic images)
+    alone: the caller adds the direct a-b interaction to W."""
+    d, f, f_err = (np.asarray(x, dtype=float) for x in (d, f, f_err))
+    if d.ndim != 1 or d.shape != f.shape or d.shape != f_err.shape or np.unique(d).size != d.size:
+        raise ValueError("d, f and f_err: one value per separation, the separations all different")
+    order = np.argsort(d)[::-1]                          # from the largest separation down
+    x, y, s = d[order], f[order], f_err[order]
+    n = x.size
+    W, W_err = np.zeros(n), np.zeros(n)
+    for k in range(1, n):
+        wgt = np.zeros(n)                                # the trapezoid's weight of every point in W[k]
+        h = x[:k] - x[1:k + 1]
+        wgt[:k] += 0.5 * h
+        wgt[1:k + 1] += 0.5 * h
+        W[k] = (wgt * y).sum()
+        W_err[k] = np.sqrt(((wgt * s) ** 2).sum())
+    out, out_err = np.empty(n), np.empty(n)
+    out[order], out_err[order] = W, W_err
+    return out, out_err
+
+
+def charging_derivative(phi, charge):
+    """dU/dlambda of a solute set at charges lambda q, per replica: sum_a q_a phi_a with phi (R, S) of
+    Batch.solute_forces(details=True) and the FULL charges q (S,)."""
+    phi, q = np.asarray(phi, dtype=float), np.asarray(charge, dtype=float)
+    if phi.ndim != 2 or phi.shape[1:] != q.shape:
+        raise ValueError("phi (R, S) and charge (S,)")
+    return phi @ q
+
+
+def charging_free_energy(lams, mean, err):
+    """The charging free energy by thermodynamic integration, the trapezoid of <sum_a q_a phi_a>_lambda
+    over the coupling values lams (increasing), with the errors of the independent points propagated:
+    (dA, dA_err) in K."""
+    lams, mean, err = (np.asarray(x, dtype=float) for x in (lams, mean, err))
+    if lams.ndim != 1 or lams.size < 2 or lams.shape != mean.shape or lams.shape != err.shape or np.any(np.diff(lams) <= 0):
+        raise ValueError("lams increasing, with one mean and one error each")
+    h = np.diff(lams)
+    wgt = np.zeros(lams.size)
+    wgt[:-1] += 0.5 * h
+    wgt[1:] += 0.5 * h
+    return float((wgt * mean).sum()), float(np.sqrt(((wgt * err) ** 2).sum()))
+
+
 # ---- parallel tempering: per-rung views of per-replica results --------------------------------------
 def by_rung(values, rung, n_rungs):
     """Regroup a per-replica array [R, ...] (energies, or the per_replica=True result of any
